@@ -17,11 +17,17 @@ plus, for N>1, the one RCCL collective that assembles the presented image on ran
 N>1 shards the 8x8 pixel tiles of the SAME image over the ranks (config C3's decomposition), so
 the total work per step is fixed: "scaling": "strong".
 
-The timed region -- EXACTLY K steps between barrier + synchronize -- is repeated (--reps, default 5, and until the
-repetitions add up to >= 1 s of GPU time): `value` / `ms_per_step` are the MEDIAN repetition, `value_min` / `value_max`
-/ `values` the spread (a single 0.15 s sample moved by +-3 % from run to run on one box).
+The timed region -- EXACTLY K steps between barrier + synchronize -- runs once in a plain run, which sets up, warms up, times
+the K steps, writes its outputs (--dump-outputs DIR) and prints the line: `ms_per_step` is that region's time / K.  With --full
+(or --reps R) it is repeated (--full: --reps, default 5, and until the repetitions add up to >= 1 s of GPU time): `value` /
+`ms_per_step` are the MEDIAN repetition, `value_min` / `value_max` / `values` the spread (a single 0.15 s sample moved by
++-3 % from run to run on one box).
 
-Beside the headline the default single-GPU run appends, OUTSIDE the timed region, the legs VERDICT r01 asked for:
+--dump-outputs DIR: after the timed steps, what the last one left to a caller of pt_render -- the film (float32), the rgba8
+display image (as float32) and the ray count (float64) -- as DIR/<name>.npy; at most 64 MB in all (a larger film keeps a
+fixed, seeded sample of pixels, named by pixel_index.npy).  Same arguments, same inputs: two builds compare output for output.
+
+Beside the headline a single-GPU run with --full appends, OUTSIDE the timed region, the legs VERDICT r01 asked for:
   * `c2_exact`            K = 2 (= 64 spp, exactly BASELINE config C2) in one call;
   * `latency_ms_1frame`   the reference's own dispatch shape: one blocking pt_render per frame (main.cpp:647-685);
   * `roofline.valu_*`     the VALU-issue side of the Cornell traversal kernel from LIVE block counters;
@@ -617,7 +623,7 @@ LEG_SHAPE = {"c4": dict(spp=32, depth=8, tris=0), "c5": dict(spp=16, depth=16, t
 
 
 def extra_leg(pt, ctx, W, H, config, frames, rank, live=False, oracle_walk=False):
-    """The traversal kernel of another BASELINE config (C4 / C5 / C5x) in the default line: `frames` warm-up frames, then the
+    """The traversal kernel of another BASELINE config (C4 / C5 / C5x) in the --full line: `frames` warm-up frames, then the
     same `frames` frames timed with per-launch events (identical launches, so rocprofv3's average over the whole process
     equals this leg's), then the same frames through the instrumented kernel for the visit and block counts."""
     sh = LEG_SHAPE[config]
@@ -693,7 +699,7 @@ def extra_leg(pt, ctx, W, H, config, frames, rank, live=False, oracle_walk=False
     if live:   # the leg's traffic counted like the headline's: the same frames in a child process under rocprofv3's counters
         lt = None
         try:
-            lt = live_traffic(["--pmc-child", "--config", config, "--steps", str(frames), "--warmup", "0", "--reps", "1", "--no-cpu-baseline", "--no-extra-legs",
+            lt = live_traffic(["--pmc-child", "--full", "--config", config, "--steps", str(frames), "--warmup", "0", "--reps", "1", "--no-cpu-baseline", "--no-extra-legs",
                                "--width", str(W), "--height", str(H), "--pipeline", "wavefront"], prefixes=("k_extend",))
         except Exception:
             lt = None
@@ -904,6 +910,36 @@ def compact_line(out):
     return c
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(directory, image, film, rays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path holds after its last step, one `<name>.npy` each -- `film` (the float running mean, H x W x 3;
+    N > 1: the image presented on rank 0), `display_bgra8` (N = 1: the reference's rgba8 storage image, bytes B,G,R,A as float32) and `rays` (the
+    timed call's ray count, float64).  When the pixel arrays exceed `limit` bytes, all of them keep the same fixed, seeded sample of pixels, sorted,
+    whose row-major indices are `pixel_index` (float64)."""
+    import numpy as np
+    img = image.detach().float().cpu().numpy() if hasattr(image, "detach") else np.asarray(image, np.float32)
+    h, w = img.shape[:2]
+    pix = {"film": img.reshape(h * w, -1)}
+    if film is not None:
+        pix["display_bgra8"] = film.read_bgra8().astype(np.float32).reshape(h * w, -1)
+    per_pixel = sum(a.shape[1] * 4 for a in pix.values())
+    out = {"rays": np.array([rays], np.float64)}
+    if per_pixel * h * w <= limit:
+        out.update({k: a.reshape(h, w, -1) for k, a in pix.items()})
+    else:
+        n = max(1, (limit - 4096) // (per_pixel + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, size=n, replace=False))
+        out.update({k: np.ascontiguousarray(a[idx]) for k, a in pix.items()})
+        out["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return sorted(out)
+
+
 def emit(out, args):
     """Rank 0's output: the legs' full blocks first, one `# detail` line each, then the one JSON line of the contract (--full-line: the whole record as that line,
     for the dev scripts that read single keys of it)."""
@@ -932,7 +968,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="frames per timed region (default 16; --config c3: 32 = 1024 spp)")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed region (median reported); more are run until they add up to >= 1 s")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed region (median reported); default 1, with --full 5 and more "
+                                                            "until they add up to >= 1 s")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the repetitions, roofline blocks, live counter passes, CPU baseline, "
+                                                        "frame-0 check against the oracle and the extra legs (the default run times the K steps once)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left to a caller (film, display image, ray count) as DIR/<name>.npy")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--config", choices=["c2", "c3", "c4", "c5", "c5x"], default="c2",
@@ -972,6 +1013,8 @@ def main():
                     help="seconds of oracle time for cpu_baseline (it renders as many spp of frame 0 as fit; when that is the "
                          "whole frame, film and ray count are compared with the GPU's)")
     args = ap.parse_args()
+    if not args.full:      # a plain run measures the headline alone: everything else it used to add is --full's
+        args.no_cpu_baseline = args.no_extra_legs = args.no_live_pmc = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))    # no launcher: bench.py is its own
@@ -1066,8 +1109,9 @@ def main():
                 sys.exit(2)
 
     # ---- the timed region: EXACTLY `steps` frames (+ the one collective that presents the image for N > 1) between
-    # barrier + synchronize, repeated; the film is cleared and the counters reset between repetitions, outside of it
+    # barrier + synchronize, once (--reps / --full: repeated); the film is cleared and the counters reset between repetitions, outside of it
     reps = []       # (seconds, present seconds, stats) per repetition; seconds = MAX over ranks
+    n_reps = args.reps if args.reps is not None else (5 if args.full else 1)
     presented = film_t
     while True:
         film.clear()
@@ -1089,8 +1133,13 @@ def main():
             dt, tp = float(tm[0].item()), float(tm[1].item())
         reps.append((dt, tp, ctx.stats()))
         # (every rank sees the same reduced times, so all ranks stop together)
-        if len(reps) >= max(1, args.reps) and (sum(r[0] for r in reps) >= 1.0 or len(reps) >= 25):
+        if len(reps) >= max(1, n_reps) and (not args.full or sum(r[0] for r in reps) >= 1.0 or len(reps) >= 25):
             break
+    if args.dump_outputs:
+        # what the last repetition's last step left (the film is cleared at the start of each repetition); the ray count is a collective for N > 1
+        last_rays = ptd.sum_counters([reps[-1][2].rays], cdev)[0]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, presented, film if world == 1 else None, last_rays)
     order = sorted(range(len(reps)), key=lambda i: reps[i][0])
     med = order[len(order) // 2]            # the median repetition: its time, its counters, its per-kernel events
     dt, present_s, st = reps[med]
@@ -1169,7 +1218,7 @@ def main():
         frame0_rays_gpu = frame0_film_gpu = None
         cst = None
         live = world == 1 and not (args.no_extra_legs or args.no_live_pmc or args.pmc_child)
-        child_common = (["--mem-budget-mb", str(args.mem_budget_mb)] if args.mem_budget_mb is not None else []) + ["--pmc-child", "--config", args.config, "--steps", str(args.steps), "--warmup", "0", "--reps", "1", "--no-cpu-baseline", "--no-extra-legs",
+        child_common = (["--mem-budget-mb", str(args.mem_budget_mb)] if args.mem_budget_mb is not None else []) + ["--pmc-child", "--full", "--config", args.config, "--steps", str(args.steps), "--warmup", "0", "--reps", "1", "--no-cpu-baseline", "--no-extra-legs",
                         "--width", str(W), "--height", str(H), "--spp", str(args.spp), "--depth", str(args.depth), "--extend", args.extend,
                         "--frames-in-flight", str(args.frames_in_flight), "--sample-groups", str(args.sample_groups), "--sort-rays", args.sort_rays,
                         "--bvh-quality", args.bvh_quality] + (["--soup-tris", str(args.soup_tris)] if args.soup_tris else [])
@@ -1180,7 +1229,7 @@ def main():
                 pt.render(scene, scratch, pt.default_params(frame=0, frame_count=1, **common))
                 frame0_rays_gpu, frame0_film_gpu = ctx.stats().rays, scratch.read_f32()
                 scratch.close()
-            if st.launches_extend and st.ms_extend > 0:
+            if args.full and st.launches_extend and st.ms_extend > 0:
                 kname = "k_fused_inst" if info.n_instances else "k_fused"
                 model = fused_block_model(pt, ctx, scene, W, H, args.steps, args.spp, args.depth, rank, world) if kname == "k_fused" and not args.pmc_child else None
                 out["roofline"] = fused_roofline_block(st, mean_len, scene_config, kname, model)
@@ -1202,7 +1251,7 @@ def main():
                     out["wavefront"] = wl
                 except Exception as e:
                     out["wavefront"] = {"error": repr(e)}
-        else:
+        elif args.full:
             cst, frame0_film_gpu, frame0_rays_gpu = count_visits(pt, ctx, scene, W, H, common, args.steps, frame0=not args.no_cpu_baseline and world == 1)   # (rank 0's shard when N > 1)
         if ran != "fused" and flags and st.launches_extend and st.ms_extend > 0 and cst is not None:
             out["roofline"], out["roofline_shade"] = wavefront_roofline_blocks(pt, st, cst, info, scene_config, NOTES[args.config], mean_len)

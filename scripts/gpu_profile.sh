@@ -10,7 +10,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 run() { # name, extra rocprof flags...
   local name=$1; shift
-  rocprofv3 "$@" --kernel-trace -f csv -d $OUT/$name -o $name -- python bench.py $ARGS > $OUT/$name.log 2>&1
+  rocprofv3 "$@" --kernel-trace -f csv -d $OUT/$name -o $name -- python bench.py --full $ARGS > $OUT/$name.log 2>&1
   echo "$name rc=$? : $(tail -c 300 $OUT/$name.log | tr '\n' ' ' | cut -c1-200)"
 }
 run stats --stats

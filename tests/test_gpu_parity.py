@@ -915,7 +915,7 @@ def test_bench_multi_rank_flow_on_one_gpu(tmp_path):
     import subprocess
     import sys
     repo = os.path.dirname(HERE)
-    args = ["--steps", "2", "--warmup", "1", "--width", "320", "--height", "184", "--no-cpu-baseline", "--no-extra-legs", "--full-line"]
+    args = ["--steps", "2", "--warmup", "1", "--width", "320", "--height", "184", "--full", "--no-cpu-baseline", "--no-extra-legs", "--full-line"]
     one = subprocess.run([sys.executable, os.path.join(repo, "bench.py")] + args, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     j1 = json.loads(one.stdout.strip().splitlines()[-1])
@@ -993,6 +993,36 @@ def test_bench_config_c3_shape():
     assert r.returncode == 0, r.stderr[-2000:]
     assert j["steps"] == 32 and "1024 spp" in j["metric"] and j["config"]["workload"].startswith("C3:")
     assert j["paths"] == 160 * 96 * 32 * 32
+
+
+def test_bench_plain_run_times_k_steps_once_and_dumps_what_a_caller_gets(pt, gpu_ctx, cornell_gpu, tmp_path):
+    """A plain run (no --full) times the K steps once and adds no other leg; --dump-outputs writes the film, the rgba8 display image and the ray
+    count its last step left -- the same bytes a caller of pt_params_default gets for frames 0 .. K-1 -- and two runs write the same outputs."""
+    W, H, K = 320, 184, 3
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r, j = _bench(["--steps", str(K), "--warmup", "1", "--width", str(W), "--height", str(H), "--full-line", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert j["steps"] == K and j["reps"] == 1 and len(j["values"]) == 1 and j["ms_per_step"] > 0
+        for k in ("roofline", "cpu_baseline", "c2_exact", "latency_1frame", "reference_dispatch", "roofline_c4", "roofline_c5", "roofline_c5x", "wavefront"):
+            assert k not in j, k
+        assert sorted(os.listdir(d)) == ["display_bgra8.npy", "film.npy", "rays.npy"]
+        out = {n: np.load(d / (n + ".npy")) for n in ("film", "display_bgra8", "rays")}
+        assert out["film"].dtype == np.float32 and out["film"].shape == (H, W, 3)
+        assert out["display_bgra8"].dtype == np.float32 and out["display_bgra8"].shape == (H, W, 4)
+        assert out["rays"].dtype == np.float64 and int(out["rays"][0]) == j["rays"]
+        assert abs(out["film"].astype(np.float64).sum() - j["presented_checksum"]) <= 1e-9 * abs(j["presented_checksum"])
+        dumps.append(out)
+    for n in ("film", "display_bgra8", "rays"):
+        assert dumps[0][n].tobytes() == dumps[1][n].tobytes(), n
+    film = pt.Film(gpu_ctx, W, H)
+    gpu_ctx.reset_stats()
+    pt.render(cornell_gpu, film, pt.library_default_params(frame=0, frame_count=K, width=W, height=H))
+    assert gpu_ctx.stats().rays == int(dumps[0]["rays"][0])
+    assert film.read_f32().tobytes() == dumps[0]["film"].tobytes()
+    assert film.read_bgra8().astype(np.float32).tobytes() == dumps[0]["display_bgra8"].tobytes()
+    film.close()
 
 
 def test_pt_main_two_ranks_on_one_device_is_a_clean_error():

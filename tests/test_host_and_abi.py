@@ -359,6 +359,41 @@ def test_fast_division_by_the_pdf_is_proven_for_every_float(tmp_path):
     assert "mismatches 0" in out.stdout and "tried 3690987522" in out.stdout
 
 
+def test_bench_dump_outputs_whole_or_a_fixed_bounded_sample(tmp_path):
+    """bench.py --dump-outputs: the arrays whole while they fit the size limit; above it every pixel array keeps the same fixed, seeded,
+    sorted sample of pixels (pixel_index names them), the files stay within the limit, and a second dump picks the same pixels."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    H, W = 120, 100
+    img = np.random.default_rng(5).random((H, W, 3), dtype=np.float32)
+    bgra = np.random.default_rng(6).integers(0, 256, (H, W, 4), dtype=np.uint8)
+
+    class Film:
+        def read_bgra8(self):
+            return bgra
+
+    assert b.dump_outputs(str(tmp_path / "whole"), img, Film(), 77) == ["display_bgra8", "film", "rays"]
+    assert np.load(tmp_path / "whole" / "film.npy").tobytes() == img.tobytes()
+    assert np.load(tmp_path / "whole" / "display_bgra8.npy").tobytes() == bgra.astype(np.float32).tobytes()
+    assert np.load(tmp_path / "whole" / "rays.npy").tolist() == [77.0]
+    limit = 4096 + 1000 * 36
+    got = []
+    for k in range(2):
+        d = tmp_path / f"sample{k}"
+        assert b.dump_outputs(str(d), img, Film(), 77, limit=limit) == ["display_bgra8", "film", "pixel_index", "rays"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= limit
+        idx = np.load(d / "pixel_index.npy")
+        assert idx.dtype == np.float64 and len(idx) == 1000 and (np.diff(idx) > 0).all() and idx[-1] < H * W
+        i = idx.astype(np.int64)
+        f = np.load(d / "film.npy")
+        assert f.dtype == np.float32 and f.tobytes() == img.reshape(-1, 3)[i].tobytes()
+        assert np.load(d / "display_bgra8.npy").tobytes() == bgra.reshape(-1, 4)[i].astype(np.float32).tobytes()
+        got.append(idx)
+    assert got[0].tobytes() == got[1].tobytes()
+
+
 def test_bench_counter_csv_sums_and_the_fallback(tmp_path, monkeypatch):
     """bench.py measures `roofline.traffic` itself: the same frames under `rocprofv3 --pmc` in a child process.  What can be checked without
     a GPU: the sum over rocprofv3's counter CSVs (kernels by short-name prefix, the instrumented instantiations left out, dispatches

@@ -10,7 +10,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = np.load(os.path.join(HERE, "golden", "spirv_pixels.npz"))
-REF_SHADERS = "/root/reference/shaders/"
+# the reference's compiled shaders, copied from a checkout of the reference by the oracle's build (oracle/Makefile `ref`; not in git)
+REF_SHADERS = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "shaders") + os.sep
 
 
 def _progressive(orc, scene, w, h, x, y, n_frames):
@@ -105,14 +106,16 @@ def test_oracle_equals_reference_shaders_at_the_references_own_launch(orc, corne
             assert list(bgra[0, [2, 1, 0, 3]]) == list(g["rgba8"][frame, k]), (x, y, frame)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SHADERS + "raygen.rgen.spv"), reason="needs /root/reference (build container only)")
-def test_fixture_is_reproducible_from_the_reference_binaries(orc, cornell_oracle):
+@pytest.mark.skipif(not os.path.exists(REF_SHADERS + "raygen.rgen.spv"),
+                    reason="needs the reference's compiled shaders in oracle/_ref/shaders (the oracle's build copies them from a reference checkout)")
+def test_fixture_is_reproducible_from_the_reference_binaries(orc, cornell_oracle, monkeypatch):
     """Re-executes the reference's SPIR-V here for a few pixels: the committed fixture is what the binaries give,
     also with the driver's closest hit taken from the LBVH walk instead of brute force."""
     import sys
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_spirv_goldens as gen
     from oracle import spirv_vm as vm
+    monkeypatch.setattr(gen, "REF", REF_SHADERS)
     w, h = [int(v) for v in G["a_launch"]]
     gen._init()
     for k in (0, 3, 57, 140, 201, 274):
