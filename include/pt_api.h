@@ -192,18 +192,22 @@ enum {
      * expectation): next-event estimation.  At every hit one point on one emitter (chosen by area) is sampled and a
      * SHADOW ray queued -- a third queue, compacted like the others and traced by the same extend kernels as an
      * any-hit query; the emission of a surface the path runs into counts for camera rays only.  Same random stream
-     * otherwise (three more numbers per hit).  Fully specified arithmetic like the reference path's (the tests' CPU checker restates it bit for bit).  Instanced scenes sample every instance's copy of the emitters (world space, one cdf). */
+     * otherwise (three more numbers per hit).  Fully specified arithmetic like the reference path's (the tests' CPU checker restates it bit for bit).  Instanced scenes sample every instance's copy of the emitters (world space, one cdf).
+     * One sample group per pixel.  The same estimator is PT_FLAG_NEE on any pipeline value: WAVEFRONT | PT_FLAG_NEE is this pipeline. */
     PT_PIPELINE_WAVEFRONT_NEE = 1,
     /* The reference's estimator, bit for bit, as ONE persistent kernel -- the shape of the reference's own raygen shader
      * (raygen.rgen:41-91: one invocation owns its path): traversal and shading in the same lane, path state in LDS, no
      * queues in HBM; the workspace is the per-slot radiance only (16 B per slot instead of ~150).  For scenes whose
      * triangles fit LDS: single-level ones (the Cornell-box class) and instanced ones of 2 .. 32767 instances over such a
      * BLAS (the TLAS stays in L2); PT_ERR_UNSUPPORTED otherwise, tmin > 0, blocking calls only.  Same films, same ray
-     * counts as PT_PIPELINE_WAVEFRONT.                                                                                   */
+     * counts as PT_PIPELINE_WAVEFRONT.  With PT_FLAG_NEE: the NEE estimator in the same single kernel (the shadow ray walks in the lane, between
+     * a hit and its bounce), same films and ray counts as PT_PIPELINE_WAVEFRONT_NEE -- single-level scenes only, one sample group, no
+     * PT_FLAG_COUNT_VISITS (PT_ERR_UNSUPPORTED otherwise).                                                             */
     PT_PIPELINE_FUSED = 2,
     /* What pt_params_default returns: the fastest pipeline that renders the reference's estimator bit for bit for THIS scene and call --
      * PT_PIPELINE_FUSED where it applies (scenes that live in LDS, see above; blocking calls without PT_FLAG_COUNT_VISITS), else
-     * PT_PIPELINE_WAVEFRONT.  Films, rgba8 images and ray counts do not depend on the choice; pt_stats.pipeline says which one ran.  */
+     * PT_PIPELINE_WAVEFRONT.  Films, rgba8 images and ray counts do not depend on the choice; pt_stats.pipeline says which one ran.
+     * With PT_FLAG_NEE: PT_PIPELINE_FUSED where it would be chosen for a single-level scene, else PT_PIPELINE_WAVEFRONT_NEE.  */
     PT_PIPELINE_AUTO = 3
 };
 enum {
@@ -214,7 +218,12 @@ enum {
     /* Ray sorting (scenes walked out of HBM): before every extend pass after the first the queue is put in (origin cell,
      * direction octant) order by a device radix sort of a permutation.  AUTO (neither flag): on when the traversal
      * working set (BVH4 nodes + triangles) exceeds the 256 MiB Infinity Cache.  Results do not depend on it.        */
-    PT_FLAG_SORT_RAYS = 8u, PT_FLAG_NO_SORT_RAYS = 16u
+    PT_FLAG_SORT_RAYS = 8u, PT_FLAG_NO_SORT_RAYS = 16u,
+    /* The estimator of PT_PIPELINE_WAVEFRONT_NEE (next-event estimation, see there), independent of the implementation: WAVEFRONT | NEE =
+     * PT_PIPELINE_WAVEFRONT_NEE; FUSED | NEE = the fused NEE kernel (single-level scenes of the fused class, one sample group, no
+     * PT_FLAG_COUNT_VISITS); AUTO | NEE = the fused NEE kernel where AUTO would pick the fused kernel for a single-level scene, else
+     * PT_PIPELINE_WAVEFRONT_NEE.  pt_stats.pipeline reports PT_PIPELINE_FUSED or PT_PIPELINE_WAVEFRONT_NEE.  (API version 6)            */
+    PT_FLAG_NEE = 32u
 };
 /* Which closest-hit kernel runs.  All variants implement the same closest-hit definition and
  * return identical bits; AUTO picks by scene size. */

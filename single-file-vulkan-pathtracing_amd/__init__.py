@@ -35,6 +35,7 @@ FLAG_COUNT_VISITS = 2
 FLAG_ASYNC = 4
 FLAG_SORT_RAYS = 8
 FLAG_NO_SORT_RAYS = 16
+FLAG_NEE = 32         # the NEE estimator on any pipeline value (include/pt_api.h PT_FLAG_NEE)
 EXTEND_AUTO, EXTEND_LDS, EXTEND_HBM, EXTEND_HBM8 = 0, 2, 3, 4
 EXTEND_FLAT = 1   # deprecated: the brute-force loop was removed in API version 5 (PT_ERR_UNSUPPORTED); the name is kept for source compatibility
 BVH_PREFER_FAST_TRACE, BVH_PREFER_FAST_BUILD = 0, 1

@@ -24,6 +24,7 @@ extern "C" int pt_debug_fused_hist(void *device_u32_2x8192x16)
 #endif
 
 #include "fused_cull.h"
+#include "nee_sample.h"  // the light sample of k_fused_nee (shared with k_shade)
 
 namespace {
 using namespace ptw;
@@ -87,9 +88,13 @@ pt_status plan_fused_inst(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPl
 }
 }  // namespace
 
-pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPlan &fp)
+pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPlan &fp, bool nee)
 {
     pt_ctx *ctx = s->ctx;
+    if (s->n_inst && nee) {
+        ctx->err = "PT_PIPELINE_FUSED with PT_FLAG_NEE is for single-level scenes (instanced scenes: PT_PIPELINE_WAVEFRONT_NEE)";
+        return PT_ERR_UNSUPPORTED;
+    }
     if (s->n_inst) return plan_fused_inst(s, pl, tmin, fp);
     const size_t tables = sizeof(float4) * 5 * (size_t)s->n_tris;  // shade4 + tangent frames (the vertices are the kz = 2 triangle copy)
     if (pl.variant != PT_EXTEND_LDS || pl.spill || !(tmin > 0.f) || tables > 16 * 1024) {
@@ -103,6 +108,25 @@ pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPla
     fp.smem = (size_t)fp.lds_stack * FTB * sizeof(uint32_t) + (pl.smem - (size_t)pl.lds_stack * TB * sizeof(uint32_t)) + tables +
               sizeof(uint32_t) * FS_FIELDS * FTB + sizeof(uint32_t) * (FTB / 64) * PT_FUSED_WTILES;
     fp.pairs = pl.pairs;
+    if (nee) {  // k_fused_nee: the shadow ray's state behind the waves' tile words (fused_kernel.h FS_NEE_*), and the occupancy of that plan
+        fp.nee = true;
+        fp.smem += sizeof(uint32_t) * FS_NEE_FIELDS * FTB;
+        int per_cu = ctx->fused_per_cu[2];
+        const size_t key2 = (fp.smem << 1) | (pl.pairs ? 1u : 0u);
+        if (ctx->fused_smem[2] != key2 || per_cu <= 0) {
+            for (const void *fn : { reinterpret_cast<const void *>(k_fused_nee<true>), reinterpret_cast<const void *>(k_fused_nee<false>) })
+                if (fp.smem > 48 * 1024) PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.smem));
+            PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pl.pairs ? reinterpret_cast<const void *>(k_fused_nee<true>) : reinterpret_cast<const void *>(k_fused_nee<false>), FTB, fp.smem));
+            ctx->fused_smem[2] = key2;
+            ctx->fused_per_cu[2] = per_cu;
+        }
+        per_cu = std::max(1, std::min(per_cu, 8));
+        per_cu = pt_tuned(ctx->tune.extend_blocks, per_cu, 1, per_cu);
+        fp.grid = ctx->num_cus * per_cu;
+        fp.block = FTB;
+        fp.refill = pt_tuned(ctx->tune.refill, 36, 1, 64);  // (the reference estimator's value: not swept for NEE)
+        return PT_OK;
+    }
     int per_cu = ctx->fused_per_cu[0];
     const size_t key0 = (fp.smem << 1) | (pl.pairs ? 1u : 0u);
     if (ctx->fused_smem[0] != key0 || per_cu <= 0) {
@@ -160,6 +184,16 @@ void ptw_launch_fused(const FusedPlan &fp, bool grouped, const ptw::RenderConst 
                           s->d_shade4, s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots, next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack, div_frames)
 #define PT_LAUNCH_FUSED(G, P) PT_LAUNCH_FUSED_K(k_fused, G, P)
     const int mode = rc.tail ? 2 : (grouped ? 1 : 0);
+    if (fp.nee) {  // (one sample group, no head + tail: render.hip never plans another shape for it)
+        if (mode != 0) return;
+#define PT_LAUNCH_FUSED_NEE(P)                                                                                                                  \
+    hipExtLaunchKernelGGL((k_fused_nee<P>), dim3(fp.grid), dim3(FTB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_wide, s->d_tri4, s->d_shade4, \
+                          s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots, next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack, div_frames, s->d_lights,  \
+                          s->n_lights, s->light_area)
+        if (fp.pairs) PT_LAUNCH_FUSED_NEE(true); else PT_LAUNCH_FUSED_NEE(false);
+#undef PT_LAUNCH_FUSED_NEE
+        return;
+    }
     if (fp.count) {  // the instrumented twins (pair-leaf trees: what the compact class gets by default)
         if (mode == 2) PT_LAUNCH_FUSED_K(k_fused_count, 2, true); else if (mode == 1) PT_LAUNCH_FUSED_K(k_fused_count, 1, true); else PT_LAUNCH_FUSED_K(k_fused_count, 0, true);
         return;

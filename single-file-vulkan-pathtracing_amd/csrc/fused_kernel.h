@@ -63,6 +63,17 @@ enum : int { FS_SLOT = 0, FS_CTR, FS_SEED, FS_WR, FS_WG, FS_WB, FS_PXY, FS_A, FS
 // FS_A..C: the slot's colour (one sample group) | FS_A: its term count (several groups)
 // FS_MB: maxSamples * frame + 1 of the slot's frame (raygen.rgen:47: the seed's multiplier less the sample number), kept so that a
 // sample's camera ray does not decode slot -> frame again (two divisions by run-time constants, at the ten lanes of that block)
+// NEE (PT_FLAG_NEE, k_fused_nee): a shadow ray walks between a hit and its bounce.  What the lane needs across that walk, [field][thread] behind the
+// waves' tile words (where the instrumented twin keeps its counters: NEE has no such twin):
+//   FS_NEE_POS: PT_MISS while a path ray walks; while a shadow ray walks, the hit it left (its bounce is drawn when it returns)
+//   FS_NEE_R..B: the light sample's contribution, added if the shadow ray reaches the light
+// (the hit's position is the shadow ray's origin: read back from the permuted origin the walk keeps in registers)
+enum : int { FS_NEE_POS = 0, FS_NEE_R, FS_NEE_G, FS_NEE_B, FS_NEE_FIELDS };
+// waves per SIMD of the NEE instantiation: its four more dwords per thread leave room for two 512-thread blocks per CU (the Cornell box:
+// ~60 KB each), so the compiler may use the registers of four waves
+#ifndef PT_FUSED_WAVES_NEE
+#define PT_FUSED_WAVES_NEE 4
+#endif
 
 // PAIRS: every leaf is one triangle or one fan pair (k_extend_lds7p's trees); else leaves of up to four triangles (k_extend_lds7's)
 // MODE 0: one sample group (a slot is a pixel's whole frame; radiance added in LDS); 1: several groups (every slot logs its radiance terms);
@@ -110,16 +121,22 @@ enum FusedBlock : int {
     FB_POPTOP,     // a node step whose four children all missed takes the stack's top entry, read with the node, from a register
     FB_N
 };
-template <int MODE, bool PAIRS, bool COUNT>
+// NEE: next-event estimation (the oracle's `nee` mode, k_shade<.., NEE>): emission at the camera ray's hit only; at every hit before the last
+// one light sample (ptn::nee_sample, three random numbers before the bounce's two) whose shadow ray this lane walks next -- an any-hit walk up to
+// the sample's own tmax -- then the bounce.  Per sample the adds are the depth-0 emission, the light samples hit by hit, env at the miss: the
+// oracle's order.  One sample group only (MODE 0).
+template <int MODE, bool PAIRS, bool COUNT, bool NEE = false>
 __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *__restrict__ tiles_arg, Radiance rad_arg,
                                            const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
                                            const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
                                            uint32_t n_wide, uint32_t n_tris, uint32_t slot_base_arg, uint32_t n_slots_arg,
                                            uint32_t *next_slot_arg, unsigned long long *stats_arg, int refill_arg, float tmin_arg,
-                                           float tmax_arg, int lds_stack, FastDiv div_frames_arg)
+                                           float tmax_arg, int lds_stack, FastDiv div_frames_arg,
+                                           const float4 *__restrict__ lights_arg = nullptr, uint32_t n_lights_arg = 0u, float light_area_arg = 0.f)
 {
     constexpr uint32_t LEAF_BIT = 0x2000u, DONE = 0x3FFFu;
     constexpr bool GROUPED = MODE == 1, HYB = MODE == 2;
+    static_assert(!NEE || (MODE == 0 && !COUNT), "NEE: one sample group, no instrumented twin");
     // (everything the persistent loop reads: a scalar register of its own -- own_sgprs)
     const RenderConst rc = ptm::own_sgprs(rc_arg);
     const Radiance rad = ptm::own_sgprs(rad_arg);
@@ -130,6 +147,14 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     const uint32_t slot_base = ptm::own_sgprs(slot_base_arg), n_slots = ptm::own_sgprs(n_slots_arg);
     const int refill = ptm::own_sgprs(refill_arg);
     const float tmin = ptm::own_sgprs(tmin_arg), tmax = ptm::own_sgprs(tmax_arg);
+    const float4 *lights = nullptr;  // NEE: the emitter table (pt_scene::d_lights: 5 float4 per emitter, cdf in .w), read through the cache
+    uint32_t n_lights = 0u;
+    float light_area = 0.f;
+    if constexpr (NEE) {
+        lights = ptm::own_sgprs(lights_arg);
+        n_lights = ptm::own_sgprs(n_lights_arg);
+        light_area = ptm::own_sgprs(light_area_arg);
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // ---- LDS: stack | BVH4 nodes | three permuted triangle copies | shade4 | tangent frames | path state
     float4 *s_wide = reinterpret_cast<float4 *>(smem + (size_t)lds_stack * FTB * sizeof(uint32_t));
@@ -199,6 +224,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     // kernel loses 1 % with it and keeps the frame-major order (profiles/r04ag_ab_fused_tilemajor.log).  (Slot numbers, and with them the radiance arrays, are frame-major as before.)
     const uint32_t part_len = ((n_slots + PT_FUSED_PARTS - 1) / PT_FUSED_PARTS + 63u) & ~63u;  // (several groups)
     lds_u32 *s_wtile = (lds_u32 *)reinterpret_cast<uint32_t *>(s_frame + 2 * (size_t)n_tris) + FS_FIELDS * FTB + (threadIdx.x >> 6) * PT_FUSED_WTILES;
+    lds_u32 *my_nee = (lds_u32 *)reinterpret_cast<uint32_t *>(s_frame + 2 * (size_t)n_tris) + FS_FIELDS * FTB + (FTB / 64) * PT_FUSED_WTILES + threadIdx.x;  // (NEE)
     ptm::f3 inv{}, invf{}, on{}, of{}, orgp{};
     ptm::RayPre pre{};
     uint32_t ax = 0, ay = 0, az = 0, tri_base = 0;
@@ -238,6 +264,9 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
             float wr = 0.f, wg = 0.f, wb = 0.f;
             ptm::f3 org{}, dir{};
             bool got_ray = false, need_primary = false, bounce = false;
+            bool shadow = false;  // NEE: the lane's next ray is the shadow ray of a light sample (org, dir = the hit, wi; tmax nc.w)
+            uint32_t bpos = 0u;   // NEE: the hit whose bounce step (3) draws (its position is in org)
+            float4 nc{};          // NEE: the light sample's contribution | the shadow ray's tmax
             if (in_blk) { PT_FB(FB_SHADE) }
             // (1) the hit of the ray that just ended: radiance, then bounce / next sample / slot complete
             if (in_blk && path) {
@@ -251,7 +280,15 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 float er, eg, eb;
                 bool terminated, add;
                 const uint32_t pos = best_pos;
-                if (pos == PT_MISS) {  // miss.rmiss:10-11 then raygen.rgen:76, 81-83
+                const uint32_t npos = NEE ? (uint32_t)my_nee[FS_NEE_POS * FTB] : PT_MISS;
+                if (NEE && npos != PT_MISS) {  // NEE: the shadow ray of hit npos ended -- its light sample counts if nothing was in the way; then that hit's bounce
+                    er = __uint_as_float(my_nee[FS_NEE_R * FTB]); eg = __uint_as_float(my_nee[FS_NEE_G * FTB]); eb = __uint_as_float(my_nee[FS_NEE_B * FTB]);
+                    add = pos == PT_MISS;
+                    terminated = false;
+                    bpos = npos;
+                    // (the hit's position was the shadow ray's origin: the permuted copy the walk kept, put back in order -- selects, same bits)
+                    org = { ptm::sel3(pre.kz, orgp.z, orgp.y, orgp.x), ptm::sel3(pre.kz, orgp.x, orgp.z, orgp.y), ptm::sel3(pre.kz, orgp.y, orgp.x, orgp.z) };
+                } else if (pos == PT_MISS) {  // miss.rmiss:10-11 then raygen.rgen:76, 81-83
                     PT_FB(FB_MISS)
                     er = wr * rc.env[0]; eg = wg * rc.env[1]; eb = wb * rc.env[2];
                     add = true;
@@ -261,8 +298,24 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     const float4 s1 = s_shade[3 * pos + 1], s2 = s_shade[3 * pos + 2];
                     er = wr * s1.z; eg = wg * s1.w; eb = wb * s2.x;
                     add = !(er == 0.f && eg == 0.f && eb == 0.f);
+                    if (NEE) add = add && depth == 0u;  // (NEE: the emitters are sampled explicitly, running into one counts for camera rays only)
                     depth++;
                     terminated = depth >= rc.max_depth;  // raygen.rgen:62
+                    if (NEE && !terminated) {  // (no light sample at the path's last hit: k_shade<.., NEE>)
+                        // closesthit.rchit:56-57 as k_shade computes it -- the light sample's origin, then the bounce's
+                        float hu, hv;
+                        ptm::div2_dominant(best_V, best_W, best_det, hu, hv);
+                        const float4 a = verts[3 * pos + 0], b = verts[3 * pos + 1], c = verts[3 * pos + 2];
+                        const float b0 = (1.0f - hu) - hv;
+                        org = { (a.x * b0 + b.x * hu) + c.x * hv, (a.y * b0 + b.y * hu) + c.y * hv, (a.z * b0 + b.z * hu) + c.z * hv };
+                        bpos = pos;
+                        if (n_lights) {  // three random numbers, drawn before the bounce's
+                            const float4 s0 = s_shade[3 * pos + 0];
+                            ptm::f3 wi;
+                            shadow = ptn::nee_sample(lights, n_lights, light_area, seed, org, { s0.x, s0.y, s0.z }, s0.w, s1.x, s1.y, wr, wg, wb, wi, nc);
+                            if (shadow) dir = wi;
+                        }
+                    }
                 }
                 const bool logs = GROUPED || (HYB && slot >= rc.n_head);  // (a slot whose radiance goes through the term log)
                 const uint32_t lslot = HYB ? slot - rc.n_head : slot;     // ... its place in the log arrays
@@ -293,7 +346,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     }
                 }
                 if (!terminated) {
-                    bounce = true;  // (the bounce itself: step (3), beside the camera rays)
+                    bounce = !shadow;  // (the bounce itself: step (3), beside the camera rays -- NEE: after the shadow ray, if there is one)
+                    got_ray = shadow;
                 } else {
                     PT_FB(FB_NEXT)
                     sample++;
@@ -472,7 +526,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     dir = { q1, q2, q3 };
                 } else {
                     PT_FB(FB_BOUNCE)
-                    const uint32_t pos = best_pos;
+                    const uint32_t pos = NEE ? bpos : best_pos;
                     const float4 s0 = s_shade[3 * pos + 0], s1 = s_shade[3 * pos + 1];
                     const ptm::f3 nrm = { s0.x, s0.y, s0.z };
                     const float4 f0 = s_frame[2 * pos + 0], f1 = s_frame[2 * pos + 1];
@@ -481,10 +535,12 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     float fr = s0.w * dt, fg = s1.x * dt, fb = s1.y * dt;
                     ptm::div3_by_pdf(fr, fg, fb);
                     wr = wr * fr; wg = wg * fg; wb = wb * fb;
-                    const float4 a = verts[3 * pos + 0], b = verts[3 * pos + 1], c = verts[3 * pos + 2];
-                    const float hu = q1, hv = q2;
-                    const float b0 = (1.0f - hu) - hv;
-                    org = { (a.x * b0 + b.x * hu) + c.x * hv, (a.y * b0 + b.y * hu) + c.y * hv, (a.z * b0 + b.z * hu) + c.z * hv };
+                    if (!NEE) {  // (NEE: org is the hit's position already, step (1))
+                        const float4 a = verts[3 * pos + 0], b = verts[3 * pos + 1], c = verts[3 * pos + 2];
+                        const float hu = q1, hv = q2;
+                        const float b0 = (1.0f - hu) - hv;
+                        org = { (a.x * b0 + b.x * hu) + c.x * hv, (a.y * b0 + b.y * hu) + c.y * hv, (a.z * b0 + b.z * hu) + c.z * hv };
+                    }
                 }
                 got_ray = true;
             }
@@ -494,6 +550,12 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 my_state[FS_SLOT * FTB] = slot; my_state[FS_CTR * FTB] = ctr; my_state[FS_SEED * FTB] = seed;
                 my_state[FS_WR * FTB] = __float_as_uint(wr); my_state[FS_WG * FTB] = __float_as_uint(wg); my_state[FS_WB * FTB] = __float_as_uint(wb);
                 my_state[FS_PXY * FTB] = pxy;
+                if constexpr (NEE) {
+                    my_nee[FS_NEE_POS * FTB] = shadow ? bpos : PT_MISS;
+                    if (shadow) {
+                        my_nee[FS_NEE_R * FTB] = __float_as_uint(nc.x); my_nee[FS_NEE_G * FTB] = __float_as_uint(nc.y); my_nee[FS_NEE_B * FTB] = __float_as_uint(nc.z);
+                    }
+                }
                 pre = ptm::ray_setup<true>(org, dir);
                 inv = { ptm::safe_inv(dir.x), ptm::safe_inv(dir.y), ptm::safe_inv(dir.z) };
                 slab_setup(org, inv, invf, on, of);
@@ -502,7 +564,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 az = inv.z < 0.f ? 48u : 0u;
                 tri_base = (uint32_t)pre.kz * 3u * n_tris;
                 orgp = { ptm::sel3(pre.kz, org.y, org.z, org.x), ptm::sel3(pre.kz, org.z, org.x, org.y), ptm::sel3(pre.kz, org.x, org.y, org.z) };
-                best_t = tmax; best_V = 0.f; best_W = 0.f; best_det = 1.f;
+                best_t = (NEE && shadow) ? nc.w : tmax;  // (a shadow ray: its own tmax, k_extend's ray_tmax)
+                best_V = 0.f; best_W = 0.f; best_det = 1.f;
                 best_pos = PT_MISS;
                 cur = 0u;
                 sp = 0;
@@ -560,7 +623,11 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     const uint32_t first = cur & 0x7FFu;
                     ptl::pair_leaf_test<true>(tri4, (size_t)tri_base + 3 * (size_t)first, ((cur >> 11) & 3u) != 0u, first, pre, orgp, tmin, tmax,
                                         [&](float t, float V, float W, float det, uint32_t pos, uint32_t) {
-                                            ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos);
+                                            [[maybe_unused]] const bool closer =
+                                                ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos);
+                                            if constexpr (NEE) {  // a shadow ray: any hit below its tmax will do, nothing pending any more
+                                                if (closer && my_nee[FS_NEE_POS * FTB] != PT_MISS) sp = 0;
+                                            }
                                         },
                                         [&] { PT_FB(FB_DIV) });
                 } else {
@@ -574,7 +641,10 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                             bool closer = t < best_t;  // closest t; equal t -> lowest gl_PrimitiveID (the first vertex of a record carries it)
                             if (!closer && t == best_t)
                                 closer = best_pos == PT_MISS || __float_as_uint(a.w) < __float_as_uint(tri4[(size_t)tri_base + 3 * (size_t)best_pos].w);
-                            if (closer) { best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos; }
+                            if (closer) {
+                                best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos;
+                                if (NEE && my_nee[FS_NEE_POS * FTB] != PT_MISS) sp = 0;  // (a shadow ray: any hit will do)
+                            }
                         }
                     }
                 }
@@ -604,6 +674,20 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES) void k_fused(RenderConst rc, c
 {
     fused_body<MODE, PAIRS, false>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill, tmin,
                                    tmax, lds_stack, div_frames);
+}
+// PT_FLAG_NEE: next-event estimation, one sample group; the emitter table beside the scene's (pt_scene::d_lights).  Its own LDS plan (FS_NEE_*)
+// and occupancy (fused.hip); the instantiations above do not carry any of it
+template <bool PAIRS>
+__global__ __launch_bounds__(FTB, PT_FUSED_WAVES_NEE) void k_fused_nee(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad,
+                                                                      const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
+                                                                      const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
+                                                                      uint32_t n_wide, uint32_t n_tris, uint32_t slot_base, uint32_t n_slots,
+                                                                      uint32_t *next_slot, unsigned long long *stats, int refill, float tmin,
+                                                                      float tmax, int lds_stack, FastDiv div_frames,
+                                                                      const float4 *__restrict__ lights, uint32_t n_lights, float light_area)
+{
+    fused_body<0, PAIRS, false, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill,
+                                      tmin, tmax, lds_stack, div_frames, lights, n_lights, light_area);
 }
 // the instrumented twin (PT_FLAG_COUNT_VISITS): the same LDS plan and block size, so a wave holds what it holds in the timed kernel; the counters
 // cost registers (spills), so it is slower and never timed

@@ -53,8 +53,8 @@ struct pt_ctx {
     pt_tuning tune;            // include/pt_api.h: defaults (-1) + PT_TUNE, filled once by pt_ctx_create
     // fused.hip: the launch attributes / occupancy of the fused kernels for the last LDS size planned ([0] single-level, [1] two-level):
     // a blocking call per frame plans twice (PT_PIPELINE_AUTO's look, then the render) and should not pay five runtime calls each time
-    size_t fused_smem[2] = { 0, 0 };
-    int fused_per_cu[2] = { 0, 0 };
+    size_t fused_smem[3] = { 0, 0, 0 };  // (single-level, two-level, single-level NEE)
+    int fused_per_cu[3] = { 0, 0, 0 };
 };
 // The workspace budget a context plans within when the caller names none: 8 GB.  Round 6, one MI355X, Grays/s at 2 / 4 / 8 / 16 / 32 GB / no
 // bound: the 10 000-instance grid through the queues 13.6 / 15.0 / 15.0 / 15.1 / 15.4 / 15.3 (the fused kernel 15.5 in 0.6 GB at every budget);

@@ -34,7 +34,7 @@ pt_status check_params(pt_scene *s, pt_film *f, const pt_params *p)
         ctx->err = "the fused pipeline has no asynchronous form";
         return PT_ERR_UNSUPPORTED;
     }
-    if (p->pipeline == PT_PIPELINE_WAVEFRONT_NEE) {
+    if (p->pipeline == PT_PIPELINE_WAVEFRONT_NEE || (p->flags & PT_FLAG_NEE)) {  // (both NEE pipelines: the wavefront one and k_fused_nee)
         if (p->sample_groups > 1) { ctx->err = "the NEE pipeline runs one sample group per pixel"; return PT_ERR_UNSUPPORTED; }
     }
     return PT_OK;
@@ -565,6 +565,10 @@ void fused_shape_defaults(const pt_film *f, const pt_params *p, const FusedPlan 
         q.frames_in_flight = (p->frame_count + batches - 1) / batches;
     }
     q.frames_in_flight = std::max(1u, std::min(q.frames_in_flight, p->frame_count));
+    if (fp.nee) {  // k_fused_nee: one sample group (a slot is a pixel's whole frame), so no term log and no redo
+        q.sample_groups = 1;
+        return;
+    }
     if (q.sample_groups == 0) {
         // every sample its own slot (the smallest divisor of spp that is >= 32, or spp itself) where the launch has little more than one walked
         // slot per lane of the grid -- small films, whatever the frames: 256 x 256 x 4 frames 1.23 ms against 2.50 with one group -- and for a
@@ -624,8 +628,13 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
         return PT_ERR_UNSUPPORTED;
     }
     FusedPlan fp;
-    pt_status rc_ = ptw_plan_fused(s, pl, p_in->tmin, fp);
+    const bool nee = (p_in->flags & PT_FLAG_NEE) != 0;
+    pt_status rc_ = ptw_plan_fused(s, pl, p_in->tmin, fp, nee);
     if (rc_ != PT_OK) return rc_;
+    if (nee && (p_in->flags & PT_FLAG_COUNT_VISITS)) {
+        ctx->err = "PT_FLAG_COUNT_VISITS on the fused pipeline: not with PT_FLAG_NEE (the NEE kernel has no instrumented form)";
+        return PT_ERR_UNSUPPORTED;
+    }
     if (p_in->flags & PT_FLAG_COUNT_VISITS) {  // the instrumented twin of the single-level kernel (wave-level block counts: pt_get_block_counts)
         if (fp.inst || !fp.pairs) {
             ctx->err = "PT_FLAG_COUNT_VISITS on the fused pipeline: single-level scenes with pair leaves only (the two-level kernel has no instrumented form)";
@@ -642,7 +651,7 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
     // HEAD + TAIL slots (fused_kernel.h MODE 2): where the library picks the groups itself and the launch holds few frames, a pixel's frame is one
     // head slot of spp - S samples and S one-sample tail slots -- the launch ends with short work and only the tail's radiance terms go through
     // the log (see fused_tail_samples for S).
-    const uint32_t tail = (!fp.inst && !nested && p_in->sample_groups == 0) ? fused_tail_samples(ctx, f, p_in, q.frames_in_flight, rect) : 0u;
+    const uint32_t tail = (!fp.inst && !fp.nee && !nested && p_in->sample_groups == 0) ? fused_tail_samples(ctx, f, p_in, q.frames_in_flight, rect) : 0u;
     if (tail) {
         q.sample_groups = 1;
         sh = RenderShape{};
@@ -681,6 +690,10 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
         ctx->stats.tail_samples = sh.tail;
     }
     if (rc_ != PT_OK) return rc_;
+    if (fp.nee && (sh.groups != 1 || sh.tail || sh.bounded)) {  // (fused_shape_defaults plans nothing else for it: k_fused_nee is MODE 0 only)
+        ctx->err = "PT_FLAG_NEE on the fused pipeline: one sample group only";
+        return PT_ERR_UNSUPPORTED;
+    }
     ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
     if (prepare_only) return PT_OK;
     {
@@ -787,16 +800,27 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
 // 14.9 against 13.9: profiles/r05c_fused_batch1.log) in a workspace of 16 B per slot.  So: fused for the scenes fused.hip plans (they live in
 // LDS) when the call is one it can serve (blocking, not instrumented, tmin > 0, image <= 65535^2, the closest-hit kernel left to AUTO);
 // the wavefront pipeline for everything else -- big scenes need its queues, sorting and long launches.
+//
+// PT_FLAG_NEE names the estimator, not the implementation: WAVEFRONT | NEE is PT_PIPELINE_WAVEFRONT_NEE, FUSED | NEE is k_fused_nee (single-level
+// scenes of the fused class), and AUTO | NEE is k_fused_nee wherever AUTO would run the fused kernel for a single-level scene, else the
+// wavefront NEE pipeline (instanced scenes, asynchronous or instrumented calls, a named closest-hit kernel, big scenes, oversized images).
+// Measured on one MI355X, Cornell box, spp 32, depth 8, three alternations, ms per frame wavefront NEE / fused NEE (Grays/s with the shadow rays):
+// 1080p 16 frames per call 14.90 / 10.40 (24.4 / 35.0); 1080p one blocking frame per call 26.06 / 12.94 (14.0 / 28.1); the reference's 1024 x 1024
+// launch, one blocking frame 18.0 / 8.33 (10.2 / 22.1) -- same frame-0 film.  Fused NEE is ahead at every shape: no shape rule.
 uint32_t resolve_pipeline(pt_scene *s, const pt_params *p, const ExtendPlan &pl)
 {
+    const bool nee = (p->flags & PT_FLAG_NEE) != 0;
+    if (nee && p->pipeline == PT_PIPELINE_WAVEFRONT) return PT_PIPELINE_WAVEFRONT_NEE;
     if (p->pipeline != PT_PIPELINE_AUTO) return p->pipeline;
+    const uint32_t wavefront = nee ? PT_PIPELINE_WAVEFRONT_NEE : PT_PIPELINE_WAVEFRONT;
     if ((p->flags & (PT_FLAG_ASYNC | PT_FLAG_COUNT_VISITS)) || p->extend != PT_EXTEND_AUTO || p->width > 0xFFFFu || p->height > 0xFFFFu)
-        return PT_PIPELINE_WAVEFRONT;
+        return wavefront;
     FusedPlan fp;
     const std::string keep = s->ctx->err;
-    const pt_status rc = ptw_plan_fused(s, pl, p->tmin, fp);
+    const pt_status rc = ptw_plan_fused(s, pl, p->tmin, fp, nee);  // (NEE: refuses instanced scenes)
     if (rc != PT_OK) s->ctx->err = keep;  // (not an error of this call: the scene is simply not the fused kernel's)
-    if (rc != PT_OK) return PT_PIPELINE_WAVEFRONT;
+    if (rc != PT_OK) return wavefront;
+    if (nee) return PT_PIPELINE_FUSED;
     // Two-level scenes: the fused two-level kernel, in 0.4 .. 5 GB.  With the pixels that look past the instances out of its queues (the cull)
     // the wavefront pipeline is the faster one on launches of few frames -- the 10 000-instance grid at 1080p, ms per frame fused / wavefront:
     // 1 frame 11.95 / 10.40, 2 frames 11.41 / 10.98, 4 frames 11.08 / 10.55, 8 frames 10.49 / 10.39, 16 frames 10.21 / 10.30

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "fused_cull.h"
+#include "nee_sample.h"  // nee_sample: shared with the fused kernel's NEE instantiation
 
 namespace {
 using namespace ptw;
@@ -80,38 +81,6 @@ __global__ __launch_bounds__(TB) void k_generate(RenderConst rc, const uint32_t 
             atomicAdd(stats + 19, (unsigned long long)n_culled);   // pt_stats.rays_culled
         }
     }
-}
-
-// One light sample for the hit at `pos` (normal n, brdf, path weight w); the operations and their order are part of the
-// pipeline's definition (the CPU checker of the tests restates them, and the two agree bit for bit).  Returns false when no shadow ray is needed.
-__device__ __forceinline__ bool nee_sample(const float4 *__restrict__ lights, uint32_t n_lights, float light_area, uint32_t &seed,
-                                           const ptm::f3 pos, const ptm::f3 n, float br, float bg, float bb, float wr, float wg,
-                                           float wb, ptm::f3 &wi, float4 &contrib)
-{
-    const float rl = ptm::rnd(seed), ru = ptm::rnd(seed), rv = ptm::rnd(seed);
-    const float pick = rl * light_area;
-    // first emitter whose running area exceeds pick (the last one if none does): binary search of the cdf
-    uint32_t li = 0, hi_ = n_lights - 1u;
-    while (li < hi_) {
-        const uint32_t mid = (li + hi_) >> 1;
-        if (lights[5 * (size_t)mid].w > pick) hi_ = mid; else li = mid + 1u;
-    }
-    const float4 A = lights[5 * (size_t)li + 0], B = lights[5 * (size_t)li + 1], C = lights[5 * (size_t)li + 2],
-                 N = lights[5 * (size_t)li + 3], Ke = lights[5 * (size_t)li + 4];
-    const float su = ptm::fsqrt(ru);
-    const float b0 = 1.0f - su, b1 = su * (1.0f - rv), b2 = su * rv;
-    const float dx = ((A.x * b0 + B.x * b1) + C.x * b2) - pos.x, dy = ((A.y * b0 + B.y * b1) + C.y * b2) - pos.y,
-                dz = ((A.z * b0 + B.z * b1) + C.z * b2) - pos.z;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (!(d2 > 0.0f)) return false;
-    const float dist = ptm::fsqrt(d2);
-    ptm::div3_dominant(dx, dy, dz, dist, wi.x, wi.y, wi.z);
-    const float cs = (wi.x * n.x + wi.y * n.y) + wi.z * n.z;
-    const float cl = fabsf((wi.x * N.x + wi.y * N.y) + wi.z * N.z);
-    if (!(cs > 0.0f && cl > 0.0f)) return false;
-    const float fgeo = ptm::fdiv(cs * cl, d2) * light_area;
-    contrib = make_float4(((wr * br) * Ke.x) * fgeo, ((wg * bg) * Ke.y) * fgeo, ((wb * bb) * Ke.z) * fgeo, dist * 0.999f);
-    return true;
 }
 
 // after the shadow rays were traced: the contributions of those that reached their light
@@ -338,7 +307,7 @@ __global__ __launch_bounds__(TB, NEE ? 4 : INST ? PT_SHADE_WAVES_INST : PT_SHADE
                     if (NEE && n_lights) {  // one light sample -> shadow queue (three random numbers, drawn before the bounce's)
                         ptm::f3 wi;
                         float4 cb;
-                        if (nee_sample(lights, n_lights, light_area, seed, org, nrm, s0.w, s1.x, s1.y, wr, wg, wb, wi, cb)) {
+                        if (ptn::nee_sample(lights, n_lights, light_area, seed, org, nrm, s0.w, s1.x, s1.y, wr, wg, wb, wi, cb)) {
                             s_alive[it] = true;
                             s_rayA[it] = make_float4(org.x, org.y, org.z, wi.x);
                             s_rayB[it] = make_float2(wi.y, wi.z);

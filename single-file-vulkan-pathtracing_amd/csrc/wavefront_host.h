@@ -86,12 +86,13 @@ struct FusedPlan {
     int grid = 0, block = 0, lds_stack = 0, refill = 40;
     bool pairs = true;                   // single-level: the pair-leaf instantiation (ExtendPlan::pairs)
     bool count = false;                  // PT_FLAG_COUNT_VISITS: the instrumented twin (single-level scenes; wave-level block counts)
+    bool nee = false;                    // PT_FLAG_NEE: k_fused_nee (single-level scenes, one sample group; its own LDS plan and occupancy)
     bool inst = false;                   // two-level scene: k_fused_inst (fused_inst_kernel.h) around k_extend_inst16's walk
     uint32_t n_tlas_lds = 0;             // ... its TLAS nodes staged in LDS
     uint32_t *spill = nullptr;           // ... its stack entries beyond lds_stack: [levels][grid * block] dwords of the context's spill area
     const float4 *inst_frame = nullptr;  // ... the (instance, triangle) normal + tangent table, or null
 };
-pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPlan &fp);
+pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPlan &fp, bool nee = false);
 void ptw_launch_fused(const FusedPlan &fp, bool grouped, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad,
                       const pt_scene *s, uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax,
                       hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);

@@ -5,12 +5,14 @@
 //
 //   pt_main [--obj assets/CornellBox-Original.obj] [--width 1024] [--height 1024]
 //           [--frames 1] [--spp 32] [--depth 8] [--device 0] [--batch N]
-//           [--ppm out.ppm] [--pfm out.pfm] [--pipeline auto|wavefront|fused|nee]
+//           [--ppm out.ppm] [--pfm out.pfm] [--pipeline auto|wavefront|fused|nee] [--nee]
 //           [--ranks N [--devices 0,1,...] [--selftest]]
 // --ranks N renders with N GPUs: one host thread and one context per GPU, the 8x8 pixel tiles interleaved over the
 // ranks (pt_params.rank/world), and ONE RCCL gather of the packed tiles to rank 0 per presented image
 // (pt_film_present); the image written is the presented one.  --selftest: before rendering, every rank presents a film whose own tiles
 // carry its colour through the same collective and rank 0 checks that every tile arrived from its owner (and that RCCL connected N ranks).
+// --nee: the NEE estimator (PT_FLAG_NEE) on whatever --pipeline names -- `--pipeline auto --nee` runs the fused NEE kernel where the scene
+// lives in LDS; --pipeline nee is PT_PIPELINE_WAVEFRONT_NEE as before.
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -38,6 +40,7 @@ struct Options {
     uint32_t width = 1024, height = 1024, frames = 1, spp = 32, depth = 8, batch = 0;
     int device = 0;
     uint32_t pipeline = PT_PIPELINE_AUTO;
+    bool nee = false;            // --nee: PT_FLAG_NEE
     uint32_t ranks = 1;          // --ranks N: one host thread + one GPU per rank, tiles interleaved, RCCL gather to rank 0
     std::vector<int> devices;    // --devices a,b,...: HIP ordinals of the ranks (default 0..N-1)
     bool selftest = false;       // --selftest (with --ranks N): the presentation collective on a rank-coloured film before the render
@@ -140,6 +143,7 @@ void run_rank(const Options &o, const pth_scene &hs, uint32_t rank, const pt_uni
         p.width = o.width; p.height = o.height; p.spp_per_frame = o.spp; p.max_depth = o.depth;
         p.frames_in_flight = o.batch;
         p.pipeline = o.pipeline;
+        if (o.nee) p.flags |= PT_FLAG_NEE;
         p.rank = rank; p.world = o.ranks;
         // the reference dispatches one frame per loop iteration (main.cpp:647-685); frames are
         // independent until the blend, so they are handed over in one call and batched on the device
@@ -213,6 +217,7 @@ int main(int argc, char **argv)
             else if (v == "nee") o.pipeline = PT_PIPELINE_WAVEFRONT_NEE;
             else die("unknown pipeline " + v + " (auto, wavefront, fused, nee)");
         }
+        else if (a == "--nee") o.nee = true;
         else if (a == "--ppm") o.ppm = val();
         else if (a == "--pfm") o.pfm = val();
         else die("unknown option " + a);
