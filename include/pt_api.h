@@ -128,7 +128,7 @@ typedef struct pt_scene_info {
     uint32_t leaf_max;        /* triangles per BVH4 leaf of the collapse rule (bvh4 read-back)    */
     uint32_t bvh4_builder;    /* which BVH4 is traversed: 0 collapsed LBVH, 1 surface-area sweep (small scenes), 2 PLOC tree */
     float    bbox_min[3], bbox_max[3];
-    float    build_ms;        /* device time of the LBVH build (reported apart from rendering) */
+    float    build_ms;        /* device time of the LBVH build, or of the last pt_scene_update (reported apart from rendering) */
     uint64_t device_bytes;    /* resident scene + BVH bytes of the BVH4 path, incl. the source arrays kept for rebuilds (72 B per triangle) */
     uint32_t n_wide8_nodes;   /* 8-wide nodes (64 B each: byte planes) of the PT_EXTEND_HBM8 path, levels of that tree */
     uint32_t wide8_levels;
@@ -150,6 +150,28 @@ pt_status pt_scene_get_info(const pt_scene *scene, pt_scene_info *info);
  * a big scene rebuilds its tree.  Call before pt_scene_set_instances.                                       */
 typedef enum pt_bvh_quality { PT_BVH_PREFER_FAST_TRACE = 0, PT_BVH_PREFER_FAST_BUILD = 1 } pt_bvh_quality;
 pt_status pt_scene_set_bvh_quality(pt_scene *scene, uint32_t quality);
+
+/* Moves the scene's geometry: the counterpart of eAllowUpdate + BuildAccelerationStructureModeKHR::eUpdate.  vertices /
+ * indices as for pt_scene_create, n_tris equal to the scene's (PT_ERR_INVALID_ARG otherwise, and on any argument error the
+ * scene is left as it was); the per-face materials stay.  Blocking, and ordered after the work already queued on the context's
+ * stream (a PT_FLAG_ASYNC render of the scene sees the old geometry); films are not touched.  Afterwards every render, trace and
+ * read-back sees the new geometry, and images, ray counts and hit records equal those of a scene freshly created from the same
+ * arrays, in either mode:
+ *   PT_SCENE_UPDATE_REFIT    keeps the trees' topology (sorted order, leaves, node layout) and recomputes every box, table and
+ *                            emitter from the new positions.  No sort and no new hierarchy: cheaper than a rebuild on small and
+ *                            mid-size scenes, not yet on scenes of millions of triangles.  The trees degrade as
+ *                            the geometry moves away from what they were built for: tree_area_lbvh is recomputed for the refitted
+ *                            LBVH; tree_area_ploc keeps its build-time sum (the PLOC tree's binary form is not held after the
+ *                            collapse).  build_ms spans the update on the stream, its host synchronisations included.  A quad whose
+ *                            two halves no longer share their vertices bit for bit cannot stay one pair leaf: such a call rebuilds.
+ *   PT_SCENE_UPDATE_REBUILD  builds the tree products again at the scene's quality: pt_scene_read_bvh4 then returns what a fresh
+ *                            scene of the same arrays returns.
+ * Instanced scenes: the BLAS is updated, then the TLAS is built again from the instances' transforms.  A failed update (out of
+ * memory) leaves the scene broken like a failed rebuild (PT_BROKEN_SCENE_MSG): it holds the new triangles and builds its trees
+ * from them on its next use, never a mix of old and new.                                                                   */
+enum { PT_SCENE_UPDATE_REFIT = 0, PT_SCENE_UPDATE_REBUILD = 1 };
+pt_status pt_scene_update(pt_scene *scene, const float *vertices, uint32_t n_verts,
+                          const uint32_t *indices, uint32_t n_tris, uint32_t mode);
 
 /* Debug/parity read-back of the device-built LBVH.  keys/prim_of_pos: n_tris entries each;
  * nodes16: n_nodes x 16 dwords {lmin[3] lmax[3] rmin[3] rmax[3] left right 0 0}, child bit31 =

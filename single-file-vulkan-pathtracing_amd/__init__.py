@@ -39,6 +39,7 @@ FLAG_NEE = 32         # the NEE estimator on any pipeline value (include/pt_api.
 EXTEND_AUTO, EXTEND_LDS, EXTEND_HBM, EXTEND_HBM8 = 0, 2, 3, 4
 EXTEND_FLAT = 1   # deprecated: the brute-force loop was removed in API version 5 (PT_ERR_UNSUPPORTED); the name is kept for source compatibility
 BVH_PREFER_FAST_TRACE, BVH_PREFER_FAST_BUILD = 0, 1
+SCENE_UPDATE_REFIT, SCENE_UPDATE_REBUILD = 0, 1   # pt_scene_update modes
 EXTEND_NAMES = {2: "BVH4, scene staged in LDS", 3: "BVH4, scene in HBM/L2",
                 4: "8-wide tree (64-B nodes with byte planes, one stack entry per node), scene in HBM/L2"}
 MISS = 0xFFFFFFFF
@@ -107,7 +108,7 @@ HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
 
 # every symbol include/pt_api.h and include/pt_host.h declare
 API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "pt_scene_create", "pt_scene_destroy",
-               "pt_scene_set_instances", "pt_scene_set_bvh_quality",
+               "pt_scene_set_instances", "pt_scene_set_bvh_quality", "pt_scene_update",
                "pt_scene_get_info", "pt_scene_read_bvh", "pt_scene_read_bvh4", "pt_scene_read_bvh8", "pt_film_create", "pt_film_create_external", "pt_film_clear",
                "pt_film_read_f32", "pt_film_read_bgra8", "pt_film_destroy", "pt_params_default", "pt_render",
                "pt_render_prepare", "pt_trace",
@@ -152,6 +153,7 @@ def lib_amd():
         L.pt_scene_destroy.restype = None
         L.pt_scene_set_instances.argtypes = [vp, vp, C.c_uint32]
         L.pt_scene_set_bvh_quality.argtypes = [vp, C.c_uint32]
+        L.pt_scene_update.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
         L.pt_scene_get_info.argtypes = [vp, C.POINTER(SceneInfo)]
         L.pt_scene_read_bvh.argtypes = [vp, vp, vp, vp]
         L.pt_scene_read_bvh4.argtypes = [vp, vp]
@@ -394,6 +396,15 @@ class Scene:
     def set_bvh_quality(self, quality):
         """BVH_PREFER_FAST_TRACE (default; main.cpp:419) or BVH_PREFER_FAST_BUILD (always the collapsed LBVH)."""
         self.ctx._check(lib_amd().pt_scene_set_bvh_quality(self.h, quality))
+
+    def update(self, vertices, indices, mode=SCENE_UPDATE_REFIT):
+        """New positions for the scene's triangles (pt_scene_update): same triangle count, materials kept.  SCENE_UPDATE_REFIT
+        keeps the trees' topology and refits them; SCENE_UPDATE_REBUILD builds them again.  Images and hits equal a fresh scene's."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1)
+        i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        if v.size % 3 or i.size % 3:
+            raise ValueError("vertices must be 3*nv, indices 3*nt")
+        self.ctx._check(lib_amd().pt_scene_update(self.h, v.ctypes.data, v.size // 3, i.ctypes.data, i.size // 3, mode))
 
     def info(self):
         i = SceneInfo()

@@ -83,6 +83,15 @@ struct BvhOut {
 pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, uint32_t n, uint32_t leaf_max, BvhOut &out, int top_down = 0,
                         bool ploc = false);
 void ptb_norm_box(const float *bmin, const float *bmax, float *c, float *sv, float *rs);
+// pt_scene_update (REFIT), lbvh_build.hip: the scene box of new triangle boxes (tlo / thi in primitive order) and the binary LBVH
+// refitted in place -- same sorted order and child words; area_lbvh gets its area sum when n > 2
+pt_status ptb_refit_lbvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, const uint32_t *d_prim_of, uint32_t n, float4 *nodes,
+                         float *bmin, float *bmax, double *area_lbvh);
+// bvh_refit.hip: a wide tree refitted bottom-up in place.  format 0: 128-B BVH4 (float planes), 1: 64-B BVH4 (fp16 planes, k_w4_emit),
+// 2: 64-B 8-wide nodes (byte planes, k_w8_emit).  prim_of: leaf position of that tree -> primitive; pad: leaf_pad of the scene box;
+// norm_c / norm_rs: the normalisation of formats 1 and 2
+pt_status ptb_refit_wide(pt_ctx *ctx, int format, void *nodes, uint32_t n_nodes, const float4 *d_tlo, const float4 *d_thi,
+                         const uint32_t *d_prim_of, uint32_t n_tris, float pad, const float *norm_c, const float *norm_rs);
 // ploc_build.hip
 pt_status ptb_tree_area(pt_ctx *ctx, uint32_t n, const float4 *d_blo, const float4 *d_bhi, double *out);
 pt_status ptb_ploc_refine(pt_ctx *ctx, uint32_t n, int radius, double area_lbvh, double *area_ploc, uint2 *d_topo, uint2 *d_range,

@@ -587,8 +587,62 @@ __global__ __launch_bounds__(TB) void k_bounds(const float4 *__restrict__ tlo, c
 }
 
 
+// pt_scene_update (REFIT): the Karras links of a built LBVH recovered from its child words (the build frees its parent arrays)
+__global__ __launch_bounds__(TB) void k_nodes_links(const float4 *__restrict__ nodes, int n, uint2 *__restrict__ topo,
+                                                    uint32_t *__restrict__ parent_int, uint32_t *__restrict__ parent_leaf)
+{
+    const int i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n - 1) return;
+    const float4 w = nodes[4 * (size_t)i + 3];
+    const uint32_t l = __float_as_uint(w.x), r = __float_as_uint(w.y);
+    if (l & PT_LEAF) parent_leaf[l & ~PT_LEAF] = (uint32_t)i; else parent_int[l] = (uint32_t)i;
+    if (r & PT_LEAF) parent_leaf[r & ~PT_LEAF] = (uint32_t)i; else parent_int[r] = (uint32_t)i;
+    topo[i] = make_uint2(l, r);
+}
 
 }  // namespace
+
+// pt_scene_update (REFIT): the scene box of the new triangle boxes, and the binary LBVH `nodes` refitted in place by k_refit (same
+// sorted order, same child words, boxes padded by the new box's leaf_pad); area_lbvh: its area sum when n > 2 (else left alone)
+pt_status ptb_refit_lbvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, const uint32_t *d_prim_of, uint32_t n, float4 *nodes,
+                         float *bmin, float *bmax, double *area_lbvh)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t gt = (n + TB - 1) / TB;
+    DevBuf<uint32_t> d_scene, d_pint, d_pleaf, d_flags, d_height;
+    DevBuf<uint2> d_topo;
+    DevBuf<float4> d_blo, d_bhi;
+    PT_HIP(ctx, d_scene.alloc(6));
+    PT_HIP(ctx, d_height.alloc(1));
+    const uint32_t ord_init[6] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u };
+    PT_HIP(ctx, hipMemcpyAsync(d_scene.p, ord_init, sizeof(ord_init), hipMemcpyHostToDevice, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));  // ord_init is a stack array
+    k_bounds<<<gt, TB, 0, st>>>(d_tlo, d_thi, n, d_scene.p);
+    if (n > 1) {
+        PT_HIP(ctx, d_topo.alloc(n));
+        PT_HIP(ctx, d_pint.alloc(n));
+        PT_HIP(ctx, d_pleaf.alloc(n));
+        PT_HIP(ctx, d_flags.alloc(n));
+        PT_HIP(ctx, d_blo.alloc(2 * (size_t)n));
+        PT_HIP(ctx, d_bhi.alloc(2 * (size_t)n));
+        PT_HIP(ctx, hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t) * (size_t)n, st));
+        k_nodes_links<<<(n - 1 + TB - 1) / TB, TB, 0, st>>>(nodes, (int)n, d_topo.p, d_pint.p, d_pleaf.p);
+        k_refit<<<gt, TB, 0, st>>>(d_tlo, d_thi, d_prim_of, (int)n, d_topo.p, d_pint.p, d_pleaf.p, d_blo.p, d_bhi.p, d_flags.p, d_scene.p,
+                                   nodes, d_height.p);
+    } else {
+        k_single<<<1, 1, 0, st>>>(d_tlo, d_thi, d_scene.p, nodes, d_height.p);
+    }
+    if (n > 2) {
+        const pt_status arc = ptb_tree_area(ctx, n, d_blo.p, d_bhi.p, area_lbvh);
+        if (arc != PT_OK) return arc;
+    }
+    uint32_t ord[6];
+    PT_HIP(ctx, hipMemcpyAsync(ord, d_scene.p, sizeof(ord), hipMemcpyDeviceToHost, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipGetLastError());
+    for (int k = 0; k < 3; k++) { bmin[k] = ord2f(ord[k]); bmax[k] = ord2f(ord[3 + k]); }
+    return PT_OK;
+}
 
 // the normalisation of the fp16 node formats: x' = (x - c) * rs with c the centre and 1/rs the half extent of the scene box
 void ptb_norm_box(const float *bmin, const float *bmax, float *c, float *sv, float *rs)

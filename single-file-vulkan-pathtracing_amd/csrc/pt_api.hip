@@ -220,6 +220,20 @@ pt_status pt_scene_set_bvh_quality(pt_scene *s, uint32_t quality)
     return guarded(s->ctx, [&] { return ptb_set_bvh_quality(s, quality); });
 }
 
+pt_status pt_scene_update(pt_scene *s, const float *vertices, uint32_t n_verts, const uint32_t *indices, uint32_t n_tris, uint32_t mode)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = s->ctx;
+    if (!vertices || !indices) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    if (mode > PT_SCENE_UPDATE_REBUILD) { ctx->err = "unknown update mode"; return PT_ERR_INVALID_ARG; }
+    if (n_tris == 0 || n_verts == 0) { ctx->err = "empty scene"; return PT_ERR_INVALID_ARG; }
+    if (n_tris != s->n_tris) { ctx->err = "an update keeps the scene's triangles (and their materials): n_tris must equal the scene's"; return PT_ERR_INVALID_ARG; }
+    for (size_t i = 0; i < 3 * (size_t)n_tris; i++)
+        if (indices[i] >= n_verts) { ctx->err = "vertex index out of range"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    return guarded(ctx, [&] { return ptb_update_scene(s, vertices, n_verts, indices, mode); });
+}
+
 pt_status pt_scene_get_info(const pt_scene *s, pt_scene_info *info)
 {
     if (!s || !info) return PT_ERR_INVALID_ARG;

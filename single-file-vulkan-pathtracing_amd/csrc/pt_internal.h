@@ -122,6 +122,7 @@ struct pt_scene {
     uint32_t n_lights = 0;
     float light_area = 0.f;
     std::vector<float4> h_lights;   // host copy of d_lights: instancing makes its world-space copies from it
+    std::vector<uint32_t> h_light_prim;  // the primitive of each emitter (pt_scene_update recomputes the records from new vertices)
     // instanced scenes: every instance's emitters in world space, gl_InstanceID-major, same 5-float4 layout and running cdf
     std::vector<float> h_xforms;    // the instance set's object->world matrices as given (gl_InstanceID order): ptb_ensure_inst_lights
     float4 *d_lights_inst = nullptr;  // built on the first NEE render of the instance set
@@ -204,6 +205,8 @@ constexpr uint64_t PT_SOURCE_BYTES_PER_TRI = 72;  // d_tri_orig + d_faces, kept 
 pt_status ptb_ensure_inst_frames(pt_scene *s);  // the table k_shade reads instead of transforming the normal per hit (instanced scenes)
 pt_status ptb_repair(pt_scene *s);        // no-op unless a rebuild of the tree products failed earlier: then one more try
 pt_status ptb_ensure_wide8(pt_scene *s);  // builds the 8-wide nodes of a scene that was created without them
+// pt_scene_update: new positions for the scene's triangles (mode PT_SCENE_UPDATE_REFIT / _REBUILD; arguments checked by the caller)
+pt_status ptb_update_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices, uint32_t mode);
 constexpr uint32_t PT_SAH_MAX_TRIS = 2048;
 // bvh4_sah_device.hip: surface-area sweep on the device (one workgroup) -> BVH4 rows (32 dwords each) + leaf order
 // pair_with_next (nullable): [n] flags, triangle i and i+1 are the two halves (v0,v1,v2),(v0,v2,v3) of a quad and form ONE primitive

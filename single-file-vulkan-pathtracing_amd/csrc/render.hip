@@ -842,7 +842,9 @@ uint32_t resolve_pipeline(pt_scene *s, const pt_params *p, const ExtendPlan &pl)
 pt_status ptw_prepare(pt_scene *s, pt_film *f, const pt_params *p_in)
 {
     pt_ctx *ctx = s->ctx;
-    pt_status rc_ = check_params(s, f, p_in);
+    pt_status rc_ = s->broken ? ptb_repair(s) : PT_OK;  // first: a repair may bring back the instance set a failed pt_scene_update parked
+    if (rc_ != PT_OK) return rc_;
+    rc_ = check_params(s, f, p_in);
     if (rc_ != PT_OK) return rc_;
     ExtendPlan pl;
     rc_ = ptw_plan_extend(s, p_in->extend, pl);
@@ -870,7 +872,9 @@ pt_status ptw_prepare(pt_scene *s, pt_film *f, const pt_params *p_in)
 
 pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p_in)
 {
-    pt_status rc_ = check_params(s, f, p_in);
+    pt_status rc_ = s->broken ? ptb_repair(s) : PT_OK;  // first: a repair may bring back the instance set a failed pt_scene_update parked
+    if (rc_ != PT_OK) return rc_;
+    rc_ = check_params(s, f, p_in);
     if (rc_ != PT_OK) return rc_;
     ExtendPlan pl;
     rc_ = ptw_plan_extend(s, p_in->extend, pl);

@@ -171,21 +171,40 @@ static pt_status build_tree_products_unguarded(pt_scene *s, uint32_t quality, bo
 // pt_scene_set_instances answer PT_ERR_UNSUPPORTED instead of launching kernels on null tables.  The triangles and materials
 // (d_tri_orig, d_faces) are untouched, so a later pt_scene_set_bvh_quality -- or the next render's request for the 8-wide
 // nodes -- can build again; success clears the mark.
+static void mark_broken(pt_scene *s, uint32_t quality)
+{
+    (void)hipGetLastError();  // an out-of-memory error is sticky until read
+    free_tree_products(s);
+    s->n_nodes = s->n_wide = s->n_wide_lbvh = 0;
+    s->stack_need = s->stack_need_lbvh = 0xFFFFFFFFu;
+    s->device_bytes = s->device_bytes8 = 0;
+    s->quality = quality;  // what the scene is meant to have: ptb_repair / the next pt_scene_set_bvh_quality build exactly that
+    s->broken = true;
+}
+
+// An instanced scene whose BLAS could not be built (pt_scene_update) keeps its instance set parked in h_xforms while n_inst = 0 and the
+// scene is broken.  Every successful build of the tree products ends here and sets the instances again; if that fails, the scene is
+// broken again with the set still parked, so no way out of the broken state drops the instances.
+static pt_status restore_parked_instances(pt_scene *s, uint32_t quality)
+{
+    if (s->n_inst || s->h_xforms.empty()) return PT_OK;
+    const std::vector<float> xf = s->h_xforms;
+    const pt_status rc = ptb_set_instances(s, xf.data(), (uint32_t)(xf.size() / 12));
+    if (rc != PT_OK) {
+        const std::string err = s->ctx->err;
+        mark_broken(s, quality);
+        s->h_xforms = xf;
+        s->ctx->err = err;
+    }
+    return rc;
+}
+
 static pt_status build_tree_products(pt_scene *s, uint32_t quality, bool want8)
 {
     const pt_status rc = build_tree_products_unguarded(s, quality, want8);
-    if (rc != PT_OK) {
-        (void)hipGetLastError();  // an out-of-memory error is sticky until read
-        free_tree_products(s);
-        s->n_nodes = s->n_wide = s->n_wide_lbvh = 0;
-        s->stack_need = s->stack_need_lbvh = 0xFFFFFFFFu;
-        s->device_bytes = s->device_bytes8 = 0;
-        s->quality = quality;  // what the scene is meant to have: ptb_repair / the next pt_scene_set_bvh_quality build exactly that
-        s->broken = true;
-    } else {
-        s->broken = false;
-    }
-    return rc;
+    if (rc != PT_OK) { mark_broken(s, quality); return rc; }
+    s->broken = false;
+    return restore_parked_instances(s, quality);
 }
 
 static pt_status build_tree_products_unguarded(pt_scene *s, uint32_t quality, bool want8)
@@ -260,11 +279,38 @@ pt_status ptb_ensure_wide8(pt_scene *s)
 pt_status ptb_repair(pt_scene *s)
 {
     if (!s->broken) return PT_OK;
-    if (s->n_inst) { s->ctx->err = PT_BROKEN_SCENE_MSG; return PT_ERR_UNSUPPORTED; }  // (cannot happen: rebuilds are refused on instanced scenes)
+    if (s->n_inst) { s->ctx->err = PT_BROKEN_SCENE_MSG; return PT_ERR_UNSUPPORTED; }  // (cannot happen: a broken scene has its instances parked)
     PT_HIP(s->ctx, hipStreamSynchronize(s->ctx->stream));
     const pt_status rc = build_tree_products(s, s->quality, s->ctx->tune.hbm8 != 0);
     if (rc != PT_OK) s->ctx->err = std::string(PT_BROKEN_SCENE_MSG) + " [" + s->ctx->err + "]";
     return rc;
+}
+
+// one emitter record of the NEE pipeline (pt_internal.h d_lights): normal as closesthit.rchit:43-48, area = |cross| / 2, cdf = the
+// running float sum of the areas in primitive order (this file is compiled with -ffp-contract=off on the host side too)
+static void push_emitter(const float *a, const float *b, const float *c, const float4 ke, float &run, std::vector<float4> &lights)
+{
+    const float e1[3] = { b[0] - a[0], b[1] - a[1], b[2] - a[2] }, e2[3] = { c[0] - a[0], c[1] - a[1], c[2] - a[2] };
+    const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+    const float len = sqrtf((cx * cx + cy * cy) + cz * cz);
+    run = run + 0.5f * len;
+    lights.push_back(make_float4(a[0], a[1], a[2], run));
+    lights.push_back(make_float4(b[0], b[1], b[2], 0.f));
+    lights.push_back(make_float4(c[0], c[1], c[2], 0.f));
+    lights.push_back(make_float4(-(cx / len), -(cy / len), -(cz / len), 0.f));
+    lights.push_back(ke);
+}
+
+// fan pairs as a loader emits them for quads: the next triangle starts at the same vertex and continues from this one's third
+// (bitwise equal coordinates); greedy, non-overlapping
+static void find_fan_pairs(const float *h_vertices, const uint32_t *h_indices, uint32_t n, std::vector<uint8_t> &pair)
+{
+    pair.assign(n, 0);
+    auto vtx = [&](uint32_t tri, int k) { return h_vertices + 3 * (size_t)h_indices[3 * (size_t)tri + k]; };
+    for (uint32_t i = 0; i + 1 < n; i++) {
+        const bool same = std::memcmp(vtx(i, 0), vtx(i + 1, 0), 12) == 0 && std::memcmp(vtx(i, 2), vtx(i + 1, 1), 12) == 0;
+        if (same) { pair[i] = 1; i++; }
+    }
 }
 
 pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices,
@@ -302,24 +348,17 @@ pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts
     // ... and scenes AUTO walks through them: more than 1 MiB of BVH4 nodes + records, ~96 B per triangle (extend_launch.hip ptw_plan_extend)
     pt_status rc = build_tree_products(s, PT_BVH_PREFER_FAST_TRACE, ctx->tune.hbm8 == 1 || n <= PT_SAH_MAX_TRIS || (ctx->tune.hbm8 != 0 && 96ull * n > (1ull << 20)));
     if (rc != PT_OK) return rc;
-    {   // emitters for the NEE pipeline: normal as closesthit.rchit:43-48, area = |cross| / 2, cdf = running float sum of the
-        // areas in primitive order (this file is compiled with -ffp-contract=off on the host side too)
+    {   // emitters for the NEE pipeline (push_emitter), and which primitives they are (pt_scene_update recomputes them)
         std::vector<float4> lights;
         float run = 0.f;
+        s->h_light_prim.clear();
         for (uint32_t t = 0; t < n; t++) {
             const float *f = h_faces + 6 * (size_t)t;
             if (!(f[3] != 0.f || f[4] != 0.f || f[5] != 0.f)) continue;
             const float *a = h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 0], *b = h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 1],
                         *c = h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 2];
-            const float e1[3] = { b[0] - a[0], b[1] - a[1], b[2] - a[2] }, e2[3] = { c[0] - a[0], c[1] - a[1], c[2] - a[2] };
-            const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-            const float len = sqrtf((cx * cx + cy * cy) + cz * cz);
-            run = run + 0.5f * len;
-            lights.push_back(make_float4(a[0], a[1], a[2], run));
-            lights.push_back(make_float4(b[0], b[1], b[2], 0.f));
-            lights.push_back(make_float4(c[0], c[1], c[2], 0.f));
-            lights.push_back(make_float4(-(cx / len), -(cy / len), -(cz / len), 0.f));
-            lights.push_back(make_float4(f[3], f[4], f[5], 0.f));
+            push_emitter(a, b, c, make_float4(f[3], f[4], f[5], 0.f), run, lights);
+            s->h_light_prim.push_back(t);
         }
         s->n_lights = (uint32_t)(lights.size() / 5);
         s->light_area = run;
@@ -341,14 +380,7 @@ pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts
             s->h_tlo[3 * i + 0] = lo[i].x; s->h_tlo[3 * i + 1] = lo[i].y; s->h_tlo[3 * i + 2] = lo[i].z;
             s->h_thi[3 * i + 0] = hi[i].x; s->h_thi[3 * i + 1] = hi[i].y; s->h_thi[3 * i + 2] = hi[i].z;
         }
-        // fan pairs as a loader emits them for quads: the next triangle starts at the same vertex and continues from
-        // this one's third (bitwise equal coordinates); greedy, non-overlapping
-        s->h_pair.assign(n, 0);
-        auto vtx = [&](uint32_t tri, int k) { return h_vertices + 3 * (size_t)h_indices[3 * (size_t)tri + k]; };
-        for (uint32_t i = 0; i + 1 < n; i++) {
-            const bool same = std::memcmp(vtx(i, 0), vtx(i + 1, 0), 12) == 0 && std::memcmp(vtx(i, 2), vtx(i + 1, 1), 12) == 0;
-            if (same) { s->h_pair[i] = 1; i++; }
-        }
+        find_fan_pairs(h_vertices, h_indices, n, s->h_pair);
         const float lbvh_ms = s->build_ms;
         PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
         const pt_status q = ptb_set_bvh_quality(s, PT_BVH_PREFER_FAST_TRACE);
@@ -372,6 +404,11 @@ pt_status ptb_set_bvh_quality(pt_scene *s, uint32_t quality)
         if (quality == s->quality && !s->broken) return PT_OK;
         PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return build_tree_products(s, quality, s->d_wide8 != nullptr);
+    }
+    if (s->broken) {  // a small scene that lost its tree in a failed pt_scene_update: the LBVH first (and any parked instances), then as asked
+        PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const pt_status rb = build_tree_products(s, quality, true);
+        if (rb != PT_OK) return rb;
     }
     const bool want_sah = quality == PT_BVH_PREFER_FAST_TRACE && s->n_tris <= PT_SAH_MAX_TRIS && s->d_tri_orig;
     if (want_sah == (s->bvh4_builder == 1u)) return PT_OK;
@@ -646,4 +683,145 @@ pt_status ptb_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n)
     s->n_tlas_wide = o.n_wide;
     s->tlas_height = std::max(o.height, o.height_tree);  // (of the tree the TLAS was collapsed from: the stack bound)
     return PT_OK;
+}
+
+// ---- pt_scene_update: new vertex positions (and indices) for the same triangles ----------------------------------------------
+// REFIT keeps the topology of every tree the scene holds and recomputes what depends on positions: the kept triangles, the binary
+// LBVH (k_refit), every wide tree in place (bvh_refit.hip), the fp16 copy of the traversed BVH4 on the new scene box, the per-triangle
+// tables in their leaf orders, the emitters, the small scenes' host boxes.  Traversal only needs conservative boxes and reports the
+// closest t / lowest primitive id, so images and hit records are those of a fresh scene; only the walk's cost drifts (pt_scene_info
+// .tree_area_lbvh shows it).  A fan pair whose shared vertices no longer coincide cannot stay one leaf (the pair test reads only the
+// second triangle's fourth vertex): the update is then a REBUILD, which builds the tree products afresh at the scene's quality.
+static pt_status refit_tree_products(pt_scene *s, const float4 *d_tlo, const float4 *d_thi)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = s->n_tris, gt = (n + TB - 1) / TB;
+    double area = s->area_lbvh;
+    pt_status rc = ptb_refit_lbvh(ctx, d_tlo, d_thi, s->d_prim_of, n, s->d_nodes, s->bmin, s->bmax, &area);
+    if (rc != PT_OK) return rc;
+    s->area_lbvh = area;
+    ptb_norm_box(s->bmin, s->bmax, s->norm_c, s->norm_s, s->norm_rs);
+    float scale = 0.f;  // leaf_pad() of the device build, same float operations
+    for (int k = 0; k < 3; k++) scale = fmaxf(scale, fmaxf(fabsf(s->bmin[k]), fabsf(s->bmax[k])));
+    const float pad = scale * 3.814697265625e-06f;
+    // leaf positions of the binary tree the collapses ran on: the PLOC tree's (builder 2), else the LBVH's
+    const uint32_t *kept = s->bvh4_builder == 2u ? s->d_prim_of_sah : s->d_prim_of;
+    rc = ptb_refit_wide(ctx, 0, s->d_wide_lbvh, s->n_wide_lbvh, d_tlo, d_thi, kept, n, pad, s->norm_c, s->norm_rs);
+    if (rc == PT_OK && s->d_wide_sah)
+        rc = ptb_refit_wide(ctx, 0, s->d_wide_sah, s->n_wide_sah, d_tlo, d_thi, s->d_prim_of_sah, n, pad, s->norm_c, s->norm_rs);
+    if (rc == PT_OK && s->d_wide16t)
+        rc = ptb_refit_wide(ctx, 1, s->d_wide16t, s->n_wide16t, d_tlo, d_thi, kept, n, pad, s->norm_c, s->norm_rs);
+    if (rc == PT_OK && s->d_wide8)
+        rc = ptb_refit_wide(ctx, 2, s->d_wide8, s->n_wide8, d_tlo, d_thi, s->d_prim_of8, n, pad, s->norm_c, s->norm_rs);
+    if (rc != PT_OK) return rc;
+    const uint32_t *order = s->bvh4_builder != 0u ? s->d_prim_of_sah : s->d_prim_of;  // the traversed leaf order
+    if (s->d_wide8)  // (d_shade4 is scratch here: the k_pack below writes it)
+        k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, s->d_prim_of8, n, s->d_tri4_8, s->d_shade4, s->d_shade64_8, s->d_ke4_8);
+    k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, order, n, s->d_tri4, s->d_shade4, s->d_shade64, s->d_ke4, s->d_frame4);
+    k_wide_half<<<(s->n_wide + TB - 1) / TB, TB, 0, st>>>(s->d_wide, s->n_wide, s->norm_c[0], s->norm_c[1], s->norm_c[2], s->norm_rs[0],
+                                                         s->norm_rs[1], s->norm_rs[2], reinterpret_cast<uint4 *>(s->d_wide16));
+    PT_HIP(ctx, hipGetLastError());
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+static void keep_host_boxes(pt_scene *s, const std::vector<float4> &lo, const std::vector<float4> &hi)
+{
+    const uint32_t n = s->n_tris;
+    s->h_tlo.resize(3 * (size_t)n);
+    s->h_thi.resize(3 * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        s->h_tlo[3 * i + 0] = lo[i].x; s->h_tlo[3 * i + 1] = lo[i].y; s->h_tlo[3 * i + 2] = lo[i].z;
+        s->h_thi[3 * i + 0] = hi[i].x; s->h_thi[3 * i + 1] = hi[i].y; s->h_thi[3 * i + 2] = hi[i].z;
+    }
+}
+
+static pt_status update_tree_products(pt_scene *s, const float4 *d_tlo, const float4 *d_thi, bool refit)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = s->n_tris;
+    const bool small = n <= PT_SAH_MAX_TRIS;
+    if (s->n_lights) PT_HIP(ctx, hipMemcpyAsync(s->d_lights, s->h_lights.data(), sizeof(float4) * s->h_lights.size(), hipMemcpyHostToDevice, st));
+    if (small) {  // the unpadded boxes a later surface-area build reads
+        std::vector<float4> lo(n), hi(n);
+        PT_HIP(ctx, hipMemcpyAsync(lo.data(), d_tlo, sizeof(float4) * n, hipMemcpyDeviceToHost, st));
+        PT_HIP(ctx, hipMemcpyAsync(hi.data(), d_thi, sizeof(float4) * n, hipMemcpyDeviceToHost, st));
+        PT_HIP(ctx, hipStreamSynchronize(st));
+        keep_host_boxes(s, lo, hi);
+    }
+    if (refit) {
+        const pt_status rc = refit_tree_products(s, d_tlo, d_thi);
+        if (rc != PT_OK) return rc;
+        PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+        PT_HIP(ctx, hipStreamSynchronize(st));
+        PT_HIP(ctx, hipEventElapsedTime(&s->build_ms, ctx->ev_a, ctx->ev_b));
+        return PT_OK;
+    }
+    // REBUILD (or a refit that cannot keep its pair leaves): what pt_scene_create builds, at the scene's quality
+    const uint32_t quality = s->quality;
+    const bool want8 = small || s->d_wide8 != nullptr || ctx->tune.hbm8 == 1;
+    pt_status rc = build_tree_products(s, small ? PT_BVH_PREFER_FAST_TRACE : quality, want8);
+    if (rc != PT_OK || !small) return rc;
+    const float lbvh_ms = s->build_ms;
+    float sah_ms = 0.f;
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    rc = ptb_set_bvh_quality(s, quality);
+    if (rc != PT_OK) return rc;
+    s->quality = quality;  // (FAST_BUILD: the LBVH just built is already the traversed tree)
+    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipEventElapsedTime(&sah_ms, ctx->ev_a, ctx->ev_b));
+    s->build_ms = lbvh_ms + sah_ms;
+    return PT_OK;
+}
+
+pt_status ptb_update_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices, uint32_t mode)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = s->n_tris, gt = (n + TB - 1) / TB;
+    const bool small = n <= PT_SAH_MAX_TRIS;
+    PT_HIP(ctx, hipStreamSynchronize(st));  // after whatever is queued on the scene (a PT_FLAG_ASYNC render included)
+    // host-side products first: until the triangles are overwritten below, a failure leaves the scene as it was
+    std::vector<float4> lights;
+    float run = 0.f;
+    for (size_t k = 0; k < s->h_light_prim.size(); k++) {
+        const uint32_t t = s->h_light_prim[k];
+        push_emitter(h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 0], h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 1],
+                     h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 2], s->h_lights[5 * k + 4], run, lights);
+    }
+    std::vector<uint8_t> pair;
+    if (small) find_fan_pairs(h_vertices, h_indices, n, pair);
+    bool pairs_hold = true;  // every pair leaf of the held trees is still a pair (a pair that newly forms changes no bits)
+    for (uint32_t i = 0; i < s->h_pair.size() && i < pair.size(); i++)
+        if (s->h_pair[i] && !pair[i]) pairs_hold = false;
+    const bool refit = mode == PT_SCENE_UPDATE_REFIT && !s->broken && (pairs_hold || !s->d_wide_sah || !s->sah_pair_leaves);
+    DevBuf<float> d_vert;
+    DevBuf<uint32_t> d_idx;
+    DevBuf<float4> d_tlo, d_thi;
+    PT_HIP(ctx, d_vert.alloc(3 * (size_t)n_verts));
+    PT_HIP(ctx, d_idx.alloc(3 * (size_t)n));
+    PT_HIP(ctx, d_tlo.alloc(n));
+    PT_HIP(ctx, d_thi.alloc(n));
+    PT_HIP(ctx, hipMemcpyAsync(d_vert.p, h_vertices, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, st));
+    PT_HIP(ctx, hipMemcpyAsync(d_idx.p, h_indices, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));  // pageable host sources are done with
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    // from here on the scene holds the new triangles: a failure marks it broken (the repair builds from them, never from a mix)
+    const uint32_t quality = s->quality;
+    const std::vector<float> xforms = s->h_xforms;  // the instance set -- or the one an earlier failed update parked (restore_parked_instances)
+    const uint32_t n_inst = (uint32_t)(xforms.size() / 12);
+    if (n_inst) ptb_free_instances(s);  // the TLAS, the instances' frames and emitters are made again from the new BLAS below
+    k_gather<<<gt, TB, 0, st>>>(d_vert.p, d_idx.p, n, s->d_tri_orig, d_tlo.p, d_thi.p);
+    // the fan-pair relation a later surface-area build reads: the new arrays' (a pair-leaf tree the refit keeps has only pairs that still hold)
+    if (small) s->h_pair = pair;
+    s->h_lights = lights;
+    s->light_area = run;
+    const pt_status rc = update_tree_products(s, d_tlo.p, d_thi.p, refit);
+    if (rc != PT_OK) mark_broken(s, quality);
+    if (n_inst) s->h_xforms = xforms;  // parked: set again below, or by the next successful build of the broken scene
+    if (rc != PT_OK) return rc;
+    return restore_parked_instances(s, quality);
 }
