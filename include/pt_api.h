@@ -200,7 +200,7 @@ pt_status pt_film_create(pt_ctx *ctx, uint32_t width, uint32_t height, pt_film *
  * a torch tensor's data_ptr(), so a collective can reduce it in place.                      */
 pt_status pt_film_create_external(pt_ctx *ctx, uint32_t width, uint32_t height,
                                   void *device_rgb_f32, pt_film **out);
-pt_status pt_film_clear(pt_film *film);
+pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov) */
 /* rgb: width*height*3 floats, row-major, linear radiance mean over all frames so far.       */
 pt_status pt_film_read_f32(pt_film *film, float *rgb);
 /* bgra: width*height*4 bytes = what main.cpp:661-667 copies to the swapchain.               */
@@ -289,6 +289,35 @@ pt_status pt_render(pt_scene *scene, pt_film *film, const pt_params *params);
  * (the pipeline / descriptor set-up of main.cpp:540-641 plays this role in the reference).
  * pt_get_stats afterwards reports the chosen frames_in_flight / sample_groups.              */
 pt_status pt_render_prepare(pt_scene *scene, pt_film *film, const pt_params *params);
+
+/* ---- guide buffers (AOVs): what a denoiser, a segmentation mask or a depth loss starts from ---------------
+ * Per pixel, of the FIRST hit of the camera rays pt_render traces for the same params: albedo (Kd, not Kd / pi), the
+ * shading normal of closesthit.rchit (never flipped towards the ray; instanced scenes: world space), emission (Ke),
+ * depth (the hit distance t), alpha (coverage) and the {primitive, instance} id.  A frame's value of a float channel
+ * is the sum over its spp_per_frame samples in sample order (a miss adds 0 to every channel: the values are
+ * premultiplied by coverage, a consumer divides by alpha for the surface's own value) divided by spp_per_frame, and it
+ * is blended into the plane like the film, new = (value + old * frame) / (frame + 1) -- binary32, no contraction.  The
+ * id plane is not averaged: sample 0's hit of the last frame rendered, 0xFFFFFFFF twice on a miss.                  */
+enum { PT_AOV_ALBEDO = 0, PT_AOV_NORMAL = 1, PT_AOV_EMISSION = 2,   /* width*height*3 f32 each */
+       PT_AOV_DEPTH = 3, PT_AOV_ALPHA = 4,                          /* width*height   f32 each */
+       PT_AOV_ID = 5,                                               /* width*height*2 u32      */
+       PT_AOV_COUNT = 6 };
+/* Gives the film its guide buffers (dense, row-major, zeroed).  device_planes: NULL, or PT_AOV_COUNT device
+ * pointers; a non-NULL entry is caller-owned memory of that plane's size (a torch tensor's data_ptr(), as in
+ * pt_film_create_external), a NULL entry is allocated and owned by the film.  Once per film: a second call is
+ * PT_ERR_INVALID_ARG.                                                                                        */
+pt_status pt_film_enable_aov(pt_film *film, void *const *device_planes);
+/* Renders the guides of frames [frame, frame + frame_count) for params.  Blocking.  Does not touch the radiance film
+ * or the rgba8 image; pt_render does not touch the guides.  max_depth, env, frames_in_flight and sample_groups are
+ * ignored.  params->pipeline: PT_PIPELINE_WAVEFRONT generates the camera rays into a queue, traces them with the
+ * closest-hit kernel params->extend names and reduces the hit records per pixel (every scene); PT_PIPELINE_FUSED is
+ * one persistent kernel for single-level scenes that live in LDS with tmin > 0 (PT_ERR_UNSUPPORTED elsewhere, and with
+ * a named extend kernel); PT_PIPELINE_AUTO takes the single kernel where it applies; PT_PIPELINE_WAVEFRONT_NEE is
+ * PT_ERR_UNSUPPORTED.  Same bits either way; pt_stats.pipeline says which ran.  PT_FLAG_NEE is ignored, any other flag
+ * is PT_ERR_UNSUPPORTED.  pt_stats.rays / .paths grow by one per sample.  PT_ERR_INVALID_ARG on a film without guides. */
+pt_status pt_render_aov(pt_scene *scene, pt_film *film, const pt_params *params);
+/* host_out: the plane's size (see the enum).  PT_ERR_INVALID_ARG for which >= PT_AOV_COUNT or a film without guides.  */
+pt_status pt_film_read_aov(pt_film *film, uint32_t which, void *host_out);
 
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {

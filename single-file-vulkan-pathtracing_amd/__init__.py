@@ -104,6 +104,10 @@ class HostScene(C.Structure):
 # include/pt_api.h pt_fused_block, in order
 FUSED_BLOCKS = ["ITER", "SHADE", "HIT", "MISS", "SURFACE", "ADD", "BOUNCE", "NEXT", "DONE", "HANDOUT", "DRAW", "TAKE", "CULLED", "PRIMARY", "SETUP",
                 "NODE", "POP", "LEAF", "DIV", "FINISH", "TRACE", "SPAWN", "PTARGET", "PDIR", "POPTOP"]
+# include/pt_api.h PT_AOV_*: the guide planes of pt_render_aov and their (trailing shape, dtype)
+AOV_ALBEDO, AOV_NORMAL, AOV_EMISSION, AOV_DEPTH, AOV_ALPHA, AOV_ID, AOV_COUNT = 0, 1, 2, 3, 4, 5, 6
+AOV_SHAPES = {AOV_ALBEDO: ((3,), np.float32), AOV_NORMAL: ((3,), np.float32), AOV_EMISSION: ((3,), np.float32),
+              AOV_DEPTH: ((), np.float32), AOV_ALPHA: ((), np.float32), AOV_ID: ((2,), np.uint32)}
 HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("inst", "<u4")])
 
 # every symbol include/pt_api.h and include/pt_host.h declare
@@ -111,7 +115,7 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_scene_set_instances", "pt_scene_set_bvh_quality", "pt_scene_update",
                "pt_scene_get_info", "pt_scene_read_bvh", "pt_scene_read_bvh4", "pt_scene_read_bvh8", "pt_film_create", "pt_film_create_external", "pt_film_clear",
                "pt_film_read_f32", "pt_film_read_bgra8", "pt_film_destroy", "pt_params_default", "pt_render",
-               "pt_render_prepare", "pt_trace",
+               "pt_render_prepare", "pt_trace", "pt_film_enable_aov", "pt_render_aov", "pt_film_read_aov",
                "pt_get_stats", "pt_reset_stats", "pt_get_block_counts",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_ranks", "pt_comm_destroy", "pt_film_present",
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
@@ -169,6 +173,10 @@ def lib_amd():
         L.pt_params_default.restype = None
         L.pt_render.argtypes = [vp, vp, C.POINTER(Params)]
         L.pt_render_prepare.argtypes = [vp, vp, C.POINTER(Params)]
+        if hasattr(L, "pt_render_aov"):   # (guide buffers; dev A/B runs load older builds through PT_LIB_AMD)
+            L.pt_film_enable_aov.argtypes = [vp, C.POINTER(vp)]
+            L.pt_render_aov.argtypes = [vp, vp, C.POINTER(Params)]
+            L.pt_film_read_aov.argtypes = [vp, C.c_uint32, vp]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -477,6 +485,25 @@ class Film:
         self.ctx._check(lib_amd().pt_film_read_bgra8(self.h, a.ctypes.data))
         return a
 
+    def enable_aov(self, device_planes=None):
+        """Gives the film its guide buffers (include/pt_api.h pt_film_enable_aov).  device_planes: None, or AOV_COUNT entries, each None
+        (the film allocates that plane) or a device pointer to caller-owned memory of the plane's size (a torch tensor's data_ptr())."""
+        arr = None
+        if device_planes is not None:
+            assert len(device_planes) == AOV_COUNT
+            arr = (C.c_void_p * AOV_COUNT)(*[C.c_void_p(p) if p else None for p in device_planes])
+        self.ctx._check(lib_amd().pt_film_enable_aov(self.h, arr))
+
+    def read_aov(self, which):
+        """-> the guide plane `which` (AOV_*): float32 [H, W, 3] / [H, W], uint32 [H, W, 2] {prim, inst} for AOV_ID."""
+        if which in AOV_SHAPES:
+            tail, dtype = AOV_SHAPES[which]
+            a = np.zeros((self.height, self.width) + tail, dtype=dtype)
+        else:
+            a = np.zeros((self.height, self.width, 3), dtype=np.float32)  # (the library refuses the index)
+        self.ctx._check(lib_amd().pt_film_read_aov(self.h, which, a.ctypes.data))
+        return a
+
     def close(self):
         if self.h:
             lib_amd().pt_film_destroy(self.h)
@@ -570,6 +597,12 @@ def render(scene, film, params):
     """pushConstants(frame) + traceRaysKHR(W,H,1) + waitIdle (main.cpp:656-659, 683), for
     params.frame_count consecutive frames."""
     scene.ctx._check(lib_amd().pt_render(scene.h, film.h, C.byref(params)))
+
+
+def render_aov(scene, film, params):
+    """The guide buffers (first-hit albedo, normal, emission, depth, alpha, id) of params' frames into a film that has them
+    (Film.enable_aov): include/pt_api.h pt_render_aov.  Blocking; the radiance film is not touched."""
+    scene.ctx._check(lib_amd().pt_render_aov(scene.h, film.h, C.byref(params)))
 
 
 def render_prepare(scene, film, params):

@@ -327,6 +327,8 @@ pt_status pt_film_clear(pt_film *f)
     pt_ctx *ctx = f->ctx;
     PT_HIP(ctx, hipMemsetAsync(f->d_rgb, 0, sizeof(float) * 3 * (size_t)f->w * f->h, ctx->stream));
     PT_HIP(ctx, hipMemsetAsync(f->d_bgra, 0, 4 * (size_t)f->w * f->h, ctx->stream));
+    const pt_status rc = pta_clear(f, ctx->stream);  // the guide buffers, if the film has them
+    if (rc != PT_OK) return rc;
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -353,6 +355,7 @@ void pt_film_destroy(pt_film *f)
 {
     if (!f) return;
     ptw_free_work(f);
+    pta_free(f);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
     delete f;
@@ -391,6 +394,32 @@ pt_status pt_render_prepare(pt_scene *s, pt_film *f, const pt_params *p)
     if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
     PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
     return guarded(s->ctx, [&] { return ptw_prepare(s, f, p); });
+}
+
+pt_status pt_film_enable_aov(pt_film *f, void *const *device_planes)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return guarded(f->ctx, [&] { return pta_enable(f, device_planes); });
+}
+
+pt_status pt_render_aov(pt_scene *s, pt_film *f, const pt_params *p)
+{
+    if (!s || !f || !p) return PT_ERR_INVALID_ARG;
+    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return pta_render(s, f, p); });
+}
+
+pt_status pt_film_read_aov(pt_film *f, uint32_t which, void *host_out)
+{
+    if (!f || !host_out) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (!f->aov.enabled) { ctx->err = "the film has no guide buffers: pt_film_enable_aov first"; return PT_ERR_INVALID_ARG; }
+    if (which >= PT_AOV_COUNT) { ctx->err = "unknown guide buffer"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(host_out, f->aov.plane[which], pta_plane_bytes(f, which), hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)

@@ -182,6 +182,23 @@ struct pt_film {
         void *d_sort = nullptr;                       // ray_sort.hip scratch for all pipelines (ptw_ray_sort_bytes per slot range)
         size_t sort_bytes = 0;
     } work;
+    // guide buffers (pt_film_enable_aov) and the scratch of pt_render_aov (aov.hip).  The scratch is the film's and only grows:
+    // a second call of the same shape allocates nothing (`allocs` counts the device allocations made for it).
+    struct Aov {
+        bool enabled = false;
+        void *plane[PT_AOV_COUNT] = {};               // dense, row-major: see the enum in include/pt_api.h
+        bool own[PT_AOV_COUNT] = {};
+        uint32_t rank = 0, world = 0, n_tiles = 0;    // the tile list below is this rank's, row by row
+        uint64_t valid_pixels = 0;                    // ... and the pixels of it inside the image
+        std::vector<uint64_t> h_valid;                // [n_tiles + 1] running count of those pixels over the tile list
+        uint32_t *d_tiles = nullptr;                  // tile x | tile y << 16
+        float4 *d_rayA = nullptr; float2 *d_rayB = nullptr;   // queue form: one chunk of camera rays in the extend kernels' layout,
+        float4 *d_hit = nullptr; uint32_t *d_hit_inst = nullptr;  // ... and their hit records
+        size_t cap_rays = 0;
+        uint32_t *d_count = nullptr;                  // [0] rays of the chunk (what the extend kernels read), [32] next tile of the single-kernel form
+        size_t bytes = 0;                             // device bytes of the scratch
+        uint64_t allocs = 0;
+    } aov;
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -219,3 +236,9 @@ pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p);
 pt_status ptw_prepare(pt_scene *s, pt_film *f, const pt_params *p);
 pt_status ptw_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits);
 void ptw_free_work(pt_film *f);
+// aov.hip: guide buffers of the first hit
+pt_status pta_enable(pt_film *f, void *const *device_planes);
+pt_status pta_render(pt_scene *s, pt_film *f, const pt_params *p);
+pt_status pta_clear(pt_film *f, hipStream_t st);   // zeroes the planes (queued on st; no-op without guides)
+size_t pta_plane_bytes(const pt_film *f, uint32_t which);
+void pta_free(pt_film *f);

@@ -887,6 +887,9 @@ pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p_in)
     return render_wavefront(s, f, p, pl, false);
 }
 
+// (aov.hip: the same proof for the guide buffers' single kernel)
+void ptw_subject_rect(const pt_scene *s, const pt_params *p, int32_t rect[4]) { subject_rect(s, p, rect); }
+
 pt_status ptw_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)
 {
     pt_ctx *ctx = s->ctx;

@@ -112,6 +112,8 @@ pt_status ptw_tiles_subject_first(pt_film *f, const int32_t rect[4], hipStream_t
 uint64_t ptw_workspace_bytes(const pt_film *f);
 ptw::RenderConst ptw_render_const(const pt_params *p, const pt_film::Work &w, const RenderShape &sh);
 uint64_t ptw_valid_local_pixels(const pt_film *f, const pt_params *p);
+// render.hip: the pixel rectangle {x0, y0, x1, y1} outside of which no camera ray can reach the scene's box (x1 < x0: no such proof)
+void ptw_subject_rect(const pt_scene *s, const pt_params *p, int32_t rect[4]);
 
 // ---- extend_hbm.hip / ray_sort.hip (launchers of the kernels compiled with the max-ILP scheduler; the ray sorter) --------
 const void *ptw_extend_hbm_fn(bool count, bool rec64);

@@ -5,7 +5,7 @@
 //
 //   pt_main [--obj assets/CornellBox-Original.obj] [--width 1024] [--height 1024]
 //           [--frames 1] [--spp 32] [--depth 8] [--device 0] [--batch N]
-//           [--ppm out.ppm] [--pfm out.pfm] [--pipeline auto|wavefront|fused|nee] [--nee]
+//           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--pipeline auto|wavefront|fused|nee] [--nee]
 //           [--ranks N [--devices 0,1,...] [--selftest]]
 // --ranks N renders with N GPUs: one host thread and one context per GPU, the 8x8 pixel tiles interleaved over the
 // ranks (pt_params.rank/world), and ONE RCCL gather of the packed tiles to rank 0 per presented image
@@ -13,6 +13,8 @@
 // carry its colour through the same collective and rank 0 checks that every tile arrived from its owner (and that RCCL connected N ranks).
 // --nee: the NEE estimator (PT_FLAG_NEE) on whatever --pipeline names -- `--pipeline auto --nee` runs the fused NEE kernel where the scene
 // lives in LDS; --pipeline nee is PT_PIPELINE_WAVEFRONT_NEE as before.
+// --aov PREFIX (one rank): after the render, the guide buffers of the same frames (pt_render_aov: what a denoiser takes beside the
+// radiance) as PREFIX_albedo.pfm, PREFIX_normal.pfm and PREFIX_depth.pfm (the depth in all three channels).
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -23,6 +25,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/pt_api.h"
@@ -36,7 +39,7 @@ namespace {
 }
 
 struct Options {
-    std::string obj = "assets/CornellBox-Original.obj", ppm, pfm;
+    std::string obj = "assets/CornellBox-Original.obj", ppm, pfm, aov;
     uint32_t width = 1024, height = 1024, frames = 1, spp = 32, depth = 8, batch = 0;
     int device = 0;
     uint32_t pipeline = PT_PIPELINE_AUTO;
@@ -153,6 +156,26 @@ void run_rank(const Options &o, const pth_scene &hs, uint32_t rank, const pt_uni
         const auto t1 = std::chrono::steady_clock::now();
         res.render_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
         if (ok) pt_get_stats(ctx, &res.st);
+        if (ok && !o.aov.empty()) {  // the guides of the same frames, through the existing PFM writer
+            pt_params g = p;
+            g.flags = 0;
+            if (g.pipeline == PT_PIPELINE_WAVEFRONT_NEE) g.pipeline = PT_PIPELINE_AUTO;  // (the guides do not depend on the estimator)
+            const size_t np = (size_t)o.width * o.height;
+            std::vector<float> plane(3 * np), depth(np);
+            const std::pair<uint32_t, const char *> rgb_planes[2] = { { PT_AOV_ALBEDO, "_albedo.pfm" }, { PT_AOV_NORMAL, "_normal.pfm" } };
+            if (pt_film_enable_aov(film, nullptr) != PT_OK) { fail("pt_film_enable_aov"); ok = false; }
+            else if (pt_render_aov(scene, film, &g) != PT_OK) { fail("pt_render_aov"); ok = false; }
+            for (const auto &[which, suffix] : rgb_planes) {
+                if (!ok) break;
+                if (pt_film_read_aov(film, which, plane.data()) != PT_OK) { fail("pt_film_read_aov"); ok = false; }
+                else if (pth_write_pfm((o.aov + suffix).c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + o.aov + suffix; ok = false; }
+            }
+            if (ok && pt_film_read_aov(film, PT_AOV_DEPTH, depth.data()) != PT_OK) { fail("pt_film_read_aov"); ok = false; }
+            if (ok) {
+                for (size_t i = 0; i < np; i++) plane[3 * i] = plane[3 * i + 1] = plane[3 * i + 2] = depth[i];
+                if (pth_write_pfm((o.aov + "_depth.pfm").c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + o.aov + "_depth.pfm"; ok = false; }
+            }
+        }
         // the presented image lives in its own device buffer on rank 0 (main.cpp:661-667 copies the storage image)
         if (ok && o.ranks > 1 && rank == 0 && pt_device_alloc(ctx, sizeof(float) * 3 * (size_t)o.width * o.height, (void **)&d_image) != PT_OK) { fail("pt_device_alloc"); ok = false; }
         if (!peers_ok(ok)) { if (ok) res.error = peer_msg; break; }
@@ -220,11 +243,13 @@ int main(int argc, char **argv)
         else if (a == "--nee") o.nee = true;
         else if (a == "--ppm") o.ppm = val();
         else if (a == "--pfm") o.pfm = val();
+        else if (a == "--aov") o.aov = val();
         else die("unknown option " + a);
     }
     if (o.ranks > 1) {
         if (o.devices.empty()) for (uint32_t r = 0; r < o.ranks; r++) o.devices.push_back((int)r);
         if (o.devices.size() != o.ranks) die("--devices needs one ordinal per rank");
+        if (!o.aov.empty()) die("--aov writes the guide buffers of one rank (no --ranks)");
     }
 
     char err[512] = { 0 };

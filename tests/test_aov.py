@@ -1,0 +1,451 @@
+"""pt_render_aov: the guide buffers of the first hit (albedo, normal, emission, depth, alpha, id), include/pt_api.h.
+
+The expected planes come from ONE helper, `_guides`, which restates the definition with the oracle's bindings only: `orc.seed` and
+`orc.primary_ray` per sample, `Scene.trace` on the batch, `Scene.shade_hit` for the normals, float32 numpy adds in sample order,
+`orc.accumulate_f32` for the three-channel planes and the same formula in float32 numpy for the one-channel ones.  The CPU tests pin that
+helper to the oracle's own pixel loop (`render_frame` with max_depth = 1, env = 0 and Ke := the quantity in question) and check that
+every image the GPU tests use has fully covered, empty AND partially covered pixels.  Every comparison is `tobytes()` equality."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+MISS = 0xFFFFFFFF
+NAMES = ["albedo", "normal", "emission", "depth", "alpha", "id"]
+
+
+def _soup(n, seed, spread=0.1):
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(-1, 1, (n, 1, 3)).astype(np.float32)
+    v = (c + rng.uniform(-spread, spread, (n, 3, 3)).astype(np.float32)).astype(np.float32)
+    faces = rng.uniform(0, 1, (n, 6)).astype(np.float32)
+    faces[:, 3:] *= (rng.uniform(0, 1, (n, 1)) < 0.1)
+    return v.reshape(-1), np.arange(3 * n, dtype=np.uint32), faces.reshape(-1).astype(np.float32)
+
+
+def _one_instance():
+    """a single instance: rotated about z, scaled unevenly, moved -- the normal needs the inverse transpose"""
+    c, s = np.float32(np.cos(0.5)), np.float32(np.sin(0.5))
+    return np.array([[[0.9 * c, -0.7 * s, 0.0, 0.15], [0.9 * s, 0.7 * c, 0.0, -0.4], [0.0, 0.0, 1.1, 0.1]]], np.float32)
+
+
+# The 16-instance grid is a strip of 0.32 x 0.02 in the z = 0 plane.  The camera tests/test_fused_nee.py looks at it with sees a square of
+# side 2 around it (raygen.rgen:56 adds the screen position to the target, whatever the distance), in which the strip covers 0.4 % of a
+# 48 x 40 image and no pixel fully.  So: same side of the plane, target pushed far behind it -- a square of side 0.05 around three of
+# the instances (oracle alone, frame 0: 31 % / 64 % / 5.7 % of the pixels at alpha 1 / 0 / between).
+GRID_CAM = dict(cam_origin=(-0.84, -1.99, 0.5), cam_target=(-0.84, -1.99, -19.5))
+SOUP_CAM = dict(cam_origin=(0.0, 0.0, 4.5), cam_target=(0.0, 0.0, 1.5))           # (the default camera: 22 % / 64 % / 14 %)
+# name -> (scene, width, height, spp, camera).  Every image a GPU test renders is one of these; test_fixtures_have_partial_coverage
+# asserts the coverage condition on each.
+CASES = {
+    "cornell": ("cornell", 48, 40, 4, {}),
+    "cornell_wide": ("cornell", 96, 56, 8, {}),
+    "cornell_odd": ("cornell", 52, 36, 4, {}),          # width and height no multiples of 8
+    "grid16": ("grid16", 48, 40, 4, GRID_CAM),
+    "one_inst": ("one_inst", 48, 40, 4, {}),
+    "soup": ("soup", 48, 40, 4, SOUP_CAM),
+    "cornell_moved": ("cornell_moved", 48, 40, 4, {}),  # what Scene.update turns the Cornell box into
+}
+_cache = {}
+
+
+def _arrays(pt, scene):
+    """-> (vertices, indices, faces, instances or None)"""
+    if scene == "soup":
+        return _soup(3000, 5) + (None,)
+    v, i, f = pt.load_obj(pt.ASSET_CORNELL)
+    if scene == "cornell_moved":
+        v = (np.asarray(v, np.float32).reshape(-1, 3) * np.float32([0.8, 1.0, 0.9]) + np.float32([0.1, -0.05, 0.0])).astype(np.float32).reshape(-1)
+    inst = pt.cornell_grid_instances()[:16] if scene == "grid16" else _one_instance() if scene == "one_inst" else None
+    return v, i, f, inst
+
+
+def _oracle_scene(pt, orc, scene, faces=None):
+    v, i, f, inst = _arrays(pt, scene)
+    osc = orc.Scene(v, i, f if faces is None else faces)
+    if inst is not None:
+        osc.set_instances(inst)
+    return osc
+
+
+def _guides(pt, orc, case, frames):
+    """The definition, with the oracle's bindings: the six planes after `frames` (ascending frame indices, blended one after the
+    other into zeroed planes) -> {name: array}."""
+    key = (case, tuple(frames))
+    if key in _cache:
+        return _cache[key]
+    scene, w, h, spp, cam = CASES[case]
+    faces = np.asarray(_arrays(pt, scene)[2], np.float32).reshape(-1, 6)
+    osc = _oracle_scene(pt, orc, scene)
+    out = {"albedo": np.zeros((h, w, 3), np.float32), "normal": np.zeros((h, w, 3), np.float32), "emission": np.zeros((h, w, 3), np.float32),
+           "depth": np.zeros((h, w), np.float32), "alpha": np.zeros((h, w), np.float32), "id": np.zeros((h, w, 2), np.uint32)}
+    normals = {}
+    for F in frames:
+        p = orc.default_params(frame=F, width=w, height=h, spp_per_frame=spp, **cam)
+        rays = np.zeros((h, w, spp, 6), np.float32)
+        for y in range(h):
+            for x in range(w):
+                for s in range(spp):
+                    o, d, _ = orc.primary_ray(p, x, y, orc.seed(x, y, s, F, spp))
+                    rays[y, x, s, :3] = o
+                    rays[y, x, s, 3:] = d
+        hits, _ = osc.trace(rays.reshape(-1, 6), p.tmin, p.tmax)
+        hits = hits.reshape(h, w, spp)
+        val = np.zeros((h, w, spp, 11), np.float32)   # albedo 0:3, normal 3:6, emission 6:9, depth 9, alpha 10 -- all 0 on a miss
+        for y, x, s in zip(*np.nonzero(hits["prim"] != MISS)):
+            hit = hits[y, x, s]
+            k = (int(hit["inst"]), int(hit["prim"]))
+            if k not in normals:
+                normals[k] = osc.shade_hit(hit)[1]    # depends on (instance, primitive) only
+            val[y, x, s, 0:3] = faces[k[1], 0:3]
+            val[y, x, s, 3:6] = normals[k]
+            val[y, x, s, 6:9] = faces[k[1], 3:6]
+            val[y, x, s, 9] = hit["t"]
+            val[y, x, s, 10] = np.float32(1.0)
+        acc = np.zeros((h, w, 11), np.float32)
+        for s in range(spp):
+            acc = acc + val[:, :, s]                  # float32, sample order
+        value = acc / np.float32(spp)
+        for name, sl in (("albedo", slice(0, 3)), ("normal", slice(3, 6)), ("emission", slice(6, 9))):
+            orc.accumulate_f32(out[name], np.ascontiguousarray(value[:, :, sl]), F)
+        for name, c in (("depth", 9), ("alpha", 10)):
+            out[name] = value[:, :, c] if F == 0 else (value[:, :, c] + out[name] * np.float32(F)) / np.float32(F + 1)
+            assert out[name].dtype == np.float32
+        out["id"][:, :, 0] = hits["prim"][:, :, 0]
+        out["id"][:, :, 1] = np.where(hits["prim"][:, :, 0] == MISS, MISS, hits["inst"][:, :, 0])
+    _cache[key] = out
+    return out
+
+
+def _n_rays(case, n_frames, mask=None):
+    _, w, h, spp, _ = CASES[case]
+    return (w * h if mask is None else int(mask.sum())) * spp * n_frames
+
+
+# ---- without a GPU --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("frame", [0, 3])
+def test_helper_equals_the_oracles_pixel_loop(pt, orc, frame):
+    """albedo / emission of the helper == the oracle's render_frame at max_depth = 1, env = 0 with Ke := Kd / Ke unchanged (weight * Ke is
+    1.0f * Ke there: the same sum); its ray count is width * height * spp; the helper's ids are its first_hits."""
+    scene, w, h, spp, cam = CASES["cornell"]
+    g = _guides(pt, orc, "cornell", [frame])
+    faces = np.asarray(_arrays(pt, scene)[2], np.float32).reshape(-1, 6)
+    as_ke = faces.copy()
+    as_ke[:, 3:6] = faces[:, 0:3]
+    p = orc.default_params(frame=frame, width=w, height=h, spp_per_frame=spp, max_depth=1, env=(0.0, 0.0, 0.0), **cam)
+    for name, ff in (("albedo", as_ke), ("emission", faces)):
+        img, rays, _, fh = _oracle_scene(pt, orc, scene, ff.reshape(-1)).render_frame(p, want_first_hits=True)
+        film = np.zeros_like(img)
+        orc.accumulate_f32(film, img, frame)
+        assert rays == w * h * spp
+        assert g[name].tobytes() == film.tobytes(), name
+        fh = fh.reshape(h, w)
+        assert g["id"][:, :, 0].tobytes() == np.ascontiguousarray(fh["prim"]).tobytes()
+        hit = fh["prim"] != MISS
+        assert (g["id"][:, :, 1][hit] == fh["inst"][hit]).all() and (g["id"][:, :, 1][~hit] == MISS).all()
+    assert g["albedo"].any() and g["emission"].any() and g["normal"].any() and g["depth"].any()
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_fixtures_have_partial_coverage(pt, orc, case):
+    """Every image the GPU tests render: >= 25 % of the pixels fully covered, >= 5 % empty, >= 1 % strictly between (where
+    premultiplication and the order of the adds matter) -- by the oracle alone."""
+    a = _guides(pt, orc, case, [0])["alpha"]
+    full, empty, part = float((a == 1).mean()), float((a == 0).mean()), float(((a > 0) & (a < 1)).mean())
+    print(f"{case}: alpha 1 / 0 / between = {full:.3f} / {empty:.3f} / {part:.3f}")
+    assert full >= 0.25 and empty >= 0.05 and part >= 0.01, (case, full, empty, part)
+
+
+# ---- on the GPU -----------------------------------------------------------------------------------------------------------------
+def _gpu_scene(pt, ctx, scene):
+    v, i, f, inst = _arrays(pt, scene)
+    sc = pt.Scene(ctx, v, i, f)
+    if inst is not None:
+        sc.set_instances(inst)
+    return sc
+
+
+def _params(pt, case, **kw):
+    _, w, h, spp, cam = CASES[case]
+    return pt.default_params(width=w, height=h, spp_per_frame=spp, **cam, **kw)
+
+
+def _read(film, pt):
+    return {n: film.read_aov(k) for k, n in enumerate(NAMES)}
+
+
+def _same(got, want, what=""):
+    for n in NAMES:
+        assert got[n].dtype == want[n].dtype and got[n].shape == want[n].shape, (what, n)
+        assert got[n].tobytes() == want[n].tobytes(), (what, n, int((got[n] != want[n]).sum()))
+
+
+def _run(pt, ctx, sc, case, calls, **kw):
+    """calls: [(first frame, frame count)] into one fresh film -> (planes, stats of all calls)"""
+    _, w, h, _, _ = CASES[case]
+    film = pt.Film(ctx, w, h)
+    film.enable_aov()
+    ctx.reset_stats()
+    for f0, n in calls:
+        pt.render_aov(sc, film, _params(pt, case, frame=f0, frame_count=n, **kw))
+    out = _read(film, pt), ctx.stats()
+    film.close()
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", ["WAVEFRONT", "FUSED", "AUTO"])
+def test_aov_cornell(pt, orc, gpu_ctx, cornell_gpu, pipeline):
+    """One call of three frames from frame 0, and three calls of one frame each from frame 5, through every pipeline value."""
+    pl = getattr(pt, "PIPELINE_" + pipeline)
+    ran = pt.PIPELINE_WAVEFRONT if pipeline == "WAVEFRONT" else pt.PIPELINE_FUSED
+    got, st = _run(pt, gpu_ctx, cornell_gpu, "cornell", [(0, 3)], pipeline=pl)
+    assert st.pipeline == ran and st.rays == _n_rays("cornell", 3) and st.paths == st.rays
+    assert (st.rays_culled > 0) == (ran == pt.PIPELINE_FUSED) and st.rays_culled % CASES["cornell"][3] == 0   # whole pixels, counted as the rays they are
+    _same(got, _guides(pt, orc, "cornell", [0, 1, 2]), pipeline)
+    got, st = _run(pt, gpu_ctx, cornell_gpu, "cornell", [(5, 1), (6, 1), (7, 1)], pipeline=pl)
+    assert st.pipeline == ran and st.rays == _n_rays("cornell", 3)
+    _same(got, _guides(pt, orc, "cornell", [5, 6, 7]), pipeline)
+    # the per-triangle leaf loop (pt_tuning.pair_kernel = 0: k_extend_lds7's walk instead of the pair-leaf one), and every camera ray
+    # walked (pt_tuning.cull = 0: the single kernel otherwise finishes the pixels that cannot see the scene's box without a walk)
+    for knob in ("pair_kernel", "cull"):
+        old = gpu_ctx.set_tuning(**{knob: 0})
+        try:
+            got, st = _run(pt, gpu_ctx, cornell_gpu, "cornell", [(0, 3)], pipeline=pl)
+        finally:
+            gpu_ctx.set_tuning(**old)
+        assert st.pipeline == ran and st.rays == _n_rays("cornell", 3)
+        assert knob != "cull" or st.rays_culled == 0
+        _same(got, _guides(pt, orc, "cornell", [0, 1, 2]), f"{pipeline} with {knob} = 0")
+    # PT_FLAG_NEE names an estimator, which the guides do not depend on: ignored
+    got, st = _run(pt, gpu_ctx, cornell_gpu, "cornell", [(0, 3)], pipeline=pl, flags=pt.FLAG_NEE)
+    assert st.pipeline == ran
+    _same(got, _guides(pt, orc, "cornell", [0, 1, 2]), pipeline + " | NEE")
+
+
+@pytest.mark.gpu
+def test_aov_fused_class_rules(pt, orc, gpu_ctx, cornell_gpu):
+    """A named closest-hit kernel and tmin <= 0 take the queue form under AUTO and are refused by FUSED, as in pt_render."""
+    want = _guides(pt, orc, "cornell", [0, 1])
+    got, st = _run(pt, gpu_ctx, cornell_gpu, "cornell", [(0, 2)], pipeline=pt.PIPELINE_AUTO, extend=pt.EXTEND_LDS)
+    assert st.pipeline == pt.PIPELINE_WAVEFRONT
+    _same(got, want, "AUTO + EXTEND_LDS")
+    got, st = _run(pt, gpu_ctx, cornell_gpu, "cornell", [(0, 2)], pipeline=pt.PIPELINE_WAVEFRONT, extend=pt.EXTEND_HBM)
+    _same(got, want, "EXTEND_HBM")
+    for kw in (dict(extend=pt.EXTEND_LDS), dict(tmin=0.0)):
+        with pytest.raises(pt.PtError) as e:
+            _run(pt, gpu_ctx, cornell_gpu, "cornell", [(0, 1)], pipeline=pt.PIPELINE_FUSED, **kw)
+        assert e.value.status == 5
+    _, st = _run(pt, gpu_ctx, cornell_gpu, "cornell", [(0, 1)], pipeline=pt.PIPELINE_AUTO, tmin=0.0)
+    assert st.pipeline == pt.PIPELINE_WAVEFRONT and st.rays == _n_rays("cornell", 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["grid16", "one_inst"])
+def test_aov_instanced(pt, orc, gpu_ctx, case):
+    """16 instances of the Cornell grid and a one-instance scene: AUTO is the queue form, FUSED is refused; with the (instance,
+    triangle) normal table of pt_tuning.inst_frames and without it."""
+    sc = _gpu_scene(pt, gpu_ctx, CASES[case][0])
+    want = _guides(pt, orc, case, [0, 1])
+    try:
+        for frames_knob in (0, -1):
+            old = gpu_ctx.set_tuning(inst_frames=frames_knob)
+            try:
+                got, st = _run(pt, gpu_ctx, sc, case, [(0, 2)], pipeline=pt.PIPELINE_AUTO)
+            finally:
+                gpu_ctx.set_tuning(**old)
+            assert st.pipeline == pt.PIPELINE_WAVEFRONT and st.rays == _n_rays(case, 2)
+            _same(got, want, f"{case} inst_frames={frames_knob}")
+        with pytest.raises(pt.PtError) as e:
+            _run(pt, gpu_ctx, sc, case, [(0, 1)], pipeline=pt.PIPELINE_FUSED)
+        assert e.value.status == 5
+    finally:
+        sc.close()
+
+
+@pytest.mark.gpu
+def test_aov_soup_through_every_closest_hit_kernel(pt, orc, gpu_ctx):
+    sc = _gpu_scene(pt, gpu_ctx, "soup")
+    want = _guides(pt, orc, "soup", [0, 1])
+    try:
+        for ext in ("EXTEND_AUTO", "EXTEND_HBM", "EXTEND_HBM8"):
+            got, st = _run(pt, gpu_ctx, sc, "soup", [(0, 2)], pipeline=pt.PIPELINE_AUTO, extend=getattr(pt, ext))
+            assert st.pipeline == pt.PIPELINE_WAVEFRONT and st.rays == _n_rays("soup", 2)
+            _same(got, want, ext)
+        with pytest.raises(pt.PtError) as e:
+            _run(pt, gpu_ctx, sc, "soup", [(0, 1)], pipeline=pt.PIPELINE_FUSED)
+        assert e.value.status == 5
+    finally:
+        sc.close()
+
+
+@pytest.mark.gpu
+def test_aov_chunks_and_odd_sizes(pt, orc, cornell_arrays):
+    """mem_budget_mb = 1 leaves the queue form 46 tiles of 64 x 8 rays per chunk: the 84 tiles of the 96 x 56 image run as one full and
+    one partial chunk.  52 x 36 has cut tiles in its last column and row."""
+    ctx = pt.Context(0)
+    ctx.set_tuning(mem_budget_mb=1)
+    sc = pt.Scene(ctx, *cornell_arrays)
+    try:
+        got, st = _run(pt, ctx, sc, "cornell_wide", [(0, 2)], pipeline=pt.PIPELINE_WAVEFRONT)
+        assert st.rays == _n_rays("cornell_wide", 2)
+        assert st.launches_extend == 4, st.launches_extend   # two chunks per frame
+        _same(got, _guides(pt, orc, "cornell_wide", [0, 1]), "chunks")
+        for pipeline in (pt.PIPELINE_WAVEFRONT, pt.PIPELINE_FUSED):
+            got, st = _run(pt, ctx, sc, "cornell_odd", [(0, 2)], pipeline=pipeline)
+            assert st.rays == _n_rays("cornell_odd", 2)
+            _same(got, _guides(pt, orc, "cornell_odd", [0, 1]), f"odd {pipeline}")
+    finally:
+        sc.close()
+        ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", ["WAVEFRONT", "FUSED"])
+def test_aov_every_rank_of_world_3(pt, orc, gpu_ctx, cornell_gpu, pipeline):
+    from importlib import import_module
+    dist = import_module("single-file-vulkan-pathtracing_amd.distributed")
+    _, w, h, _, _ = CASES["cornell_odd"]
+    want = _guides(pt, orc, "cornell_odd", [0, 1])
+    total = {n: np.zeros_like(want[n]) for n in NAMES}
+    rays = 0
+    for rank in range(3):
+        mask = dist.owned_mask(w, h, rank, 3)
+        got, st = _run(pt, gpu_ctx, cornell_gpu, "cornell_odd", [(0, 2)], pipeline=getattr(pt, "PIPELINE_" + pipeline), rank=rank, world=3)
+        assert st.rays == _n_rays("cornell_odd", 2, mask)
+        rays += st.rays
+        for n in NAMES:
+            assert not got[n][~mask].any(), (rank, n)               # pixels of other ranks are not written
+            assert got[n][mask].tobytes() == want[n][mask].tobytes(), (rank, n)
+            total[n] += got[n]
+    assert rays == _n_rays("cornell_odd", 2)
+    _same(total, want, "sum over the ranks")
+
+
+@pytest.mark.gpu
+def test_aov_external_planes(pt, orc, gpu_ctx, cornell_gpu):
+    """Two planes in caller memory, the rest owned by the film: read through read_aov and through the caller's buffers."""
+    _, w, h, _, _ = CASES["cornell"]
+    want = _guides(pt, orc, "cornell", [0, 1])
+    normal = pt.DeviceBuffer(gpu_ctx, w * h * 3 * 4)
+    ids = pt.DeviceBuffer(gpu_ctx, w * h * 2 * 4)
+    junk = np.full(w * h * 3, 7.0, np.float32)
+    normal.write(junk)
+    film = pt.Film(gpu_ctx, w, h)
+    planes = [None] * pt.AOV_COUNT
+    planes[pt.AOV_NORMAL], planes[pt.AOV_ID] = normal.ptr, ids.ptr
+    film.enable_aov(planes)
+    assert not normal.read(np.float32, (h, w, 3)).any()                 # zeroed by enable_aov
+    pt.render_aov(cornell_gpu, film, _params(pt, "cornell", frame=0, frame_count=2, pipeline=pt.PIPELINE_AUTO))
+    _same(_read(film, pt), want, "read_aov")
+    assert normal.read(np.float32, (h, w, 3)).tobytes() == want["normal"].tobytes()
+    assert ids.read(np.uint32, (h, w, 2)).tobytes() == want["id"].tobytes()
+    film.close()                                                        # frees the film's planes, not the caller's
+    assert normal.read(np.float32, (h, w, 3)).tobytes() == want["normal"].tobytes()
+    normal.close()
+    ids.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", ["WAVEFRONT", "AUTO"])
+def test_aov_is_independent_of_render(pt, orc, gpu_ctx, cornell_gpu, pipeline):
+    """render, render_aov, render leaves film, rgba8 image and guides as each kind alone does; Film.clear zeroes the guides."""
+    _, w, h, spp, _ = CASES["cornell"]
+    pl = getattr(pt, "PIPELINE_" + pipeline)
+    kw = dict(width=w, height=h, spp_per_frame=spp, max_depth=4, pipeline=pl)
+    alone = pt.Film(gpu_ctx, w, h)
+    pt.render(cornell_gpu, alone, pt.default_params(frame=0, frame_count=1, **kw))
+    pt.render(cornell_gpu, alone, pt.default_params(frame=1, frame_count=1, **kw))
+    film = pt.Film(gpu_ctx, w, h)
+    film.enable_aov()
+    pt.render(cornell_gpu, film, pt.default_params(frame=0, frame_count=1, **kw))
+    pt.render_aov(cornell_gpu, film, _params(pt, "cornell", frame=0, frame_count=2, pipeline=pl))
+    pt.render(cornell_gpu, film, pt.default_params(frame=1, frame_count=1, **kw))
+    assert film.read_f32().tobytes() == alone.read_f32().tobytes() and film.read_bgra8().tobytes() == alone.read_bgra8().tobytes()
+    _same(_read(film, pt), _guides(pt, orc, "cornell", [0, 1]), "guides after render")
+    film.clear()
+    for n, a in _read(film, pt).items():
+        assert not a.any(), n
+    assert not film.read_f32().any()
+    pt.render_aov(cornell_gpu, film, _params(pt, "cornell", frame=0, frame_count=2, pipeline=pl))
+    _same(_read(film, pt), _guides(pt, orc, "cornell", [0, 1]), "guides after clear")
+    film.close()
+    alone.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", ["WAVEFRONT", "AUTO"])
+def test_aov_after_scene_update(pt, orc, gpu_ctx, cornell_arrays, pipeline):
+    """After Scene.update (refit) the guides are those of the new vertex array."""
+    sc = pt.Scene(gpu_ctx, *cornell_arrays)
+    try:
+        pl = getattr(pt, "PIPELINE_" + pipeline)
+        got, _ = _run(pt, gpu_ctx, sc, "cornell", [(0, 1)], pipeline=pl)
+        _same(got, _guides(pt, orc, "cornell", [0]), "before")
+        v, i, _, _ = _arrays(pt, "cornell_moved")
+        sc.update(v, i, pt.SCENE_UPDATE_REFIT)
+        got, st = _run(pt, gpu_ctx, sc, "cornell_moved", [(0, 2)], pipeline=pl)
+        assert st.rays == _n_rays("cornell_moved", 2)
+        _same(got, _guides(pt, orc, "cornell_moved", [0, 1]), "after the refit")
+    finally:
+        sc.close()
+
+
+@pytest.mark.gpu
+def test_aov_refusals(pt, orc, gpu_ctx, cornell_gpu):
+    _, w, h, _, _ = CASES["cornell"]
+    film = pt.Film(gpu_ctx, w, h)
+    p = _params(pt, "cornell", frame=0, frame_count=1, pipeline=pt.PIPELINE_AUTO)
+
+    def status(fn):
+        with pytest.raises(pt.PtError) as e:
+            fn()
+        return e.value.status
+
+    assert status(lambda: pt.render_aov(cornell_gpu, film, p)) == 1           # no guides enabled
+    assert status(lambda: film.read_aov(pt.AOV_DEPTH)) == 1
+    film.enable_aov()
+    assert status(lambda: film.enable_aov()) == 1                             # once per film
+    assert status(lambda: film.read_aov(pt.AOV_COUNT)) == 1
+    for flags in (pt.FLAG_ASYNC, pt.FLAG_COUNT_VISITS, pt.FLAG_NEE | pt.FLAG_ASYNC):
+        assert status(lambda: pt.render_aov(cornell_gpu, film, _params(pt, "cornell", frame=0, frame_count=1, pipeline=pt.PIPELINE_AUTO, flags=flags))) == 5
+    assert status(lambda: pt.render_aov(cornell_gpu, film, _params(pt, "cornell", frame=0, frame_count=1, pipeline=pt.PIPELINE_WAVEFRONT_NEE))) == 5
+    assert status(lambda: pt.render_aov(cornell_gpu, film, pt.default_params(width=w + 8, height=h, frame=0, frame_count=1))) == 1
+    for n, a in _read(film, pt).items():
+        assert not a.any(), n                                                 # a refused call writes nothing
+    # the film renders correctly afterwards: guides and radiance
+    pt.render_aov(cornell_gpu, film, _params(pt, "cornell", frame=0, frame_count=2, pipeline=pt.PIPELINE_AUTO))
+    _same(_read(film, pt), _guides(pt, orc, "cornell", [0, 1]), "after the refusals")
+    _, _, _, spp, _ = CASES["cornell"]
+    kw = dict(width=w, height=h, spp_per_frame=spp, max_depth=3, frame=0, frame_count=1)
+    pt.render(cornell_gpu, film, pt.default_params(**kw))
+    img, _, _, _ = orc.Scene(*pt.load_obj(pt.ASSET_CORNELL)).render_frame(orc.default_params(width=w, height=h, spp_per_frame=spp, max_depth=3, frame=0))
+    assert film.read_f32().tobytes() == img.tobytes()
+    film.close()
+
+
+@pytest.mark.gpu
+def test_pt_main_writes_the_guides(pt, orc, tmp_path):
+    """pt_main --aov PREFIX: albedo, normal and depth (in all three channels) of the rendered frames as PFM files; the render's own
+    figures in the JSON line are those of a run without --aov."""
+    _, w, h, spp, _ = CASES["cornell"]
+    exe = os.path.join(os.path.dirname(pt.__file__), "pt_main")
+    if not os.path.exists(exe):
+        pt.build()
+    args = [exe, "--obj", pt.ASSET_CORNELL, "--width", str(w), "--height", str(h), "--frames", "2", "--spp", str(spp), "--depth", "3"]
+    plain = subprocess.run(args, check=True, capture_output=True, text=True, cwd=pt.REPO)
+    out = subprocess.run(args + ["--aov", str(tmp_path / "g")], check=True, capture_output=True, text=True, cwd=pt.REPO)
+    a, b = (json.loads(x.stdout.strip().splitlines()[-1]) for x in (plain, out))
+    assert a["rays"] == b["rays"] and a["paths"] == b["paths"] == w * h * spp * 2
+    want = _guides(pt, orc, "cornell", [0, 1])
+    head = f"PF\n{w} {h}\n-1.0\n".encode()
+    for name in ("albedo", "normal", "depth"):
+        raw = open(tmp_path / f"g_{name}.pfm", "rb").read()
+        assert raw.startswith(head), name
+        img = np.frombuffer(raw[len(head):], np.float32).reshape(h, w, 3)[::-1]
+        ref = want[name] if name != "depth" else np.repeat(want["depth"][:, :, None], 3, axis=2)
+        assert img.tobytes() == np.ascontiguousarray(ref).tobytes(), name
+    bad = subprocess.run(args + ["--aov", str(tmp_path / "g"), "--ranks", "2"], capture_output=True, text=True, cwd=pt.REPO)
+    assert bad.returncode != 0 and "--aov" in bad.stderr
