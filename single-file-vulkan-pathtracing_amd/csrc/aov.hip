@@ -188,29 +188,13 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
 {
     const AovConst ac = ptm::own_sgprs(ac_arg);
     const AovPlanes planes = ptm::own_sgprs(planes_arg);
-    constexpr uint32_t LEAF_BIT = 0x2000u, DONE = 0x3FFFu;
+    constexpr uint32_t LEAF_BIT = C14_LEAF, DONE = C14_DONE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4 *s_wide = reinterpret_cast<float4 *>(smem + (size_t)lds_stack * TB * sizeof(uint32_t));
     float4 *s_tri = s_wide + LDS_NODE_F4 * (size_t)n_wide;
     float4 *s_rec = s_tri + 9 * (size_t)n_tris;
-    for (uint32_t i = threadIdx.x; i < 8 * n_wide; i += TB) {  // (as extend_body stages them)
-        float4 v = g_wide[i];
-        if ((i & 7u) == 6u) {  // the four child words
-            auto cw = [](float f) {
-                const uint32_t w = __float_as_uint(f);
-                const uint32_t c = (w & PT_LEAF) ? (0x2000u | (((w >> 28) & 3u) << 11) | (w & 0x7FFu)) : (w & 0x1FFFu);
-                return __uint_as_float(w == SENTINEL ? 0x3FFFu : c);
-            };
-            v = make_float4(cw(v.x), cw(v.y), cw(v.z), cw(v.w));
-        }
-        s_wide[(i >> 3) * LDS_NODE_F4 + (i & 7u)] = v;
-    }
-    for (uint32_t i = threadIdx.x; i < 3 * n_tris; i += TB) {
-        const float4 v = g_tri4[i];
-        s_tri[i] = make_float4(v.y, v.z, v.x, v.w);               // kz = 0: (kx,ky,kz) = (1,2,0)
-        s_tri[3 * n_tris + i] = make_float4(v.z, v.x, v.y, v.w);  // kz = 1: (2,0,1)
-        s_tri[6 * n_tris + i] = v;                                // kz = 2: (0,1,2)
-    }
+    lds_stage_nodes<TB, true>(s_wide, g_wide, n_wide);
+    lds_stage_tris<TB>(s_tri, g_tri4, n_tris);
     for (uint32_t pos = threadIdx.x; pos < n_tris; pos += TB) {
         const float4 n = g_shade4[3 * (size_t)pos];
         const float prim_bits = g_tri4[3 * (size_t)pos].w;
@@ -421,6 +405,8 @@ AovPlanes planes_of(const pt_film *f)
 
 // the single-kernel form's class and launch shape
 struct AovFusedPlan { size_t smem = 0; int grid = 0; bool pairs = false; };
+using AovFusedFn = decltype(&k_aov_fused<true>);
+AovFusedFn pick_aov_fused(bool pairs) { return pairs ? k_aov_fused<true> : k_aov_fused<false>; }
 pt_status plan_aov_fused(pt_scene *s, const pt_params *p, const ExtendPlan &pl, AovFusedPlan &fp)
 {
     pt_ctx *ctx = s->ctx;
@@ -432,13 +418,10 @@ pt_status plan_aov_fused(pt_scene *s, const pt_params *p, const ExtendPlan &pl, 
     }
     fp.smem = smem;
     fp.pairs = pl.pairs;
-    const void *fn = pl.pairs ? reinterpret_cast<const void *>(k_aov_fused<true>) : reinterpret_cast<const void *>(k_aov_fused<false>);
-    if (smem > 48 * 1024) PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     int per_cu = 0;
-    PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TB, smem));
-    per_cu = std::max(1, std::min(per_cu, 8));
+    const pt_status rc = ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_aov_fused(pl.pairs)), TB, smem, &per_cu);
     fp.grid = ctx->num_cus * per_cu;
-    return PT_OK;
+    return rc;
 }
 
 pt_status render_aov_fused(pt_scene *s, pt_film *f, const pt_params *p, const ExtendPlan &pl, const AovFusedPlan &fp, const AovConst &ac)
@@ -449,12 +432,8 @@ pt_status render_aov_fused(pt_scene *s, pt_film *f, const pt_params *p, const Ex
     if (a.n_tiles == 0) return PT_OK;
     PT_HIP(ctx, hipMemsetAsync(a.d_count + AOV_NEXT_TILE, 0, sizeof(uint32_t), st));
     const int grid = (int)std::min<uint32_t>((uint32_t)fp.grid, (a.n_tiles + TB / 64 - 1) / (TB / 64));  // a wave per tile at least
-    if (fp.pairs)
-        hipLaunchKernelGGL(k_aov_fused<true>, dim3(grid), dim3(TB), (uint32_t)fp.smem, st, ac, a.d_tiles, a.n_tiles, p->frame, p->frame_count, s->d_wide, s->d_tri4,
-                           s->d_shade4, s->d_faces, s->n_wide, s->n_tris, pl.lds_stack, planes_of(f), a.d_count + AOV_NEXT_TILE, ctx->d_stats);
-    else
-        hipLaunchKernelGGL(k_aov_fused<false>, dim3(grid), dim3(TB), (uint32_t)fp.smem, st, ac, a.d_tiles, a.n_tiles, p->frame, p->frame_count, s->d_wide, s->d_tri4,
-                           s->d_shade4, s->d_faces, s->n_wide, s->n_tris, pl.lds_stack, planes_of(f), a.d_count + AOV_NEXT_TILE, ctx->d_stats);
+    hipLaunchKernelGGL(pick_aov_fused(fp.pairs), dim3(grid), dim3(TB), (uint32_t)fp.smem, st, ac, a.d_tiles, a.n_tiles, p->frame, p->frame_count, s->d_wide, s->d_tri4,
+                       s->d_shade4, s->d_faces, s->n_wide, s->n_tris, pl.lds_stack, planes_of(f), a.d_count + AOV_NEXT_TILE, ctx->d_stats);
     PT_HIP(ctx, hipGetLastError());
     ctx->stats.launches_extend++;
     return PT_OK;

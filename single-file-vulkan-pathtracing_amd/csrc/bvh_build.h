@@ -5,8 +5,6 @@
 
 namespace {
 
-constexpr int TB = 256;
-
 // ---- float <-> order-preserving uint (for atomicMin/Max on floats) --------------------------
 __device__ __forceinline__ uint32_t f2ord(float f)
 {

@@ -16,14 +16,24 @@
 
 // rec64 (pt_tuning.rec64 != 0, the default): the leaf step reads the 64-B per-triangle records k_shade gathers anyway
 // (extend_kernel.h, REC64) instead of the 48-B tri4 records.
-const void *ptw_extend_hbm_fn(bool count, bool rec64)
+namespace {
+using ExtendHbmFn = decltype(&k_extend<false, false, true>);
+ExtendHbmFn pick_extend_hbm(bool count, bool rec64)
 {
-    if (rec64)
-        return count ? reinterpret_cast<const void *>(k_extend<false, true, true, false, true>)
-                     : reinterpret_cast<const void *>(k_extend<false, false, true, false, true>);
-    return count ? reinterpret_cast<const void *>(k_extend<false, true, true>)
-                 : reinterpret_cast<const void *>(k_extend<false, false, true>);
+    if (rec64) return count ? k_extend<false, true, true, false, true> : k_extend<false, false, true, false, true>;
+    return count ? k_extend<false, true, true> : k_extend<false, false, true>;
 }
+// (spill-free and uninstrumented: also as the 72-VGPR instantiation, seven waves per SIMD)
+using Extend8Fn = decltype(&k_extend8<false, false, 6>);
+Extend8Fn pick_extend8(bool count, bool spills, bool waves7)
+{
+    if (spills) return count ? k_extend8<true, true, 6> : k_extend8<false, true, 6>;
+    if (count) return k_extend8<true, false, 6>;
+    return waves7 ? k_extend8<false, false, 7> : k_extend8<false, false, 6>;
+}
+}  // namespace
+
+const void *ptw_extend_hbm_fn(bool count, bool rec64) { return reinterpret_cast<const void *>(pick_extend_hbm(count, rec64)); }
 
 void ptw_launch_extend_hbm(bool count, bool rec64, int grid, size_t smem, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
                            const float4 *wide, const uint2 *wide16, const float *norm_c, const float *norm_s,
@@ -32,26 +42,13 @@ void ptw_launch_extend_hbm(bool count, bool rec64, int grid, size_t smem, hipStr
                            unsigned long long *stats, uint2 *spill, uint32_t spill_stride, int refill, float tmin,
                            float tmax, int lds_stack, int raw_hit, const uint32_t *perm, const float *ray_tmax)
 {
-    const NormBox nb = { norm_c[0], norm_c[1], norm_c[2], norm_s[0], norm_s[1], norm_s[2], norm_rs[0], norm_rs[1], norm_rs[2] };
-#define PT_LAUNCH_HBM(C, R)                                                                                               \
-    hipExtLaunchKernelGGL((k_extend<false, C, true, false, R>), dim3(grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, wide, wide16, \
-                          nb, tri4, n_wide, n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill, spill_stride, refill, tmin, \
-                          tmax, lds_stack, raw_hit, perm, ray_tmax, rec64_tab)
-    if (rec64 && rec64_tab) {
-        if (count) PT_LAUNCH_HBM(true, true); else PT_LAUNCH_HBM(false, true);
-    } else {
-        if (count) PT_LAUNCH_HBM(true, false); else PT_LAUNCH_HBM(false, false);
-    }
-#undef PT_LAUNCH_HBM
+    hipExtLaunchKernelGGL(pick_extend_hbm(count, rec64 && rec64_tab), dim3(grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, wide, wide16,
+                          norm_box(norm_c, norm_s, norm_rs), tri4, n_wide, n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill, spill_stride,
+                          refill, tmin, tmax, lds_stack, raw_hit, perm, ray_tmax, rec64_tab);
 }
 
 // ---- BVH8 kernel (extend8_kernel.h), same translation unit for the same scheduler --------------------------------
-const void *ptw_extend8_fn(bool count, bool spills, bool waves7)
-{
-    if (spills) return count ? reinterpret_cast<const void *>(k_extend8<true, true, 6>) : reinterpret_cast<const void *>(k_extend8<false, true, 6>);
-    if (count) return reinterpret_cast<const void *>(k_extend8<true, false, 6>);
-    return waves7 ? reinterpret_cast<const void *>(k_extend8<false, false, 7>) : reinterpret_cast<const void *>(k_extend8<false, false, 6>);
-}
+const void *ptw_extend8_fn(bool count, bool spills, bool waves7) { return reinterpret_cast<const void *>(pick_extend8(count, spills, waves7)); }
 
 void ptw_launch_extend8(bool count, bool spills, bool waves7, int grid, size_t smem, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const uint4 *nodes8,
                         const float *norm_c, const float *norm_s, const float *norm_rs, const float4 *tri4, const float4 *rec64, const float4 *rayA,
@@ -59,13 +56,6 @@ void ptw_launch_extend8(bool count, bool spills, bool waves7, int grid, size_t s
                         uint2 *spill, uint32_t spill_stride, int refill, float tmin, float tmax, int lds_stack, int raw_hit,
                         const uint32_t *perm, const float *ray_tmax)
 {
-    const NormBox nb = { norm_c[0], norm_c[1], norm_c[2], norm_s[0], norm_s[1], norm_s[2], norm_rs[0], norm_rs[1], norm_rs[2] };
-#define PT_LAUNCH8(C, S, W)                                                                                                           \
-    hipExtLaunchKernelGGL((k_extend8<C, S, W>), dim3(grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, nodes8, nb, tri4, rec64, rayA, rayB, hit, \
-                          count_in, count_zero, stats, spill, spill_stride, refill, tmin, tmax, lds_stack, raw_hit, perm, ray_tmax)
-    if (spills) { if (count) PT_LAUNCH8(true, true, 6); else PT_LAUNCH8(false, true, 6); }
-    else if (count) PT_LAUNCH8(true, false, 6);
-    else if (waves7) PT_LAUNCH8(false, false, 7);
-    else PT_LAUNCH8(false, false, 6);
-#undef PT_LAUNCH8
+    hipExtLaunchKernelGGL(pick_extend8(count, spills, waves7), dim3(grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, nodes8, norm_box(norm_c, norm_s, norm_rs),
+                          tri4, rec64, rayA, rayB, hit, count_in, count_zero, stats, spill, spill_stride, refill, tmin, tmax, lds_stack, raw_hit, perm, ray_tmax);
 }

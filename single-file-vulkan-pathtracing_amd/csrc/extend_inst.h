@@ -35,13 +35,8 @@ __global__ __launch_bounds__(TB) void k_extend_inst(const float4 *__restrict__ t
     if (LDS_BLAS) {  // the BLAS is shared by every instance: keep it (and 3 permuted triangle copies) in LDS
         float4 *s_blas = reinterpret_cast<float4 *>(smem + (size_t)LDS_STACK * TB * sizeof(uint2));
         float4 *s_tri = s_blas + LDS_NODE_F4 * (size_t)n_blas_wide;
-        for (uint32_t i = threadIdx.x; i < 8 * n_blas_wide; i += TB) s_blas[(i >> 3) * LDS_NODE_F4 + (i & 7u)] = g_blas[i];
-        for (uint32_t i = threadIdx.x; i < 3 * n_tris; i += TB) {
-            const float4 v = g_tri4[i];
-            s_tri[i] = make_float4(v.y, v.z, v.x, v.w);
-            s_tri[3 * n_tris + i] = make_float4(v.z, v.x, v.y, v.w);
-            s_tri[6 * n_tris + i] = v;
-        }
+        lds_stage_nodes<TB, false>(s_blas, g_blas, n_blas_wide);
+        lds_stage_tris<TB>(s_tri, g_tri4, n_tris);
         __syncthreads();
         blas = s_blas;
         tri4 = s_tri;

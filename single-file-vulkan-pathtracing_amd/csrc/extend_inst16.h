@@ -17,9 +17,6 @@
 
 namespace {
 
-constexpr uint32_t I16_EXIT = 0x7FFFu, I16_DONE = 0xFFFFu, I16_LEAF = 0x8000u;
-constexpr uint32_t I16_NODE_DW = 20;  // dwords per BLAS node in LDS (16 used): 80-B stride spreads the banks
-
 // whole 16-B loads in each branch, then a register barrier: left alone the compiler turns the near / far plane selects
 // into address selects and reads the node with thirteen FLAT loads that serve both address spaces
 #define PT_REG_BARRIER16(A, B, C, D)                                                                                   \
@@ -41,28 +38,10 @@ __global__ __launch_bounds__(TB) void k_extend_inst16(const uint4 *__restrict__ 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint32_t *s_stack = reinterpret_cast<uint32_t *>(smem);  // [lds_stack][TB]
     uint32_t *s_blas = s_stack + (size_t)lds_stack * TB;      // [n_blas_wide + n_tlas_lds][I16_NODE_DW]
-    // the first n_tlas_lds TLAS nodes -- its top levels: the builder numbers the nodes level by level -- sit behind the BLAS
-    // nodes, so a visit to one of them is the same LDS read as a BLAS node instead of four loads from L2
+    // (the TLAS's top levels behind the BLAS nodes: lds_scene.h)
     float4 *s_tri = reinterpret_cast<float4 *>(s_blas + (size_t)I16_NODE_DW * (n_blas_wide + n_tlas_lds));
-    for (uint32_t i = threadIdx.x; i < 4 * n_tlas_lds; i += TB)
-        *reinterpret_cast<uint4 *>(s_blas + (size_t)(n_blas_wide + (i >> 2)) * I16_NODE_DW + 4 * (i & 3u)) = tlas16[i];
-    for (uint32_t i = threadIdx.x; i < 4 * n_blas_wide; i += TB) {
-        uint4 v = g_blas16[i];
-        if ((i & 3u) == 3u) {  // the four child words -> 16-bit codes
-            auto code = [](uint32_t w) {
-                if (w == SENTINEL) return I16_DONE;
-                return (w & PT_LEAF) ? (I16_LEAF | (((w >> 28) & 3u) << 11) | (w & 0x7FFu)) : (w & 0x7FFFu);
-            };
-            v = make_uint4(code(v.x), code(v.y), code(v.z), code(v.w));
-        }
-        *reinterpret_cast<uint4 *>(s_blas + (size_t)(i >> 2) * I16_NODE_DW + 4 * (i & 3u)) = v;
-    }
-    for (uint32_t i = threadIdx.x; i < 3 * n_tris; i += TB) {  // three axis-permuted copies (ptm::tri_test_perm)
-        const float4 v = g_tri4[i];
-        s_tri[i] = make_float4(v.y, v.z, v.x, v.w);
-        s_tri[3 * n_tris + i] = make_float4(v.z, v.x, v.y, v.w);
-        s_tri[6 * n_tris + i] = v;
-    }
+    lds_stage_nodes16<TB>(s_blas, g_blas16, n_blas_wide, tlas16, n_tlas_lds);
+    lds_stage_tris<TB>(s_tri, g_tri4, n_tris);
     __syncthreads();
     const uint32_t n = *count_in;
     if (blockIdx.x == 0 && threadIdx.x == 0) {

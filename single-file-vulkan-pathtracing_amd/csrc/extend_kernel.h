@@ -8,16 +8,9 @@
 #include "pt_internal.h"
 #include "pt_math.h"
 #include "pair_leaf.h"
+#include "lds_scene.h"  // the LDS image of a scene: node strides, child codes, staging, byte counts
 
 #include <hip/hip_ext.h>
-
-#ifndef PT_TB_DEFINED
-#define PT_TB_DEFINED
-namespace {
-constexpr int TB = 256;                     // threads per block of every kernel of the library
-constexpr uint32_t SENTINEL = 0xFFFFFFFFu;  // "no child" / "no node" in the BVH4 child words
-}  // namespace
-#endif
 
 namespace {
 
@@ -34,11 +27,6 @@ namespace {
 //  * LDS_SCENE: nodes + triangles are staged into LDS once per persistent block and traversal
 //    touches no HBM at all (scenes up to ~24 KB).
 constexpr int LDS_STACK = 8;
-// Nodes staged in LDS are spaced 144 B instead of 128 B: lanes of a wave sit on DIFFERENT nodes but read
-// the SAME field of them, and with a 128-B stride (a multiple of the bank cycle) those 16-B reads all fall
-// on the same 4 banks -- an n-way conflict for n distinct nodes.  144 B = 36 banks shifts consecutive
-// nodes by 4 banks, so 8 nodes tile the 32 banks exactly (measured: +0.6 % on C2, within noise on C4).
-constexpr uint32_t LDS_NODE_F4 = 9;  // float4 per LDS node (8 used)
 // Stack entries are one 64-bit word (child word | entry distance << 32) and the LDS part is addressed
 // through an LDS-typed pointer: with generic pointers the compiler merges the LDS and the spill
 // access into FLAT loads/stores of the two halves (seen in the ISA), which cost VMEM issue and latency.
@@ -142,6 +130,10 @@ __device__ __forceinline__ void slab_setup(const ptm::f3 org, const ptm::f3 inv,
 // dword, so the slab arithmetic costs exactly what it costs with fp32 planes; the ray is normalised the same
 // way at refill (org' = (org - c) * rs, inv' = inv * s), which leaves every distance t unchanged.
 struct NormBox { float cx, cy, cz, sx, sy, sz, rsx, rsy, rsz; };
+// of a scene's norm_c / norm_s / norm_rs (BLAS box) or tlas_norm_* (box of all instances)
+inline NormBox norm_box(const float *c, const float *s, const float *rs) { return { c[0], c[1], c[2], s[0], s[1], s[2], rs[0], rs[1], rs[2] }; }
+inline NormBox norm_box_blas(const pt_scene *s) { return norm_box(s->norm_c, s->norm_s, s->norm_rs); }
+inline NormBox norm_box_tlas(const pt_scene *s) { return norm_box(s->tlas_norm_c, s->tlas_norm_s, s->tlas_norm_rs); }
 #define PT_MIXH(DST, REG, HI, INVC, ONC) \
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[" #HI ",0,0] op_sel_hi:[1,0,0]" : "=v"(DST) : "v"(REG), "v"(INVC), "v"(ONC))
 #define PT_SLAB4H(T, REGC, HI)                                                                      \
@@ -221,8 +213,8 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
     // shading pass of the same round finds the line of the winning triangle already fetched, and tri4 drops out of the
     // working set (its primitive ids are read only when two hits have exactly the same t).
     static_assert(!REC64 || (!LDS_SCENE && SPILL), "64-B triangle records are the vote-scheduled HBM kernel's");
-    constexpr uint32_t LEAF_BIT = COMPACT ? 0x2000u : PT_LEAF;
-    constexpr uint32_t DONE = COMPACT ? 0x3FFFu : SENTINEL;
+    constexpr uint32_t LEAF_BIT = COMPACT ? C14_LEAF : PT_LEAF;
+    constexpr uint32_t DONE = COMPACT ? C14_DONE : SENTINEL;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint2 *stack = reinterpret_cast<uint2 *>(smem);  // [LDS_STACK][TB]
@@ -231,26 +223,8 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
     if (LDS_SCENE) {
         float4 *s_wide = reinterpret_cast<float4 *>(smem + (size_t)lds_stack * TB * (COMPACT ? sizeof(uint32_t) : sizeof(uint2)));
         float4 *s_tri = s_wide + LDS_NODE_F4 * (size_t)n_wide;
-        for (uint32_t i = threadIdx.x; i < 8 * n_wide; i += TB) {
-            float4 v = g_wide[i];
-            if (COMPACT && (i & 7u) == 6u) {  // the four child words
-                auto cw = [](float f) {
-                    const uint32_t w = __float_as_uint(f);
-                    const uint32_t c = (w & PT_LEAF) ? (0x2000u | (((w >> 28) & 3u) << 11) | (w & 0x7FFu)) : (w & 0x1FFFu);
-                    return __uint_as_float(w == SENTINEL ? 0x3FFFu : c);
-                };
-                v = make_float4(cw(v.x), cw(v.y), cw(v.z), cw(v.w));
-            }
-            s_wide[(i >> 3) * LDS_NODE_F4 + (i & 7u)] = v;
-        }
-        // three copies of the triangles with components permuted to (kx,ky,kz) for kz = 0,1,2:
-        // the triangle test then needs no per-lane component selects (ptm::tri_test_perm)
-        for (uint32_t i = threadIdx.x; i < 3 * n_tris; i += TB) {
-            const float4 v = g_tri4[i];
-            s_tri[i] = make_float4(v.y, v.z, v.x, v.w);                    // kz = 0: (kx,ky,kz) = (1,2,0)
-            s_tri[3 * n_tris + i] = make_float4(v.z, v.x, v.y, v.w);       // kz = 1: (2,0,1)
-            s_tri[6 * n_tris + i] = v;                                     // kz = 2: (0,1,2)
-        }
+        lds_stage_nodes<TB, COMPACT>(s_wide, g_wide, n_wide);
+        lds_stage_tris<TB>(s_tri, g_tri4, n_tris);
         __syncthreads();
         wide = s_wide;
         tri4 = s_tri;

@@ -17,6 +17,34 @@
 
 namespace {
 
+// ---- one picker per kernel family: the plan prepares what it returns, the launch launches it ---------------------------------------
+// single-level scenes in LDS.  compact: one-dword stack entries (ExtendPlan::spill == false and tmin > 0), else the 8-byte-entry
+// kernel; the instrumented twin (count) has no shadow-ray form, it takes ray_tmax as a run-time argument
+using ExtendFn = decltype(&k_extend<true, false, true>);
+ExtendFn pick_extend_lds(bool compact, bool pairs, bool count, bool shadow)
+{
+    if (!compact) return count ? k_extend<true, true, true> : k_extend<true, false, true>;
+    if (count) return pairs ? k_extend<true, true, false, true> : k_extend<true, true, false>;
+    if (pairs) return shadow ? k_extend_lds7p_sh : k_extend_lds7p;
+    return shadow ? k_extend_lds7_sh : k_extend_lds7;
+}
+// two-level scenes, fp32 nodes (shadow rays: no instrumented twin)
+using ExtendInstFn = decltype(&k_extend_inst<false, false>);
+ExtendInstFn pick_extend_inst(bool lds_blas, bool count, bool shadow)
+{
+    if (shadow) return lds_blas ? k_extend_inst<false, true, true> : k_extend_inst<false, false, true>;
+    if (count) return lds_blas ? k_extend_inst<true, true> : k_extend_inst<true, false>;
+    return lds_blas ? k_extend_inst<false, true> : k_extend_inst<false, false>;
+}
+// two-level scenes, fp16 nodes and 15-bit child codes
+using ExtendInst16Fn = decltype(&k_extend_inst16<false, false>);
+ExtendInst16Fn pick_extend_inst16(bool pairs, bool count, bool shadow)
+{
+    if (shadow) return pairs ? k_extend_inst16<false, true, true> : k_extend_inst16<false, false, true>;
+    if (count) return pairs ? k_extend_inst16<true, true> : k_extend_inst16<true, false>;
+    return pairs ? k_extend_inst16<false, true> : k_extend_inst16<false, false>;
+}
+
 }  // namespace
 
 pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
@@ -49,14 +77,12 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
     if (s->n_inst) {  // two-level scenes: one kernel variant (BVH4s read through L1/L2)
         if (want == PT_EXTEND_LDS) { ctx->err = "instanced scenes only have the HBM extend variant"; return PT_ERR_UNSUPPORTED; }
         pl.variant = PT_EXTEND_HBM;
-        const size_t blas_bytes = 16 * LDS_NODE_F4 * (size_t)s->n_wide + sizeof(float4) * 9 * (size_t)s->n_tris;
+        const size_t blas_bytes = lds_scene_bytes(s->n_wide, s->n_tris);
         pl.lds_scene = blas_bytes <= 24 * 1024;  // here: the BLAS (shared by all instances) is staged in LDS
         pl.smem = (size_t)LDS_STACK * TB * sizeof(uint2) + (pl.lds_scene ? blas_bytes : 0);
         int per_cu_i = 0;
-        PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                        &per_cu_i, pl.lds_scene ? reinterpret_cast<const void *>(k_extend_inst<false, true>)
-                                                : reinterpret_cast<const void *>(k_extend_inst<false, false>), TB, pl.smem));
-        per_cu_i = std::max(1, std::min(per_cu_i, 8));
+        const pt_status rci = ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_extend_inst(pl.lds_scene, false, false)), TB, pl.smem, &per_cu_i);
+        if (rci != PT_OK) return rci;
         pl.refill = 64;  // a wave takes new rays only when all its lanes are done: entering an instance (ray transform, three
                          // divides) and the TLAS root are too expensive to run for a few refilled lanes.  C4: 16: 8.2, 32: 8.85,
                          // 48: 9.26, 56: 9.2, 64: 9.38 Grays/s
@@ -64,7 +90,7 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
         pl.grid = ctx->num_cus * per_cu_i;
         pl.smem_inst_fallback = pl.smem; pl.grid_inst_fallback = pl.grid;
         // the round-2 kernel when both levels fit its 15-bit child codes and the BLAS fits LDS
-        const size_t smem16_scene = sizeof(uint32_t) * I16_NODE_DW * (size_t)s->n_wide + sizeof(float4) * 9 * (size_t)s->n_tris;
+        const size_t smem16_scene = lds_scene16_bytes(s->n_wide, s->n_tris);
         const int lds16 = pt_tuned(ctx->tune.lds_stack, 16, 1, 32);
         pl.inst16 = s->d_tlas16 && s->d_wide16 && s->n_inst < 32768u && s->n_tlas16 < 32767u && s->n_wide < 32767u && s->n_tris <= 2047u &&
                     smem16_scene <= 24 * 1024 && ctx->tune.inst16 != 0;
@@ -74,22 +100,21 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
             // C4: 0 / 4 / 8 / 16 / 24 KB -> 11.95 / 12.16 / 12.31 / 10.7 / 11.1 Grays/s (profiles/r02i_ab_c4_tlas_lds.log) --
             // from 16 KB on the four resident blocks leave the other pipeline's k_shade no LDS to run beside them
             const size_t tlas_lds_bytes = (size_t)pt_tuned(ctx->tune.tlas_lds_kb, 8, 0, 96) * 1024;
-            pl.n_tlas_lds = (uint32_t)std::min<size_t>(s->n_tlas16, tlas_lds_bytes / (sizeof(uint32_t) * I16_NODE_DW));
-            pl.smem = (size_t)lds16 * TB * sizeof(uint32_t) + smem16_scene + sizeof(uint32_t) * I16_NODE_DW * (size_t)pl.n_tlas_lds;
-            const void *fn16 = s->pair_leaves ? reinterpret_cast<const void *>(k_extend_inst16<false, true>)
-                                              : reinterpret_cast<const void *>(k_extend_inst16<false, false>);
-            if (pl.smem > 48 * 1024)
-                for (const void *f : { reinterpret_cast<const void *>(k_extend_inst16<false, true>), reinterpret_cast<const void *>(k_extend_inst16<false, false>),
-                                       reinterpret_cast<const void *>(k_extend_inst16<true, true>), reinterpret_cast<const void *>(k_extend_inst16<true, false>),
-                                       // (the shadow-ray twins of the NEE pipeline: the same launch shape)
-                                       reinterpret_cast<const void *>(k_extend_inst16<false, true, true>), reinterpret_cast<const void *>(k_extend_inst16<false, false, true>) })
-                    PT_HIP(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem));
+            pl.n_tlas_lds = (uint32_t)std::min<size_t>(s->n_tlas16, tlas_lds_bytes / lds_nodes16_bytes(1));
+            pl.smem = (size_t)lds16 * TB * sizeof(uint32_t) + smem16_scene + lds_nodes16_bytes(pl.n_tlas_lds);
+            // the instrumented twin and the shadow-ray twin (NEE pipeline) run with the same launch shape; the grid is the product kernel's
             int per16 = 0;
-            PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per16, fn16, TB, pl.smem));
+            const auto prepare16 = [&](bool count, bool shadow, int *per_cu) {
+                return ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_extend_inst16(s->pair_leaves, count, shadow)), TB, pl.smem, per_cu);
+            };
+            pt_status rc16 = prepare16(true, false, nullptr);
+            if (rc16 == PT_OK) rc16 = prepare16(false, true, nullptr);
+            if (rc16 == PT_OK) rc16 = prepare16(false, false, &per16);
+            if (rc16 != PT_OK) return rc16;
             // four blocks per CU and refill at 48 idle lanes measured best on the 10 000-instance grid (C4: 4/48 10.73,
             // 5/48 10.33, 4/40 10.66, 4/56 10.35, 4/64 9.74 Grays/s; the fp32 kernel at its best, 4/64: 9.33)
             per16 = pt_tuned(ctx->tune.inst16_blocks, std::min(per16, 4), 1, 8);
-            pl.grid = ctx->num_cus * std::max(1, std::min(per16, 8));
+            pl.grid = ctx->num_cus * per16;
             pl.refill = pt_tuned(ctx->tune.refill, 48, 1, 64);
         }
         // TLAS pushes <= 3 per level + 3 extra instances of a leaf, + EXIT, + the BLAS walk: the exact bound of the
@@ -98,17 +123,9 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
         const uint32_t blas_bound = s->stack_need != 0xFFFFFFFFu ? s->stack_need + 1u : 3u * (s->height_tree / 2u + 1u);
         const uint32_t bound_i = 3u * (std::max(s->tlas_height / 2u + 1u, s->tlas16_levels)) + 4u + blas_bound + 2u;
         pl.spill_levels = bound_i > (uint32_t)LDS_STACK ? bound_i - (uint32_t)LDS_STACK : 0u;  // (sized for the 8-entry fallback kernel)
-        const size_t need_i = PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)std::max(pl.grid, pl.grid_inst_fallback) * TB * sizeof(uint2);
-        if (need_i > ctx->spill_bytes) {
-            (void)hipFree(ctx->d_spill);
-            ctx->d_spill = nullptr;
-            ctx->spill_bytes = 0;
-            PT_HIP(ctx, hipMalloc((void **)&ctx->d_spill, need_i));
-            ctx->spill_bytes = need_i;
-        }
-        return PT_OK;
+        return ptw_reserve_spill(ctx, PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)std::max(pl.grid, pl.grid_inst_fallback) * TB * sizeof(uint2));
     }
-    const size_t scene_bytes = 16 * LDS_NODE_F4 * (size_t)s->n_wide + sizeof(float4) * 9 * (size_t)s->n_tris;  // 3 permuted triangle copies
+    const size_t scene_bytes = lds_scene_bytes(s->n_wide, s->n_tris);
     // (round 2's 128-B eight-wide node with fp16 planes visited 26 % fewer nodes and fetched as many 128-B LINES -- two 64-B
     // BVH4 siblings share one -- and lost: 458 vs 395 ms of kernel time per 4 frames of C5; the 64-B node above is its successor)
     const bool auto8 = want == PT_EXTEND_AUTO && scene_bytes > 24 * 1024 && s->d_wide8 && (ctx->tune.hbm8 == 1 || auto8_big);
@@ -129,22 +146,14 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
         pl.waves7 = !spills8 && pl.lds_stack <= 10 &&
                     (ctx->tune.extend_blocks == 7 || (ctx->tune.extend_blocks < 0 && 64ull * s->n_wide8 + 64ull * s->n_tris > (256ull << 20)));
         int per_cu8 = 0;
-        PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu8, ptw_extend8_fn(false, spills8, pl.waves7), TB, pl.smem));
-        per_cu8 = std::max(1, std::min(per_cu8, 8));
+        const pt_status rc8b = ptw_prepare_kernel(ctx, ptw_extend8_fn(false, spills8, pl.waves7), TB, pl.smem, &per_cu8);
+        if (rc8b != PT_OK) return rc8b;
         // with the triangle vote at 16 lanes (launch_extend) the refill optimum moved from 32 idle lanes to 12: C5 2 907 ->
         // 3 240 Mrays/s, C5x 2 715 -> 2 960 for both together (profiles/r03bb_*, r03bc_*: 32: 3 025, 24: 3 140, 16: 3 230, 8: 3 235, 4: 3 170)
         pl.refill = pt_tuned(ctx->tune.refill, 12, 1, 64);
         pl.grid = ctx->num_cus * per_cu8;
         pl.spill_levels = bound8 > (uint32_t)pl.lds_stack ? bound8 - (uint32_t)pl.lds_stack : 0u;
-        const size_t need8 = PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)pl.grid * TB * sizeof(uint2);
-        if (need8 > ctx->spill_bytes) {
-            (void)hipFree(ctx->d_spill);
-            ctx->d_spill = nullptr;
-            ctx->spill_bytes = 0;
-            PT_HIP(ctx, hipMalloc((void **)&ctx->d_spill, need8));
-            ctx->spill_bytes = need8;
-        }
-        return PT_OK;
+        return ptw_reserve_spill(ctx, PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)pl.grid * TB * sizeof(uint2));
     }
     if (want == PT_EXTEND_LDS && scene_bytes > 96 * 1024) { ctx->err = "scene does not fit LDS"; return PT_ERR_UNSUPPORTED; }
     pl.lds_scene = want == PT_EXTEND_LDS || (want == PT_EXTEND_AUTO && scene_bytes <= 24 * 1024);
@@ -160,28 +169,22 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
     pl.pairs = !pl.spill && s->pair_leaves && ctx->tune.pair_kernel != 0;
     pl.smem_wide_entries = (size_t)pl.lds_stack * TB * sizeof(uint2) + (pl.lds_scene ? scene_bytes : 0);
     pl.smem = pl.spill ? pl.smem_wide_entries : (size_t)pl.lds_stack * TB * sizeof(uint32_t) + scene_bytes;
-    if (!pl.spill && pl.smem_wide_entries > 48 * 1024) {
-        PT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_extend<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem_wide_entries));
-        PT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_extend<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem_wide_entries));
-    }
-    const void *fn = pl.pairs ? reinterpret_cast<const void *>(k_extend_lds7p)
-                     : !pl.spill ? reinterpret_cast<const void *>(k_extend_lds7)
-                     : pl.lds_scene ? reinterpret_cast<const void *>(k_extend<true, false, true>)
-                                    : ptw_extend_hbm_fn(false, ctx->tune.rec64 != 0);
-    const void *fn_count = pl.pairs ? reinterpret_cast<const void *>(k_extend<true, true, false, true>)
-                           : !pl.spill ? reinterpret_cast<const void *>(k_extend<true, true, false>)
-                           : pl.lds_scene ? reinterpret_cast<const void *>(k_extend<true, true, true>)
-                                          : ptw_extend_hbm_fn(true, ctx->tune.rec64 != 0);
-    if (pl.smem > 48 * 1024)
-        PT_HIP(ctx, hipFuncSetAttribute(fn_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem));
-    if (pl.smem > 48 * 1024) PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem));
-    if (pl.smem > 48 * 1024 && !pl.spill)  // the shadow-ray twins of the two compact kernels (NEE pipeline)
-        PT_HIP(ctx, hipFuncSetAttribute(pl.pairs ? reinterpret_cast<const void *>(k_extend_lds7p_sh) : reinterpret_cast<const void *>(k_extend_lds7_sh),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem));
+    // every kernel ptw_launch_extend can take for this plan, with the LDS size it would be launched with: the 8-byte-entry kernels of a
+    // compact plan (tmin <= 0), the instrumented twin, the shadow-ray twin of a compact kernel (NEE pipeline), the product kernel --
+    // whose occupancy makes the grid of them all
+    const auto kernel_of = [&](bool compact, bool count, bool shadow) {
+        return pl.lds_scene ? reinterpret_cast<const void *>(pick_extend_lds(compact, pl.pairs, count, shadow)) : ptw_extend_hbm_fn(count, ctx->tune.rec64 != 0);
+    };
     int per_cu = 0;
-    PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TB, pl.smem));
-    per_cu = std::max(1, std::min(per_cu, 8));
-    per_cu = pt_tuned(ctx->tune.extend_blocks, per_cu, 1, per_cu);
+    pt_status rck = PT_OK;
+    if (!pl.spill)
+        for (const bool count : { false, true })
+            if (rck == PT_OK) rck = ptw_prepare_kernel(ctx, kernel_of(false, count, false), TB, pl.smem_wide_entries);
+    if (rck == PT_OK) rck = ptw_prepare_kernel(ctx, kernel_of(!pl.spill, true, false), TB, pl.smem);
+    if (rck == PT_OK && !pl.spill) rck = ptw_prepare_kernel(ctx, kernel_of(true, false, true), TB, pl.smem);
+    if (rck == PT_OK) rck = ptw_prepare_kernel(ctx, kernel_of(!pl.spill, false, false), TB, pl.smem, &per_cu);
+    if (rck != PT_OK) return rck;
+    per_cu = ptw_tuned_blocks(ctx, per_cu);
     // big scenes (vote-scheduled steps): 32 idle lanes measured best on C5 (16: -2.5 %, 48: -3 %)
     pl.refill = pt_tuned(ctx->tune.refill, pl.lds_scene ? REFILL_MIN_IDLE : 32, 1, 64);
     pl.grid = ctx->num_cus * per_cu;
@@ -193,15 +196,7 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
     const uint32_t bound = pl.topdown4 ? 3u * s->levels4t + 1u
                            : s->stack_need != 0xFFFFFFFFu ? s->stack_need + 1u : 3u * (s->height_tree / 2u + 1u) + 1u;
     pl.spill_levels = bound > (uint32_t)pl.lds_stack ? bound - (uint32_t)pl.lds_stack : 0u;
-    const size_t need = PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)pl.grid * TB * sizeof(uint2);
-    if (need > ctx->spill_bytes) {
-        (void)hipFree(ctx->d_spill);
-        ctx->d_spill = nullptr;
-        ctx->spill_bytes = 0;
-        PT_HIP(ctx, hipMalloc((void **)&ctx->d_spill, need));
-        ctx->spill_bytes = need;
-    }
-    return PT_OK;
+    return ptw_reserve_spill(ctx, PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)pl.grid * TB * sizeof(uint2));
 }
 
 void ptw_launch_extend(const ExtendPlan &pl, pt_scene *s, const float4 *rayA, const float2 *rayB, float4 *hit, uint32_t *hit_inst,
@@ -217,9 +212,6 @@ void ptw_launch_extend(const ExtendPlan &pl, pt_scene *s, const float4 *rayA, co
         // own region of the spill buffer, counted in dwords (the buffer is sized in 8-byte entries for the larger grid)
         uint32_t *sp32 = reinterpret_cast<uint32_t *>(reinterpret_cast<uint2 *>(s->ctx->d_spill) + (size_t)pipe * std::max(pl.spill_levels, 1u) * (size_t)std::max(pl.grid, pl.grid_inst_fallback) * TB);
         const uint32_t str = (uint32_t)pl.grid * TB;
-        const NormBox nbt = { s->tlas_norm_c[0], s->tlas_norm_c[1], s->tlas_norm_c[2], s->tlas_norm_s[0], s->tlas_norm_s[1], s->tlas_norm_s[2],
-                              s->tlas_norm_rs[0], s->tlas_norm_rs[1], s->tlas_norm_rs[2] };
-        const NormBox nbb = { s->norm_c[0], s->norm_c[1], s->norm_c[2], s->norm_s[0], s->norm_s[1], s->norm_s[2], s->norm_rs[0], s->norm_rs[1], s->norm_rs[2] };
         const int enter_min = pt_tuned(s->ctx->tune.enter_min, 16, 1, 64);  // lanes that wait to enter an instance together (8, 16, 24 measured alike within 1 %)
         // ... and lanes that wait with a triangle leaf (extend_inst16.h): 8 until round 6; on the BLAS with the least-area cut 8 / 12 / 14 / 20 -> 16.12 / 16.33 /
         // 16.34 / 16.19 Grays/s on the 10 000-instance grid (profiles/r06o_c4_wavefront_knobs.log)
@@ -227,15 +219,10 @@ void ptw_launch_extend(const ExtendPlan &pl, pt_scene *s, const float4 *rayA, co
         // the node loop yields to the lanes waiting with a leaf once fewer than 1/6 of the wave's rays still descend
         // (C4 11.7 -> 12.2 Grays/s; 2, 3, 4, 8 measured within 1 % of it, 0 = never: profiles/r02i_ab_c4_node_yield.log)
         const int node_yield = pt_tuned(s->ctx->tune.node_yield, 6, 0, 64);
-#define PT_LAUNCH_INST16(C, P, S)                                                                                           \
-    hipExtLaunchKernelGGL((k_extend_inst16<C, P, S>), dim3(pl.grid), dim3(TB), (uint32_t)pl.smem, st, ev0, ev1, 0u, s->d_tlas16, nbt, \
-                          reinterpret_cast<const uint4 *>(s->d_wide16), nbb, s->d_tri4, s->n_wide, s->n_tris, s->d_inst6,     \
-                          s->d_tlas_prim_of, rayA, rayB, hit, hit_inst, count_in, count_zero, stats, sp32, str, pl.refill, tmin, \
-                          tmax, raw, pl.lds_stack, enter_min, leaf_min, node_yield, pl.n_tlas_lds, ray_tmax)
-        if (ray_tmax) { if (s->pair_leaves) PT_LAUNCH_INST16(false, true, true); else PT_LAUNCH_INST16(false, false, true); }  // shadow rays (NEE)
-        else if (s->pair_leaves) { if (count) PT_LAUNCH_INST16(true, true, false); else PT_LAUNCH_INST16(false, true, false); }
-        else { if (count) PT_LAUNCH_INST16(true, false, false); else PT_LAUNCH_INST16(false, false, false); }
-#undef PT_LAUNCH_INST16
+        hipExtLaunchKernelGGL(pick_extend_inst16(s->pair_leaves, count, ray_tmax != nullptr), dim3(pl.grid), dim3(TB), (uint32_t)pl.smem, st, ev0, ev1, 0u, s->d_tlas16,
+                              norm_box_tlas(s), reinterpret_cast<const uint4 *>(s->d_wide16), norm_box_blas(s), s->d_tri4, s->n_wide, s->n_tris, s->d_inst6,
+                              s->d_tlas_prim_of, rayA, rayB, hit, hit_inst, count_in, count_zero, stats, sp32, str, pl.refill, tmin,
+                              tmax, raw, pl.lds_stack, enter_min, leaf_min, node_yield, pl.n_tlas_lds, ray_tmax);
         return;
     }
     if (s->n_inst) {
@@ -243,17 +230,9 @@ void ptw_launch_extend(const ExtendPlan &pl, pt_scene *s, const float4 *rayA, co
         const size_t smem_i = pl.inst16 ? pl.smem_inst_fallback : pl.smem;
         uint2 *sp = reinterpret_cast<uint2 *>(s->ctx->d_spill) + (size_t)pipe * std::max(pl.spill_levels, 1u) * (size_t)std::max(pl.grid, pl.grid_inst_fallback) * TB;
         const uint32_t str = (uint32_t)grid_i * TB;
-#define PT_LAUNCH_INST(C, L, S)                                                                                          \
-    hipExtLaunchKernelGGL((k_extend_inst<C, L, S>), dim3(grid_i), dim3(TB), (uint32_t)smem_i, st, ev0, ev1, 0u, s->d_tlas_wide, \
-                          s->d_wide, s->d_tri4, s->n_wide, s->n_tris, s->d_inst6, s->d_tlas_prim_of, rayA, rayB, hit,           \
-                          hit_inst, count_in, count_zero, stats, sp, str, pl.refill, tmin, tmax, raw, ray_tmax)
-        if (ray_tmax) { if (pl.lds_scene) PT_LAUNCH_INST(false, true, true); else PT_LAUNCH_INST(false, false, true); }  // shadow rays (NEE)
-        else if (pl.lds_scene) {
-            if (count) PT_LAUNCH_INST(true, true, false); else PT_LAUNCH_INST(false, true, false);
-        } else {
-            if (count) PT_LAUNCH_INST(true, false, false); else PT_LAUNCH_INST(false, false, false);
-        }
-#undef PT_LAUNCH_INST
+        hipExtLaunchKernelGGL(pick_extend_inst(pl.lds_scene, count, ray_tmax != nullptr), dim3(grid_i), dim3(TB), (uint32_t)smem_i, st, ev0, ev1, 0u, s->d_tlas_wide,
+                              s->d_wide, s->d_tri4, s->n_wide, s->n_tris, s->d_inst6, s->d_tlas_prim_of, rayA, rayB, hit,
+                              hit_inst, count_in, count_zero, stats, sp, str, pl.refill, tmin, tmax, raw, ray_tmax);
         return;
     }
     uint2 *spill = reinterpret_cast<uint2 *>(s->ctx->d_spill) + spill_off;
@@ -268,39 +247,18 @@ void ptw_launch_extend(const ExtendPlan &pl, pt_scene *s, const float4 *rayA, co
                            count_in, count_zero, stats, spill, stride, pl.refill | (tri_enter << 8) | (tri_stay << 16), tmin, tmax, pl.lds_stack, raw, perm, ray_tmax);
         return;
     }
-    const NormBox nbox = { s->norm_c[0], s->norm_c[1], s->norm_c[2], s->norm_s[0], s->norm_s[1], s->norm_s[2],
-                           s->norm_rs[0], s->norm_rs[1], s->norm_rs[2] };
     // one-dword stack entries truncate the entry distance toward zero, which is only conservative for t >= 0, and the
     // sort of the one-dword keys takes entry distances for positive floats (tmin = 0 could make one -0): a tmin <= 0
     // (not valid in Vulkan, accepted here) runs the same plan through the 8-byte-entry kernel
     const bool no_spill = !pl.spill && tmin > 0.f;
     const size_t smem = (!pl.spill && !no_spill) ? pl.smem_wide_entries : pl.smem;
-#define PT_LAUNCH_EXTEND(L, C, S)                                                                                     \
-    hipExtLaunchKernelGGL((k_extend<L, C, S>), dim3(pl.grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, s->d_wide, \
-                          s->d_wide16, nbox,                                                                          \
-                          s->d_tri4, s->n_wide, s->n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill, stride, \
-                          pl.refill, tmin, tmax, pl.lds_stack, raw, nullptr, ray_tmax, nullptr)
-    if (no_spill && pl.pairs) {
-        if (count)
-            hipExtLaunchKernelGGL((k_extend<true, true, false, true>), dim3(pl.grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, s->d_wide,
-                                  s->d_wide16, nbox, s->d_tri4, s->n_wide, s->n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill,
-                                  stride, pl.refill, tmin, tmax, pl.lds_stack, raw, nullptr, ray_tmax, nullptr);
-        else
-            hipExtLaunchKernelGGL(ray_tmax ? k_extend_lds7p_sh : k_extend_lds7p, dim3(pl.grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, s->d_wide, s->d_wide16, nbox,
-                                  s->d_tri4, s->n_wide, s->n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill, stride,
-                                  pl.refill, tmin, tmax, pl.lds_stack, raw, nullptr, ray_tmax, nullptr);
-    } else if (no_spill) {
-        if (count) PT_LAUNCH_EXTEND(true, true, false);
-        else
-            hipExtLaunchKernelGGL(ray_tmax ? k_extend_lds7_sh : k_extend_lds7, dim3(pl.grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, s->d_wide, s->d_wide16, nbox,
-                                  s->d_tri4, s->n_wide, s->n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill, stride,
-                                  pl.refill, tmin, tmax, pl.lds_stack, raw, nullptr, ray_tmax, nullptr);
-    } else if (pl.lds_scene) {
-        if (count) PT_LAUNCH_EXTEND(true, true, true); else PT_LAUNCH_EXTEND(true, false, true);
-    } else {
+    if (!pl.lds_scene) {
         ptw_launch_extend_hbm(count, s->ctx->tune.rec64 != 0, pl.grid, smem, st, ev0, ev1, s->d_wide, pl.topdown4 ? reinterpret_cast<const uint2 *>(s->d_wide16t) : s->d_wide16, s->norm_c, s->norm_s, s->norm_rs, s->d_tri4,
                               s->d_shade64, s->n_wide, s->n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill, stride,
                               pl.refill | (pt_tuned(s->ctx->tune.tri_enter, 0, 0, 64) << 8), tmin, tmax, pl.lds_stack, raw, perm, ray_tmax);
+        return;
     }
-#undef PT_LAUNCH_EXTEND
+    hipExtLaunchKernelGGL(pick_extend_lds(no_spill, pl.pairs, count, ray_tmax != nullptr), dim3(pl.grid), dim3(TB), (uint32_t)smem, st, ev0, ev1, 0u, s->d_wide,
+                          s->d_wide16, norm_box_blas(s), s->d_tri4, s->n_wide, s->n_tris, rayA, rayB, hit, count_in, count_zero, stats, spill, stride,
+                          pl.refill, tmin, tmax, pl.lds_stack, raw, nullptr, ray_tmax, nullptr);
 }

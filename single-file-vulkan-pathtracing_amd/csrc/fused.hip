@@ -34,6 +34,46 @@ using namespace ptw;
 constexpr size_t FUSED_COUNT_LDS = sizeof(uint32_t) * 2 * FB_N * (FTB / 64);  // the instrumented twin's per-wave block counters, behind the product plan
 static_assert((int)FB_N == (int)PT_FB_COUNT && FB_N <= PT_N_BLOCKS, "fused_kernel.h FusedBlock mirrors include/pt_api.h pt_fused_block");
 
+// ---- one picker per kernel family: the plan prepares what it returns, the launch launches it ---------------------------------------
+// mode: 0 one sample group, 1 several, 2 head + tail slots; count: the instrumented twin (pair-leaf trees: what the compact class gets by default)
+using FusedFn = decltype(&k_fused<0, true>);
+template <int MODE>
+FusedFn pick_fused_mode(bool pairs, bool count)
+{
+    if (count) return k_fused_count<MODE, true>;
+    return pairs ? k_fused<MODE, true> : k_fused<MODE, false>;
+}
+FusedFn pick_fused(int mode, bool pairs, bool count)
+{
+    return mode == 2 ? pick_fused_mode<2>(pairs, count) : mode == 1 ? pick_fused_mode<1>(pairs, count) : pick_fused_mode<0>(pairs, count);
+}
+using FusedNeeFn = decltype(&k_fused_nee<true>);
+FusedNeeFn pick_fused_nee(bool pairs) { return pairs ? k_fused_nee<true> : k_fused_nee<false>; }
+using FusedInstFn = decltype(&k_fused_inst<false, true>);
+FusedInstFn pick_fused_inst(bool grouped, bool pairs)
+{
+    if (grouped) return pairs ? k_fused_inst<true, true> : k_fused_inst<true, false>;
+    return pairs ? k_fused_inst<false, true> : k_fused_inst<false, false>;
+}
+
+// Blocks per CU of a fused plan, remembered per context and family (pt_ctx::fused_smem: 0 single-level, 1 two-level, 2 single-level NEE)
+// for the last LDS size and leaf kind: `prepare(per_cu)` -- ptw_prepare_kernel on every kernel the family's picker returns for the plan --
+// runs only when they change.
+template <class Prepare>
+pt_status fused_blocks_per_cu(pt_ctx *ctx, int family, size_t smem, bool pairs, int &per_cu, Prepare &&prepare)
+{
+    const size_t key = (smem << 1) | (pairs ? 1u : 0u);
+    if (ctx->fused_smem[family] != key || ctx->fused_per_cu[family] <= 0) {
+        int n = 0;
+        const pt_status rc = prepare(&n);
+        if (rc != PT_OK) return rc;
+        ctx->fused_smem[family] = key;
+        ctx->fused_per_cu[family] = n;
+    }
+    per_cu = ptw_tuned_blocks(ctx, ctx->fused_per_cu[family]);
+    return PT_OK;
+}
+
 // two-level scenes: k_extend_inst16's class (extend_launch.hip: both levels in 15-bit child codes, BLAS in LDS, pair leaves)
 pt_status plan_fused_inst(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPlan &fp)
 {
@@ -49,35 +89,23 @@ pt_status plan_fused_inst(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPl
     // TLAS nodes staged in LDS: the wavefront kernel keeps 8 KB of them because the other pipeline's k_shade needs LDS beside it
     // (extend_launch.hip); this kernel has the CU to itself
     const size_t tlas_lds_bytes = (size_t)pt_tuned(ctx->tune.tlas_lds_kb, PT_FUSEDI_TLAS_KB, 0, 96) * 1024;
-    fp.n_tlas_lds = (uint32_t)std::min<size_t>(s->n_tlas16, tlas_lds_bytes / (sizeof(uint32_t) * I16_NODE_DW));
-    fp.smem = (size_t)fp.lds_stack * FITB * sizeof(uint32_t) + sizeof(uint32_t) * I16_NODE_DW * ((size_t)s->n_wide + fp.n_tlas_lds) +
-              sizeof(float4) * 9 * (size_t)s->n_tris + tables + sizeof(uint32_t) * FS_FIELDS * FITB + sizeof(uint32_t) * (FITB / 64) * PT_FUSED_WTILES;
+    fp.n_tlas_lds = (uint32_t)std::min<size_t>(s->n_tlas16, tlas_lds_bytes / lds_nodes16_bytes(1));
+    fp.smem = (size_t)fp.lds_stack * FITB * sizeof(uint32_t) + lds_nodes16_bytes((size_t)s->n_wide + fp.n_tlas_lds) + lds_tris_bytes(s->n_tris) + tables +
+              sizeof(uint32_t) * FS_FIELDS * FITB + sizeof(uint32_t) * (FITB / 64) * PT_FUSED_WTILES;
     if (fp.smem > 160 * 1024) { ctx->err = "PT_PIPELINE_FUSED: the two-level kernel's LDS plan exceeds 160 KB (pt_tuning lds_stack / tlas_lds_kb)"; return PT_ERR_UNSUPPORTED; }
-    int per_cu = ctx->fused_per_cu[1];
-    const size_t key1 = (fp.smem << 1) | (s->pair_leaves ? 1u : 0u);
-    if (ctx->fused_smem[1] != key1 || per_cu <= 0) {
-        for (const void *fn : { reinterpret_cast<const void *>(k_fused_inst<false, true>), reinterpret_cast<const void *>(k_fused_inst<true, true>),
-                                 reinterpret_cast<const void *>(k_fused_inst<false, false>), reinterpret_cast<const void *>(k_fused_inst<true, false>) })
-            if (fp.smem > 48 * 1024) PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.smem));
-        PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, s->pair_leaves ? reinterpret_cast<const void *>(k_fused_inst<false, true>) : reinterpret_cast<const void *>(k_fused_inst<false, false>), FITB, fp.smem));
-        ctx->fused_smem[1] = key1;
-        ctx->fused_per_cu[1] = per_cu;
-    }
-    per_cu = std::max(1, std::min(per_cu, 8));
-    per_cu = pt_tuned(ctx->tune.extend_blocks, per_cu, 1, per_cu);
+    int per_cu = 0;
+    const pt_status rcp = fused_blocks_per_cu(ctx, 1, fp.smem, s->pair_leaves, per_cu, [&](int *n) {  // (the grid: the ungrouped kernel's occupancy)
+        const pt_status rcg = ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_fused_inst(true, s->pair_leaves)), FITB, fp.smem);
+        return rcg != PT_OK ? rcg : ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_fused_inst(false, s->pair_leaves)), FITB, fp.smem, n);
+    });
+    if (rcp != PT_OK) return rcp;
     fp.grid = ctx->num_cus * per_cu;
     fp.block = FITB;
     fp.refill = pt_tuned(ctx->tune.refill, 48, 1, 64);
     // stack entries beyond the LDS ones: one dword each, [level][thread], in the context's spill area (sized by ptw_plan_extend for
     // the wavefront kernels' grids; grown here if this grid asks for more)
-    const size_t need = (size_t)std::max(pl.spill_levels, 1u) * (size_t)fp.grid * FITB * sizeof(uint32_t);
-    if (need > ctx->spill_bytes) {
-        (void)hipFree(ctx->d_spill);
-        ctx->d_spill = nullptr;
-        ctx->spill_bytes = 0;
-        PT_HIP(ctx, hipMalloc((void **)&ctx->d_spill, need));
-        ctx->spill_bytes = need;
-    }
+    const pt_status rcs = ptw_reserve_spill(ctx, (size_t)std::max(pl.spill_levels, 1u) * (size_t)fp.grid * FITB * sizeof(uint32_t));
+    if (rcs != PT_OK) return rcs;
     fp.spill = reinterpret_cast<uint32_t *>(ctx->d_spill);
     if (ctx->tune.inst_frames != 0) {
         const pt_status rcf = ptb_ensure_inst_frames(s);
@@ -105,51 +133,35 @@ pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPla
     // (one stack level more than the walk needs: level -1, never written, is what the node step's read of the stack's top entry lands on when the stack is
     // empty -- fused_kernel.h)
     fp.lds_stack = pl.lds_stack + 1;
-    fp.smem = (size_t)fp.lds_stack * FTB * sizeof(uint32_t) + (pl.smem - (size_t)pl.lds_stack * TB * sizeof(uint32_t)) + tables +
+    fp.smem = (size_t)fp.lds_stack * FTB * sizeof(uint32_t) + lds_scene_bytes(s->n_wide, s->n_tris) + tables +
               sizeof(uint32_t) * FS_FIELDS * FTB + sizeof(uint32_t) * (FTB / 64) * PT_FUSED_WTILES;
     fp.pairs = pl.pairs;
+    fp.block = FTB;
+    int per_cu = 0;
+    pt_status rcp;
     if (nee) {  // k_fused_nee: the shadow ray's state behind the waves' tile words (fused_kernel.h FS_NEE_*), and the occupancy of that plan
         fp.nee = true;
         fp.smem += sizeof(uint32_t) * FS_NEE_FIELDS * FTB;
-        int per_cu = ctx->fused_per_cu[2];
-        const size_t key2 = (fp.smem << 1) | (pl.pairs ? 1u : 0u);
-        if (ctx->fused_smem[2] != key2 || per_cu <= 0) {
-            for (const void *fn : { reinterpret_cast<const void *>(k_fused_nee<true>), reinterpret_cast<const void *>(k_fused_nee<false>) })
-                if (fp.smem > 48 * 1024) PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.smem));
-            PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pl.pairs ? reinterpret_cast<const void *>(k_fused_nee<true>) : reinterpret_cast<const void *>(k_fused_nee<false>), FTB, fp.smem));
-            ctx->fused_smem[2] = key2;
-            ctx->fused_per_cu[2] = per_cu;
-        }
-        per_cu = std::max(1, std::min(per_cu, 8));
-        per_cu = pt_tuned(ctx->tune.extend_blocks, per_cu, 1, per_cu);
-        fp.grid = ctx->num_cus * per_cu;
-        fp.block = FTB;
-        fp.refill = pt_tuned(ctx->tune.refill, 36, 1, 64);  // (the reference estimator's value: not swept for NEE)
-        return PT_OK;
+        rcp = fused_blocks_per_cu(ctx, 2, fp.smem, pl.pairs, per_cu,
+                                  [&](int *n) { return ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_fused_nee(pl.pairs)), FTB, fp.smem, n); });
+    } else {
+        // the three sample-group modes and their instrumented twins (FUSED_COUNT_LDS on top) share the launch shape: the grid comes from mode 0's product kernel
+        rcp = fused_blocks_per_cu(ctx, 0, fp.smem, pl.pairs, per_cu, [&](int *n) {
+            pt_status rc = PT_OK;
+            for (int mode = 2; mode >= 0 && rc == PT_OK; mode--) {
+                rc = ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_fused(mode, pl.pairs, true)), FTB, fp.smem + FUSED_COUNT_LDS);
+                if (rc == PT_OK) rc = ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(pick_fused(mode, pl.pairs, false)), FTB, fp.smem, mode == 0 ? n : nullptr);
+            }
+            return rc;
+        });
     }
-    int per_cu = ctx->fused_per_cu[0];
-    const size_t key0 = (fp.smem << 1) | (pl.pairs ? 1u : 0u);
-    if (ctx->fused_smem[0] != key0 || per_cu <= 0) {
-        for (const void *fn : { reinterpret_cast<const void *>(k_fused_count<0, true>), reinterpret_cast<const void *>(k_fused_count<1, true>),
-                                 reinterpret_cast<const void *>(k_fused_count<2, true>) })
-            PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fp.smem + FUSED_COUNT_LDS)));
-        for (const void *fn : { reinterpret_cast<const void *>(k_fused<0, true>), reinterpret_cast<const void *>(k_fused<1, true>),
-                                 reinterpret_cast<const void *>(k_fused<0, false>), reinterpret_cast<const void *>(k_fused<1, false>),
-                                 reinterpret_cast<const void *>(k_fused<2, true>), reinterpret_cast<const void *>(k_fused<2, false>) })
-            if (fp.smem > 48 * 1024) PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.smem));
-        PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pl.pairs ? reinterpret_cast<const void *>(k_fused<0, true>) : reinterpret_cast<const void *>(k_fused<0, false>), FTB, fp.smem));
-        ctx->fused_smem[0] = key0;
-        ctx->fused_per_cu[0] = per_cu;
-    }
-    per_cu = std::max(1, std::min(per_cu, 8));
-    per_cu = pt_tuned(ctx->tune.extend_blocks, per_cu, 1, per_cu);
+    if (rcp != PT_OK) return rcp;
     fp.grid = ctx->num_cus * per_cu;
-    fp.block = FTB;
     // of 64: the share of a wave's live lanes that must wait with a finished ray before the shade block runs for them.  The block
     // is ~4x a node step, so it pays to run it fuller than k_extend's refill (16): 8 / 16 / 24 / 32 / 40 -> 33.9 / 34.1 / 34.6 /
     // 35.7 / 36.3 Grays/s on the Cornell box at 1080p (profiles/r04b_fused_refill_sweep.txt).  Round 6, after the shade block lost a fifth of
     // its instructions (the shared spawn steps) and the tree a node: 32 / 36 / 40 / 44 / 48 -> 73.1 / 73.1 / 73.8 / 75.1 / 76.1 ms per 16 frames,
-    // one blocking frame 5.48 / 5.45 / 5.43 / 5.47 / 5.52 (profiles/r06l_refill_exit_resweep.log): 36
+    // one blocking frame 5.48 / 5.45 / 5.43 / 5.47 / 5.52 (profiles/r06l_refill_exit_resweep.log): 36.  NEE: the same value, not swept
     fp.refill = pt_tuned(ctx->tune.refill, 36, 1, 64);
     return PT_OK;
 }
@@ -159,47 +171,28 @@ void ptw_launch_fused(const FusedPlan &fp, bool grouped, const ptw::RenderConst 
                       hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
     if (fp.inst) {
-        const NormBox nbt = { s->tlas_norm_c[0], s->tlas_norm_c[1], s->tlas_norm_c[2], s->tlas_norm_s[0], s->tlas_norm_s[1], s->tlas_norm_s[2],
-                              s->tlas_norm_rs[0], s->tlas_norm_rs[1], s->tlas_norm_rs[2] };
-        const NormBox nbb = { s->norm_c[0], s->norm_c[1], s->norm_c[2], s->norm_s[0], s->norm_s[1], s->norm_s[2], s->norm_rs[0], s->norm_rs[1], s->norm_rs[2] };
         // the waiting rules of k_extend_inst16 (extend_launch.hip has the measurements), re-swept for this kernel in round 6 on the tree with the
         // least-area cut (leaves are reached a node earlier): a leaf step waits for 14 lanes (8 / 10 / 12 / 14 / 20 / 24: 16.42 / 16.60 / 16.72 / 16.76 /
         // 16.52 / 16.32 Grays/s on the 10 000-instance grid at 16 frames), an instance entry for 12 (profiles/r06m_c4_fused_knobs.log)
         const int enter_min = pt_tuned(s->ctx->tune.enter_min, 12, 1, 64), leaf_min = pt_tuned(s->ctx->tune.leaf_min, 14, 1, 64);
         const int node_yield = pt_tuned(s->ctx->tune.node_yield, 6, 0, 64);
-#define PT_LAUNCH_FUSED_INST(G, P)                                                                                                     \
-    hipExtLaunchKernelGGL((k_fused_inst<G, P>), dim3(fp.grid), dim3(FITB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_tlas16, nbt, \
-                          reinterpret_cast<const uint4 *>(s->d_wide16), nbb, s->d_tri4, s->d_shade4, s->n_wide, s->n_tris, s->d_inst6,       \
-                          s->d_tlas_prim_of, fp.inst_frame, 0u, n_slots, next_slot, stats, fp.spill, (uint32_t)fp.grid * FITB, fp.refill, \
-                          tmin, tmax, fp.lds_stack, enter_min, leaf_min, node_yield, fp.n_tlas_lds)
-        if (s->pair_leaves) { if (grouped) PT_LAUNCH_FUSED_INST(true, true); else PT_LAUNCH_FUSED_INST(false, true); }
-        else { if (grouped) PT_LAUNCH_FUSED_INST(true, false); else PT_LAUNCH_FUSED_INST(false, false); }
-#undef PT_LAUNCH_FUSED_INST
+        hipExtLaunchKernelGGL(pick_fused_inst(grouped, s->pair_leaves), dim3(fp.grid), dim3(FITB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_tlas16,
+                              norm_box_tlas(s), reinterpret_cast<const uint4 *>(s->d_wide16), norm_box_blas(s), s->d_tri4, s->d_shade4, s->n_wide, s->n_tris, s->d_inst6,
+                              s->d_tlas_prim_of, fp.inst_frame, 0u, n_slots, next_slot, stats, fp.spill, (uint32_t)fp.grid * FITB, fp.refill,
+                              tmin, tmax, fp.lds_stack, enter_min, leaf_min, node_yield, fp.n_tlas_lds);
         return;
     }
     FastDiv div_frames;  // one group: the hand-out order is tile-major (fused_kernel.h), chunk -> (tile, frame) by this
     div_frames.init(std::max(rc.lanes_active, 1u));
-#define PT_LAUNCH_FUSED_K(K, G, P)                                                                                                         \
-    hipExtLaunchKernelGGL((K<G, P>), dim3(fp.grid), dim3(FTB), (uint32_t)(fp.smem + (fp.count ? FUSED_COUNT_LDS : 0)), st, ev0, ev1, 0u, rc, tiles, rad, s->d_wide, s->d_tri4,       \
-                          s->d_shade4, s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots, next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack, div_frames)
-#define PT_LAUNCH_FUSED(G, P) PT_LAUNCH_FUSED_K(k_fused, G, P)
     const int mode = rc.tail ? 2 : (grouped ? 1 : 0);
     if (fp.nee) {  // (one sample group, no head + tail: render.hip never plans another shape for it)
         if (mode != 0) return;
-#define PT_LAUNCH_FUSED_NEE(P)                                                                                                                  \
-    hipExtLaunchKernelGGL((k_fused_nee<P>), dim3(fp.grid), dim3(FTB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_wide, s->d_tri4, s->d_shade4, \
-                          s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots, next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack, div_frames, s->d_lights,  \
-                          s->n_lights, s->light_area)
-        if (fp.pairs) PT_LAUNCH_FUSED_NEE(true); else PT_LAUNCH_FUSED_NEE(false);
-#undef PT_LAUNCH_FUSED_NEE
+        hipExtLaunchKernelGGL(pick_fused_nee(fp.pairs), dim3(fp.grid), dim3(FTB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_wide, s->d_tri4, s->d_shade4,
+                              s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots, next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack, div_frames, s->d_lights,
+                              s->n_lights, s->light_area);
         return;
     }
-    if (fp.count) {  // the instrumented twins (pair-leaf trees: what the compact class gets by default)
-        if (mode == 2) PT_LAUNCH_FUSED_K(k_fused_count, 2, true); else if (mode == 1) PT_LAUNCH_FUSED_K(k_fused_count, 1, true); else PT_LAUNCH_FUSED_K(k_fused_count, 0, true);
-        return;
-    }
-    if (fp.pairs) { if (mode == 2) PT_LAUNCH_FUSED(2, true); else if (mode == 1) PT_LAUNCH_FUSED(1, true); else PT_LAUNCH_FUSED(0, true); }
-    else { if (mode == 2) PT_LAUNCH_FUSED(2, false); else if (mode == 1) PT_LAUNCH_FUSED(1, false); else PT_LAUNCH_FUSED(0, false); }
-#undef PT_LAUNCH_FUSED
-#undef PT_LAUNCH_FUSED_K
+    hipExtLaunchKernelGGL(pick_fused(mode, fp.pairs, fp.count), dim3(fp.grid), dim3(FTB), (uint32_t)(fp.smem + (fp.count ? FUSED_COUNT_LDS : 0)), st, ev0, ev1, 0u, rc, tiles,
+                          rad, s->d_wide, s->d_tri4, s->d_shade4, s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots, next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack,
+                          div_frames);
 }

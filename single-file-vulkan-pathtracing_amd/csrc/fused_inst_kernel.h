@@ -57,11 +57,12 @@ __global__ __launch_bounds__(FITB, PT_FUSEDI_WAVES) void k_fused_inst(
     float4 *s_tri = reinterpret_cast<float4 *>(s_blas + (size_t)I16_NODE_DW * (n_blas_wide + n_tlas_lds));
     float4 *s_shade = s_tri + 9 * (size_t)n_tris;
     lds_u32 *my_state = (lds_u32 *)reinterpret_cast<uint32_t *>(s_shade + 3 * (size_t)n_tris) + threadIdx.x;
+    // lds_stage_nodes16 and lds_stage_tris (lds_scene.h) restated: through the shared helpers this kernel's register allocation changes
     for (uint32_t i = threadIdx.x; i < 4 * n_tlas_lds; i += FITB)
         *reinterpret_cast<uint4 *>(s_blas + (size_t)(n_blas_wide + (i >> 2)) * I16_NODE_DW + 4 * (i & 3u)) = tlas16[i];
     for (uint32_t i = threadIdx.x; i < 4 * n_blas_wide; i += FITB) {
         uint4 v = g_blas16[i];
-        if ((i & 3u) == 3u) {  // the four child words -> 16-bit codes (extend_inst16.h)
+        if ((i & 3u) == 3u) {  // the four child words -> 16-bit codes (lds_scene.h)
             auto code = [](uint32_t w) {
                 if (w == SENTINEL) return I16_DONE;
                 return (w & PT_LEAF) ? (I16_LEAF | (((w >> 28) & 3u) << 11) | (w & 0x7FFu)) : (w & 0x7FFFu);

@@ -134,7 +134,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                                            float tmax_arg, int lds_stack, FastDiv div_frames_arg,
                                            const float4 *__restrict__ lights_arg = nullptr, uint32_t n_lights_arg = 0u, float light_area_arg = 0.f)
 {
-    constexpr uint32_t LEAF_BIT = 0x2000u, DONE = 0x3FFFu;
+    constexpr uint32_t LEAF_BIT = C14_LEAF, DONE = C14_DONE;
     constexpr bool GROUPED = MODE == 1, HYB = MODE == 2;
     static_assert(!NEE || (MODE == 0 && !COUNT), "NEE: one sample group, no instrumented twin");
     // (everything the persistent loop reads: a scalar register of its own -- own_sgprs)
@@ -162,25 +162,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     float4 *s_shade = s_tri + 9 * (size_t)n_tris;
     float4 *s_frame = s_shade + 3 * (size_t)n_tris;
     lds_u32 *my_state = (lds_u32 *)reinterpret_cast<uint32_t *>(s_frame + 2 * (size_t)n_tris) + threadIdx.x;
-    for (uint32_t i = threadIdx.x; i < 8 * n_wide; i += FTB) {
-        float4 v = g_wide[i];
-        if ((i & 7u) == 6u) {  // the four child words -> 14-bit codes (extend_kernel.h COMPACT)
-            auto cw = [](float f) {
-                const uint32_t w = __float_as_uint(f);
-                const uint32_t c = (w & PT_LEAF) ? (0x2000u | (((w >> 28) & 3u) << 11) | (w & 0x7FFu)) : (w & 0x1FFFu);
-                return __uint_as_float(w == SENTINEL ? 0x3FFFu : c);
-            };
-            v = make_float4(cw(v.x), cw(v.y), cw(v.z), cw(v.w));
-        }
-        s_wide[(i >> 3) * LDS_NODE_F4 + (i & 7u)] = v;
-    }
-    for (uint32_t i = threadIdx.x; i < 3 * n_tris; i += FTB) {
-        const float4 v = g_tri4[i];
-        s_tri[i] = make_float4(v.y, v.z, v.x, v.w);               // kz = 0: (kx,ky,kz) = (1,2,0)
-        s_tri[3 * n_tris + i] = make_float4(v.z, v.x, v.y, v.w);  // kz = 1: (2,0,1)
-        s_tri[6 * n_tris + i] = v;                                // kz = 2: (0,1,2) -- also what the shade block reads
-        s_shade[i] = g_shade4[i];
-    }
+    lds_stage_nodes<FTB, true>(s_wide, g_wide, n_wide);  // (child words -> 14-bit codes: extend_kernel.h COMPACT)
+    lds_stage_tris<FTB, true>(s_tri, g_tri4, n_tris, s_shade, g_shade4);  // (the kz = 2 copy is also what the shade block reads)
     for (uint32_t i = threadIdx.x; i < 2 * n_tris; i += FTB) s_frame[i] = g_frame4[i];
     __syncthreads();
     const float4 *wide = s_wide, *tri4 = s_tri;

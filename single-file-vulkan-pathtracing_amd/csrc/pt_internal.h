@@ -23,6 +23,10 @@ constexpr int PT_N_STATS = 24;  // u64 slots of pt_ctx::d_stats that pt_get_stat
 constexpr int PT_N_BLOCKS = 32;  // ... followed by {wave executions, lanes} of up to this many kernel blocks (pt_get_block_counts; fused_kernel.h FusedBlock)
 constexpr int PT_N_STATS_ALL = PT_N_STATS + 2 * PT_N_BLOCKS;
 constexpr int PT_MAX_PIPES = 4;  // concurrent wavefront pipelines (streams) per pt_render
+namespace {
+constexpr int TB = 256;                     // threads per block of every kernel of the library
+constexpr uint32_t SENTINEL = 0xFFFFFFFFu;  // "no child" / "no node" in the BVH4 child words
+}  // namespace
 
 struct pt_ctx {
     int device = 0;
@@ -51,9 +55,10 @@ struct pt_ctx {
     // take 25 GB of the device without being asked (what each GB buys: profiles/r06e_mem_budget.log).
     size_t mem_budget = 0;
     pt_tuning tune;            // include/pt_api.h: defaults (-1) + PT_TUNE, filled once by pt_ctx_create
-    // fused.hip: the launch attributes / occupancy of the fused kernels for the last LDS size planned ([0] single-level, [1] two-level):
-    // a blocking call per frame plans twice (PT_PIPELINE_AUTO's look, then the render) and should not pay five runtime calls each time
-    size_t fused_smem[3] = { 0, 0, 0 };  // (single-level, two-level, single-level NEE)
+    // fused.hip: the launch attributes / occupancy of the fused kernels for the last LDS size planned ([0] single-level, [1] two-level,
+    // [2] single-level with NEE): a blocking call per frame plans twice (PT_PIPELINE_AUTO's look, then the render) and should not pay
+    // five runtime calls each time
+    size_t fused_smem[3] = { 0, 0, 0 };  // key: LDS bytes << 1 | pair-leaf kernel
     int fused_per_cu[3] = { 0, 0, 0 };
 };
 // The workspace budget a context plans within when the caller names none: 8 GB.  Round 6, one MI355X, Grays/s at 2 / 4 / 8 / 16 / 32 GB / no

@@ -2,16 +2,48 @@
 //
 //   extend_launch.hip   which closest-hit kernel walks a scene and with what launch shape (ExtendPlan), and its launch
 //   shade_kernels.hip   k_generate / k_shade / k_shadow_add / k_resolve / k_hits_to_api and their launchers
+//   extend_hbm.hip      the closest-hit kernels that walk a scene out of L2 / MALL / HBM (their own instruction scheduler)
 //   fused.hip           PT_PIPELINE_FUSED: k_fused (fused_kernel.h), its plan and its launcher
+//   aov.hip             pt_render_aov: the guide buffers' kernels, plan and launch
 //   film_work.hip       the film's workspace: how many slots a render gets (RenderShape) and the buffers behind them
 //   render.hip          pt_render / pt_render_prepare / pt_trace: batches, pipelines on streams, rounds, polls, redo
 //
 // Kernels are launched from the translation unit that defines them, so each unit exports small launchers; what crosses
-// the units is plain data (wavefront_types.h) and the structs below.
+// the units is plain data (wavefront_types.h) and the structs below.  Inside a unit every kernel family has ONE picker
+// (pick_*: the plan's switches -> a typed kernel pointer) that its plan prepares through ptw_prepare_kernel and its launcher
+// launches, so the two cannot disagree about which instantiation runs.
 #pragma once
 #include "wavefront_types.h"
 
 #include <hip/hip_ext.h>
+
+#include <algorithm>
+
+// ---- what every plan of the launch path does, once each (extend_launch.hip, extend_hbm.hip, fused.hip, aov.hip) -------------------
+// The context's stack-spill area holds at least `bytes` afterwards (it only grows).
+inline pt_status ptw_reserve_spill(pt_ctx *ctx, size_t bytes)
+{
+    if (bytes <= ctx->spill_bytes) return PT_OK;
+    (void)hipFree(ctx->d_spill);
+    ctx->d_spill = nullptr;
+    ctx->spill_bytes = 0;
+    PT_HIP(ctx, hipMalloc((void **)&ctx->d_spill, bytes));
+    ctx->spill_bytes = bytes;
+    return PT_OK;
+}
+// Makes kernel `fn` launchable with `smem` bytes of dynamic LDS (above 48 KB a kernel needs the attribute: one set on its sibling
+// does not count, so a plan passes EVERY kernel its picker can return for the launch shape through here) and, where per_cu is
+// given, asks how many blocks of `block` threads a CU holds of it: 1 .. 8.
+inline pt_status ptw_prepare_kernel(pt_ctx *ctx, const void *fn, int block, size_t smem, int *per_cu = nullptr)
+{
+    if (smem > 48 * 1024) PT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (!per_cu) return PT_OK;
+    PT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, block, smem));
+    *per_cu = std::max(1, std::min(*per_cu, 8));
+    return PT_OK;
+}
+// ... and pt_tuning.extend_blocks on top: fewer resident blocks than fit, never more
+inline int ptw_tuned_blocks(const pt_ctx *ctx, int per_cu) { return pt_tuned(ctx->tune.extend_blocks, per_cu, 1, per_cu); }
 
 // ---- extend_launch.hip ---------------------------------------------------------------------------------------------
 struct ExtendPlan {

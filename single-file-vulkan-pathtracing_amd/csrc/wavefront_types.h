@@ -12,14 +12,6 @@
 #include "pt_internal.h"
 #include "pt_math.h"
 
-#ifndef PT_TB_DEFINED
-#define PT_TB_DEFINED
-namespace {
-constexpr int TB = 256;                     // threads per block of every kernel of the library
-constexpr uint32_t SENTINEL = 0xFFFFFFFFu;  // "no child" / "no node" in the BVH4 child words
-}  // namespace
-#endif
-
 namespace ptw {
 
 // Exact unsigned division by a run-time constant without the ~28-instruction v_rcp sequence
