@@ -319,6 +319,53 @@ pt_status pt_render_aov(pt_scene *scene, pt_film *film, const pt_params *params)
 /* host_out: the plane's size (see the enum).  PT_ERR_INVALID_ARG for which >= PT_AOV_COUNT or a film without guides.  */
 pt_status pt_film_read_aov(pt_film *film, uint32_t which, void *host_out);
 
+/* ---- denoiser: guide-driven edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the radiance film ---------
+ * Reads the film and the guide planes where they live and writes a separate image.  All arithmetic is binary32, every
+ * operation rounded on its own, no contraction, operation order as written (the tests restate it in numpy, bit for bit).
+ * Per pixel p: C the film's rgb; A, N, E, Z, a the planes albedo, normal, emission, depth, alpha exactly as stored
+ * (premultiplied by coverage).
+ *   demodulation   D_c = max(A_c + (1 - a), 0.001f)      (a miss counts as a surface of albedo 1 lit by the environment)
+ *                  I_c = (C_c - E_c) / D_c
+ *   iterations k = 0 .. n-1, step s = 2^k, h = {1/16, 1/4, 3/8, 1/4, 1/16}.  num_c = den = 0; for j = -2 .. 2 (outer), i = -2 .. 2
+ *   (inner), tap q = (x + s*i, y + s*j), taps outside the image skipped:
+ *                  dn  = N_p - N_q;   x_n = ((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) * inv_n,   inv_n = 1.0f / (sigma_normal*sigma_normal)
+ *                  dz  = Z_p - Z_q;   x_z = (dz*dz) / ((sigma_depth*sigma_depth) * (Z_p*Z_p + Z_q*Z_q) + 1e-12f)
+ *                  t   = max(0, 1 - (x_n + x_z) * 0.0625f);   t = t*t, four times  (t^16: a compact-support stand-in for exp(-x))
+ *                  w   = (h_j*h_i) * t;   num_c = num_c + w * I_c(q);   den = den + w
+ *                  I'_c(p) = num_c / den                    (the centre tap always weighs 9/64: den > 0)
+ *   remodulation   out_c = I_c * D_c + E_c after the last iteration.
+ * The bgra8 form of the result is k_resolve's clamp and quantise rule on out (what the film's rgba8 image holds after frame 0 of
+ * such a colour): bytes B, G, R = (uint8)(min(max(c, 0), 1) * 255.0f + 0.5f), 0 unless c > 0; A = 255.  Denormals are kept
+ * (DESIGN.md section 2), so weights whose t^16 underflows follow IEEE gradual underflow.  NaN inputs are outside the contract.
+ * The filter stops on normal and depth only: a colour term keeps the noise without a per-pixel variance estimate, and an albedo /
+ * emission term changes little once the radiance is demodulated.
+ * The defaults (5, 0.5, 0.1) come from one CPU experiment on the Cornell box at 128 x 96 and 4 spp (relative MSE 46 x below the
+ * noisy film's); nobody has tuned them at 1080p.                                                                              */
+typedef struct pt_denoise_params {
+    uint32_t iterations;       /* 1..8; default 5 */
+    float sigma_normal;        /* default 0.5  */
+    float sigma_depth;         /* default 0.1  */
+    uint32_t reserved[5];      /* must be 0 */
+} pt_denoise_params;
+void pt_denoise_params_default(pt_denoise_params *p);
+/* Filters the film as it stands (the running mean of the frames rendered so far, with the guides of pt_render_aov) into
+ * device_out_rgb_f32: caller-owned DEVICE memory of width*height*3 floats (a torch tensor's data_ptr()), or NULL for a plane the
+ * film owns (pt_film_read_denoised).  Blocking; runs on the context's stream, ordered after the work already queued there.  Reads
+ * the film and the guides and writes only the output and its own scratch: the film, the rgba8 image, the guides and pt_stats stay as
+ * they were, so progressive rendering goes on afterwards.  The scratch (two ping-pong planes and the packed guides, 48 B per pixel,
+ * plus 16 B per pixel for the film's own output) belongs to the film, only grows, counts against the context's memory budget with the
+ * film's other workspaces (pt_tuning.mem_budget_mb) and is freed by pt_film_destroy.  device_ms (may be NULL): device time from
+ * the first kernel to the last.
+ * PT_ERR_INVALID_ARG: NULL film or params; a film without guides (pt_film_enable_aov); iterations outside 1..8; a sigma that is not
+ * finite and > 0; a nonzero reserved word.  PT_ERR_OOM: the scratch does not fit the budget (the film renders on as before).
+ * A film rendered as (rank, world) holds only its own tiles: the filter would read zeros from the other ranks' pixels.  Filtering a
+ * gathered image means a film over external planes (pt_film_create_external + pt_film_enable_aov with caller memory) on the rank
+ * that holds it; gathering the guides across ranks is not part of this library.                                                */
+pt_status pt_film_denoise(pt_film *film, const pt_denoise_params *params, void *device_out_rgb_f32, float *device_ms);
+/* The film-owned result of the last pt_film_denoise(..., NULL, ...): rgb width*height*3 floats, bgra width*height*4 bytes; either may
+ * be NULL.  PT_ERR_INVALID_ARG before any denoise into the film's own plane.                                                     */
+pt_status pt_film_read_denoised(pt_film *film, float *rgb, uint8_t *bgra);
+
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {
     uint32_t prim;  /* gl_PrimitiveID, 0xFFFFFFFF = miss                                   */

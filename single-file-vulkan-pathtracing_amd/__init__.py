@@ -96,6 +96,11 @@ class Tuning(C.Structure):
     _fields_ = [(n, C.c_int32) for n in TUNING_NAMES] + [("reserved", C.c_int32 * 2)]
 
 
+class DenoiseParams(C.Structure):
+    """include/pt_api.h pt_denoise_params: the a-trous filter of pt_film_denoise."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 class HostScene(C.Structure):
     _fields_ = [("vertices", C.POINTER(C.c_float)), ("n_verts", C.c_uint32), ("indices", C.POINTER(C.c_uint32)),
                 ("n_tris", C.c_uint32), ("faces", C.POINTER(C.c_float))]
@@ -116,6 +121,7 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_scene_get_info", "pt_scene_read_bvh", "pt_scene_read_bvh4", "pt_scene_read_bvh8", "pt_film_create", "pt_film_create_external", "pt_film_clear",
                "pt_film_read_f32", "pt_film_read_bgra8", "pt_film_destroy", "pt_params_default", "pt_render",
                "pt_render_prepare", "pt_trace", "pt_film_enable_aov", "pt_render_aov", "pt_film_read_aov",
+               "pt_denoise_params_default", "pt_film_denoise", "pt_film_read_denoised",
                "pt_get_stats", "pt_reset_stats", "pt_get_block_counts",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_ranks", "pt_comm_destroy", "pt_film_present",
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
@@ -177,6 +183,11 @@ def lib_amd():
             L.pt_film_enable_aov.argtypes = [vp, C.POINTER(vp)]
             L.pt_render_aov.argtypes = [vp, vp, C.POINTER(Params)]
             L.pt_film_read_aov.argtypes = [vp, C.c_uint32, vp]
+        if hasattr(L, "pt_film_denoise"):   # (the denoiser; dev A/B runs load older builds through PT_LIB_AMD)
+            L.pt_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
+            L.pt_denoise_params_default.restype = None
+            L.pt_film_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, C.POINTER(C.c_float)]
+            L.pt_film_read_denoised.argtypes = [vp, vp, vp]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -313,6 +324,12 @@ def default_params(**kw):
             if not hasattr(p, k):
                 raise AttributeError(k)
             setattr(p, k, v)
+    return p
+
+
+def denoise_default_params():
+    p = DenoiseParams()
+    lib_amd().pt_denoise_params_default(C.byref(p))
     return p
 
 
@@ -502,6 +519,32 @@ class Film:
         else:
             a = np.zeros((self.height, self.width, 3), dtype=np.float32)  # (the library refuses the index)
         self.ctx._check(lib_amd().pt_film_read_aov(self.h, which, a.ctypes.data))
+        return a
+
+    def denoise(self, iterations=None, sigma_normal=None, sigma_depth=None, device_out=None, params=None):
+        """The a-trous filter of include/pt_api.h pt_film_denoise over the film and its guide planes -> device ms.  Arguments left at
+        None take pt_denoise_params_default's values (or `params`, a DenoiseParams, as it stands).  device_out: None for a plane the
+        film owns (read_denoised), or a device pointer to width*height*3 floats (a torch tensor's data_ptr())."""
+        p = params if params is not None else denoise_default_params()
+        if iterations is not None:
+            p.iterations = iterations
+        if sigma_normal is not None:
+            p.sigma_normal = sigma_normal
+        if sigma_depth is not None:
+            p.sigma_depth = sigma_depth
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_film_denoise(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
+        return ms.value
+
+    def read_denoised(self):
+        """-> float32 [H, W, 3]: the film-owned result of the last denoise(device_out=None)."""
+        a = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        self.ctx._check(lib_amd().pt_film_read_denoised(self.h, a.ctypes.data, None))
+        return a
+
+    def read_denoised_bgra8(self):
+        a = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self.ctx._check(lib_amd().pt_film_read_denoised(self.h, None, a.ctypes.data))
         return a
 
     def close(self):

@@ -1,0 +1,221 @@
+// denoise.hip -- pt_film_denoise: the guide-driven edge-avoiding a-trous filter of include/pt_api.h over the radiance film.
+//
+// The definition (demodulation, the 5 x 5 taps at step 2^k in the order j outer / i inner, the t^16 weight, remodulation, the bgra8
+// form) is the header's; tests/test_denoise.py restates it in numpy and every comparison is byte equality.  So every operation here is
+// one binary32 operation in the written order (-ffp-contract=off, __fdiv_rn), and nothing is reassociated.
+//
+//   k_dn_prepare   one pass over the film and the five float guide planes (56 B per pixel, eleven scalar loads from six arrays) -> two
+//                  16-B records per pixel: illum {I.rgb, 0} and guide {N.xyz, Z}.  A tap of the iterations is then two 128-bit loads.
+//   k_dn_atrous    one launch per iteration, ping-ponging the illum records.  A block is 64 x 4 pixels, a wave one row of 64: every tap
+//                  of a wave is 64 consecutive 16-B records (1 KiB per load instruction) at any step, and the row test of a tap is
+//                  wave-uniform.  The last launch divides, remodulates (D and E from the planes again), writes `out` and its bgra8 form.
+#include "pt_internal.h"
+#include "pt_math.h"
+
+#include <cmath>
+
+namespace {
+
+struct DnConst {
+    uint32_t w, h, n_bx;  // image, blocks per row of blocks
+    int32_t step;         // 2^k
+    float inv_n, sz2;     // 1 / (sigma_normal * sigma_normal), sigma_depth * sigma_depth
+};
+struct DnPlanes {
+    const float *film, *albedo, *normal, *emission, *depth, *alpha;
+};
+struct DnOut {
+    float *rgb;      // w*h*3
+    uchar4 *bgra;    // w*h, or null (a caller-owned output has no bgra8 form)
+};
+constexpr int DN_BW = 64, DN_BH = TB / DN_BW;  // pixels of a block
+
+__device__ __forceinline__ float dn_demod(float a, float alpha) { return fmaxf(a + (1.0f - alpha), 0.001f); }
+
+__global__ __launch_bounds__(TB) void k_dn_prepare(uint32_t n_pix, DnPlanes pl, float4 *__restrict__ illum, float4 *__restrict__ guide)
+{
+    const uint32_t p = blockIdx.x * TB + threadIdx.x;
+    if (p >= n_pix) return;
+    const size_t p3 = 3 * (size_t)p;
+    const float al = pl.alpha[p];
+    const float ir = ptm::fdiv(pl.film[p3 + 0] - pl.emission[p3 + 0], dn_demod(pl.albedo[p3 + 0], al));
+    const float ig = ptm::fdiv(pl.film[p3 + 1] - pl.emission[p3 + 1], dn_demod(pl.albedo[p3 + 1], al));
+    const float ib = ptm::fdiv(pl.film[p3 + 2] - pl.emission[p3 + 2], dn_demod(pl.albedo[p3 + 2], al));
+    illum[p] = make_float4(ir, ig, ib, 0.f);
+    guide[p] = make_float4(pl.normal[p3 + 0], pl.normal[p3 + 1], pl.normal[p3 + 2], pl.depth[p]);
+}
+
+// k_resolve's clamp and quantise (shade_kernels.hip to_unorm8)
+__device__ __forceinline__ uint8_t dn_unorm8(float c)
+{
+    if (!(c > 0.0f)) return 0;
+    if (c > 1.0f) c = 1.0f;
+    return (uint8_t)(c * 255.0f + 0.5f);
+}
+
+struct DnSum {
+    float r = 0.f, g = 0.f, b = 0.f, den = 0.f;
+};
+// one tap: the weight of q seen from p, then the four adds
+__device__ __forceinline__ void dn_tap(DnSum &s, const DnConst &dc, float hh, const float4 gp, const float4 gq, const float4 iq)
+{
+    const float dx = gp.x - gq.x, dy = gp.y - gq.y, dz3 = gp.z - gq.z;
+    const float xn = ((dx * dx + dy * dy) + dz3 * dz3) * dc.inv_n;
+    const float dz = gp.w - gq.w;
+    const float xz = ptm::fdiv(dz * dz, dc.sz2 * (gp.w * gp.w + gq.w * gq.w) + 1e-12f);
+    float t = fmaxf(0.0f, 1.0f - (xn + xz) * 0.0625f);
+    t = t * t; t = t * t; t = t * t; t = t * t;
+    const float w = hh * t;
+    s.r = s.r + w * iq.x;
+    s.g = s.g + w * iq.y;
+    s.b = s.b + w * iq.z;
+    s.den = s.den + w;
+}
+__device__ __forceinline__ constexpr float dn_h(int k) { return k == 0 ? 0.375f : (k == 1 || k == -1) ? 0.25f : 0.0625f; }
+
+// I' = num / den; the last iteration goes on to out = I' * D + E and the bgra8 form
+template <bool LAST>
+__device__ __forceinline__ void dn_finish(const DnSum &s, size_t p, float4 *__restrict__ illum_out, const DnPlanes &pl, const DnOut &o)
+{
+    const float ir = ptm::fdiv(s.r, s.den), ig = ptm::fdiv(s.g, s.den), ib = ptm::fdiv(s.b, s.den);
+    if (!LAST) {
+        illum_out[p] = make_float4(ir, ig, ib, 0.f);
+        return;
+    }
+    const size_t p3 = 3 * p;
+    const float al = pl.alpha[p];
+    const float r = ir * dn_demod(pl.albedo[p3 + 0], al) + pl.emission[p3 + 0];
+    const float g = ig * dn_demod(pl.albedo[p3 + 1], al) + pl.emission[p3 + 1];
+    const float b = ib * dn_demod(pl.albedo[p3 + 2], al) + pl.emission[p3 + 2];
+    o.rgb[p3 + 0] = r; o.rgb[p3 + 1] = g; o.rgb[p3 + 2] = b;
+    if (o.bgra) o.bgra[p] = make_uchar4(dn_unorm8(b), dn_unorm8(g), dn_unorm8(r), 255);
+}
+
+template <bool LAST>
+__global__ __launch_bounds__(TB) void k_dn_atrous(DnConst dc, const float4 *__restrict__ guide, const float4 *__restrict__ illum_in,
+                                                  float4 *__restrict__ illum_out, DnPlanes pl, DnOut o)
+{
+    const uint32_t by = blockIdx.x / dc.n_bx, bx = blockIdx.x - by * dc.n_bx;
+    const int x = (int)(bx * DN_BW + (threadIdx.x & (DN_BW - 1))), y = (int)(by * DN_BH + threadIdx.x / DN_BW);
+    const int w = (int)dc.w, h = (int)dc.h, s = dc.step;
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * dc.w + (uint32_t)x;
+    const float4 gp = guide[p];
+    DnSum sum;
+#pragma unroll
+    for (int j = -2; j <= 2; j++) {
+        const int qy = y + s * j;
+        if (qy < 0 || qy >= h) continue;  // (the same for the whole wave: a wave is one row)
+        // the row's ten loads first, from addresses clamped into the row, so that they are in flight together; a tap outside the image
+        // is then skipped as a whole (its clamped operands are never used)
+        const float4 *grow = guide + (size_t)qy * dc.w, *irow = illum_in + (size_t)qy * dc.w;
+        float4 gq[5], iq[5];
+#pragma unroll
+        for (int i = -2; i <= 2; i++) {
+            const int qc = min(max(x + s * i, 0), w - 1);
+            gq[i + 2] = grow[qc];
+            iq[i + 2] = irow[qc];
+        }
+#pragma unroll
+        for (int i = -2; i <= 2; i++) {
+            const int qx = x + s * i;
+            if (qx >= 0 && qx < w) dn_tap(sum, dc, dn_h(j) * dn_h(i), gp, gq[i + 2], iq[i + 2]);
+        }
+    }
+    dn_finish<LAST>(sum, p, illum_out, pl, o);
+}
+
+// One picker for the family.  (An LDS-tiled form for steps 1 and 2 -- a block staging the (64 + 4 s) x (16 + 4 s) records its taps touch --
+// was built and measured against this one on the same tree: same bytes, 4 % slower at step 1 and 12 % slower at step 2 on a 1080p
+// frame, so it is not kept.  DESIGN.md section 13 has both sets of numbers.)
+using DnAtrousFn = decltype(&k_dn_atrous<false>);
+DnAtrousFn pick_dn_atrous(bool last) { return last ? k_dn_atrous<true> : k_dn_atrous<false>; }
+
+// n buffers or none, so that a refused call leaves the film as it was.  The film's workspaces stay within the context's memory budget
+// together: the rule of film_work.hip work_alloc, as aov.hip follows it.
+pt_status dn_alloc(pt_film *f, void **ptrs, const size_t *bytes, int n)
+{
+    pt_ctx *ctx = f->ctx;
+    size_t total = 0;
+    for (int k = 0; k < n; k++) total += bytes[k];
+    const size_t held = f->work.bytes + f->aov.bytes + f->dn.bytes;
+    if (ctx->mem_budget && held + total > ctx->mem_budget) {
+        ctx->err = "denoiser workspace exceeds the memory budget (" + std::to_string((held + total) >> 20) + " MB wanted, " + std::to_string(ctx->mem_budget >> 20) +
+                   " MB allowed)";
+        return PT_ERR_OOM;
+    }
+    for (int k = 0; k < n; k++) {
+        const hipError_t e = hipMalloc(&ptrs[k], bytes[k]);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            for (int m = 0; m < k; m++) (void)hipFree(ptrs[m]);
+            ctx->err = std::string("hipMalloc of ") + std::to_string(total >> 20) + " MB of denoiser workspace: " + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP;
+        }
+    }
+    f->dn.bytes += total;
+    return PT_OK;
+}
+
+}  // namespace
+
+void ptd_free(pt_film *f)
+{
+    pt_film::Denoise &d = f->dn;
+    (void)hipFree(d.d_guide); (void)hipFree(d.d_illum[0]); (void)hipFree(d.d_illum[1]); (void)hipFree(d.d_out); (void)hipFree(d.d_out_bgra);
+    d = pt_film::Denoise{};
+}
+
+pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms)
+{
+    pt_ctx *ctx = f->ctx;
+    pt_film::Denoise &d = f->dn;
+    if (!f->aov.enabled) { ctx->err = "the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first"; return PT_ERR_INVALID_ARG; }
+    if (p->iterations < 1 || p->iterations > 8) { ctx->err = "pt_denoise_params.iterations must be in 1..8"; return PT_ERR_INVALID_ARG; }
+    if (!(std::isfinite(p->sigma_normal) && p->sigma_normal > 0.f) || !(std::isfinite(p->sigma_depth) && p->sigma_depth > 0.f)) {
+        ctx->err = "pt_denoise_params.sigma_normal / sigma_depth must be finite and > 0";
+        return PT_ERR_INVALID_ARG;
+    }
+    for (uint32_t r : p->reserved)
+        if (r) { ctx->err = "pt_denoise_params.reserved must be 0"; return PT_ERR_INVALID_ARG; }
+    const size_t n_pix = (size_t)f->w * f->h;
+    if (!d.d_guide) {
+        void *ptrs[3] = {};
+        const size_t bytes[3] = { sizeof(float4) * n_pix, sizeof(float4) * n_pix, sizeof(float4) * n_pix };
+        const pt_status rc = dn_alloc(f, ptrs, bytes, 3);
+        if (rc != PT_OK) return rc;
+        d.d_guide = static_cast<float4 *>(ptrs[0]); d.d_illum[0] = static_cast<float4 *>(ptrs[1]); d.d_illum[1] = static_cast<float4 *>(ptrs[2]);
+    }
+    if (!device_out && !d.d_out) {
+        void *ptrs[2] = {};
+        const size_t bytes[2] = { sizeof(float) * 3 * n_pix, 4 * n_pix };
+        const pt_status rc = dn_alloc(f, ptrs, bytes, 2);
+        if (rc != PT_OK) return rc;
+        d.d_out = static_cast<float *>(ptrs[0]); d.d_out_bgra = static_cast<uint8_t *>(ptrs[1]);
+    }
+    const pt_film::Aov &a = f->aov;
+    const DnPlanes pl = { f->d_rgb, static_cast<const float *>(a.plane[PT_AOV_ALBEDO]), static_cast<const float *>(a.plane[PT_AOV_NORMAL]),
+                          static_cast<const float *>(a.plane[PT_AOV_EMISSION]), static_cast<const float *>(a.plane[PT_AOV_DEPTH]),
+                          static_cast<const float *>(a.plane[PT_AOV_ALPHA]) };
+    const DnOut out = { device_out ? static_cast<float *>(device_out) : d.d_out, device_out ? nullptr : reinterpret_cast<uchar4 *>(d.d_out_bgra) };
+    DnConst dc{};
+    dc.w = f->w; dc.h = f->h;
+    dc.n_bx = (f->w + DN_BW - 1) / DN_BW;
+    dc.inv_n = 1.0f / (p->sigma_normal * p->sigma_normal);
+    dc.sz2 = p->sigma_depth * p->sigma_depth;
+    hipStream_t st = ctx->stream;
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    k_dn_prepare<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, d.d_illum[0], d.d_guide);
+    const uint32_t n_blocks = dc.n_bx * ((f->h + DN_BH - 1) / DN_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
+    for (uint32_t k = 0; k < p->iterations; k++) {
+        dc.step = 1 << k;
+        hipLaunchKernelGGL(pick_dn_atrous(k + 1 == p->iterations), dim3(n_blocks), dim3(TB), 0, st, dc, d.d_guide, d.d_illum[k & 1], d.d_illum[(k & 1) ^ 1], pl, out);
+    }
+    PT_HIP(ctx, hipGetLastError());
+    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipGetLastError());
+    if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
+    if (!device_out) d.have_out = true;
+    return PT_OK;
+}

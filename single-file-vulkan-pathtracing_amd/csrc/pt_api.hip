@@ -356,6 +356,7 @@ void pt_film_destroy(pt_film *f)
     if (!f) return;
     ptw_free_work(f);
     pta_free(f);
+    ptd_free(f);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
     delete f;
@@ -419,6 +420,33 @@ pt_status pt_film_read_aov(pt_film *f, uint32_t which, void *host_out)
     if (which >= PT_AOV_COUNT) { ctx->err = "unknown guide buffer"; return PT_ERR_INVALID_ARG; }
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     PT_HIP(ctx, hipMemcpy(host_out, f->aov.plane[which], pta_plane_bytes(f, which), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+void pt_denoise_params_default(pt_denoise_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->iterations = 5;
+    p->sigma_normal = 0.5f;
+    p->sigma_depth = 0.1f;
+}
+
+pt_status pt_film_denoise(pt_film *f, const pt_denoise_params *p, void *device_out_rgb_f32, float *device_ms)
+{
+    if (!f || !p) return PT_ERR_INVALID_ARG;
+    PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return guarded(f->ctx, [&] { return ptd_denoise(f, p, device_out_rgb_f32, device_ms); });
+}
+
+pt_status pt_film_read_denoised(pt_film *f, float *rgb, uint8_t *bgra)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (!f->dn.have_out) { ctx->err = "no denoised image: pt_film_denoise with a NULL output first"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rgb) PT_HIP(ctx, hipMemcpy(rgb, f->dn.d_out, sizeof(float) * 3 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
+    if (bgra) PT_HIP(ctx, hipMemcpy(bgra, f->dn.d_out_bgra, 4 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

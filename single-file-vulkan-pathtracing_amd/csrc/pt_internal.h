@@ -204,6 +204,16 @@ struct pt_film {
         size_t bytes = 0;                             // device bytes of the scratch
         uint64_t allocs = 0;
     } aov;
+    // pt_film_denoise (denoise.hip).  The scratch is the film's, allocated by the first call and kept: later calls allocate nothing
+    // (the film-owned output comes with the first call that asks for it).
+    struct Denoise {
+        float4 *d_guide = nullptr;                    // per pixel {N.xyz, Z}
+        float4 *d_illum[2] = { nullptr, nullptr };    // per pixel {I.rgb, 0}: the ping-pong planes of the iterations
+        float *d_out = nullptr;                       // film-owned result, w*h*3 floats ...
+        uint8_t *d_out_bgra = nullptr;                // ... and its bgra8 form
+        bool have_out = false;                        // a denoise has written d_out / d_out_bgra
+        size_t bytes = 0;                             // device bytes of all of the above
+    } dn;
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -247,3 +257,6 @@ pt_status pta_render(pt_scene *s, pt_film *f, const pt_params *p);
 pt_status pta_clear(pt_film *f, hipStream_t st);   // zeroes the planes (queued on st; no-op without guides)
 size_t pta_plane_bytes(const pt_film *f, uint32_t which);
 void pta_free(pt_film *f);
+// denoise.hip: the a-trous filter over the film and its guide planes
+pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms);
+void ptd_free(pt_film *f);

@@ -5,7 +5,7 @@
 //
 //   pt_main [--obj assets/CornellBox-Original.obj] [--width 1024] [--height 1024]
 //           [--frames 1] [--spp 32] [--depth 8] [--device 0] [--batch N]
-//           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--pipeline auto|wavefront|fused|nee] [--nee]
+//           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--denoise [N]] [--pipeline auto|wavefront|fused|nee] [--nee]
 //           [--ranks N [--devices 0,1,...] [--selftest]]
 // --ranks N renders with N GPUs: one host thread and one context per GPU, the 8x8 pixel tiles interleaved over the
 // ranks (pt_params.rank/world), and ONE RCCL gather of the packed tiles to rank 0 per presented image
@@ -15,6 +15,9 @@
 // lives in LDS; --pipeline nee is PT_PIPELINE_WAVEFRONT_NEE as before.
 // --aov PREFIX (one rank): after the render, the guide buffers of the same frames (pt_render_aov: what a denoiser takes beside the
 // radiance) as PREFIX_albedo.pfm, PREFIX_normal.pfm and PREFIX_depth.pfm (the depth in all three channels).
+// --denoise [N] (one rank; implies the guide pass of --aov, whose files are written only with --aov): after the render, the a-trous
+// filter of pt_film_denoise with N iterations (default: pt_denoise_params_default's) over the film, written beside the normal output:
+// out.ppm -> out.denoised.ppm, out.pfm -> out.denoised.pfm.
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -47,7 +50,16 @@ struct Options {
     uint32_t ranks = 1;          // --ranks N: one host thread + one GPU per rank, tiles interleaved, RCCL gather to rank 0
     std::vector<int> devices;    // --devices a,b,...: HIP ordinals of the ranks (default 0..N-1)
     bool selftest = false;       // --selftest (with --ranks N): the presentation collective on a rank-coloured film before the render
+    int denoise = -1;            // --denoise [N]: -1 off, 0 the library's default iterations, else N
 };
+
+// out.ppm -> out.denoised.ppm
+std::string denoised_name(const std::string &path)
+{
+    const size_t dot = path.find_last_of('.'), slash = path.find_last_of('/');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return path + ".denoised";
+    return path.substr(0, dot) + ".denoised" + path.substr(dot);
+}
 
 // --ranks N: the ranks agree on success before every collective (ncclCommInitRank, the gather inside pt_film_present): a rank
 // that failed on its own -- bad ordinal, out of memory, a failed render -- would otherwise leave its peers waiting inside the
@@ -156,7 +168,7 @@ void run_rank(const Options &o, const pth_scene &hs, uint32_t rank, const pt_uni
         const auto t1 = std::chrono::steady_clock::now();
         res.render_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
         if (ok) pt_get_stats(ctx, &res.st);
-        if (ok && !o.aov.empty()) {  // the guides of the same frames, through the existing PFM writer
+        if (ok && (!o.aov.empty() || o.denoise >= 0)) {  // the guides of the same frames, through the existing PFM writer
             pt_params g = p;
             g.flags = 0;
             if (g.pipeline == PT_PIPELINE_WAVEFRONT_NEE) g.pipeline = PT_PIPELINE_AUTO;  // (the guides do not depend on the estimator)
@@ -166,14 +178,24 @@ void run_rank(const Options &o, const pth_scene &hs, uint32_t rank, const pt_uni
             if (pt_film_enable_aov(film, nullptr) != PT_OK) { fail("pt_film_enable_aov"); ok = false; }
             else if (pt_render_aov(scene, film, &g) != PT_OK) { fail("pt_render_aov"); ok = false; }
             for (const auto &[which, suffix] : rgb_planes) {
-                if (!ok) break;
+                if (!ok || o.aov.empty()) break;
                 if (pt_film_read_aov(film, which, plane.data()) != PT_OK) { fail("pt_film_read_aov"); ok = false; }
                 else if (pth_write_pfm((o.aov + suffix).c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + o.aov + suffix; ok = false; }
             }
-            if (ok && pt_film_read_aov(film, PT_AOV_DEPTH, depth.data()) != PT_OK) { fail("pt_film_read_aov"); ok = false; }
-            if (ok) {
+            if (ok && !o.aov.empty() && pt_film_read_aov(film, PT_AOV_DEPTH, depth.data()) != PT_OK) { fail("pt_film_read_aov"); ok = false; }
+            if (ok && !o.aov.empty()) {
                 for (size_t i = 0; i < np; i++) plane[3 * i] = plane[3 * i + 1] = plane[3 * i + 2] = depth[i];
                 if (pth_write_pfm((o.aov + "_depth.pfm").c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + o.aov + "_depth.pfm"; ok = false; }
+            }
+            if (ok && o.denoise >= 0) {  // the filtered image beside the normal output; the film itself stays as rendered
+                pt_denoise_params dp;
+                pt_denoise_params_default(&dp);
+                if (o.denoise > 0) dp.iterations = (uint32_t)o.denoise;
+                std::vector<uint8_t> bgra(4 * np);
+                if (pt_film_denoise(film, &dp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise"); ok = false; }
+                else if (pt_film_read_denoised(film, plane.data(), bgra.data()) != PT_OK) { fail("pt_film_read_denoised"); ok = false; }
+                else if (!o.ppm.empty() && pth_write_ppm_bgra8(denoised_name(o.ppm).c_str(), bgra.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.ppm); ok = false; }
+                else if (!o.pfm.empty() && pth_write_pfm(denoised_name(o.pfm).c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.pfm); ok = false; }
             }
         }
         // the presented image lives in its own device buffer on rank 0 (main.cpp:661-667 copies the storage image)
@@ -244,12 +266,17 @@ int main(int argc, char **argv)
         else if (a == "--ppm") o.ppm = val();
         else if (a == "--pfm") o.pfm = val();
         else if (a == "--aov") o.aov = val();
+        else if (a == "--denoise") {  // the count is optional
+            o.denoise = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') o.denoise = std::atoi(argv[++i]);
+        }
         else die("unknown option " + a);
     }
     if (o.ranks > 1) {
         if (o.devices.empty()) for (uint32_t r = 0; r < o.ranks; r++) o.devices.push_back((int)r);
         if (o.devices.size() != o.ranks) die("--devices needs one ordinal per rank");
         if (!o.aov.empty()) die("--aov writes the guide buffers of one rank (no --ranks)");
+        if (o.denoise >= 0) die("--denoise filters the film of one rank (no --ranks): a rank's film holds only its own tiles");
     }
 
     char err[512] = { 0 };
