@@ -200,7 +200,7 @@ pt_status pt_film_create(pt_ctx *ctx, uint32_t width, uint32_t height, pt_film *
  * a torch tensor's data_ptr(), so a collective can reduce it in place.                      */
 pt_status pt_film_create_external(pt_ctx *ctx, uint32_t width, uint32_t height,
                                   void *device_rgb_f32, pt_film **out);
-pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov) */
+pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov and the plane of pt_film_enable_moments) */
 /* rgb: width*height*3 floats, row-major, linear radiance mean over all frames so far.       */
 pt_status pt_film_read_f32(pt_film *film, float *rgb);
 /* bgra: width*height*4 bytes = what main.cpp:661-667 copies to the swapchain.               */
@@ -365,6 +365,54 @@ pt_status pt_film_denoise(pt_film *film, const pt_denoise_params *params, void *
 /* The film-owned result of the last pt_film_denoise(..., NULL, ...): rgb width*height*3 floats, bgra width*height*4 bytes; either may
  * be NULL.  PT_ERR_INVALID_ARG before any denoise into the film's own plane.                                                     */
 pt_status pt_film_read_denoised(pt_film *film, float *rgb, uint8_t *bgra);
+
+/* ---- second-moment plane and the variance-guided form of the filter ---------------------------------------------------------
+ * pt_film_enable_moments gives the film a plane M of width*height*3 floats, zeroed: device_m2_f32 NULL for a plane the film owns, or
+ * caller-owned DEVICE memory of that size (a torch tensor's data_ptr()).  Once per film: a second call is PT_ERR_INVALID_ARG.  Like
+ * the guide planes of pt_film_enable_aov it is a film plane, not a workspace: it is not counted against pt_tuning.mem_budget_mb.
+ * From then on every frame pt_render resolves into this film also blends M, with c the frame's colour (sum / spp, per channel):
+ *                  M_new = (c*c + M_old * (float)frame) / (float)(frame + 1)        (M_old not read when frame == 0)
+ * -- the film's blend applied to c*c, binary32, every operation rounded on its own, no contraction -- in the same launch as the
+ * film's blend (so PT_FLAG_ASYNC renders queue it with the resolve, and a batch redone after a term-log overflow blends it once).
+ * The film, the rgba8 image, the ray counts and pt_stats of a render do not depend on whether the plane exists.  The film records
+ * frames = params.frame + params.frame_count of its last pt_render; pt_film_clear zeroes M and frames.
+ * Precondition: enable the plane while the film is empty -- before its frame 0, or straight after pt_film_clear.  The call does not
+ * look at what the film holds: on a film that already has frames M starts at 0 beside a C that does not, M < C*C, v clamps to 0 and
+ * the colour stop of pt_film_denoise_variance turns into a hard stop that keeps the noise.
+ * pt_film_read_moments: m2 (width*height*3 floats) and frames, either may be NULL; PT_ERR_INVALID_ARG on a film without the plane. */
+pt_status pt_film_enable_moments(pt_film *film, void *device_m2_f32);
+pt_status pt_film_read_moments(pt_film *film, float *m2, uint32_t *frames);
+/* pt_film_denoise_variance: pt_film_denoise with a colour stop scaled by the per-pixel variance of the film's mean, which the filter
+ * carries along and propagates.  C, D, I, A, N, E, Z, a, h and the terms x_n and x_z are exactly those of pt_film_denoise; all
+ * arithmetic is binary32, operation order as written.  n = params.frames, or what the film recorded when that is 0; n >= 2.
+ *   variance of the mean, per channel    v_c = max(M_c - C_c*C_c, 0) / (float)(n - 1)
+ *   demodulated and summed               V0  = ((v_r / (D_r*D_r)) + (v_g / (D_g*D_g))) + (v_b / (D_b*D_b))
+ *                  (the expected squared distance of I from its mean: two pixels of equal true value differ by V_p + V_q in expectation)
+ *   pre-blur, once: g = {1/4, 1/2, 1/4}, S = W = 0; for j = -1 .. 1 (outer), i = -1 .. 1 (inner), taps outside the image skipped:
+ *                  S = S + (g_j*g_i) * V0(q);   W = W + (g_j*g_i);   V = S / W
+ *   iteration k: taps and order as in pt_film_denoise; per tap, with I_p, V_p, V_q those of the iteration's input:
+ *                  di  = I_p - I_q
+ *                  x_c = ((di.r*di.r + di.g*di.g) + di.b*di.b) / ((sigma_color*sigma_color) * (V_p + V_q) + 1e-12f)
+ *                  t   = max(0, 1 - ((x_n + x_z) + x_c) * 0.0625f);   t = t*t, four times;   w = (h_j*h_i) * t
+ *                  num_c = num_c + w * I_c(q);   den = den + w;   vnum = vnum + (w*w) * V_q
+ *                  I'_c(p) = num_c / den;   V'(p) = vnum / (den*den)
+ *   remodulation and the bgra8 form as in pt_film_denoise.
+ * An infinite x_c gives weight 0; NaN inputs are outside the contract.  sigma_color is in standard deviations of the difference of two
+ * pixels: 1 keeps the noise, 8 oversmooths (DESIGN.md section 14 has the experiment the default comes from).  Placement, blocking,
+ * scratch ownership (V rides in the spare word of the illumination records: the same 48 B per pixel), budget, device_ms and the caveat
+ * about (rank, world) films are those of pt_film_denoise; the film-owned result is read through pt_film_read_denoised.
+ * PT_ERR_INVALID_ARG: NULL film or params; a film without guides or without the second-moment plane; frames resolving below 2;
+ * iterations outside 1..8; a sigma that is not finite and > 0; a nonzero reserved word.  A refused call writes no result.        */
+typedef struct pt_denoise_variance_params {
+    uint32_t iterations;       /* 1..8; default 5 */
+    float sigma_normal;        /* default 0.5  */
+    float sigma_depth;         /* default 0.1  */
+    float sigma_color;         /* default 3.0: in standard deviations of the difference of two pixels */
+    uint32_t frames;           /* n: frames the film and M average; 0 = what the film recorded; must end up >= 2 */
+    uint32_t reserved[3];      /* must be 0 */
+} pt_denoise_variance_params;
+void pt_denoise_variance_params_default(pt_denoise_variance_params *p);
+pt_status pt_film_denoise_variance(pt_film *film, const pt_denoise_variance_params *params, void *device_out_rgb_f32, float *device_ms);
 
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {

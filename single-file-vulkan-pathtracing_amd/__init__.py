@@ -101,6 +101,12 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
+class DenoiseVarianceParams(C.Structure):
+    """include/pt_api.h pt_denoise_variance_params: the variance-guided filter of pt_film_denoise_variance."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_color", C.c_float),
+                ("frames", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class HostScene(C.Structure):
     _fields_ = [("vertices", C.POINTER(C.c_float)), ("n_verts", C.c_uint32), ("indices", C.POINTER(C.c_uint32)),
                 ("n_tris", C.c_uint32), ("faces", C.POINTER(C.c_float))]
@@ -122,6 +128,7 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_film_read_f32", "pt_film_read_bgra8", "pt_film_destroy", "pt_params_default", "pt_render",
                "pt_render_prepare", "pt_trace", "pt_film_enable_aov", "pt_render_aov", "pt_film_read_aov",
                "pt_denoise_params_default", "pt_film_denoise", "pt_film_read_denoised",
+               "pt_film_enable_moments", "pt_film_read_moments", "pt_denoise_variance_params_default", "pt_film_denoise_variance",
                "pt_get_stats", "pt_reset_stats", "pt_get_block_counts",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_ranks", "pt_comm_destroy", "pt_film_present",
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
@@ -188,6 +195,12 @@ def lib_amd():
             L.pt_denoise_params_default.restype = None
             L.pt_film_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, C.POINTER(C.c_float)]
             L.pt_film_read_denoised.argtypes = [vp, vp, vp]
+        if hasattr(L, "pt_film_denoise_variance"):   # (the second-moment plane and its filter; as above)
+            L.pt_film_enable_moments.argtypes = [vp, vp]
+            L.pt_film_read_moments.argtypes = [vp, vp, C.POINTER(C.c_uint32)]
+            L.pt_denoise_variance_params_default.argtypes = [C.POINTER(DenoiseVarianceParams)]
+            L.pt_denoise_variance_params_default.restype = None
+            L.pt_film_denoise_variance.argtypes = [vp, C.POINTER(DenoiseVarianceParams), vp, C.POINTER(C.c_float)]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -330,6 +343,12 @@ def default_params(**kw):
 def denoise_default_params():
     p = DenoiseParams()
     lib_amd().pt_denoise_params_default(C.byref(p))
+    return p
+
+
+def denoise_variance_default_params():
+    p = DenoiseVarianceParams()
+    lib_amd().pt_denoise_variance_params_default(C.byref(p))
     return p
 
 
@@ -534,6 +553,32 @@ class Film:
             p.sigma_depth = sigma_depth
         ms = C.c_float(0.0)
         self.ctx._check(lib_amd().pt_film_denoise(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
+        return ms.value
+
+    def enable_moments(self, device_ptr=None):
+        """Gives the film its second-moment plane (include/pt_api.h pt_film_enable_moments): from now on pt_render blends the squared frame
+        colour into it.  device_ptr: None (the film allocates it) or a device pointer to width*height*3 floats of caller-owned memory.
+        Call it while the film is empty (before frame 0, or straight after clear())."""
+        self.ctx._check(lib_amd().pt_film_enable_moments(self.h, C.c_void_p(device_ptr) if device_ptr else None))
+
+    def read_moments(self):
+        """-> (float32 [H, W, 3], frames): the second-moment plane and the number of frames it and the film average."""
+        a = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        n = C.c_uint32(0)
+        self.ctx._check(lib_amd().pt_film_read_moments(self.h, a.ctypes.data, C.byref(n)))
+        return a, n.value
+
+    def denoise_variance(self, iterations=None, sigma_normal=None, sigma_depth=None, sigma_color=None, frames=None, device_out=None, params=None):
+        """The variance-guided filter of include/pt_api.h pt_film_denoise_variance over the film, its guide planes and its second-moment
+        plane -> device ms.  Arguments as in denoise(); frames: how many frames the film averages (None / 0: what pt_render recorded).
+        The film-owned result is read with read_denoised / read_denoised_bgra8."""
+        p = params if params is not None else denoise_variance_default_params()
+        for name, v in (("iterations", iterations), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_color", sigma_color),
+                        ("frames", frames)):
+            if v is not None:
+                setattr(p, name, v)
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_film_denoise_variance(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
         return ms.value
 
     def read_denoised(self):

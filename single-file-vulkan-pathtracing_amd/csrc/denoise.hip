@@ -9,6 +9,12 @@
 //   k_dn_atrous    one launch per iteration, ping-ponging the illum records.  A block is 64 x 4 pixels, a wave one row of 64: every tap
 //                  of a wave is 64 consecutive 16-B records (1 KiB per load instruction) at any step, and the row test of a tap is
 //                  wave-uniform.  The last launch divides, remodulates (D and E from the planes again), writes `out` and its bgra8 form.
+//
+// pt_film_denoise_variance is the same filter with the header's colour stop.  The variance V of a pixel rides in the spare word of its illum
+// record, so a tap is the same two 128-bit loads and the scratch the same 48 B per pixel:
+//   k_dn_prepare_var   k_dn_prepare, and V0 from the film's second-moment plane (+ 12 B per pixel read) into illum.w
+//   k_dn_var_blur      the 3 x 3 pre-blur of .w, from one ping-pong plane into the other (rgb copied)
+//   k_dn_atrous_var    k_dn_atrous with x_c in the weight, and V' = sum w^2 V_q / den^2 into .w
 #include "pt_internal.h"
 #include "pt_math.h"
 
@@ -45,6 +51,53 @@ __global__ __launch_bounds__(TB) void k_dn_prepare(uint32_t n_pix, DnPlanes pl, 
     guide[p] = make_float4(pl.normal[p3 + 0], pl.normal[p3 + 1], pl.normal[p3 + 2], pl.depth[p]);
 }
 
+// the same, and V0 = sum_c max(M_c - C_c^2, 0) / (n - 1) / D_c^2 into the record's fourth word (nm1 = (float)(n - 1))
+__global__ __launch_bounds__(TB) void k_dn_prepare_var(uint32_t n_pix, DnPlanes pl, const float *__restrict__ m2, float nm1, float4 *__restrict__ illum,
+                                                       float4 *__restrict__ guide)
+{
+    const uint32_t p = blockIdx.x * TB + threadIdx.x;
+    if (p >= n_pix) return;
+    const size_t p3 = 3 * (size_t)p;
+    const float al = pl.alpha[p];
+    float i3[3], v3[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float col = pl.film[p3 + c], d = dn_demod(pl.albedo[p3 + c], al);
+        i3[c] = ptm::fdiv(col - pl.emission[p3 + c], d);
+        v3[c] = ptm::fdiv(ptm::fdiv(fmaxf(m2[p3 + c] - col * col, 0.0f), nm1), d * d);
+    }
+    illum[p] = make_float4(i3[0], i3[1], i3[2], (v3[0] + v3[1]) + v3[2]);
+    guide[p] = make_float4(pl.normal[p3 + 0], pl.normal[p3 + 1], pl.normal[p3 + 2], pl.depth[p]);
+}
+
+// V = the 3 x 3 binomial mean of V0 over the taps inside the image (j outer, i inner); the record's rgb goes along
+__global__ __launch_bounds__(TB) void k_dn_var_blur(DnConst dc, const float4 *__restrict__ illum_in, float4 *__restrict__ illum_out)
+{
+    const uint32_t by = blockIdx.x / dc.n_bx, bx = blockIdx.x - by * dc.n_bx;
+    const int x = (int)(bx * DN_BW + (threadIdx.x & (DN_BW - 1))), y = (int)(by * DN_BH + threadIdx.x / DN_BW);
+    const int w = (int)dc.w, h = (int)dc.h;
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * dc.w + (uint32_t)x;
+    float4 rec = illum_in[p];
+    float sum = 0.f, wsum = 0.f;
+#pragma unroll
+    for (int j = -1; j <= 1; j++) {
+        const int qy = y + j;
+        if (qy < 0 || qy >= h) continue;
+        const float4 *row = illum_in + (size_t)qy * dc.w;
+#pragma unroll
+        for (int i = -1; i <= 1; i++) {
+            const int qx = x + i;
+            if (qx < 0 || qx >= w) continue;
+            const float g = (j == 0 ? 0.5f : 0.25f) * (i == 0 ? 0.5f : 0.25f);
+            sum = sum + g * (i == 0 && j == 0 ? rec.w : row[qx].w);
+            wsum = wsum + g;
+        }
+    }
+    rec.w = ptm::fdiv(sum, wsum);
+    illum_out[p] = rec;
+}
+
 // k_resolve's clamp and quantise (shade_kernels.hip to_unorm8)
 __device__ __forceinline__ uint8_t dn_unorm8(float c)
 {
@@ -71,15 +124,37 @@ __device__ __forceinline__ void dn_tap(DnSum &s, const DnConst &dc, float hh, co
     s.b = s.b + w * iq.z;
     s.den = s.den + w;
 }
+// the tap with the colour stop: ip = {I_p, V_p}, iq = {I_q, V_q}
+struct DnSumVar : DnSum {
+    float vnum = 0.f;
+};
+__device__ __forceinline__ void dn_tap_var(DnSumVar &s, const DnConst &dc, float sc2, float hh, const float4 gp, const float4 gq, const float4 ip, const float4 iq)
+{
+    const float dx = gp.x - gq.x, dy = gp.y - gq.y, dz3 = gp.z - gq.z;
+    const float xn = ((dx * dx + dy * dy) + dz3 * dz3) * dc.inv_n;
+    const float dz = gp.w - gq.w;
+    const float xz = ptm::fdiv(dz * dz, dc.sz2 * (gp.w * gp.w + gq.w * gq.w) + 1e-12f);
+    const float dr = ip.x - iq.x, dg = ip.y - iq.y, db = ip.z - iq.z;
+    const float xc = ptm::fdiv((dr * dr + dg * dg) + db * db, sc2 * (ip.w + iq.w) + 1e-12f);
+    float t = fmaxf(0.0f, 1.0f - ((xn + xz) + xc) * 0.0625f);
+    t = t * t; t = t * t; t = t * t; t = t * t;
+    const float w = hh * t;
+    s.r = s.r + w * iq.x;
+    s.g = s.g + w * iq.y;
+    s.b = s.b + w * iq.z;
+    s.den = s.den + w;
+    s.vnum = s.vnum + (w * w) * iq.w;
+}
 __device__ __forceinline__ constexpr float dn_h(int k) { return k == 0 ? 0.375f : (k == 1 || k == -1) ? 0.25f : 0.0625f; }
 
 // I' = num / den; the last iteration goes on to out = I' * D + E and the bgra8 form
-template <bool LAST>
-__device__ __forceinline__ void dn_finish(const DnSum &s, size_t p, float4 *__restrict__ illum_out, const DnPlanes &pl, const DnOut &o)
+// (vnum: the variance kernels' sum of w^2 V_q, for V' = vnum / den^2 in the record's fourth word)
+template <bool LAST, bool VAR = false>
+__device__ __forceinline__ void dn_finish(const DnSum &s, size_t p, float4 *__restrict__ illum_out, const DnPlanes &pl, const DnOut &o, float vnum = 0.f)
 {
     const float ir = ptm::fdiv(s.r, s.den), ig = ptm::fdiv(s.g, s.den), ib = ptm::fdiv(s.b, s.den);
     if (!LAST) {
-        illum_out[p] = make_float4(ir, ig, ib, 0.f);
+        illum_out[p] = make_float4(ir, ig, ib, VAR ? ptm::fdiv(vnum, s.den * s.den) : 0.f);
         return;
     }
     const size_t p3 = 3 * p;
@@ -125,11 +200,46 @@ __global__ __launch_bounds__(TB) void k_dn_atrous(DnConst dc, const float4 *__re
     dn_finish<LAST>(sum, p, illum_out, pl, o);
 }
 
+template <bool LAST>
+__global__ __launch_bounds__(TB) void k_dn_atrous_var(DnConst dc, float sc2, const float4 *__restrict__ guide, const float4 *__restrict__ illum_in,
+                                                      float4 *__restrict__ illum_out, DnPlanes pl, DnOut o)  // sc2 = sigma_color * sigma_color
+{
+    const uint32_t by = blockIdx.x / dc.n_bx, bx = blockIdx.x - by * dc.n_bx;
+    const int x = (int)(bx * DN_BW + (threadIdx.x & (DN_BW - 1))), y = (int)(by * DN_BH + threadIdx.x / DN_BW);
+    const int w = (int)dc.w, h = (int)dc.h, s = dc.step;
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * dc.w + (uint32_t)x;
+    const float4 gp = guide[p], ip = illum_in[p];
+    DnSumVar sum;
+#pragma unroll
+    for (int j = -2; j <= 2; j++) {
+        const int qy = y + s * j;
+        if (qy < 0 || qy >= h) continue;
+        const float4 *grow = guide + (size_t)qy * dc.w, *irow = illum_in + (size_t)qy * dc.w;
+        float4 gq[5], iq[5];
+#pragma unroll
+        for (int i = -2; i <= 2; i++) {
+            const int qc = min(max(x + s * i, 0), w - 1);
+            gq[i + 2] = grow[qc];
+            iq[i + 2] = irow[qc];
+        }
+#pragma unroll
+        for (int i = -2; i <= 2; i++) {
+            const int qx = x + s * i;
+            if (qx >= 0 && qx < w) dn_tap_var(sum, dc, sc2, dn_h(j) * dn_h(i), gp, gq[i + 2], ip, iq[i + 2]);
+        }
+    }
+    dn_finish<LAST, true>(sum, p, illum_out, pl, o, sum.vnum);
+}
+
 // One picker for the family.  (An LDS-tiled form for steps 1 and 2 -- a block staging the (64 + 4 s) x (16 + 4 s) records its taps touch --
 // was built and measured against this one on the same tree: same bytes, 4 % slower at step 1 and 12 % slower at step 2 on a 1080p
 // frame, so it is not kept.  DESIGN.md section 13 has both sets of numbers.)
+// The variance family has its own picker: its kernels take sigma_color^2 beside DnConst, whose layout the first family's ISA depends on.
 using DnAtrousFn = decltype(&k_dn_atrous<false>);
+using DnAtrousVarFn = decltype(&k_dn_atrous_var<false>);
 DnAtrousFn pick_dn_atrous(bool last) { return last ? k_dn_atrous<true> : k_dn_atrous<false>; }
+DnAtrousVarFn pick_dn_atrous_var(bool last) { return last ? k_dn_atrous_var<true> : k_dn_atrous_var<false>; }
 
 // n buffers or none, so that a refused call leaves the film as it was.  The film's workspaces stay within the context's memory budget
 // together: the rule of film_work.hip work_alloc, as aov.hip follows it.
@@ -157,27 +267,15 @@ pt_status dn_alloc(pt_film *f, void **ptrs, const size_t *bytes, int n)
     return PT_OK;
 }
 
-}  // namespace
-
-void ptd_free(pt_film *f)
-{
-    pt_film::Denoise &d = f->dn;
-    (void)hipFree(d.d_guide); (void)hipFree(d.d_illum[0]); (void)hipFree(d.d_illum[1]); (void)hipFree(d.d_out); (void)hipFree(d.d_out_bgra);
-    d = pt_film::Denoise{};
-}
-
-pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms)
+// Both filters: the scratch, then prepare (+ the pre-blur), the iterations, the wait.  var: null for pt_film_denoise.
+struct DnVariance {
+    float sigma_color;
+    uint32_t frames;
+};
+pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigma_depth, const DnVariance *var, void *device_out, float *device_ms)
 {
     pt_ctx *ctx = f->ctx;
     pt_film::Denoise &d = f->dn;
-    if (!f->aov.enabled) { ctx->err = "the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first"; return PT_ERR_INVALID_ARG; }
-    if (p->iterations < 1 || p->iterations > 8) { ctx->err = "pt_denoise_params.iterations must be in 1..8"; return PT_ERR_INVALID_ARG; }
-    if (!(std::isfinite(p->sigma_normal) && p->sigma_normal > 0.f) || !(std::isfinite(p->sigma_depth) && p->sigma_depth > 0.f)) {
-        ctx->err = "pt_denoise_params.sigma_normal / sigma_depth must be finite and > 0";
-        return PT_ERR_INVALID_ARG;
-    }
-    for (uint32_t r : p->reserved)
-        if (r) { ctx->err = "pt_denoise_params.reserved must be 0"; return PT_ERR_INVALID_ARG; }
     const size_t n_pix = (size_t)f->w * f->h;
     if (!d.d_guide) {
         void *ptrs[3] = {};
@@ -201,15 +299,24 @@ pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, 
     DnConst dc{};
     dc.w = f->w; dc.h = f->h;
     dc.n_bx = (f->w + DN_BW - 1) / DN_BW;
-    dc.inv_n = 1.0f / (p->sigma_normal * p->sigma_normal);
-    dc.sz2 = p->sigma_depth * p->sigma_depth;
+    dc.inv_n = 1.0f / (sigma_normal * sigma_normal);
+    dc.sz2 = sigma_depth * sigma_depth;
     hipStream_t st = ctx->stream;
-    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    k_dn_prepare<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, d.d_illum[0], d.d_guide);
     const uint32_t n_blocks = dc.n_bx * ((f->h + DN_BH - 1) / DN_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
-    for (uint32_t k = 0; k < p->iterations; k++) {
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    uint32_t in = 0;  // the ping-pong plane the first iteration reads
+    if (var) {
+        k_dn_prepare_var<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, f->m2.d_m2, (float)(var->frames - 1), d.d_illum[0], d.d_guide);
+        k_dn_var_blur<<<n_blocks, TB, 0, st>>>(dc, d.d_illum[0], d.d_illum[1]);
+        in = 1;
+    } else {
+        k_dn_prepare<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, d.d_illum[0], d.d_guide);
+    }
+    for (uint32_t k = 0; k < iterations; k++, in ^= 1u) {
         dc.step = 1 << k;
-        hipLaunchKernelGGL(pick_dn_atrous(k + 1 == p->iterations), dim3(n_blocks), dim3(TB), 0, st, dc, d.d_guide, d.d_illum[k & 1], d.d_illum[(k & 1) ^ 1], pl, out);
+        const bool last = k + 1 == iterations;
+        if (var) hipLaunchKernelGGL(pick_dn_atrous_var(last), dim3(n_blocks), dim3(TB), 0, st, dc, var->sigma_color * var->sigma_color, d.d_guide, d.d_illum[in], d.d_illum[in ^ 1u], pl, out);
+        else hipLaunchKernelGGL(pick_dn_atrous(last), dim3(n_blocks), dim3(TB), 0, st, dc, d.d_guide, d.d_illum[in], d.d_illum[in ^ 1u], pl, out);
     }
     PT_HIP(ctx, hipGetLastError());
     PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
@@ -218,4 +325,42 @@ pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, 
     if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
     if (!device_out) d.have_out = true;
     return PT_OK;
+}
+
+}  // namespace
+
+void ptd_free(pt_film *f)
+{
+    pt_film::Denoise &d = f->dn;
+    (void)hipFree(d.d_guide); (void)hipFree(d.d_illum[0]); (void)hipFree(d.d_illum[1]); (void)hipFree(d.d_out); (void)hipFree(d.d_out_bgra);
+    d = pt_film::Denoise{};
+}
+
+pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms)
+{
+    pt_ctx *ctx = f->ctx;
+    if (!f->aov.enabled) { ctx->err = "the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first"; return PT_ERR_INVALID_ARG; }
+    if (p->iterations < 1 || p->iterations > 8) { ctx->err = "pt_denoise_params.iterations must be in 1..8"; return PT_ERR_INVALID_ARG; }
+    if (!(std::isfinite(p->sigma_normal) && p->sigma_normal > 0.f) || !(std::isfinite(p->sigma_depth) && p->sigma_depth > 0.f)) {
+        ctx->err = "pt_denoise_params.sigma_normal / sigma_depth must be finite and > 0";
+        return PT_ERR_INVALID_ARG;
+    }
+    for (uint32_t r : p->reserved)
+        if (r) { ctx->err = "pt_denoise_params.reserved must be 0"; return PT_ERR_INVALID_ARG; }
+    return dn_run(f, p->iterations, p->sigma_normal, p->sigma_depth, nullptr, device_out, device_ms);
+}
+
+pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out, float *device_ms)
+{
+    pt_ctx *ctx = f->ctx;
+    if (!f->aov.enabled) { ctx->err = "the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first"; return PT_ERR_INVALID_ARG; }
+    if (!f->m2.d_m2) { ctx->err = "the film has no second-moment plane: pt_film_enable_moments before the frames are rendered"; return PT_ERR_INVALID_ARG; }
+    if (p->iterations < 1 || p->iterations > 8) { ctx->err = "pt_denoise_variance_params.iterations must be in 1..8"; return PT_ERR_INVALID_ARG; }
+    for (float sg : { p->sigma_normal, p->sigma_depth, p->sigma_color })
+        if (!(std::isfinite(sg) && sg > 0.f)) { ctx->err = "pt_denoise_variance_params.sigma_normal / sigma_depth / sigma_color must be finite and > 0"; return PT_ERR_INVALID_ARG; }
+    for (uint32_t r : p->reserved)
+        if (r) { ctx->err = "pt_denoise_variance_params.reserved must be 0"; return PT_ERR_INVALID_ARG; }
+    const DnVariance v = { p->sigma_color, p->frames ? p->frames : f->m2.frames };
+    if (v.frames < 2) { ctx->err = "pt_film_denoise_variance: a variance estimate needs a film of at least 2 frames (params.frames, or what pt_render recorded)"; return PT_ERR_INVALID_ARG; }
+    return dn_run(f, p->iterations, p->sigma_normal, p->sigma_depth, &v, device_out, device_ms);
 }

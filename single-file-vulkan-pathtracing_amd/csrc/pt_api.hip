@@ -329,6 +329,8 @@ pt_status pt_film_clear(pt_film *f)
     PT_HIP(ctx, hipMemsetAsync(f->d_bgra, 0, 4 * (size_t)f->w * f->h, ctx->stream));
     const pt_status rc = pta_clear(f, ctx->stream);  // the guide buffers, if the film has them
     if (rc != PT_OK) return rc;
+    if (f->m2.d_m2) PT_HIP(ctx, hipMemsetAsync(f->m2.d_m2, 0, sizeof(float) * 3 * (size_t)f->w * f->h, ctx->stream));
+    f->m2.frames = 0;
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -357,6 +359,7 @@ void pt_film_destroy(pt_film *f)
     ptw_free_work(f);
     pta_free(f);
     ptd_free(f);
+    if (f->m2.own) (void)hipFree(f->m2.d_m2);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
     delete f;
@@ -448,6 +451,61 @@ pt_status pt_film_read_denoised(pt_film *f, float *rgb, uint8_t *bgra)
     if (rgb) PT_HIP(ctx, hipMemcpy(rgb, f->dn.d_out, sizeof(float) * 3 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
     if (bgra) PT_HIP(ctx, hipMemcpy(bgra, f->dn.d_out_bgra, 4 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
     return PT_OK;
+}
+
+pt_status pt_film_enable_moments(pt_film *f, void *device_m2_f32)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (f->m2.d_m2) { ctx->err = "the film already has a second-moment plane"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    return guarded(ctx, [&]() -> pt_status {
+        const size_t bytes = sizeof(float) * 3 * (size_t)f->w * f->h;
+        void *plane = device_m2_f32;
+        if (!plane) {
+            const hipError_t e = hipMalloc(&plane, bytes);
+            if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PT_ERR_OOM; }
+        }
+        // (after the renders already queued, which do not know the plane)
+        hipError_t e = hipMemsetAsync(plane, 0, bytes, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            if (!device_m2_f32) (void)hipFree(plane);
+            ctx->err = std::string("pt_film_enable_moments: ") + hipGetErrorString(e);
+            return PT_ERR_HIP;
+        }
+        f->m2.d_m2 = static_cast<float *>(plane);
+        f->m2.own = device_m2_f32 == nullptr;
+        return PT_OK;
+    });
+}
+
+pt_status pt_film_read_moments(pt_film *f, float *m2, uint32_t *frames)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (!f->m2.d_m2) { ctx->err = "the film has no second-moment plane: pt_film_enable_moments first"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (m2) PT_HIP(ctx, hipMemcpy(m2, f->m2.d_m2, sizeof(float) * 3 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
+    if (frames) *frames = f->m2.frames;
+    return PT_OK;
+}
+
+void pt_denoise_variance_params_default(pt_denoise_variance_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->iterations = 5;
+    p->sigma_normal = 0.5f;
+    p->sigma_depth = 0.1f;
+    p->sigma_color = 3.0f;
+}
+
+pt_status pt_film_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out_rgb_f32, float *device_ms)
+{
+    if (!f || !p) return PT_ERR_INVALID_ARG;
+    PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return guarded(f->ctx, [&] { return ptd_denoise_variance(f, p, device_out_rgb_f32, device_ms); });
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)

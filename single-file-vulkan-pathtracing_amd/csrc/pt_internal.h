@@ -214,6 +214,13 @@ struct pt_film {
         bool have_out = false;                        // a denoise has written d_out / d_out_bgra
         size_t bytes = 0;                             // device bytes of all of the above
     } dn;
+    // pt_film_enable_moments: the running mean of the squared frame colour, blended by the resolve kernel beside the film (shade_kernels.hip
+    // k_resolve_m2).  A film plane like the guides, not a workspace.
+    struct Moments {
+        float *d_m2 = nullptr;                        // w*h*3 floats, or null: the film has no such plane
+        bool own = false;
+        uint32_t frames = 0;                          // frame + frame_count of the last pt_render: what the film and the plane average
+    } m2;
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -259,4 +266,5 @@ size_t pta_plane_bytes(const pt_film *f, uint32_t which);
 void pta_free(pt_film *f);
 // denoise.hip: the a-trous filter over the film and its guide planes
 pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms);
+pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out, float *device_ms);
 void ptd_free(pt_film *f);

@@ -461,7 +461,7 @@ pt_status batch_finish(Job &j, int pipes_now, unsigned long long rays_before)
         redo = flag != 0ull;
     }
     if (!redo) {
-        ptw_launch_resolve(j.rc, f->work.d_tiles, j.rad, f->d_rgb, f->d_bgra, st);
+        ptw_launch_resolve(j.rc, f->work.d_tiles, j.rad, f->d_rgb, f->d_bgra, st, nullptr, f->m2.d_m2);
         ctx->stats.launches_other++;
         return PT_OK;
     }
@@ -752,7 +752,7 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
         PT_HIP(ctx, hipGetLastError());
         ctx->stats.launches_extend++;
         ctx->stats.rounds++;
-        ptw_launch_resolve(rc, w.d_tiles, rad, f->d_rgb, f->d_bgra, st, sh.bounded ? d_overflow : nullptr);
+        ptw_launch_resolve(rc, w.d_tiles, rad, f->d_rgb, f->d_bgra, st, sh.bounded ? d_overflow : nullptr, f->m2.d_m2);
         ctx->stats.launches_other++;
         bool redo = false;
         if (sh.bounded) {
@@ -883,8 +883,9 @@ pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p_in)
     p_res.pipeline = resolve_pipeline(s, p_in, pl);
     const pt_params *p = &p_res;
     s->ctx->stats.pipeline = p->pipeline;
-    if (p->pipeline == PT_PIPELINE_FUSED) return render_fused(s, f, p, pl, false, false);
-    return render_wavefront(s, f, p, pl, false);
+    rc_ = p->pipeline == PT_PIPELINE_FUSED ? render_fused(s, f, p, pl, false, false) : render_wavefront(s, f, p, pl, false);
+    if (rc_ == PT_OK) f->m2.frames = (uint32_t)p->frame + p->frame_count;  // what the film and its second-moment plane now average
+    return rc_;
 }
 
 // (aov.hip: the same proof for the guide buffers' single kernel)

@@ -6,6 +6,7 @@
 //                   the other queue with wave ballots + one atomic per 512 paths                  (raygen.rgen:76-83)
 //     k_shadow_add  PT_PIPELINE_WAVEFRONT_NEE: the unoccluded light samples of a round
 //     k_resolve     replay of the term logs in sample order, /spp, the progressive blend, rgba8     (raygen.rgen:86-90)
+//     k_resolve_m2  the same, and the blend of the colour's square into the film's second-moment plane
 //     k_hits_to_api pt_trace: hit records in the public layout
 // One round of a pipeline = one closest-hit launch (extend_launch.hip) + one k_shade launch; render.hip schedules them.
 #include "wavefront_host.h"
@@ -441,8 +442,10 @@ __device__ __forceinline__ uint8_t to_unorm8(float c)
     return (uint8_t)(c * 255.0f + 0.5f);
 }
 
-__global__ __launch_bounds__(TB) void k_resolve(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad,
-                                                float *__restrict__ film, uint8_t *__restrict__ bgra, const unsigned long long *__restrict__ skip_if_set)
+// M2: the film has a second-moment plane (pt_film_enable_moments): the frame colour's square is blended into it like the colour into the film
+template <bool M2>
+__device__ __forceinline__ void resolve_pixel(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad, float *__restrict__ film,
+                                              uint8_t *__restrict__ bgra, const unsigned long long *__restrict__ skip_if_set, float *__restrict__ m2)
 {
     const uint32_t local = blockIdx.x * TB + threadIdx.x;
     if (local >= rc.slots_per_lane) return;
@@ -453,6 +456,8 @@ __global__ __launch_bounds__(TB) void k_resolve(RenderConst rc, const uint32_t *
     const size_t pix = (size_t)py * rc.width + px;
     float fr = film[3 * pix + 0], fg = film[3 * pix + 1], fb = film[3 * pix + 2];
     uchar4 img = reinterpret_cast<uchar4 *>(bgra)[pix];  // bytes B,G,R,A
+    float mr = 0.f, mg = 0.f, mb = 0.f;
+    if (M2) { mr = m2[3 * pix + 0]; mg = m2[3 * pix + 1]; mb = m2[3 * pix + 2]; }
     const float spp = (float)rc.spp;
     for (uint32_t f = 0; f < rc.lanes_active; f++) {
         float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -497,6 +502,11 @@ __global__ __launch_bounds__(TB) void k_resolve(RenderConst rc, const uint32_t *
         fr = ptm::fdiv(cr + (first ? 0.f : fr) * ff, f1);
         fg = ptm::fdiv(cg + (first ? 0.f : fg) * ff, f1);
         fb = ptm::fdiv(cb + (first ? 0.f : fb) * ff, f1);
+        if (M2) {  // the same blend of the colour's square
+            mr = ptm::fdiv(cr * cr + (first ? 0.f : mr) * ff, f1);
+            mg = ptm::fdiv(cg * cg + (first ? 0.f : mg) * ff, f1);
+            mb = ptm::fdiv(cb * cb + (first ? 0.f : mb) * ff, f1);
+        }
         // reference display image: rgba8 load -> blend -> clamp + quantise on store
         const float orr = first ? 0.f : ptm::fdiv((float)img.z, 255.0f);
         const float og = first ? 0.f : ptm::fdiv((float)img.y, 255.0f);
@@ -511,6 +521,19 @@ __global__ __launch_bounds__(TB) void k_resolve(RenderConst rc, const uint32_t *
     film[3 * pix + 1] = fg;
     film[3 * pix + 2] = fb;
     reinterpret_cast<uchar4 *>(bgra)[pix] = img;
+    if (M2) { m2[3 * pix + 0] = mr; m2[3 * pix + 1] = mg; m2[3 * pix + 2] = mb; }
+}
+
+__global__ __launch_bounds__(TB) void k_resolve(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad,
+                                                float *__restrict__ film, uint8_t *__restrict__ bgra, const unsigned long long *__restrict__ skip_if_set)
+{
+    resolve_pixel<false>(rc, tiles, rad, film, bgra, skip_if_set, nullptr);
+}
+
+__global__ __launch_bounds__(TB) void k_resolve_m2(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad, float *__restrict__ film,
+                                                   uint8_t *__restrict__ bgra, const unsigned long long *__restrict__ skip_if_set, float *__restrict__ m2)
+{
+    resolve_pixel<true>(rc, tiles, rad, film, bgra, skip_if_set, m2);
 }
 
 // hit records of the internal layout (sorted position) -> API layout (gl_PrimitiveID)
@@ -569,9 +592,11 @@ void ptw_launch_shadow_add(const ptw::RenderConst &rc, const ptw::Radiance &rad,
 }
 
 void ptw_launch_resolve(const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, float *film, uint8_t *bgra, hipStream_t st,
-                        const unsigned long long *skip_if_set)
+                        const unsigned long long *skip_if_set, float *m2)
 {
-    k_resolve<<<(rc.slots_per_lane + TB - 1) / TB, TB, 0, st>>>(rc, tiles, rad, film, bgra, skip_if_set);
+    const uint32_t grid = (rc.slots_per_lane + TB - 1) / TB;
+    if (m2) k_resolve_m2<<<grid, TB, 0, st>>>(rc, tiles, rad, film, bgra, skip_if_set, m2);
+    else k_resolve<<<grid, TB, 0, st>>>(rc, tiles, rad, film, bgra, skip_if_set);
 }
 
 void ptw_launch_hits_to_api(const float4 *hit, const float4 *tri4, const uint32_t *hit_inst, const uint32_t *inst_id, uint32_t n, pt_hit *out,

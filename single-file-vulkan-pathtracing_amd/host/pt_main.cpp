@@ -5,7 +5,7 @@
 //
 //   pt_main [--obj assets/CornellBox-Original.obj] [--width 1024] [--height 1024]
 //           [--frames 1] [--spp 32] [--depth 8] [--device 0] [--batch N]
-//           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--denoise [N]] [--pipeline auto|wavefront|fused|nee] [--nee]
+//           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--denoise [N] [--sigma-color S]] [--pipeline auto|wavefront|fused|nee] [--nee]
 //           [--ranks N [--devices 0,1,...] [--selftest]]
 // --ranks N renders with N GPUs: one host thread and one context per GPU, the 8x8 pixel tiles interleaved over the
 // ranks (pt_params.rank/world), and ONE RCCL gather of the packed tiles to rank 0 per presented image
@@ -17,7 +17,8 @@
 // radiance) as PREFIX_albedo.pfm, PREFIX_normal.pfm and PREFIX_depth.pfm (the depth in all three channels).
 // --denoise [N] (one rank; implies the guide pass of --aov, whose files are written only with --aov): after the render, the a-trous
 // filter of pt_film_denoise with N iterations (default: pt_denoise_params_default's) over the film, written beside the normal output:
-// out.ppm -> out.denoised.ppm, out.pfm -> out.denoised.pfm.
+// out.ppm -> out.denoised.ppm, out.pfm -> out.denoised.pfm.  With --sigma-color S the film gets its second-moment plane before the render
+// (pt_film_enable_moments) and the same files hold the variance-guided filter's result (pt_film_denoise_variance, sigma_color = S).
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -50,6 +51,7 @@ struct Options {
     uint32_t ranks = 1;          // --ranks N: one host thread + one GPU per rank, tiles interleaved, RCCL gather to rank 0
     std::vector<int> devices;    // --devices a,b,...: HIP ordinals of the ranks (default 0..N-1)
     bool selftest = false;       // --selftest (with --ranks N): the presentation collective on a rank-coloured film before the render
+    float sigma_color = 0.f;     // --sigma-color S (with --denoise): > 0 = the variance-guided filter of pt_film_denoise_variance
     int denoise = -1;            // --denoise [N]: -1 off, 0 the library's default iterations, else N
 };
 
@@ -163,8 +165,9 @@ void run_rank(const Options &o, const pth_scene &hs, uint32_t rank, const pt_uni
         // the reference dispatches one frame per loop iteration (main.cpp:647-685); frames are
         // independent until the blend, so they are handed over in one call and batched on the device
         p.frame = 0; p.frame_count = o.frames;
+        if (o.sigma_color > 0.f && pt_film_enable_moments(film, nullptr) != PT_OK) { fail("pt_film_enable_moments"); ok = false; }  // (before the frames: the render blends it)
         const auto t0 = std::chrono::steady_clock::now();
-        if (pt_render(scene, film, &p) != PT_OK) { fail("pt_render"); ok = false; }
+        if (ok && pt_render(scene, film, &p) != PT_OK) { fail("pt_render"); ok = false; }
         const auto t1 = std::chrono::steady_clock::now();
         res.render_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
         if (ok) pt_get_stats(ctx, &res.st);
@@ -190,9 +193,13 @@ void run_rank(const Options &o, const pth_scene &hs, uint32_t rank, const pt_uni
             if (ok && o.denoise >= 0) {  // the filtered image beside the normal output; the film itself stays as rendered
                 pt_denoise_params dp;
                 pt_denoise_params_default(&dp);
-                if (o.denoise > 0) dp.iterations = (uint32_t)o.denoise;
+                pt_denoise_variance_params vp;   // --sigma-color: the variance-guided form, same files
+                pt_denoise_variance_params_default(&vp);
+                vp.sigma_color = o.sigma_color;
+                if (o.denoise > 0) dp.iterations = vp.iterations = (uint32_t)o.denoise;
                 std::vector<uint8_t> bgra(4 * np);
-                if (pt_film_denoise(film, &dp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise"); ok = false; }
+                if (o.sigma_color > 0.f && pt_film_denoise_variance(film, &vp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise_variance"); ok = false; }
+                else if (!(o.sigma_color > 0.f) && pt_film_denoise(film, &dp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise"); ok = false; }
                 else if (pt_film_read_denoised(film, plane.data(), bgra.data()) != PT_OK) { fail("pt_film_read_denoised"); ok = false; }
                 else if (!o.ppm.empty() && pth_write_ppm_bgra8(denoised_name(o.ppm).c_str(), bgra.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.ppm); ok = false; }
                 else if (!o.pfm.empty() && pth_write_pfm(denoised_name(o.pfm).c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.pfm); ok = false; }
@@ -270,8 +277,14 @@ int main(int argc, char **argv)
             o.denoise = 0;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') o.denoise = std::atoi(argv[++i]);
         }
+        else if (a == "--sigma-color") {
+            o.sigma_color = (float)std::atof(val());
+            if (!(o.sigma_color > 0.f)) die("--sigma-color needs a value > 0");
+        }
         else die("unknown option " + a);
     }
+    if (o.sigma_color > 0.f && o.denoise < 0) die("--sigma-color belongs to --denoise (the variance-guided filter)");
+    if (o.sigma_color > 0.f && o.ranks > 1) die("--sigma-color filters the film of one rank (no --ranks)");
     if (o.ranks > 1) {
         if (o.devices.empty()) for (uint32_t r = 0; r < o.ranks; r++) o.devices.push_back((int)r);
         if (o.devices.size() != o.ranks) die("--devices needs one ordinal per rank");
