@@ -329,30 +329,19 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
     if (lane == 0 && n_cull_wave && stats) atomicAdd(stats + 19, n_cull_wave);  // (pt_stats.rays_culled)
 }
 
-// this rank's 8x8 tiles, row by row (the rule of pt_render: tile (tx, ty) belongs to rank (tx + ty) % world)
+// this rank's 8x8 tiles, row by row (pt_render's own list before its hand-out order: pt_rank_tiles)
 pt_status ensure_tiles(pt_film *f, uint32_t rank, uint32_t world)
 {
     pt_film::Aov &a = f->aov;
-    pt_ctx *ctx = f->ctx;
     if (a.d_tiles && a.rank == rank && a.world == world) return PT_OK;
     std::vector<uint32_t> tiles;
-    std::vector<uint64_t> prefix(1, 0);
-    uint64_t valid = 0;
-    const uint32_t tiles_x = (f->w + 7) / 8, tiles_y = (f->h + 7) / 8;
-    for (uint32_t ty = 0; ty < tiles_y; ty++)
-        for (uint32_t tx = 0; tx < tiles_x; tx++)
-            if ((tx + ty) % world == rank) {
-                tiles.push_back(tx | (ty << 16));
-                valid += (uint64_t)std::min(8u, f->w - tx * 8) * std::min(8u, f->h - ty * 8);
-                prefix.push_back(valid);
-            }
-    if (a.d_tiles) { (void)hipFree(a.d_tiles); a.bytes -= sizeof(uint32_t) * std::max<size_t>(a.n_tiles, 1); }
-    a.d_tiles = nullptr;
+    std::vector<uint64_t> prefix;
+    const uint64_t valid = pt_rank_tiles(f->w, f->h, rank, world, &tiles, &prefix);
+    const size_t held = a.d_tiles ? sizeof(uint32_t) * std::max<size_t>(a.n_tiles, 1) : 0;
     a.n_tiles = 0;
-    PT_HIP(ctx, hipMalloc((void **)&a.d_tiles, sizeof(uint32_t) * std::max<size_t>(tiles.size(), 1)));
-    a.allocs++;
-    a.bytes += sizeof(uint32_t) * std::max<size_t>(tiles.size(), 1);
-    if (!tiles.empty()) PT_HIP(ctx, hipMemcpy(a.d_tiles, tiles.data(), sizeof(uint32_t) * tiles.size(), hipMemcpyHostToDevice));
+    const pt_status rc = pt_scratch_alloc(f->ctx, "guide-buffer workspace", { pt_buf_of(a.d_tiles, sizeof(uint32_t) * std::max<size_t>(tiles.size(), 1)) }, &a.bytes, held);
+    if (rc != PT_OK) return rc;
+    if (!tiles.empty()) PT_HIP(f->ctx, hipMemcpy(a.d_tiles, tiles.data(), sizeof(uint32_t) * tiles.size(), hipMemcpyHostToDevice));
     a.rank = rank; a.world = world; a.n_tiles = (uint32_t)tiles.size(); a.valid_pixels = valid;
     a.h_valid.swap(prefix);
     return PT_OK;
@@ -362,38 +351,20 @@ pt_status ensure_count(pt_film *f)
 {
     pt_film::Aov &a = f->aov;
     if (a.d_count) return PT_OK;
-    PT_HIP(f->ctx, hipMalloc((void **)&a.d_count, sizeof(uint32_t) * 64));
-    a.allocs++;
-    a.bytes += sizeof(uint32_t) * 64;
-    return PT_OK;
+    return pt_scratch_alloc(f->ctx, "guide-buffer workspace", { pt_buf_of(a.d_count, sizeof(uint32_t) * 64) }, &a.bytes, 0);
 }
 
-// Ray scratch for `rays` rays (grow only).  The film's workspaces stay within the context's memory budget together: the rule of
-// film_work.hip work_alloc.
+// Ray scratch for `rays` rays (grow only, all four or none).  Not checked against the budget here: render_aov_queues sizes the chunk to it beforehand.
 pt_status ensure_rays(pt_film *f, size_t rays)
 {
     pt_film::Aov &a = f->aov;
-    pt_ctx *ctx = f->ctx;
     if (rays <= a.cap_rays) return PT_OK;
-    (void)hipFree(a.d_rayA); (void)hipFree(a.d_rayB); (void)hipFree(a.d_hit); (void)hipFree(a.d_hit_inst);
-    a.d_rayA = a.d_hit = nullptr; a.d_rayB = nullptr; a.d_hit_inst = nullptr;
-    a.bytes -= a.cap_rays * AOV_RAY_BYTES;
+    const size_t held = a.cap_rays * AOV_RAY_BYTES;
     a.cap_rays = 0;
-    hipError_t e = hipMalloc((void **)&a.d_rayA, sizeof(float4) * rays);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.d_rayB, sizeof(float2) * rays);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.d_hit, sizeof(float4) * rays);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.d_hit_inst, sizeof(uint32_t) * rays);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(a.d_rayA); (void)hipFree(a.d_rayB); (void)hipFree(a.d_hit); (void)hipFree(a.d_hit_inst);
-        a.d_rayA = a.d_hit = nullptr; a.d_rayB = nullptr; a.d_hit_inst = nullptr;
-        ctx->err = std::string("hipMalloc of ") + std::to_string((rays * AOV_RAY_BYTES) >> 20) + " MB of guide-buffer workspace: " + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP;
-    }
-    a.allocs += 4;
-    a.cap_rays = rays;
-    a.bytes += rays * AOV_RAY_BYTES;
-    return PT_OK;
+    const pt_status rc = pt_scratch_alloc(f->ctx, "guide-buffer workspace", { pt_buf_of(a.d_rayA, sizeof(float4) * rays), pt_buf_of(a.d_rayB, sizeof(float2) * rays),
+                                                                              pt_buf_of(a.d_hit, sizeof(float4) * rays), pt_buf_of(a.d_hit_inst, sizeof(uint32_t) * rays) }, &a.bytes, held);
+    if (rc == PT_OK) a.cap_rays = rays;
+    return rc;
 }
 
 AovPlanes planes_of(const pt_film *f)
@@ -545,7 +516,8 @@ void pta_free(pt_film *f)
         a.plane[k] = nullptr;
         a.own[k] = false;
     }
-    (void)hipFree(a.d_tiles); (void)hipFree(a.d_rayA); (void)hipFree(a.d_rayB); (void)hipFree(a.d_hit); (void)hipFree(a.d_hit_inst); (void)hipFree(a.d_count);
+    pt_scratch_free({ pt_buf_of(a.d_tiles), pt_buf_of(a.d_rayA), pt_buf_of(a.d_rayB), pt_buf_of(a.d_hit), pt_buf_of(a.d_hit_inst), pt_buf_of(a.d_count) },
+                    &a.bytes, a.bytes);
     a = pt_film::Aov{};
 }
 
@@ -579,9 +551,7 @@ pt_status pta_render(pt_scene *s, pt_film *f, const pt_params *p)
     if (rc == PT_OK) rc = ensure_count(f);
     if (rc != PT_OK) return rc;
     AovConst ac{};
-    ac.cam = { p->cam_origin[0], p->cam_origin[1], p->cam_origin[2], p->cam_target[0], p->cam_target[1], p->cam_target[2], (float)p->width, (float)p->height,
-               // (ptw_render_const: the reciprocals of the launch size for sizes the three-FMA quotient is proven for)
-               p->width <= (1u << 20) ? 1.0f / (float)p->width : 0.0f, p->height <= (1u << 20) ? 1.0f / (float)p->height : 0.0f };
+    ac.cam = ptw_camera(p);
     ac.tmin = p->tmin; ac.tmax = p->tmax;
     ac.width = p->width; ac.height = p->height; ac.spp = p->spp_per_frame;
     ac.div_spp.init(p->spp_per_frame);

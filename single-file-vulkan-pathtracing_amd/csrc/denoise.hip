@@ -241,32 +241,6 @@ using DnAtrousVarFn = decltype(&k_dn_atrous_var<false>);
 DnAtrousFn pick_dn_atrous(bool last) { return last ? k_dn_atrous<true> : k_dn_atrous<false>; }
 DnAtrousVarFn pick_dn_atrous_var(bool last) { return last ? k_dn_atrous_var<true> : k_dn_atrous_var<false>; }
 
-// n buffers or none, so that a refused call leaves the film as it was.  The film's workspaces stay within the context's memory budget
-// together: the rule of film_work.hip work_alloc, as aov.hip follows it.
-pt_status dn_alloc(pt_film *f, void **ptrs, const size_t *bytes, int n)
-{
-    pt_ctx *ctx = f->ctx;
-    size_t total = 0;
-    for (int k = 0; k < n; k++) total += bytes[k];
-    const size_t held = f->work.bytes + f->aov.bytes + f->dn.bytes;
-    if (ctx->mem_budget && held + total > ctx->mem_budget) {
-        ctx->err = "denoiser workspace exceeds the memory budget (" + std::to_string((held + total) >> 20) + " MB wanted, " + std::to_string(ctx->mem_budget >> 20) +
-                   " MB allowed)";
-        return PT_ERR_OOM;
-    }
-    for (int k = 0; k < n; k++) {
-        const hipError_t e = hipMalloc(&ptrs[k], bytes[k]);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            for (int m = 0; m < k; m++) (void)hipFree(ptrs[m]);
-            ctx->err = std::string("hipMalloc of ") + std::to_string(total >> 20) + " MB of denoiser workspace: " + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP;
-        }
-    }
-    f->dn.bytes += total;
-    return PT_OK;
-}
-
 // Both filters: the scratch, then prepare (+ the pre-blur), the iterations, the wait.  var: null for pt_film_denoise.
 struct DnVariance {
     float sigma_color;
@@ -277,20 +251,16 @@ pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigm
     pt_ctx *ctx = f->ctx;
     pt_film::Denoise &d = f->dn;
     const size_t n_pix = (size_t)f->w * f->h;
-    if (!d.d_guide) {
-        void *ptrs[3] = {};
-        const size_t bytes[3] = { sizeof(float4) * n_pix, sizeof(float4) * n_pix, sizeof(float4) * n_pix };
-        const pt_status rc = dn_alloc(f, ptrs, bytes, 3);
-        if (rc != PT_OK) return rc;
-        d.d_guide = static_cast<float4 *>(ptrs[0]); d.d_illum[0] = static_cast<float4 *>(ptrs[1]); d.d_illum[1] = static_cast<float4 *>(ptrs[2]);
-    }
-    if (!device_out && !d.d_out) {
-        void *ptrs[2] = {};
-        const size_t bytes[2] = { sizeof(float) * 3 * n_pix, 4 * n_pix };
-        const pt_status rc = dn_alloc(f, ptrs, bytes, 2);
-        if (rc != PT_OK) return rc;
-        d.d_out = static_cast<float *>(ptrs[0]); d.d_out_bgra = static_cast<uint8_t *>(ptrs[1]);
-    }
+    // each set whole or not at all, so that a refused call leaves the film as it was; all of the film's workspaces count against the budget
+    const size_t others = f->work.bytes + f->aov.bytes, px4 = sizeof(float4) * n_pix;
+    pt_status rc = PT_OK;
+    if (!d.d_guide)
+        rc = pt_scratch_alloc(ctx, "denoiser workspace", { pt_buf_of(d.d_guide, px4), pt_buf_of(d.d_illum[0], px4), pt_buf_of(d.d_illum[1], px4) }, &d.bytes, 0, others,
+                              ctx->mem_budget);
+    if (rc == PT_OK && !device_out && !d.d_out)
+        rc = pt_scratch_alloc(ctx, "denoiser workspace", { pt_buf_of(d.d_out, sizeof(float) * 3 * n_pix), pt_buf_of(d.d_out_bgra, 4 * n_pix) }, &d.bytes, 0, others,
+                              ctx->mem_budget);
+    if (rc != PT_OK) return rc;
     const pt_film::Aov &a = f->aov;
     const DnPlanes pl = { f->d_rgb, static_cast<const float *>(a.plane[PT_AOV_ALBEDO]), static_cast<const float *>(a.plane[PT_AOV_NORMAL]),
                           static_cast<const float *>(a.plane[PT_AOV_EMISSION]), static_cast<const float *>(a.plane[PT_AOV_DEPTH]),
@@ -332,7 +302,7 @@ pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigm
 void ptd_free(pt_film *f)
 {
     pt_film::Denoise &d = f->dn;
-    (void)hipFree(d.d_guide); (void)hipFree(d.d_illum[0]); (void)hipFree(d.d_illum[1]); (void)hipFree(d.d_out); (void)hipFree(d.d_out_bgra);
+    pt_scratch_free({ pt_buf_of(d.d_guide), pt_buf_of(d.d_illum[0]), pt_buf_of(d.d_illum[1]), pt_buf_of(d.d_out), pt_buf_of(d.d_out_bgra) }, &d.bytes, d.bytes);
     d = pt_film::Denoise{};
 }
 

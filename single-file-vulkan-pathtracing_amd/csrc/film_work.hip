@@ -1,6 +1,7 @@
 // film_work.hip -- the film's wavefront workspace: how many path slots a render gets (frames in flight x sample groups x pixels,
 // RenderShape) and the device buffers behind them (queues, hit records, radiance accumulators or term logs).
 // Buffers only ever grow; a grow that does not fit leaves the film usable (PT_ERR_OOM, AUTO shapes are planned again smaller).
+// Also what every scratch of a film goes through (pt_internal.h): pt_scratch_alloc / pt_scratch_free, the rank's tile list, the camera of a launch.
 #include "wavefront_host.h"
 
 #include <algorithm>
@@ -34,44 +35,95 @@ WorkNeed work_need(uint64_t n_slots, uint32_t groups, uint32_t term_cap, uint32_
     return n;
 }
 
-// One workspace allocation.  Out of memory (the device's, or the context's PT_MEM_BUDGET_MB) is PT_ERR_OOM, and HIP's
-// sticky error is cleared so that the context stays usable.
-pt_status work_alloc(pt_ctx *ctx, pt_film::Work &w, void **p, size_t bytes, size_t limit)
+size_t set_bytes(const std::vector<pt_buf> &set)
 {
-    *p = nullptr;
-    if (limit && w.bytes + bytes > limit) {
-        ctx->err = "wavefront workspace exceeds the memory budget (" + std::to_string((w.bytes + bytes) >> 20) + " MB wanted, " +
-                   std::to_string(limit >> 20) + " MB allowed): fewer frames_in_flight / sample_groups fit";
-        return PT_ERR_OOM;
-    }
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        ctx->err = std::string("hipMalloc of ") + std::to_string(bytes >> 20) + " MB of wavefront workspace: " + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP;
-    }
-    w.bytes += bytes;
-    return PT_OK;
+    size_t total = 0;
+    for (const pt_buf &b : set) total += b.bytes;
+    return total;
 }
 
-// Frees the shape-dependent buffers (everything but the tile list and the counters) and zeroes their capacities:
-// the state after a failed grow -- the film itself (d_rgb / d_bgra) is untouched and the next render re-allocates.
+// The shape-dependent buffers of the workspace (everything but the tile list, the counters, the ray-sort scratch and the shadow queue) as
+// the sets that grow together, each with its capacity word (slots or log entries); pt_buf::bytes is per unit of capacity here.
+constexpr int N_SHAPE_SETS = 6;
+struct ShapeSet { std::vector<pt_buf> bufs; size_t *cap; };
+ShapeSet shape_set(pt_film::Work &w, int k)
+{
+    switch (k) {
+    case 0:  // the queue set and the hit records
+        return { { pt_buf_of(w.d_qid[0], sizeof(uint2)), pt_buf_of(w.d_qstate[0], sizeof(float4)), pt_buf_of(w.d_qrayA[0], sizeof(float4)),
+                   pt_buf_of(w.d_qrayB[0], sizeof(float2)), pt_buf_of(w.d_qid[1], sizeof(uint2)), pt_buf_of(w.d_qstate[1], sizeof(float4)),
+                   pt_buf_of(w.d_qrayA[1], sizeof(float4)), pt_buf_of(w.d_qrayB[1], sizeof(float2)), pt_buf_of(w.d_hit, sizeof(float4)),
+                   pt_buf_of(w.d_hit_inst, sizeof(uint32_t)) }, &w.cap_slots };
+    case 1: return { { pt_buf_of(w.d_nterm, sizeof(uint32_t)), pt_buf_of(w.d_spill_head, sizeof(uint32_t)) }, &w.cap_meta };
+    case 2: return { { pt_buf_of(w.d_color, sizeof(float4)) }, &w.cap_color };
+    // primary log: term_pcap entries per slot (dense, what is normally touched); overflow: the rest of the
+    // worst case (one entry per ray), allocated but rarely touched
+    case 3: return { { pt_buf_of(w.d_terms, sizeof(float4)) }, &w.cap_terms };
+    case 4: return { { pt_buf_of(w.d_terms_over, sizeof(float4)) }, &w.cap_terms_over };
+    default: return { { pt_buf_of(w.d_spill, sizeof(float4)) }, &w.cap_spill };
+    }
+}
+
+// Frees the shape buffers and zeroes their capacities: the state after a failed grow -- the film itself (d_rgb / d_bgra) is
+// untouched and the next render re-allocates.  (Leaves w.bytes == w.sort_bytes: the ray-sort scratch is not a shape buffer.)
 void free_shape_buffers(pt_film::Work &w)
 {
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(w.d_qid[i]); (void)hipFree(w.d_qstate[i]); (void)hipFree(w.d_qrayA[i]); (void)hipFree(w.d_qrayB[i]);
-        w.d_qid[i] = nullptr; w.d_qstate[i] = w.d_qrayA[i] = nullptr; w.d_qrayB[i] = nullptr;
+    for (int k = 0; k < N_SHAPE_SETS; k++) {
+        const ShapeSet s = shape_set(w, k);
+        pt_scratch_free(s.bufs, &w.bytes, set_bytes(s.bufs) * *s.cap);
+        *s.cap = 0;
     }
-    (void)hipFree(w.d_hit); (void)hipFree(w.d_hit_inst); (void)hipFree(w.d_nterm); (void)hipFree(w.d_spill_head);
-    (void)hipFree(w.d_color); (void)hipFree(w.d_terms); (void)hipFree(w.d_terms_over); (void)hipFree(w.d_spill);
-    w.d_hit = nullptr; w.d_hit_inst = nullptr; w.d_nterm = nullptr; w.d_spill_head = nullptr;
-    w.d_color = nullptr; w.d_terms = nullptr; w.d_terms_over = nullptr; w.d_spill = nullptr;
-    w.cap_slots = w.cap_meta = w.cap_color = w.cap_terms = w.cap_terms_over = 0;
-    w.bytes = w.sort_bytes;  // (the ray-sort scratch is not a shape buffer)
 }
 
 }  // namespace
+
+void pt_scratch_free(const std::vector<pt_buf> &set, size_t *counter, size_t held)
+{
+    for (const pt_buf &b : set) {
+        if (*b.p) (void)hipFree(*b.p);
+        *b.p = nullptr;
+    }
+    if (counter) *counter -= held;
+}
+
+pt_status pt_scratch_alloc(pt_ctx *ctx, const char *what, const std::vector<pt_buf> &set, size_t *counter, size_t held, size_t others, size_t limit,
+                           const char *hint)
+{
+    pt_scratch_free(set, counter, held);
+    const size_t total = set_bytes(set), before = (counter ? *counter : 0) + others;
+    if (limit && before + total > limit) {
+        ctx->err = std::string(what) + " exceeds the memory budget (" + std::to_string((before + total) >> 20) + " MB wanted, " +
+                   std::to_string(limit >> 20) + " MB allowed)" + hint;
+        return PT_ERR_OOM;
+    }
+    for (const pt_buf &b : set) {
+        const hipError_t e = hipMalloc(b.p, b.bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *b.p = nullptr;
+            pt_scratch_free(set, nullptr, 0);
+            ctx->err = std::string("hipMalloc of ") + std::to_string(total >> 20) + " MB of " + what + ": " + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP;
+        }
+    }
+    if (counter) *counter += total;
+    return PT_OK;
+}
+
+uint64_t pt_rank_tiles(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, std::vector<uint32_t> *tiles, std::vector<uint64_t> *valid)
+{
+    uint64_t n_valid = 0;
+    if (valid) valid->assign(1, 0);
+    const uint32_t tiles_x = (w + 7) / 8, tiles_y = (h + 7) / 8;
+    for (uint32_t ty = 0; ty < tiles_y; ty++)
+        for (uint32_t tx = 0; tx < tiles_x; tx++)
+            if ((tx + ty) % world == rank) {
+                n_valid += (uint64_t)std::min(8u, w - tx * 8) * std::min(8u, h - ty * 8);
+                if (tiles) tiles->push_back(tx | (ty << 16));
+                if (valid) valid->push_back(n_valid);
+            }
+    return n_valid;
+}
 
 // Workspace for (rank, world) tiles, `lanes` frames in flight and `groups` sample groups.  Buffers only
 // ever grow: a later call with a smaller shape reuses them (hipMalloc of tens of GB costs 100s of ms).
@@ -97,9 +149,7 @@ pt_status ptw_ensure_work(pt_film *f, uint32_t rank, uint32_t world, uint32_t la
         w.d_tiles = nullptr;
         const uint32_t tiles_x = (f->w + 7) / 8, tiles_y = (f->h + 7) / 8;
         std::vector<uint32_t> tiles;
-        for (uint32_t ty = 0; ty < tiles_y; ty++)
-            for (uint32_t tx = 0; tx < tiles_x; tx++)
-                if ((tx + ty) % world == rank) tiles.push_back(tx | (ty << 16));
+        pt_rank_tiles(f->w, f->h, rank, world, &tiles);
         if (order == 1u) {
             auto ring = [&](uint32_t t) {  // Chebyshev distance from the image centre in units of the half extent, 0 .. 1
                 const float cx = 0.5f * (float)tiles_x, cy = 0.5f * (float)tiles_y;
@@ -129,64 +179,17 @@ pt_status ptw_ensure_work(pt_film *f, uint32_t rank, uint32_t world, uint32_t la
     }
     const WorkNeed need = work_need(n_slots64, groups, term_cap, term_pcap, queues, tail);
     const size_t ns = need.slots;
-    const size_t limit = ctx->mem_budget;
+    // every set that is too small goes as a whole; the budget counts what the shape buffers (and the ray-sort scratch) hold so far
+    const size_t want[N_SHAPE_SETS] = { queues ? ns : 0, ns, need.color, need.terms, need.terms_over, (groups > 1 || tail) ? (size_t)SPILL_POOL_ENTRIES : 0 };
     pt_status rc = PT_OK;
-#define PT_WORK_ALLOC(PTR, BYTES) \
-    if (rc == PT_OK) rc = work_alloc(ctx, w, (void **)&(PTR), (BYTES), limit)
-    if (queues && ns > w.cap_slots) {
-        // the queue set goes as a whole: free first (peak = the new size, not old + new)
-        for (int i = 0; i < 2; i++) {
-            (void)hipFree(w.d_qid[i]); (void)hipFree(w.d_qstate[i]); (void)hipFree(w.d_qrayA[i]); (void)hipFree(w.d_qrayB[i]);
-            w.d_qid[i] = nullptr; w.d_qstate[i] = w.d_qrayA[i] = nullptr; w.d_qrayB[i] = nullptr;
-        }
-        (void)hipFree(w.d_hit); (void)hipFree(w.d_hit_inst);
-        w.d_hit = nullptr; w.d_hit_inst = nullptr;
-        w.bytes -= w.cap_slots * SLOT_BYTES_QUEUES;
-        w.cap_slots = 0;
-        for (int i = 0; i < 2; i++) {
-            PT_WORK_ALLOC(w.d_qid[i], sizeof(uint2) * ns);
-            PT_WORK_ALLOC(w.d_qstate[i], sizeof(float4) * ns);
-            PT_WORK_ALLOC(w.d_qrayA[i], sizeof(float4) * ns);
-            PT_WORK_ALLOC(w.d_qrayB[i], sizeof(float2) * ns);
-        }
-        PT_WORK_ALLOC(w.d_hit, sizeof(float4) * ns);
-        PT_WORK_ALLOC(w.d_hit_inst, sizeof(uint32_t) * ns);
-        if (rc == PT_OK) w.cap_slots = ns;
+    for (int k = 0; k < N_SHAPE_SETS && rc == PT_OK; k++) {
+        ShapeSet s = shape_set(w, k);
+        if (want[k] <= *s.cap) continue;
+        const size_t held = set_bytes(s.bufs) * *s.cap;
+        for (pt_buf &b : s.bufs) b.bytes *= want[k];
+        rc = pt_scratch_alloc(ctx, "wavefront workspace", s.bufs, &w.bytes, held, 0, ctx->mem_budget, ": fewer frames_in_flight / sample_groups fit");
+        *s.cap = rc == PT_OK ? want[k] : 0;
     }
-    if (rc == PT_OK && ns > w.cap_meta) {
-        (void)hipFree(w.d_nterm); (void)hipFree(w.d_spill_head);
-        w.d_nterm = nullptr; w.d_spill_head = nullptr;
-        w.bytes -= w.cap_meta * SLOT_BYTES_META;
-        w.cap_meta = 0;
-        PT_WORK_ALLOC(w.d_nterm, sizeof(uint32_t) * ns);
-        PT_WORK_ALLOC(w.d_spill_head, sizeof(uint32_t) * ns);
-        if (rc == PT_OK) w.cap_meta = ns;
-    }
-    if (rc == PT_OK && need.color > w.cap_color) {
-        (void)hipFree(w.d_color);
-        w.bytes -= sizeof(float4) * w.cap_color;
-        w.d_color = nullptr; w.cap_color = 0;
-        PT_WORK_ALLOC(w.d_color, sizeof(float4) * need.color);
-        if (rc == PT_OK) w.cap_color = need.color;
-    }
-    // primary log: term_pcap entries per slot (dense, what is normally touched); overflow: the rest of the
-    // worst case (one entry per ray), allocated but rarely touched
-    if (rc == PT_OK && need.terms > w.cap_terms) {
-        (void)hipFree(w.d_terms);
-        w.bytes -= sizeof(float4) * w.cap_terms;
-        w.d_terms = nullptr; w.cap_terms = 0;
-        PT_WORK_ALLOC(w.d_terms, sizeof(float4) * need.terms);
-        if (rc == PT_OK) w.cap_terms = need.terms;
-    }
-    if (rc == PT_OK && need.terms_over > w.cap_terms_over) {
-        (void)hipFree(w.d_terms_over);
-        w.bytes -= sizeof(float4) * w.cap_terms_over;
-        w.d_terms_over = nullptr; w.cap_terms_over = 0;
-        PT_WORK_ALLOC(w.d_terms_over, sizeof(float4) * need.terms_over);
-        if (rc == PT_OK) w.cap_terms_over = need.terms_over;
-    }
-    if (rc == PT_OK && (groups > 1 || tail) && !w.d_spill) PT_WORK_ALLOC(w.d_spill, sizeof(float4) * (size_t)SPILL_POOL_ENTRIES);
-#undef PT_WORK_ALLOC
     if (rc != PT_OK) {
         free_shape_buffers(w);
         w.lanes = w.groups = w.term_cap = 0;
@@ -363,14 +366,19 @@ pt_status ptw_shape_and_work(pt_film *f, const pt_params *p_in, RenderShape &sh,
     return rc;
 }
 
+ptm::Camera ptw_camera(const pt_params *p)
+{
+    return { p->cam_origin[0], p->cam_origin[1], p->cam_origin[2], p->cam_target[0], p->cam_target[1], p->cam_target[2],
+             (float)p->width, (float)p->height,
+             // (pt_math.h primary_target: the reciprocals of the launch size by the host's correctly rounded divide, for sizes the three-FMA
+             // quotient is proven for)
+             p->width <= (1u << 20) ? 1.0f / (float)p->width : 0.0f, p->height <= (1u << 20) ? 1.0f / (float)p->height : 0.0f };
+}
+
 ptw::RenderConst ptw_render_const(const pt_params *p, const pt_film::Work &w, const RenderShape &sh)
 {
     ptw::RenderConst rc{};
-    rc.cam = { p->cam_origin[0], p->cam_origin[1], p->cam_origin[2], p->cam_target[0], p->cam_target[1], p->cam_target[2],
-               (float)p->width, (float)p->height,
-               // (pt_math.h primary_target: the reciprocals of the launch size by the host's correctly rounded divide, for sizes the three-FMA
-               // quotient is proven for)
-               p->width <= (1u << 20) ? 1.0f / (float)p->width : 0.0f, p->height <= (1u << 20) ? 1.0f / (float)p->height : 0.0f };
+    rc.cam = ptw_camera(p);
     for (int k = 0; k < 3; k++) rc.env[k] = p->env[k];
     rc.tmin = p->tmin; rc.tmax = p->tmax;
     rc.width = p->width; rc.height = p->height; rc.tiles_x = (p->width + 7) / 8;
@@ -389,47 +397,23 @@ ptw::RenderConst ptw_render_const(const pt_params *p, const pt_film::Work &w, co
 }
 
 // pixels of this rank's 8x8 tiles that lie inside the image (samples started = that x spp x frames)
-uint64_t ptw_valid_local_pixels(const pt_film *f, const pt_params *p)
-{
-    uint64_t valid = 0;
-    const uint32_t tiles_x = (f->w + 7) / 8, tiles_y = (f->h + 7) / 8;
-    for (uint32_t ty = 0; ty < tiles_y; ty++)
-        for (uint32_t tx = 0; tx < tiles_x; tx++)
-            if ((tx + ty) % p->world == p->rank)
-                valid += (uint64_t)std::min(8u, f->w - tx * 8) * std::min(8u, f->h - ty * 8);
-    return valid;
-}
+uint64_t ptw_valid_local_pixels(const pt_film *f, const pt_params *p) { return pt_rank_tiles(f->w, f->h, p->rank, p->world); }
 
 // what pt_stats.workspace_bytes reports: everything the film's wavefront workspace holds + the context's stack-spill area
 uint64_t ptw_workspace_bytes(const pt_film *f)
 {
     const pt_film::Work &w = f->work;
-    return (uint64_t)w.bytes + (uint64_t)w.cap_sq * (16 + 8 + 16 + 4 + 4 + 16) + (uint64_t)f->ctx->spill_bytes;
+    return (uint64_t)w.bytes + (uint64_t)w.sq_bytes + (uint64_t)f->ctx->spill_bytes;
 }
 
 
 void ptw_free_work(pt_film *f)
 {
     pt_film::Work &w = f->work;
-    (void)hipFree(w.d_tiles);
-    (void)hipFree(w.d_color);
-    (void)hipFree(w.d_terms);
-    (void)hipFree(w.d_terms_over);
-    (void)hipFree(w.d_nterm);
-    (void)hipFree(w.d_spill_head);
-    (void)hipFree(w.d_spill);
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(w.d_qid[i]);
-        (void)hipFree(w.d_qstate[i]);
-        (void)hipFree(w.d_qrayA[i]);
-        (void)hipFree(w.d_qrayB[i]);
-    }
-    (void)hipFree(w.d_hit);
-    (void)hipFree(w.d_hit_inst);
-    (void)hipFree(w.d_count);
-    (void)hipFree(w.d_sort);
-    (void)hipFree(w.d_sq_rayA); (void)hipFree(w.d_sq_rayB); (void)hipFree(w.d_sq_contrib); (void)hipFree(w.d_sq_slot);
-    (void)hipFree(w.d_sq_tmax); (void)hipFree(w.d_sq_hit); (void)hipFree(w.d_sq_count);
+    free_shape_buffers(w);
+    pt_scratch_free({ pt_buf_of(w.d_sort) }, &w.bytes, w.sort_bytes);
+    pt_scratch_free({ pt_buf_of(w.d_sq_rayA), pt_buf_of(w.d_sq_rayB), pt_buf_of(w.d_sq_contrib), pt_buf_of(w.d_sq_slot), pt_buf_of(w.d_sq_tmax),
+                      pt_buf_of(w.d_sq_hit) }, &w.sq_bytes, w.sq_bytes);
+    pt_scratch_free({ pt_buf_of(w.d_tiles), pt_buf_of(w.d_count), pt_buf_of(w.d_sq_count) }, nullptr, 0);
     w = pt_film::Work{};
 }
-

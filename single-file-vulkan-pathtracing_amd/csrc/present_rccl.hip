@@ -73,15 +73,11 @@ bool rccl_load()
     return g_rccl.lib && g_rccl.err.empty();
 }
 
-// tiles of rank r in the order ensure_work() enumerates them (row major over the tile grid)
-std::vector<uint32_t> tiles_of(uint32_t w, uint32_t h, uint32_t rank, uint32_t world)
+uint32_t tile_count(uint32_t w, uint32_t h, uint32_t rank, uint32_t world)
 {
     std::vector<uint32_t> t;
-    const uint32_t tiles_x = (w + 7) / 8, tiles_y = (h + 7) / 8;
-    for (uint32_t ty = 0; ty < tiles_y; ty++)
-        for (uint32_t tx = 0; tx < tiles_x; tx++)
-            if ((tx + ty) % world == rank) t.push_back(tx | (ty << 16));
-    return t;
+    pt_rank_tiles(w, h, rank, world, &t);
+    return (uint32_t)t.size();
 }
 
 // one thread per float of the packed buffer: [tile][pixel 0..63][rgb]
@@ -116,7 +112,8 @@ struct TileList {
 };
 pt_status upload_tiles(pt_ctx *ctx, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, TileList &out)
 {
-    const std::vector<uint32_t> t = tiles_of(w, h, rank, world);
+    std::vector<uint32_t> t;
+    pt_rank_tiles(w, h, rank, world, &t);
     out.n = (uint32_t)t.size();
     out.d = nullptr;
     PT_HIP(ctx, hipMalloc((void **)&out.d, sizeof(uint32_t) * std::max<size_t>(t.size(), 1)));
@@ -154,7 +151,7 @@ extern "C" {
 pt_status pt_film_tile_count(const pt_film *f, uint32_t rank, uint32_t world, uint32_t *n_tiles)
 {
     if (!f || !n_tiles || world == 0 || rank >= world) return PT_ERR_INVALID_ARG;
-    *n_tiles = (uint32_t)tiles_of(f->w, f->h, rank, world).size();
+    *n_tiles = tile_count(f->w, f->h, rank, world);
     return PT_OK;
 }
 
@@ -264,7 +261,7 @@ pt_status pt_film_present(pt_film *f, pt_comm *c, uint32_t root, float *d_image)
                 const pt_status rc = upload_tiles(ctx, f->w, f->h, r, c->world, c->tiles[r]);
                 if (rc != PT_OK) return rc;
             } else {
-                c->tiles[r].n = (uint32_t)tiles_of(f->w, f->h, r, c->world).size();
+                c->tiles[r].n = tile_count(f->w, f->h, r, c->world);
             }
             c->recv_off[r + 1] = c->recv_off[r] + (size_t)c->tiles[r].n * TILE_FLOATS;
         }

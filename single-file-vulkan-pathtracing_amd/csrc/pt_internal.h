@@ -178,17 +178,17 @@ struct pt_film {
         float4 *d_hit = nullptr;                      // {bits(pos), t, u, v}
         uint32_t *d_hit_inst = nullptr;               // instance (TLAS sorted position); only for two-level scenes
         uint32_t *d_count = nullptr;                  // [2] queue sizes
-        size_t cap_slots = 0, cap_meta = 0, cap_color = 0, cap_terms = 0, cap_terms_over = 0;  // allocated capacities (buffers only grow); cap_slots: queues + hit records, cap_meta: d_nterm / d_spill_head
+        size_t cap_slots = 0, cap_meta = 0, cap_color = 0, cap_terms = 0, cap_terms_over = 0, cap_spill = 0;  // allocated capacities (buffers only grow); cap_slots: queues + hit records, cap_meta: d_nterm / d_spill_head
         size_t bytes = 0;                             // device bytes held by the buffers above
         // shadow queue of the NEE pipeline (one entry per hit whose light sample faces it)
         float4 *d_sq_rayA = nullptr; float2 *d_sq_rayB = nullptr; float4 *d_sq_contrib = nullptr;  // {r, g, b, tmax}
         uint32_t *d_sq_slot = nullptr; float *d_sq_tmax = nullptr; float4 *d_sq_hit = nullptr; uint32_t *d_sq_count = nullptr;
-        size_t cap_sq = 0;
+        size_t cap_sq = 0, sq_bytes = 0;              // (its bytes are counted here, not in `bytes`: no shape is planned against them)
         void *d_sort = nullptr;                       // ray_sort.hip scratch for all pipelines (ptw_ray_sort_bytes per slot range)
         size_t sort_bytes = 0;
     } work;
     // guide buffers (pt_film_enable_aov) and the scratch of pt_render_aov (aov.hip).  The scratch is the film's and only grows:
-    // a second call of the same shape allocates nothing (`allocs` counts the device allocations made for it).
+    // a second call of the same shape allocates nothing.
     struct Aov {
         bool enabled = false;
         void *plane[PT_AOV_COUNT] = {};               // dense, row-major: see the enum in include/pt_api.h
@@ -202,7 +202,6 @@ struct pt_film {
         size_t cap_rays = 0;
         uint32_t *d_count = nullptr;                  // [0] rays of the chunk (what the extend kernels read), [32] next tile of the single-kernel form
         size_t bytes = 0;                             // device bytes of the scratch
-        uint64_t allocs = 0;
     } aov;
     // pt_film_denoise (denoise.hip).  The scratch is the film's, allocated by the first call and kept: later calls allocate nothing
     // (the film-owned output comes with the first call that asks for it).
@@ -253,6 +252,21 @@ uint32_t pt_wide_stack_need(const std::vector<uint32_t> &rows32);
 pt_status pt_sah_build_bvh4_device(pt_ctx *ctx, const float *tlo, const float *thi, uint32_t n, const uint8_t *pair_with_next, float pad,
                                    uint32_t leaf_max_prims, std::vector<uint32_t> &rows32, std::vector<uint32_t> &order);
 void ptb_free_instances(pt_scene *s);
+// film_work.hip: device scratch that hangs on a film (the wavefront workspace, the guide buffers' ray scratch, the denoiser's planes).
+// A workspace names its buffers in SETS that are allocated and freed together, and keeps one byte counter ("Film scratch").
+struct pt_buf { void **p; size_t bytes; };  // one buffer of a set: where its pointer lives, the bytes it is to have (not read when it is freed)
+template <class T> inline pt_buf pt_buf_of(T *&p, size_t bytes = 0) { return { reinterpret_cast<void **>(&p), bytes }; }
+// Frees the set's buffers, nulls its pointers and takes `held` (the bytes the set held) off *counter (null: a set nobody counts).
+void pt_scratch_free(const std::vector<pt_buf> &set, size_t *counter, size_t held);
+// Gives every buffer of the set its bytes, or none.  What the set holds now (`held` bytes) is freed FIRST, so that the peak is the new size and not
+// old + new.  limit != 0: *counter + others + the set's bytes have to stay within it, else PT_ERR_OOM (message: `what` exceeds the memory budget,
+// then `hint`) and nothing is allocated.  A hipMalloc that fails frees the buffers already made, nulls the set, clears HIP's sticky error and is
+// PT_ERR_OOM for hipErrorOutOfMemory, PT_ERR_HIP otherwise: the context and the film stay usable.  *counter grows by the set's bytes on success only.
+pt_status pt_scratch_alloc(pt_ctx *ctx, const char *what, const std::vector<pt_buf> &set, size_t *counter, size_t held, size_t others = 0,
+                           size_t limit = 0, const char *hint = "");
+// The 8x8 tiles of rank `rank` of `world` -- tile (tx, ty) belongs to rank (tx + ty) % world -- row by row as tx | ty << 16, appended to *tiles;
+// *valid gets the running count of their pixels inside the w x h image, [n + 1] entries.  Both nullable.  -> that count over all of them.
+uint64_t pt_rank_tiles(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, std::vector<uint32_t> *tiles = nullptr, std::vector<uint64_t> *valid = nullptr);
 // render.hip / film_work.hip
 pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p);
 pt_status ptw_prepare(pt_scene *s, pt_film *f, const pt_params *p);

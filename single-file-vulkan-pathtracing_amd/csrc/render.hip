@@ -228,14 +228,11 @@ pt_status job_setup(Job &j)
         // one scratch area per pipeline, sized for that pipeline's share of the slots (+ slack for the uneven split)
         const size_t per_pipe = ptw_ray_sort_bytes((size_t)w.n_slots / (size_t)j.n_pipes + (size_t)j.rc.slots_per_lane + 1);
         const size_t need = per_pipe * (size_t)j.n_pipes;
-        if (need > w.sort_bytes) {
-            (void)hipFree(w.d_sort);
-            w.d_sort = nullptr;
-            w.bytes -= w.sort_bytes;
-            w.sort_bytes = 0;
-            const hipError_t e = hipMalloc(&w.d_sort, need);
-            if (e != hipSuccess) { (void)hipGetLastError(); j.sort_rays = false; }  // no room: render unsorted
-            else { w.sort_bytes = need; w.bytes += need; }
+        if (need > w.sort_bytes) {  // (in w.bytes, but no budget is asked; no room: render unsorted, and that is no error)
+            const std::string keep = ctx->err;
+            const bool ok = pt_scratch_alloc(ctx, "ray-sort scratch", { pt_buf_of(w.d_sort, need) }, &w.bytes, w.sort_bytes) == PT_OK;
+            w.sort_bytes = ok ? need : 0;
+            if (!ok) { j.sort_rays = false; ctx->err = keep; }
         }
     }
     j.nee = p->pipeline == PT_PIPELINE_WAVEFRONT_NEE;
@@ -248,18 +245,16 @@ pt_status job_setup(Job &j)
     j.nee_n_lights = s->n_inst ? s->n_lights_inst : s->n_lights;
     j.nee_light_area = s->n_inst ? s->light_area_inst : s->light_area;
     if (j.nee && (size_t)w.n_slots > w.cap_sq) {  // the shadow queue: at most one entry per live path and round
-        (void)hipFree(w.d_sq_rayA); (void)hipFree(w.d_sq_rayB); (void)hipFree(w.d_sq_contrib); (void)hipFree(w.d_sq_slot);
-        (void)hipFree(w.d_sq_tmax); (void)hipFree(w.d_sq_hit);
-        w.d_sq_rayA = w.d_sq_contrib = w.d_sq_hit = nullptr; w.d_sq_rayB = nullptr; w.d_sq_slot = nullptr; w.d_sq_tmax = nullptr;
-        w.cap_sq = 0;
         const size_t ns = w.n_slots;
-        PT_HIP(ctx, hipMalloc((void **)&w.d_sq_rayA, sizeof(float4) * ns));
-        PT_HIP(ctx, hipMalloc((void **)&w.d_sq_rayB, sizeof(float2) * ns));
-        PT_HIP(ctx, hipMalloc((void **)&w.d_sq_contrib, sizeof(float4) * ns));
-        PT_HIP(ctx, hipMalloc((void **)&w.d_sq_slot, sizeof(uint32_t) * ns));
-        PT_HIP(ctx, hipMalloc((void **)&w.d_sq_tmax, sizeof(float) * ns));
-        PT_HIP(ctx, hipMalloc((void **)&w.d_sq_hit, sizeof(float4) * ns));
-        if (!w.d_sq_count) PT_HIP(ctx, hipMalloc((void **)&w.d_sq_count, sizeof(uint32_t) * PT_MAX_PIPES));
+        w.cap_sq = 0;
+        // (the pipelines' count words first: allocated once, kept, and not part of what pt_stats.workspace_bytes reports)
+        pt_status rcq = w.d_sq_count ? PT_OK : pt_scratch_alloc(ctx, "shadow queue", { pt_buf_of(w.d_sq_count, sizeof(uint32_t) * PT_MAX_PIPES) }, nullptr, 0);
+        if (rcq == PT_OK)
+            rcq = pt_scratch_alloc(ctx, "shadow queue", { pt_buf_of(w.d_sq_rayA, sizeof(float4) * ns), pt_buf_of(w.d_sq_rayB, sizeof(float2) * ns),
+                                                          pt_buf_of(w.d_sq_contrib, sizeof(float4) * ns), pt_buf_of(w.d_sq_slot, sizeof(uint32_t) * ns),
+                                                          pt_buf_of(w.d_sq_tmax, sizeof(float) * ns), pt_buf_of(w.d_sq_hit, sizeof(float4) * ns) },
+                                   &w.sq_bytes, w.sq_bytes);
+        if (rcq != PT_OK) return rcq;
         w.cap_sq = ns;
     }
     ctx->stats.extend_variant = j.pl.variant;

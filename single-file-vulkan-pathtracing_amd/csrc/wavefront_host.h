@@ -142,6 +142,7 @@ pt_status ptw_ensure_work(pt_film *f, uint32_t rank, uint32_t world, uint32_t la
 pt_status ptw_shape_and_work(pt_film *f, const pt_params *p, RenderShape &sh, int launch_class, bool queues = true);
 pt_status ptw_tiles_subject_first(pt_film *f, const int32_t rect[4], hipStream_t st);  // fused pipeline: tiles that can see the scene first (film_work.hip)
 uint64_t ptw_workspace_bytes(const pt_film *f);
+ptm::Camera ptw_camera(const pt_params *p);  // the camera of a launch: pt_render and pt_render_aov start the same rays from it
 ptw::RenderConst ptw_render_const(const pt_params *p, const pt_film::Work &w, const RenderShape &sh);
 uint64_t ptw_valid_local_pixels(const pt_film *f, const pt_params *p);
 // render.hip: the pixel rectangle {x0, y0, x1, y1} outside of which no camera ray can reach the scene's box (x1 < x0: no such proof)
