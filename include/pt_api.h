@@ -200,7 +200,7 @@ pt_status pt_film_create(pt_ctx *ctx, uint32_t width, uint32_t height, pt_film *
  * a torch tensor's data_ptr(), so a collective can reduce it in place.                      */
 pt_status pt_film_create_external(pt_ctx *ctx, uint32_t width, uint32_t height,
                                   void *device_rgb_f32, pt_film **out);
-pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov and the plane of pt_film_enable_moments) */
+pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov and the planes of pt_film_enable_moments / pt_film_enable_history) */
 /* rgb: width*height*3 floats, row-major, linear radiance mean over all frames so far.       */
 pt_status pt_film_read_f32(pt_film *film, float *rgb);
 /* bgra: width*height*4 bytes = what main.cpp:661-667 copies to the swapchain.               */
@@ -413,6 +413,79 @@ typedef struct pt_denoise_variance_params {
 } pt_denoise_variance_params;
 void pt_denoise_variance_params_default(pt_denoise_variance_params *p);
 pt_status pt_film_denoise_variance(pt_film *film, const pt_denoise_variance_params *params, void *device_out_rgb_f32, float *device_ms);
+
+/* ---- temporal accumulation: a film rendered at a new camera takes over the history of the film of the previous camera ---------------
+ * pt_film_enable_history gives the film a plane L of width*height floats, zeroed: the history length of a pixel, in reprojection steps.
+ * device_len_f32 NULL for a plane the film owns, or caller-owned DEVICE memory of that size (a torch tensor's data_ptr()).  Once per film: a
+ * second call is PT_ERR_INVALID_ARG.  Like the guide planes of pt_film_enable_aov and the plane of pt_film_enable_moments it is a film plane,
+ * not a workspace: it is not counted against pt_tuning.mem_budget_mb.  pt_film_clear zeroes it; pt_render does not know it (the film, the
+ * rgba8 image, the ray counts and pt_stats.workspace_bytes of a render do not depend on whether the plane exists).
+ * pt_film_read_history: len width*height floats; PT_ERR_INVALID_ARG on a film without the plane or a NULL len.
+ *
+ * pt_film_reproject(film, prev, params, device_ms).  `film` holds the frames and the guides (pt_render, pt_render_aov) of the camera
+ * (cam_origin, cam_target); `prev` those of (prev_cam_origin, prev_cam_target), and the history its own pt_film_reproject left in it.  The
+ * call works IN PLACE on `film`: it rewrites C (the film), M (the second-moment plane) and L, and the film's bgra8 image by k_resolve's clamp
+ * and quantise rule on the new C (pt_film_denoise's text above has the rule).  It leaves film's guides, everything of prev and pt_stats as
+ * they were, and needs no scratch.  The result is a film again: pt_film_denoise, pt_film_denoise_variance and pt_film_present work on it
+ * unchanged.  Blocking; runs on the context's stream, ordered after the work already queued there.  device_ms (may be NULL): device time of
+ * the call's kernel.  prev == NULL starts a sequence: every pixel takes the "no history" path.  M is blended when both films have the plane
+ * (prev == NULL: when film has it) and is not touched otherwise.
+ * All arithmetic is binary32, every operation rounded on its own, no contraction, denormals kept, operation order as written (the tests
+ * restate it in numpy, bit for bit).  Per pixel p = (x, y) of film: C, M its planes; N, Z, a, ID its normal, depth, alpha and id planes
+ * exactly as stored (premultiplied by coverage); primed names are prev's; (o, t) = (cam_origin, cam_target), (o', t') the previous pair;
+ * w, h the float sizes.
+ *   Cc = C_p * gain;  Mc = M_p * gain                                      (per channel)
+ *   NO HISTORY:  C_p = Cc;  M_p = Mc;  L_p = 1
+ *   if prev == NULL or !(a_p > 0): NO HISTORY
+ *   r   = Z_p / a_p                                                        (the first hit's distance along the camera ray)
+ *   vx  = (((((float)x + 0.5f) / w) * 2 - 1) + t.x) - o.x;   vy likewise with y, h;   vz = t.z - o.z
+ *   len = sqrt((vx*vx + vy*vy) + vz*vz)
+ *   P   = o + (v / len) * r                                                (divide, multiply, add; per component)
+ *   u   = P - o';   vz' = t'.z - o'.z
+ *   if !(u.z * vz' > 0): NO HISTORY                                        (the point lies behind the previous camera)
+ *   s   = vz' / u.z
+ *   ex  = (u.x * s + o'.x) - t'.x;   ey likewise
+ *   fx  = ((ex + 1) * 0.5f) * w - 0.5f;   fy likewise with h
+ *   if !(fx > -1 && fx < w && fy > -1 && fy < h): NO HISTORY               (a NaN fails)
+ *   x0 = floor(fx); bx = fx - x0;  y0, by likewise;   d = sqrt((u.x*u.x + u.y*u.y) + u.z*u.z)
+ *   W = 0, Ch = Mh = 0, Lh = 0;   for j = 0, 1 (outer), i = 0, 1 (inner), q = (x0 + i, y0 + j), taps outside the image skipped:
+ *       wq = (i ? bx : 1 - bx) * (j ? by : 1 - by)
+ *       the tap counts when all of:  a'_q > 0;  L'_q > 0;  wq > 0;
+ *           flags & PT_REPROJECT_MATCH_ID: both words of ID'_q equal ID_p's;
+ *           |Z'_q - d * a'_q| <= (depth_tol * d) * a'_q;
+ *           ((N_p.x*N'_q.x + N_p.y*N'_q.y) + N_p.z*N'_q.z) >= normal_min * (a_p * a'_q)
+ *       W = W + wq;  Ch_c = Ch_c + wq * C'_q,c;  Mh_c = Mh_c + wq * M'_q,c;  Lh = Lh + wq * L'_q
+ *   if !(W >= 0.01f): NO HISTORY
+ *   Ch = Ch / W;  Mh = Mh / W;  Lh = min(Lh / W, (float)max_history)
+ *   al = max(alpha, 1 / (Lh + 1))
+ *   C_p = Ch + al * (Cc - Ch);   M_p = Mh + al * (Mc - Mh);   L_p = Lh + 1
+ * The camera ray is pt_render's at jitter (0.5, 0.5).  NaN planes are outside the contract.
+ * gain: a film cleared and then rendered at frames [f0, f0 + n) holds sum / (f0 + n), by k_resolve's blend new = (value + old * frame) /
+ * (frame + 1); gain = (float)(f0 + n) / (float)n scales it back to the mean of its n frames.  The time steps of a sequence must render at
+ * different `frame` values, or a static camera repeats its samples.  The guides can always be rendered at frame 0: every use of them above
+ * is homogeneous in their scale (Z / a, and both sides of the depth and the normal test carry a_p * a'_q or a'_q).
+ * alpha is the least weight of the new frames: 0 makes a static sequence the running mean of its steps up to max_history, 1 keeps no history.
+ * After pt_scene_update the validation simply rejects what moved (there are no motion vectors); a (rank, world) film holds only its own tiles,
+ * the caveat of pt_film_denoise.  DESIGN.md section 15 has the experiment the defaults were run on.
+ * PT_ERR_INVALID_ARG: NULL film or params; prev == film; prev of another size or context; film or prev without guides or without L; exactly
+ * one of the two with a second-moment plane; a camera component, gain or depth_tol that is not finite, gain or depth_tol not > 0, alpha outside
+ * [0, 1], normal_min outside [-1, 1], max_history outside 1..65535; unknown flag bits; a nonzero reserved word.  A refused call writes nothing. */
+pt_status pt_film_enable_history(pt_film *film, void *device_len_f32);
+pt_status pt_film_read_history(pt_film *film, float *len);
+enum { PT_REPROJECT_MATCH_ID = 1u };   /* a tap counts only if its {primitive, instance} id equals the pixel's */
+typedef struct pt_reproject_params {
+    float cam_origin[3], cam_target[3];            /* camera of `film`'s guides and frames */
+    float prev_cam_origin[3], prev_cam_target[3];  /* camera of `prev`'s */
+    float gain;            /* default 1 */
+    float alpha;           /* default 0.2: least weight of the new frames; [0, 1] */
+    float depth_tol;       /* default 0.1: relative */
+    float normal_min;      /* default 0.9: least cosine; [-1, 1] */
+    uint32_t max_history;  /* default 32; 1..65535 */
+    uint32_t flags;        /* default PT_REPROJECT_MATCH_ID */
+    uint32_t reserved[4];  /* must be 0 */
+} pt_reproject_params;     /* 88 bytes */
+void pt_reproject_params_default(pt_reproject_params *p);   /* the cameras: pt_params_default's */
+pt_status pt_film_reproject(pt_film *film, pt_film *prev, const pt_reproject_params *params, float *device_ms);
 
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {

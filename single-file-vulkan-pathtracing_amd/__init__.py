@@ -107,6 +107,16 @@ class DenoiseVarianceParams(C.Structure):
                 ("frames", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+REPROJECT_MATCH_ID = 1   # include/pt_api.h PT_REPROJECT_MATCH_ID
+
+
+class ReprojectParams(C.Structure):
+    """include/pt_api.h pt_reproject_params: the temporal accumulation step of pt_film_reproject."""
+    _fields_ = [("cam_origin", C.c_float * 3), ("cam_target", C.c_float * 3), ("prev_cam_origin", C.c_float * 3), ("prev_cam_target", C.c_float * 3),
+                ("gain", C.c_float), ("alpha", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
+                ("max_history", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
 class HostScene(C.Structure):
     _fields_ = [("vertices", C.POINTER(C.c_float)), ("n_verts", C.c_uint32), ("indices", C.POINTER(C.c_uint32)),
                 ("n_tris", C.c_uint32), ("faces", C.POINTER(C.c_float))]
@@ -129,6 +139,7 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_render_prepare", "pt_trace", "pt_film_enable_aov", "pt_render_aov", "pt_film_read_aov",
                "pt_denoise_params_default", "pt_film_denoise", "pt_film_read_denoised",
                "pt_film_enable_moments", "pt_film_read_moments", "pt_denoise_variance_params_default", "pt_film_denoise_variance",
+               "pt_film_enable_history", "pt_film_read_history", "pt_reproject_params_default", "pt_film_reproject",
                "pt_get_stats", "pt_reset_stats", "pt_get_block_counts",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_ranks", "pt_comm_destroy", "pt_film_present",
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
@@ -201,6 +212,12 @@ def lib_amd():
             L.pt_denoise_variance_params_default.argtypes = [C.POINTER(DenoiseVarianceParams)]
             L.pt_denoise_variance_params_default.restype = None
             L.pt_film_denoise_variance.argtypes = [vp, C.POINTER(DenoiseVarianceParams), vp, C.POINTER(C.c_float)]
+        if hasattr(L, "pt_film_reproject"):   # (temporal accumulation; as above)
+            L.pt_film_enable_history.argtypes = [vp, vp]
+            L.pt_film_read_history.argtypes = [vp, vp]
+            L.pt_reproject_params_default.argtypes = [C.POINTER(ReprojectParams)]
+            L.pt_reproject_params_default.restype = None
+            L.pt_film_reproject.argtypes = [vp, vp, C.POINTER(ReprojectParams), C.POINTER(C.c_float)]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -349,6 +366,12 @@ def denoise_default_params():
 def denoise_variance_default_params():
     p = DenoiseVarianceParams()
     lib_amd().pt_denoise_variance_params_default(C.byref(p))
+    return p
+
+
+def reproject_default_params():
+    p = ReprojectParams()
+    lib_amd().pt_reproject_params_default(C.byref(p))
     return p
 
 
@@ -579,6 +602,38 @@ class Film:
                 setattr(p, name, v)
         ms = C.c_float(0.0)
         self.ctx._check(lib_amd().pt_film_denoise_variance(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
+        return ms.value
+
+    def enable_history(self, device_ptr=None):
+        """Gives the film its history-length plane L (include/pt_api.h pt_film_enable_history), which pt_film_reproject reads and writes.
+        device_ptr: None (the film allocates it) or a device pointer to width*height floats of caller-owned memory."""
+        self.ctx._check(lib_amd().pt_film_enable_history(self.h, C.c_void_p(device_ptr) if device_ptr else None))
+
+    def read_history(self):
+        """-> float32 [H, W]: the history length of every pixel, in reprojection steps (0 before the first reproject)."""
+        a = np.zeros((self.height, self.width), dtype=np.float32)
+        self.ctx._check(lib_amd().pt_film_read_history(self.h, a.ctypes.data))
+        return a
+
+    def reproject(self, prev, cam=None, prev_cam=None, params=None, **overrides):
+        """Temporal accumulation (include/pt_api.h pt_film_reproject): this film, rendered (render + render_aov) at camera `cam`, takes over
+        the history of `prev`, rendered at `prev_cam` (prev None: starts a sequence) -> device ms.  In place: rewrites this film, its
+        second-moment plane, its history length and its bgra8 image.  cam / prev_cam: dicts as default_params takes them (cam_origin,
+        cam_target; missing keys are the defaults).  overrides: gain, alpha, depth_tol, normal_min, max_history, flags; anything left out
+        takes pt_reproject_params_default's value (or `params`, a ReprojectParams, as it stands -- its cameras too when cam / prev_cam
+        are None)."""
+        p = ReprojectParams.from_buffer_copy(params) if params is not None else reproject_default_params()   # (the caller's object stays as it is)
+        for dst, c in (("", cam), ("prev_", prev_cam)):
+            for k, v in (c or {}).items():
+                if k not in ("cam_origin", "cam_target"):
+                    raise AttributeError(k)
+                setattr(p, dst + k, (C.c_float * 3)(*v))
+        for k, v in overrides.items():
+            if k not in ("gain", "alpha", "depth_tol", "normal_min", "max_history", "flags"):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_film_reproject(self.h, prev.h if prev is not None else None, C.byref(p), C.byref(ms)))
         return ms.value
 
     def read_denoised(self):

@@ -331,6 +331,7 @@ pt_status pt_film_clear(pt_film *f)
     if (rc != PT_OK) return rc;
     if (f->m2.d_m2) PT_HIP(ctx, hipMemsetAsync(f->m2.d_m2, 0, sizeof(float) * 3 * (size_t)f->w * f->h, ctx->stream));
     f->m2.frames = 0;
+    if (f->hist.d_len) PT_HIP(ctx, hipMemsetAsync(f->hist.d_len, 0, sizeof(float) * (size_t)f->w * f->h, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -360,6 +361,7 @@ void pt_film_destroy(pt_film *f)
     pta_free(f);
     ptd_free(f);
     if (f->m2.own) (void)hipFree(f->m2.d_m2);
+    if (f->hist.own) (void)hipFree(f->hist.d_len);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
     delete f;
@@ -506,6 +508,68 @@ pt_status pt_film_denoise_variance(pt_film *f, const pt_denoise_variance_params 
     if (!f || !p) return PT_ERR_INVALID_ARG;
     PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
     return guarded(f->ctx, [&] { return ptd_denoise_variance(f, p, device_out_rgb_f32, device_ms); });
+}
+
+pt_status pt_film_enable_history(pt_film *f, void *device_len_f32)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (f->hist.d_len) { ctx->err = "the film already has a history-length plane"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    return guarded(ctx, [&]() -> pt_status {
+        const size_t bytes = sizeof(float) * (size_t)f->w * f->h;
+        void *plane = device_len_f32;
+        if (!plane) {
+            const hipError_t e = hipMalloc(&plane, bytes);
+            if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PT_ERR_OOM; }
+        }
+        hipError_t e = hipMemsetAsync(plane, 0, bytes, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            if (!device_len_f32) (void)hipFree(plane);
+            ctx->err = std::string("pt_film_enable_history: ") + hipGetErrorString(e);
+            return PT_ERR_HIP;
+        }
+        f->hist.d_len = static_cast<float *>(plane);
+        f->hist.own = device_len_f32 == nullptr;
+        return PT_OK;
+    });
+}
+
+pt_status pt_film_read_history(pt_film *f, float *len)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (!len) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    if (!f->hist.d_len) { ctx->err = "the film has no history-length plane: pt_film_enable_history first"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(len, f->hist.d_len, sizeof(float) * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+void pt_reproject_params_default(pt_reproject_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    pt_params cam;
+    pt_params_default(&cam);
+    for (int k = 0; k < 3; k++) {
+        p->cam_origin[k] = p->prev_cam_origin[k] = cam.cam_origin[k];
+        p->cam_target[k] = p->prev_cam_target[k] = cam.cam_target[k];
+    }
+    p->gain = 1.0f;
+    p->alpha = 0.2f;
+    p->depth_tol = 0.1f;
+    p->normal_min = 0.9f;
+    p->max_history = 32;
+    p->flags = PT_REPROJECT_MATCH_ID;
+}
+
+pt_status pt_film_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms)
+{
+    if (!f || !p) return PT_ERR_INVALID_ARG;
+    PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return guarded(f->ctx, [&] { return ptr_reproject(f, prev, p, device_ms); });
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)

@@ -220,6 +220,11 @@ struct pt_film {
         bool own = false;
         uint32_t frames = 0;                          // frame + frame_count of the last pt_render: what the film and the plane average
     } m2;
+    // pt_film_enable_history: the history length of pt_film_reproject (reproject.hip), in reprojection steps.  A film plane like M.
+    struct History {
+        float *d_len = nullptr;                       // w*h floats, or null: the film has no such plane
+        bool own = false;
+    } hist;
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -282,3 +287,5 @@ void pta_free(pt_film *f);
 pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms);
 pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out, float *device_ms);
 void ptd_free(pt_film *f);
+// reproject.hip: temporal accumulation -- `f` takes over the history of `prev` (null: starts a sequence); validates everything but the null checks
+pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms);

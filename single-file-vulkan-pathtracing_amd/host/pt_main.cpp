@@ -7,6 +7,7 @@
 //           [--frames 1] [--spp 32] [--depth 8] [--device 0] [--batch N]
 //           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--denoise [N] [--sigma-color S]] [--pipeline auto|wavefront|fused|nee] [--nee]
 //           [--ranks N [--devices 0,1,...] [--selftest]]
+//           [--temporal K --cam-step dx,dy,dz]
 // --ranks N renders with N GPUs: one host thread and one context per GPU, the 8x8 pixel tiles interleaved over the
 // ranks (pt_params.rank/world), and ONE RCCL gather of the packed tiles to rank 0 per presented image
 // (pt_film_present); the image written is the presented one.  --selftest: before rendering, every rank presents a film whose own tiles
@@ -19,6 +20,9 @@
 // filter of pt_film_denoise with N iterations (default: pt_denoise_params_default's) over the film, written beside the normal output:
 // out.ppm -> out.denoised.ppm, out.pfm -> out.denoised.pfm.  With --sigma-color S the film gets its second-moment plane before the render
 // (pt_film_enable_moments) and the same files hold the variance-guided filter's result (pt_film_denoise_variance, sigma_color = S).
+// --temporal K --cam-step dx,dy,dz (one rank; --frames is not used): K time steps of one frame each, step k at frame = k with the camera's
+// origin and target moved k times by the step, accumulated across the moves by pt_film_reproject (gain = k + 1; two films, ping-ponged, each
+// cleared before its step; guides at frame 0).  The image written is the last step's film; --denoise [N] filters that film.
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -53,6 +57,9 @@ struct Options {
     bool selftest = false;       // --selftest (with --ranks N): the presentation collective on a rank-coloured film before the render
     float sigma_color = 0.f;     // --sigma-color S (with --denoise): > 0 = the variance-guided filter of pt_film_denoise_variance
     int denoise = -1;            // --denoise [N]: -1 off, 0 the library's default iterations, else N
+    uint32_t temporal = 0;       // --temporal K: K time steps accumulated by pt_film_reproject (0: off)
+    float cam_step[3] = { 0.f, 0.f, 0.f };   // --cam-step dx,dy,dz: the camera's move per time step
+    bool have_cam_step = false;
 };
 
 // out.ppm -> out.denoised.ppm
@@ -232,6 +239,85 @@ void run_rank(const Options &o, const pth_scene &hs, uint32_t rank, const pt_uni
     pt_scene_destroy(scene);
     pt_ctx_destroy(ctx);
 }
+
+// --temporal K: the frame loop with a moving camera.  Step k renders frame k and the guides into a cleared film at the k-th camera, and
+// that film takes over the history of the previous step's film (pt_film_reproject); two films, ping-ponged.
+void run_temporal(const Options &o, const pth_scene &hs, RankResult &res, std::vector<float> *image_f32, std::vector<uint8_t> *image_bgra8)
+{
+    pt_ctx *ctx = nullptr;
+    pt_scene *scene = nullptr;
+    pt_film *films[2] = { nullptr, nullptr };
+    auto fail = [&](const char *what) { res.error = std::string(what) + ": " + (ctx ? pt_last_error(ctx) : pt_last_error(nullptr)); };
+    do {
+        if (pt_ctx_create(o.device, nullptr, &ctx) != PT_OK) { fail("pt_ctx_create"); break; }
+        if (pt_scene_create(ctx, hs.vertices, hs.n_verts, hs.indices, hs.n_tris, hs.faces, &scene) != PT_OK) { fail("pt_scene_create"); break; }
+        pt_scene_get_info(scene, &res.info);
+        bool ok = true;
+        for (pt_film *&f : films)
+            if (ok && (pt_film_create(ctx, o.width, o.height, &f) != PT_OK || pt_film_enable_aov(f, nullptr) != PT_OK || pt_film_enable_history(f, nullptr) != PT_OK)) { fail("film set-up"); ok = false; }
+        if (!ok) break;
+        pt_params p;
+        pt_params_default(&p);
+        p.width = o.width; p.height = o.height; p.spp_per_frame = o.spp; p.max_depth = o.depth;
+        p.frames_in_flight = o.batch;
+        p.pipeline = o.pipeline;
+        if (o.nee) p.flags |= PT_FLAG_NEE;
+        p.frame_count = 1;
+        pt_reproject_params rp;
+        pt_reproject_params_default(&rp);
+        const pt_params base = p;
+        pt_film *film = nullptr, *prev = nullptr;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t k = 0; k < o.temporal && ok; k++) {
+            film = films[k & 1];
+            for (int c = 0; c < 3; c++) {
+                const float move = o.cam_step[c] * (float)k;
+                p.cam_origin[c] = base.cam_origin[c] + move;
+                p.cam_target[c] = base.cam_target[c] + move;
+                rp.prev_cam_origin[c] = k ? rp.cam_origin[c] : p.cam_origin[c];
+                rp.prev_cam_target[c] = k ? rp.cam_target[c] : p.cam_target[c];
+                rp.cam_origin[c] = p.cam_origin[c];
+                rp.cam_target[c] = p.cam_target[c];
+            }
+            p.frame = (int32_t)k;
+            pt_params g = p;   // the guides: frame 0, no estimator flags
+            g.frame = 0; g.flags = 0;
+            if (g.pipeline == PT_PIPELINE_WAVEFRONT_NEE) g.pipeline = PT_PIPELINE_AUTO;
+            rp.gain = (float)(k + 1);   // a cleared film after frame k alone holds colour / (k + 1)
+            if (pt_film_clear(film) != PT_OK) { fail("pt_film_clear"); ok = false; }
+            else if (pt_render(scene, film, &p) != PT_OK) { fail("pt_render"); ok = false; }
+            else if (pt_render_aov(scene, film, &g) != PT_OK) { fail("pt_render_aov"); ok = false; }
+            else if (pt_film_reproject(film, prev, &rp, nullptr) != PT_OK) { fail("pt_film_reproject"); ok = false; }
+            prev = film;
+        }
+        if (!ok) break;
+        res.render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pt_get_stats(ctx, &res.st);
+        const size_t np = (size_t)o.width * o.height;
+        if (o.denoise >= 0) {
+            pt_denoise_params dp;
+            pt_denoise_params_default(&dp);
+            if (o.denoise > 0) dp.iterations = (uint32_t)o.denoise;
+            std::vector<float> plane(3 * np);
+            std::vector<uint8_t> bgra(4 * np);
+            if (pt_film_denoise(film, &dp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise"); break; }
+            if (pt_film_read_denoised(film, plane.data(), bgra.data()) != PT_OK) { fail("pt_film_read_denoised"); break; }
+            if (!o.ppm.empty() && pth_write_ppm_bgra8(denoised_name(o.ppm).c_str(), bgra.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.ppm); break; }
+            if (!o.pfm.empty() && pth_write_pfm(denoised_name(o.pfm).c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.pfm); break; }
+        }
+        if (image_f32) {
+            image_f32->resize(3 * np);
+            if (pt_film_read_f32(film, image_f32->data()) != PT_OK) { fail("pt_film_read_f32"); break; }
+        }
+        if (image_bgra8) {
+            image_bgra8->resize(4 * np);
+            if (pt_film_read_bgra8(film, image_bgra8->data()) != PT_OK) { fail("pt_film_read_bgra8"); break; }
+        }
+    } while (false);
+    for (pt_film *f : films) pt_film_destroy(f);
+    pt_scene_destroy(scene);
+    pt_ctx_destroy(ctx);
+}
 }  // namespace
 
 int main(int argc, char **argv)
@@ -281,8 +367,21 @@ int main(int argc, char **argv)
             o.sigma_color = (float)std::atof(val());
             if (!(o.sigma_color > 0.f)) die("--sigma-color needs a value > 0");
         }
+        else if (a == "--temporal") {
+            o.temporal = (uint32_t)std::max(0, std::atoi(val()));
+            if (o.temporal == 0) die("--temporal needs a number of time steps >= 1");
+        }
+        else if (a == "--cam-step") {
+            char tail = 0;
+            if (std::sscanf(val(), "%f,%f,%f%c", &o.cam_step[0], &o.cam_step[1], &o.cam_step[2], &tail) != 3) die("--cam-step needs dx,dy,dz");
+            o.have_cam_step = true;
+        }
         else die("unknown option " + a);
     }
+    if (o.have_cam_step && !o.temporal) die("--cam-step belongs to --temporal K");
+    if (o.temporal && !o.have_cam_step) die("--temporal K needs --cam-step dx,dy,dz (0,0,0 for a camera that stands still)");
+    if (o.temporal && (o.ranks > 1 || !o.aov.empty() || o.sigma_color > 0.f)) die("--temporal accumulates the film of one rank (no --ranks, --aov or --sigma-color)");
+    if (o.temporal) o.frames = o.temporal;   // (the JSON line's frame count)
     if (o.sigma_color > 0.f && o.denoise < 0) die("--sigma-color belongs to --denoise (the variance-guided filter)");
     if (o.sigma_color > 0.f && o.ranks > 1) die("--sigma-color filters the film of one rank (no --ranks)");
     if (o.ranks > 1) {
@@ -303,7 +402,9 @@ int main(int argc, char **argv)
     std::vector<uint8_t> image_bgra8;
     const bool want_f32 = !o.pfm.empty() || (o.ranks > 1 && !o.ppm.empty());
     const auto t2 = std::chrono::steady_clock::now();
-    if (o.ranks == 1) {
+    if (o.temporal) {
+        run_temporal(o, hs, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr);
+    } else if (o.ranks == 1) {
         run_rank(o, hs, 0, nullptr, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr, nullptr);
     } else {
         // one host thread per GPU (north star: host code stays C++; the reference has one device, main.cpp:105)
