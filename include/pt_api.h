@@ -200,7 +200,7 @@ pt_status pt_film_create(pt_ctx *ctx, uint32_t width, uint32_t height, pt_film *
  * a torch tensor's data_ptr(), so a collective can reduce it in place.                      */
 pt_status pt_film_create_external(pt_ctx *ctx, uint32_t width, uint32_t height,
                                   void *device_rgb_f32, pt_film **out);
-pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov and the planes of pt_film_enable_moments / pt_film_enable_history) */
+pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov and the planes of pt_film_enable_moments / pt_film_enable_history / pt_film_enable_motion) */
 /* rgb: width*height*3 floats, row-major, linear radiance mean over all frames so far.       */
 pt_status pt_film_read_f32(pt_film *film, float *rgb);
 /* bgra: width*height*4 bytes = what main.cpp:661-667 copies to the swapchain.               */
@@ -465,7 +465,7 @@ pt_status pt_film_denoise_variance(pt_film *film, const pt_denoise_variance_para
  * different `frame` values, or a static camera repeats its samples.  The guides can always be rendered at frame 0: every use of them above
  * is homogeneous in their scale (Z / a, and both sides of the depth and the normal test carry a_p * a'_q or a'_q).
  * alpha is the least weight of the new frames: 0 makes a static sequence the running mean of its steps up to max_history, 1 keeps no history.
- * After pt_scene_update the validation simply rejects what moved (there are no motion vectors); a (rank, world) film holds only its own tiles,
+ * After pt_scene_update the validation simply rejects what moved (pt_film_reproject_motion below follows it); a (rank, world) film holds only its own tiles,
  * the caveat of pt_film_denoise.  DESIGN.md section 15 has the experiment the defaults were run on.
  * PT_ERR_INVALID_ARG: NULL film or params; prev == film; prev of another size or context; film or prev without guides or without L; exactly
  * one of the two with a second-moment plane; a camera component, gain or depth_tol that is not finite, gain or depth_tol not > 0, alpha outside
@@ -486,6 +486,67 @@ typedef struct pt_reproject_params {
 } pt_reproject_params;     /* 88 bytes */
 void pt_reproject_params_default(pt_reproject_params *p);   /* the cameras: pt_params_default's */
 pt_status pt_film_reproject(pt_film *film, pt_film *prev, const pt_reproject_params *params, float *device_ms);
+
+/* ---- motion for moved geometry: where a pixel's surface point was, and a reprojection that starts from it ------------------------------
+ * The caller's time step:  pt_scene_snapshot_previous -> pt_scene_update / pt_scene_set_instances (any number) -> pt_render, pt_render_aov
+ * -> pt_film_motion -> pt_film_reproject_motion.
+ *
+ * pt_scene_snapshot_previous(scene) remembers the scene as it stands now as "the previous geometry": a device copy of the triangles' vertex
+ * positions in primitive order (48 B per triangle) and the instance set's object->world matrices in gl_InstanceID order (48 B each, plus the
+ * same again as the place pt_film_motion uploads the current matrices to) with their count n_i' (0: single-level).  Ordered after the work
+ * queued on the context's stream; blocking.  A second call replaces the first.  The bytes are part of pt_scene_info.device_bytes from the
+ * first call on (a scene that never calls it holds and reports what it did before) and are freed with the scene.  It is an explicit call and
+ * not a side effect of pt_scene_update: one time step may be several updates and a pt_scene_set_instances.  A scene that lost its
+ * acceleration structure is repaired first, as pt_render does it, and the call fails as that repair fails.
+ *
+ * pt_film_enable_motion gives the film a plane Q of width*height*4 floats, zeroed: per pixel {x, y, z, valid}.  device_q_f32x4 NULL for a
+ * plane the film owns, or caller-owned DEVICE memory of that size, 16-byte aligned (a torch tensor's data_ptr()).  Once per film.  The rules
+ * of pt_film_enable_history: a film plane outside pt_tuning.mem_budget_mb, zeroed by pt_film_clear, unknown to pt_render.
+ * pt_film_read_motion: q4 width*height*4 floats; PT_ERR_INVALID_ARG on a film without the plane or a NULL q4.
+ *
+ * pt_film_motion(scene, film, params, device_ms) fills Q from the film's guides -- those rendered (pt_render_aov) for the scene as it is NOW
+ * at the camera of params.  Blocking; runs on the context's stream; writes Q only (pt_stats, the guides and the film stay as they were).
+ * Arithmetic as in pt_film_reproject: binary32, every operation rounded on its own, no contraction, denormals kept, order as written.  Per
+ * pixel p, with n_tris the scene's triangles, n_i its instance count, (o, t) the camera, slack = bary_slack:
+ *   Q_p = (0, 0, 0, 0)
+ *   prim = ID_p.x;  inst = ID_p.y
+ *   if !(a_p > 0) or prim >= n_tris or inst >= max(n_i, 1): done        (a miss, or an id plane that holds something else)
+ *   P as in pt_film_reproject                                           (r = Z_p / a_p; v, len at jitter (0.5, 0.5); P = o + (v / len) * r)
+ *   A, B, C = the triangle's vertices now;  A', B', C' = the snapshot's
+ *   n_i > 0: every vertex V becomes, per row m of the instance's 3x4 matrix,  ((m0*V.x + m1*V.y) + m2*V.z) + m3
+ *            (now: the scene's matrix of `inst`; primed: the snapshot's matrix of `inst`)
+ *   e1 = B - A;  e2 = C - A;  g = P - A;   e1' = B' - A';  e2' = C' - A'
+ *   d11 = e1.e1;  d12 = e1.e2;  d22 = e2.e2;  p1 = g.e1;  p2 = g.e2     (each (x*x + y*y) + z*z)
+ *   det = d11*d22 - d12*d12
+ *   u = (d22*p1 - d12*p2) / det;   v = (d11*p2 - d12*p1) / det
+ *   if det > 0 and u >= -slack and v >= -slack and (u + v) <= 1 + slack   (a NaN fails):
+ *       Q_p = ((A'.x + u*e1'.x) + v*e2'.x, likewise y, z, 1)
+ * The barycentrics are the orthogonal projection of P onto the triangle's plane: P is an average over jittered samples and does not lie
+ * on it exactly, and the id is sample 0's.  bary_slack bounds how far outside that triangle the pixel's centre may fall (in barycentric units:
+ * 1 admits the neighbouring triangles of a regular tessellation, 0 only the triangle itself).  No inverse matrix is used: six vertices go
+ * forward.  Primitive ids survive PT_SCENE_UPDATE_REFIT and _REBUILD, so nothing is remapped.
+ * PT_ERR_INVALID_ARG, and nothing written: NULL scene, film or params; a film without guides or without Q; a film of another context than
+ * the scene's; a scene without a snapshot; n_i different from the snapshot's; a camera component or bary_slack that is not finite,
+ * bary_slack < 0; a nonzero reserved word.
+ *
+ * pt_film_reproject_motion(film, prev, params, device_ms) is pt_film_reproject -- the same parameters, refusals (plus: a film without Q),
+ * effects and bgra8 rule -- with two changes to its text and nothing else:
+ *   u = Q_p.xyz - o'   replaces   u = P - o'          (r, v, len and P are not computed)
+ *   !(Q_p.w > 0) joins !(a_p > 0) on the NO HISTORY line
+ * d = |u| is then the distance the surface point HAD from the previous camera, which is what prev's depth plane holds.  The id test needs no
+ * change.  The normal test compares today's normal with yesterday's: an object that turns by more than acos(normal_min) per step loses its
+ * history there (there is no previous-normal channel).  pt_film_reproject itself is unchanged.  DESIGN.md section 16 has the experiment. */
+pt_status pt_scene_snapshot_previous(pt_scene *scene);
+pt_status pt_film_enable_motion(pt_film *film, void *device_q_f32x4);
+pt_status pt_film_read_motion(pt_film *film, float *q4);
+typedef struct pt_motion_params {
+    float cam_origin[3], cam_target[3];   /* camera of the film's guides */
+    float bary_slack;                     /* default 1; finite, >= 0 */
+    uint32_t reserved[5];                 /* must be 0 */
+} pt_motion_params;                       /* 48 bytes */
+void pt_motion_params_default(pt_motion_params *p);   /* the camera: pt_params_default's */
+pt_status pt_film_motion(pt_scene *scene, pt_film *film, const pt_motion_params *params, float *device_ms);
+pt_status pt_film_reproject_motion(pt_film *film, pt_film *prev, const pt_reproject_params *params, float *device_ms);
 
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {

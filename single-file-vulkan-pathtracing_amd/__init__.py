@@ -117,6 +117,11 @@ class ReprojectParams(C.Structure):
                 ("max_history", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
+class MotionParams(C.Structure):
+    """include/pt_api.h pt_motion_params: the camera of the guides pt_film_motion reads, and the barycentric slack."""
+    _fields_ = [("cam_origin", C.c_float * 3), ("cam_target", C.c_float * 3), ("bary_slack", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 class HostScene(C.Structure):
     _fields_ = [("vertices", C.POINTER(C.c_float)), ("n_verts", C.c_uint32), ("indices", C.POINTER(C.c_uint32)),
                 ("n_tris", C.c_uint32), ("faces", C.POINTER(C.c_float))]
@@ -143,7 +148,9 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_get_stats", "pt_reset_stats", "pt_get_block_counts",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_ranks", "pt_comm_destroy", "pt_film_present",
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
-               "pt_device_alloc", "pt_device_free", "pt_device_read", "pt_device_write", "pt_ctx_get_tuning", "pt_ctx_set_tuning"]
+               "pt_device_alloc", "pt_device_free", "pt_device_read", "pt_device_write", "pt_ctx_get_tuning", "pt_ctx_set_tuning",
+               "pt_scene_snapshot_previous", "pt_film_enable_motion", "pt_film_read_motion", "pt_motion_params_default", "pt_film_motion",
+               "pt_film_reproject_motion"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium"]
 
@@ -218,6 +225,14 @@ def lib_amd():
             L.pt_reproject_params_default.argtypes = [C.POINTER(ReprojectParams)]
             L.pt_reproject_params_default.restype = None
             L.pt_film_reproject.argtypes = [vp, vp, C.POINTER(ReprojectParams), C.POINTER(C.c_float)]
+        if hasattr(L, "pt_film_motion"):   # (motion for moved geometry; as above)
+            L.pt_scene_snapshot_previous.argtypes = [vp]
+            L.pt_film_enable_motion.argtypes = [vp, vp]
+            L.pt_film_read_motion.argtypes = [vp, vp]
+            L.pt_motion_params_default.argtypes = [C.POINTER(MotionParams)]
+            L.pt_motion_params_default.restype = None
+            L.pt_film_motion.argtypes = [vp, vp, C.POINTER(MotionParams), C.POINTER(C.c_float)]
+            L.pt_film_reproject_motion.argtypes = [vp, vp, C.POINTER(ReprojectParams), C.POINTER(C.c_float)]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -375,6 +390,12 @@ def reproject_default_params():
     return p
 
 
+def motion_default_params():
+    p = MotionParams()
+    lib_amd().pt_motion_params_default(C.byref(p))
+    return p
+
+
 class Context:
     """One GPU + one stream (reference: Context, main.cpp:74-267)."""
 
@@ -472,6 +493,11 @@ class Scene:
         if v.size % 3 or i.size % 3:
             raise ValueError("vertices must be 3*nv, indices 3*nt")
         self.ctx._check(lib_amd().pt_scene_update(self.h, v.ctypes.data, v.size // 3, i.ctypes.data, i.size // 3, mode))
+
+    def snapshot_previous(self):
+        """Remembers the scene as it stands now -- vertex positions and instance matrices -- as "the previous geometry" of Film.motion
+        (pt_scene_snapshot_previous).  Call it before the update / set_instances of a time step; a second call replaces the first."""
+        self.ctx._check(lib_amd().pt_scene_snapshot_previous(self.h))
 
     def info(self):
         i = SceneInfo()
@@ -615,6 +641,39 @@ class Film:
         self.ctx._check(lib_amd().pt_film_read_history(self.h, a.ctypes.data))
         return a
 
+    def enable_motion(self, device_ptr=None):
+        """Gives the film its motion plane Q (include/pt_api.h pt_film_enable_motion), which pt_film_motion writes and
+        pt_film_reproject_motion reads.  device_ptr: None (the film allocates it) or a device pointer to width*height*4 floats of
+        caller-owned, 16-byte aligned memory."""
+        self.ctx._check(lib_amd().pt_film_enable_motion(self.h, C.c_void_p(device_ptr) if device_ptr else None))
+
+    def read_motion(self):
+        """-> float32 [H, W, 4]: per pixel where its surface point was in the previous geometry {x, y, z} and 1, or zeros (none known)."""
+        a = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self.ctx._check(lib_amd().pt_film_read_motion(self.h, a.ctypes.data))
+        return a
+
+    def motion(self, scene, cam=None, bary_slack=None, params=None):
+        """Fills the motion plane from this film's guides, rendered (render_aov) for `scene` as it is now at camera `cam`, and the scene's
+        snapshot_previous() (include/pt_api.h pt_film_motion) -> device ms.  cam: a dict as default_params takes it (cam_origin,
+        cam_target; missing keys are the defaults); bary_slack None: pt_motion_params_default's 1 (or `params`, a MotionParams, as it
+        stands)."""
+        p = MotionParams.from_buffer_copy(params) if params is not None else motion_default_params()
+        for k, v in (cam or {}).items():
+            if k not in ("cam_origin", "cam_target"):
+                raise AttributeError(k)
+            setattr(p, k, (C.c_float * 3)(*v))
+        if bary_slack is not None:
+            p.bary_slack = bary_slack
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_film_motion(scene.h, self.h, C.byref(p), C.byref(ms)))
+        return ms.value
+
+    def reproject_motion(self, prev, cam=None, prev_cam=None, params=None, **overrides):
+        """reproject() started from the motion plane (include/pt_api.h pt_film_reproject_motion): a pixel looks for its history where its
+        surface point WAS, so an object moved by Scene.update / set_instances keeps it.  Arguments as reproject()."""
+        return self._reproject("pt_film_reproject_motion", prev, cam, prev_cam, params, overrides)
+
     def reproject(self, prev, cam=None, prev_cam=None, params=None, **overrides):
         """Temporal accumulation (include/pt_api.h pt_film_reproject): this film, rendered (render + render_aov) at camera `cam`, takes over
         the history of `prev`, rendered at `prev_cam` (prev None: starts a sequence) -> device ms.  In place: rewrites this film, its
@@ -622,6 +681,9 @@ class Film:
         cam_target; missing keys are the defaults).  overrides: gain, alpha, depth_tol, normal_min, max_history, flags; anything left out
         takes pt_reproject_params_default's value (or `params`, a ReprojectParams, as it stands -- its cameras too when cam / prev_cam
         are None)."""
+        return self._reproject("pt_film_reproject", prev, cam, prev_cam, params, overrides)
+
+    def _reproject(self, fn, prev, cam, prev_cam, params, overrides):
         p = ReprojectParams.from_buffer_copy(params) if params is not None else reproject_default_params()   # (the caller's object stays as it is)
         for dst, c in (("", cam), ("prev_", prev_cam)):
             for k, v in (c or {}).items():
@@ -633,7 +695,7 @@ class Film:
                 raise AttributeError(k)
             setattr(p, k, v)
         ms = C.c_float(0.0)
-        self.ctx._check(lib_amd().pt_film_reproject(self.h, prev.h if prev is not None else None, C.byref(p), C.byref(ms)))
+        self.ctx._check(getattr(lib_amd(), fn)(self.h, prev.h if prev is not None else None, C.byref(p), C.byref(ms)))
         return ms.value
 
     def read_denoised(self):

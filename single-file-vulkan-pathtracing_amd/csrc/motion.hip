@@ -1,0 +1,141 @@
+// motion.hip -- pt_scene_snapshot_previous and pt_film_motion: where the surface point of every pixel's first hit was before the geometry moved.
+//
+// The definition (the first hit put back into the world as pt_film_reproject does it, its barycentrics in the triangle the id plane names by
+// orthogonal projection, the same barycentrics in the snapshot's triangle) is the header's; tests/test_motion.py restates it in numpy and every
+// comparison is byte equality.  So every operation here is one binary32 operation in the written order (-ffp-contract=off, __fdiv_rn, the
+// correctly rounded square root), and nothing is reassociated.
+//
+//   k_motion<INST>   one launch, the denoiser's block: 64 x 4 pixels, a wave one row of 64.  A pixel reads 16 B of guides (Z, a and the id pair),
+//                    then gathers six float4 vertex records -- the triangle now (d_tri_orig) and in the snapshot -- and, with INST, the three
+//                    rows of the instance's matrix now and in the snapshot; it writes one float4 of Q.  The indices are clamped into their
+//                    arrays and a pixel whose ids name nothing is dropped by a select, so no load stands behind a lane's branch; the loaded
+//                    values are pinned after the last load (MO_KEEP), as reproject.hip does it.  No LDS, no scratch.  Its body is mo_pixel
+//                    (motion_kernel.h).  DESIGN.md section 16 has what the assembly shows.
+#include "pt_internal.h"
+#include "pt_math.h"
+#include "wavefront_host.h"  // ptw_camera
+
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+#define MO_KEEP(v) asm volatile("" : "+v"(v))  // the value exists in a vector register at this point: its load cannot move below
+#include "motion_kernel.h"  // MoConst, MoScene, MoFilm, mo_pixel: the kernel's body
+
+template <bool INST>
+__global__ __launch_bounds__(TB) void k_motion(MoConst mc, MoScene sc, MoFilm fl)
+{
+    const uint32_t by_ = blockIdx.x / mc.n_bx, bx_ = blockIdx.x - by_ * mc.n_bx;
+    const int x = (int)(bx_ * MO_BW + (threadIdx.x & (MO_BW - 1))), y = (int)(by_ * MO_BH + threadIdx.x / MO_BW);
+    if (x >= (int)mc.w || y >= (int)mc.h) return;
+    mo_pixel<INST>(mc, sc, fl, x, y);
+}
+
+using MoFn = decltype(&k_motion<false>);
+MoFn pick_motion(bool inst) { return inst ? k_motion<true> : k_motion<false>; }
+
+bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+}  // namespace
+
+void ptm_free_previous(pt_scene *s)
+{
+    (void)hipFree(s->prev.d_tri);
+    (void)hipFree(s->prev.d_xf);
+    s->prev = pt_scene::Previous{};
+}
+
+pt_status ptm_snapshot(pt_scene *s)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const pt_status rb = s->broken ? ptb_repair(s) : PT_OK;  // (as pt_render: a repair may bring back a parked instance set)
+    if (rb != PT_OK) return rb;
+    const uint32_t n_inst = s->n_inst;
+    if (s->h_xforms.size() != 12 * (size_t)n_inst) { ctx->err = "pt_scene_snapshot_previous: the scene's instance set is incomplete"; return PT_ERR_UNSUPPORTED; }
+    const size_t tri_bytes = sizeof(float4) * 3 * (size_t)s->n_tris, xf_bytes = sizeof(float4) * 3 * (size_t)n_inst;
+    // both new copies are made first and swapped in at the end, the old ones freed after them: a call that fails at any point leaves the
+    // previous snapshot -- triangles and matrices -- as it was
+    float4 *d_tri = nullptr, *d_xf = nullptr;
+    auto fail = [&](hipError_t e, pt_status rc) {
+        (void)hipGetLastError();
+        (void)hipFree(d_tri);
+        (void)hipFree(d_xf);
+        ctx->err = std::string("pt_scene_snapshot_previous: ") + hipGetErrorString(e);
+        return rc;
+    };
+    hipError_t e = hipMalloc((void **)&d_tri, tri_bytes);
+    if (e != hipSuccess) { d_tri = nullptr; return fail(e, PT_ERR_OOM); }
+    if (n_inst) {
+        e = hipMalloc((void **)&d_xf, 2 * xf_bytes);
+        if (e != hipSuccess) { d_xf = nullptr; return fail(e, PT_ERR_OOM); }
+    }
+    // ordered after the work queued on the stream (an update's gather, a render that still reads the triangles)
+    e = hipMemcpyAsync(d_tri, s->d_tri_orig, tri_bytes, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && n_inst) e = hipMemcpyAsync(d_xf, s->h_xforms.data(), xf_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(e, PT_ERR_HIP);
+    (void)hipFree(s->prev.d_tri);
+    (void)hipFree(s->prev.d_xf);
+    s->prev.have = true;
+    s->prev.d_tri = d_tri;
+    s->prev.d_xf = d_xf;
+    s->prev.h_now.clear();  // (the new array's second half holds nothing yet)
+    s->prev.n_inst = n_inst;
+    s->prev.bytes = tri_bytes + 2 * xf_bytes;
+    return PT_OK;
+}
+
+pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *device_ms)
+{
+    pt_ctx *ctx = s->ctx;
+    auto bad = [&](const char *msg) { ctx->err = msg; return PT_ERR_INVALID_ARG; };
+    // every refusal of the header, before anything is written
+    if (f->ctx != ctx) return bad("scene and film belong to different contexts");
+    if (!f->aov.enabled) return bad("the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
+    if (!f->mo.d_q) return bad("the film has no motion plane: pt_film_enable_motion first");
+    if (!s->prev.have) return bad("the scene has no previous geometry: pt_scene_snapshot_previous first");
+    if (!finite3(p->cam_origin) || !finite3(p->cam_target)) return bad("pt_motion_params: the camera must be finite");
+    if (!(std::isfinite(p->bary_slack) && p->bary_slack >= 0.f)) return bad("pt_motion_params.bary_slack must be finite and >= 0");
+    for (uint32_t r : p->reserved)
+        if (r) return bad("pt_motion_params.reserved must be 0");
+    const pt_status rb = s->broken ? ptb_repair(s) : PT_OK;
+    if (rb != PT_OK) return rb;
+    const uint32_t n_inst = s->n_inst;
+    if (n_inst != s->prev.n_inst) return bad("the scene's instance count differs from the snapshot's");
+    if (s->h_xforms.size() != 12 * (size_t)n_inst) { ctx->err = "pt_film_motion: the scene's instance set is incomplete"; return PT_ERR_UNSUPPORTED; }
+    pt_params cp{};
+    for (int k = 0; k < 3; k++) { cp.cam_origin[k] = p->cam_origin[k]; cp.cam_target[k] = p->cam_target[k]; }
+    cp.width = f->w; cp.height = f->h;
+    MoConst mc{};
+    mc.w = f->w; mc.h = f->h;
+    mc.n_bx = (f->w + MO_BW - 1) / MO_BW;
+    mc.n_tris = s->n_tris;
+    mc.n_inst = n_inst ? n_inst : 1u;
+    mc.cam = ptw_camera(&cp);   // the camera pt_render and pt_render_aov start their rays from
+    mc.slack = p->bary_slack;
+    const size_t xf_rows = 3 * (size_t)n_inst;
+    const MoScene sc = { s->d_tri_orig, s->prev.d_tri, n_inst ? s->prev.d_xf + xf_rows : nullptr, s->prev.d_xf };
+    const pt_film::Aov &a = f->aov;
+    const MoFilm fl = { static_cast<const float *>(a.plane[PT_AOV_DEPTH]), static_cast<const float *>(a.plane[PT_AOV_ALPHA]),
+                        static_cast<const uint2 *>(a.plane[PT_AOV_ID]), f->mo.d_q };
+    hipStream_t st = ctx->stream;
+    // the scene's matrices as they are now, in gl_InstanceID order, into the second half of the snapshot's array
+    // (once per pt_scene_set_instances, not once per call; compared as bytes: -0 is not +0 here)
+    if (n_inst && (s->prev.h_now.size() != s->h_xforms.size() || std::memcmp(s->prev.h_now.data(), s->h_xforms.data(), sizeof(float) * s->h_xforms.size()) != 0)) {
+        s->prev.h_now.clear();
+        PT_HIP(ctx, hipMemcpyAsync(s->prev.d_xf + xf_rows, s->h_xforms.data(), sizeof(float4) * xf_rows, hipMemcpyHostToDevice, st));
+        PT_HIP(ctx, hipStreamSynchronize(st));
+        s->prev.h_now = s->h_xforms;
+    }
+    const uint32_t n_blocks = mc.n_bx * ((f->h + MO_BH - 1) / MO_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    hipLaunchKernelGGL(pick_motion(n_inst != 0), dim3(n_blocks), dim3(TB), 0, st, mc, sc, fl);
+    PT_HIP(ctx, hipGetLastError());
+    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipGetLastError());
+    if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
+    return PT_OK;
+}

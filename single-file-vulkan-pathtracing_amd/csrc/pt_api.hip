@@ -208,6 +208,7 @@ pt_status pt_scene_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n
 void pt_scene_destroy(pt_scene *s)
 {
     if (!s) return;
+    ptm_free_previous(s);
     ptb_free_instances(s);
     ptb_free_scene_buffers(s);
     delete s;
@@ -246,7 +247,7 @@ pt_status pt_scene_get_info(const pt_scene *s, pt_scene_info *info)
     info->bvh4_builder = s->bvh4_builder;
     for (int k = 0; k < 3; k++) { info->bbox_min[k] = s->bmin[k]; info->bbox_max[k] = s->bmax[k]; }
     info->build_ms = s->build_ms;
-    info->device_bytes = s->device_bytes;
+    info->device_bytes = s->device_bytes + s->prev.bytes;  // (prev: 0 until pt_scene_snapshot_previous)
     // (normalised by the root's area = the scene box's: the same for both trees)
     const double ex = (double)s->bmax[0] - s->bmin[0], ey = (double)s->bmax[1] - s->bmin[1], ez = (double)s->bmax[2] - s->bmin[2];
     const double root = (ex * ey + ey * ez) + ez * ex;
@@ -332,6 +333,7 @@ pt_status pt_film_clear(pt_film *f)
     if (f->m2.d_m2) PT_HIP(ctx, hipMemsetAsync(f->m2.d_m2, 0, sizeof(float) * 3 * (size_t)f->w * f->h, ctx->stream));
     f->m2.frames = 0;
     if (f->hist.d_len) PT_HIP(ctx, hipMemsetAsync(f->hist.d_len, 0, sizeof(float) * (size_t)f->w * f->h, ctx->stream));
+    if (f->mo.d_q) PT_HIP(ctx, hipMemsetAsync(f->mo.d_q, 0, sizeof(float4) * (size_t)f->w * f->h, ctx->stream));
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -362,6 +364,7 @@ void pt_film_destroy(pt_film *f)
     ptd_free(f);
     if (f->m2.own) (void)hipFree(f->m2.d_m2);
     if (f->hist.own) (void)hipFree(f->hist.d_len);
+    if (f->mo.own) (void)hipFree(f->mo.d_q);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
     delete f;
@@ -570,6 +573,77 @@ pt_status pt_film_reproject(pt_film *f, pt_film *prev, const pt_reproject_params
     if (!f || !p) return PT_ERR_INVALID_ARG;
     PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
     return guarded(f->ctx, [&] { return ptr_reproject(f, prev, p, device_ms); });
+}
+
+pt_status pt_scene_snapshot_previous(pt_scene *s)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return ptm_snapshot(s); });
+}
+
+pt_status pt_film_enable_motion(pt_film *f, void *device_q_f32x4)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (f->mo.d_q) { ctx->err = "the film already has a motion plane"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    return guarded(ctx, [&]() -> pt_status {
+        const size_t bytes = sizeof(float4) * (size_t)f->w * f->h;
+        void *plane = device_q_f32x4;
+        if (!plane) {
+            const hipError_t e = hipMalloc(&plane, bytes);
+            if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PT_ERR_OOM; }
+        } else if (reinterpret_cast<uintptr_t>(plane) & 15u) {
+            ctx->err = "pt_film_enable_motion: the plane must be 16-byte aligned";
+            return PT_ERR_INVALID_ARG;
+        }
+        hipError_t e = hipMemsetAsync(plane, 0, bytes, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            if (!device_q_f32x4) (void)hipFree(plane);
+            ctx->err = std::string("pt_film_enable_motion: ") + hipGetErrorString(e);
+            return PT_ERR_HIP;
+        }
+        f->mo.d_q = static_cast<float4 *>(plane);
+        f->mo.own = device_q_f32x4 == nullptr;
+        return PT_OK;
+    });
+}
+
+pt_status pt_film_read_motion(pt_film *f, float *q4)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (!q4) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    if (!f->mo.d_q) { ctx->err = "the film has no motion plane: pt_film_enable_motion first"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(q4, f->mo.d_q, sizeof(float4) * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+void pt_motion_params_default(pt_motion_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    pt_params cam;
+    pt_params_default(&cam);
+    for (int k = 0; k < 3; k++) { p->cam_origin[k] = cam.cam_origin[k]; p->cam_target[k] = cam.cam_target[k]; }
+    p->bary_slack = 1.0f;
+}
+
+pt_status pt_film_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *device_ms)
+{
+    if (!s || !f || !p) return PT_ERR_INVALID_ARG;
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return ptm_motion(s, f, p, device_ms); });
+}
+
+pt_status pt_film_reproject_motion(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms)
+{
+    if (!f || !p) return PT_ERR_INVALID_ARG;
+    PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return guarded(f->ctx, [&] { return ptr_reproject(f, prev, p, device_ms, true); });
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)

@@ -145,6 +145,17 @@ struct pt_scene {
     uint32_t n_tlas16 = 0, tlas16_levels = 0;
     float tlas_norm_c[3]{}, tlas_norm_s[3]{1.f, 1.f, 1.f}, tlas_norm_rs[3]{1.f, 1.f, 1.f};
     float tlas_bmin[3]{}, tlas_bmax[3]{};  // the union of the instances' world boxes (k_inst_boxes): what no ray outside of can hit
+    // pt_scene_snapshot_previous (motion.hip): "the previous geometry" of pt_film_motion.  Nothing of it exists before the first call.
+    struct Previous {
+        bool have = false;
+        float4 *d_tri = nullptr;   // a copy of d_tri_orig as it stood: 3 float4 per triangle in primitive order
+        // [0, 3 n_inst): the instance matrices as they stood, 3 rows of float4 each in gl_InstanceID order; [3 n_inst, 6 n_inst): the place
+        // pt_film_motion uploads the scene's current matrices to (the device holds those in TLAS leaf order only).  Null when n_inst == 0.
+        float4 *d_xf = nullptr;
+        uint32_t n_inst = 0;       // 0: single-level
+        std::vector<float> h_now;  // what the second half of d_xf holds (empty: nothing yet): pt_film_motion uploads only when h_xforms differs
+        uint64_t bytes = 0;        // device bytes of both: added to pt_scene_info.device_bytes
+    } prev;
 };
 
 struct pt_film {
@@ -225,6 +236,11 @@ struct pt_film {
         float *d_len = nullptr;                       // w*h floats, or null: the film has no such plane
         bool own = false;
     } hist;
+    // pt_film_enable_motion: where the surface point of a pixel's first hit was in the previous geometry (motion.hip).  A film plane like L.
+    struct Motion {
+        float4 *d_q = nullptr;                        // w*h float4 {x, y, z, valid}, or null: the film has no such plane
+        bool own = false;
+    } mo;
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -288,4 +304,9 @@ pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, 
 pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out, float *device_ms);
 void ptd_free(pt_film *f);
 // reproject.hip: temporal accumulation -- `f` takes over the history of `prev` (null: starts a sequence); validates everything but the null checks
-pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms);
+// motion: pt_film_reproject_motion -- the reprojection starts from the film's plane Q
+pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms, bool motion = false);
+// motion.hip: the previous geometry of a scene and the plane Q made from it (everything but the null checks is validated there)
+pt_status ptm_snapshot(pt_scene *s);
+void ptm_free_previous(pt_scene *s);
+pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *device_ms);

@@ -12,6 +12,9 @@
 //                        the validity terms are flags combined with & (a && chain became branches with loads behind them), and the loaded
 //                        values are pinned after the last load (RP_KEEP) -- section 15 has what the assembly shows.  No LDS, no scratch; the film is
 //                        rewritten in place, a pixel touching no other pixel of it.  Its body is rp_pixel (reproject_kernel.h).
+//   k_reproject_motion<HAS_M>   pt_film_reproject_motion: rp_pixel<HAS_M, true>.  The point that goes through the previous camera is read from
+//                        the film's plane Q (16 B more per pixel) instead of being put back into the world from Z / a; everything after it is
+//                        k_reproject's.  A kernel of its own with an argument of its own.
 #include "pt_internal.h"
 #include "pt_math.h"
 #include "wavefront_host.h"  // ptw_camera
@@ -35,16 +38,31 @@ __global__ __launch_bounds__(TB) void k_reproject(RpConst rc, RpFilm fl, RpPrev 
 using RpFn = decltype(&k_reproject<false>);
 RpFn pick_reproject(bool has_m) { return has_m ? k_reproject<true> : k_reproject<false>; }
 
+// pt_film_reproject_motion: the same body started from the film's plane Q, which is an argument of these instantiations alone (k_reproject's
+// argument block, and with it its scalar loads, stay as they are)
+template <bool HAS_M>
+__global__ __launch_bounds__(TB) void k_reproject_motion(RpConst rc, RpFilm fl, RpPrev pv, const float *__restrict__ motion)
+{
+    const uint32_t by_ = blockIdx.x / rc.n_bx, bx_ = blockIdx.x - by_ * rc.n_bx;
+    const int x = (int)(bx_ * RP_BW + (threadIdx.x & (RP_BW - 1))), y = (int)(by_ * RP_BH + threadIdx.x / RP_BW);
+    if (x >= (int)rc.w || y >= (int)rc.h) return;
+    rp_pixel<HAS_M, true>(rc, fl, pv, x, y, motion);
+}
+
+using RpMotionFn = decltype(&k_reproject_motion<false>);
+RpMotionFn pick_reproject_motion(bool has_m) { return has_m ? k_reproject_motion<true> : k_reproject_motion<false>; }
+
 bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 // every refusal of the header, in one place; nothing is written before it returns PT_OK
-pt_status rp_validate(pt_film *f, pt_film *prev, const pt_reproject_params *p)
+pt_status rp_validate(pt_film *f, pt_film *prev, const pt_reproject_params *p, bool motion)
 {
     pt_ctx *ctx = f->ctx;
     auto bad = [&](const char *msg) { ctx->err = msg; return PT_ERR_INVALID_ARG; };
     if (prev == f) return bad("pt_film_reproject: prev is the film itself (the history is read while the film is rewritten: two films, ping-ponged)");
     if (!f->aov.enabled) return bad("the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
     if (!f->hist.d_len) return bad("the film has no history-length plane: pt_film_enable_history first");
+    if (motion && !f->mo.d_q) return bad("the film has no motion plane: pt_film_enable_motion (and pt_film_motion) first");
     if (prev) {
         if (prev->ctx != ctx) return bad("film and prev belong to different contexts");
         if (prev->w != f->w || prev->h != f->h) return bad("film and prev differ in size");
@@ -67,10 +85,10 @@ pt_status rp_validate(pt_film *f, pt_film *prev, const pt_reproject_params *p)
 
 }  // namespace
 
-pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms)
+pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms, bool motion)
 {
     pt_ctx *ctx = f->ctx;
-    const pt_status rv = rp_validate(f, prev, p);
+    const pt_status rv = rp_validate(f, prev, p, motion);
     if (rv != PT_OK) return rv;
     pt_params cp{};
     for (int k = 0; k < 3; k++) { cp.cam_origin[k] = p->cam_origin[k]; cp.cam_target[k] = p->cam_target[k]; }
@@ -97,7 +115,8 @@ pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p,
     hipStream_t st = ctx->stream;
     const uint32_t n_blocks = rc.n_bx * ((f->h + RP_BH - 1) / RP_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
     PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    hipLaunchKernelGGL(pick_reproject(f->m2.d_m2 != nullptr), dim3(n_blocks), dim3(TB), 0, st, rc, fl, pv);
+    if (motion) hipLaunchKernelGGL(pick_reproject_motion(f->m2.d_m2 != nullptr), dim3(n_blocks), dim3(TB), 0, st, rc, fl, pv, reinterpret_cast<const float *>(f->mo.d_q));
+    else hipLaunchKernelGGL(pick_reproject(f->m2.d_m2 != nullptr), dim3(n_blocks), dim3(TB), 0, st, rc, fl, pv);
     PT_HIP(ctx, hipGetLastError());
     PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
     PT_HIP(ctx, hipStreamSynchronize(st));

@@ -38,9 +38,10 @@ struct RpTap {
     uint2 id;
 };
 
-// one pixel (x, y) inside the image: everything k_reproject does
-template <bool HAS_M>
-__device__ __forceinline__ void rp_pixel(const RpConst &rc, const RpFilm &fl, const RpPrev &pv, int x, int y)
+// one pixel (x, y) inside the image: everything k_reproject does.  MOTION (pt_film_reproject_motion): the point that goes through the previous
+// camera is the film's plane Q (`motion`, 4 floats per pixel {x, y, z, valid}: where the surface point was) instead of the first hit P
+template <bool HAS_M, bool MOTION = false>
+__device__ __forceinline__ void rp_pixel(const RpConst &rc, const RpFilm &fl, const RpPrev &pv, int x, int y, const float *motion = nullptr)
 {
     const int w = (int)rc.w, h = (int)rc.h;
     const size_t p = (size_t)y * rc.w + (uint32_t)x, p3 = 3 * p;
@@ -62,13 +63,17 @@ __device__ __forceinline__ void rp_pixel(const RpConst &rc, const RpFilm &fl, co
         const float len = ptm::fsqrt((vx * vx + vy * vy) + vz * vz);
         float dx, dy, dz;
         ptm::div3_dominant(vx, vy, vz, len, dx, dy, dz);
-        const float ux = (rc.cam.ox + dx * t) - rc.pox, uy = (rc.cam.oy + dy * t) - rc.poy, uz = (rc.cam.oz + dz * t) - rc.poz;
+        // MOTION: where the surface point was instead (pt_film_motion; one aligned 16-B record), and nothing of the above is computed
+        const float *mq = MOTION ? static_cast<const float *>(__builtin_assume_aligned(motion + 4 * p, 16)) : nullptr;
+        const float qx = MOTION ? mq[0] : 0.f, qy = MOTION ? mq[1] : 0.f, qz = MOTION ? mq[2] : 0.f, qw = MOTION ? mq[3] : 1.f;
+        const float ux = MOTION ? qx - rc.pox : (rc.cam.ox + dx * t) - rc.pox, uy = MOTION ? qy - rc.poy : (rc.cam.oy + dy * t) - rc.poy,
+                    uz = MOTION ? qz - rc.poz : (rc.cam.oz + dz * t) - rc.poz;
         // ... and through the previous camera: the inverse of primary_target
         const float vzp = rc.ptz - rc.poz;
         const float s = ptm::fdiv(vzp, uz);
         const float ex = (ux * s + rc.pox) - rc.ptx, ey = (uy * s + rc.poy) - rc.pty;
         const float fx = ((ex + 1.0f) * 0.5f) * rc.cam.w - 0.5f, fy = ((ey + 1.0f) * 0.5f) * rc.cam.h - 0.5f;
-        const bool inside = (ap > 0.0f) & (uz * vzp > 0.0f) & (fx > -1.0f) & (fx < rc.cam.w) & (fy > -1.0f) & (fy < rc.cam.h);  // (a NaN fails)
+        const bool inside = (MOTION ? (ap > 0.0f) & (qw > 0.0f) : (ap > 0.0f)) & (uz * vzp > 0.0f) & (fx > -1.0f) & (fx < rc.cam.w) & (fy > -1.0f) & (fy < rc.cam.h);  // (a NaN fails)
         const float x0f = floorf(fx), y0f = floorf(fy);
         const float bx = fx - x0f, by = fy - y0f;
         const float d = ptm::fsqrt((ux * ux + uy * uy) + uz * uz);
