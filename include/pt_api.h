@@ -548,6 +548,51 @@ void pt_motion_params_default(pt_motion_params *p);   /* the camera: pt_params_d
 pt_status pt_film_motion(pt_scene *scene, pt_film *film, const pt_motion_params *params, float *device_ms);
 pt_status pt_film_reproject_motion(pt_film *film, pt_film *prev, const pt_reproject_params *params, float *device_ms);
 
+/* ---- per-pixel variance for reprojected films ------------------------------------------------------------------------------------------
+ * pt_film_denoise_history is pt_film_denoise_variance for the film pt_film_reproject leaves: every pixel there has a history length L of
+ * its own, so one caller-named n fits no pixel, and a pixel that just restarted (L = 1) holds M = C*C exactly -- its variance estimate is 0
+ * and the colour stop a hard stop that keeps the noise.  This call makes V0 per pixel (the step SVGF calls variance estimation): the temporal
+ * moments where the history is long enough, a spatial estimate over the 5 x 5 neighbourhood where it is not.  All arithmetic is binary32,
+ * every operation rounded on its own, no contraction, denormals kept, operation order as written.  C, D, I, A, N, E, Z, a, h, x_n and x_z are
+ * exactly those of pt_film_denoise; M and L are the film's planes as stored; mh = min_history.  Per pixel p = (x, y):
+ *   LONG HISTORY, L_p >= mh (a NaN fails):
+ *                  n   = min(L_p * (float)step_frames, n_max)
+ *                  v_c = max(M_c - C_c*C_c, 0) / (n - 1)
+ *                  V0  = ((v_r / (D_r*D_r)) + (v_g / (D_g*D_g))) + (v_b / (D_b*D_b))
+ *   SHORT HISTORY, every other pixel (L = 0, a film that was never reprojected, included):
+ *                  S = 0, s1_c = 0, s2_c = 0;  for j = -2 .. 2 (outer), i = -2 .. 2 (inner), q = (x + i, y + j), taps outside the image skipped:
+ *                  t   = max(0, 1 - (x_n + x_z) * 0.0625f);   t = t*t, four times               (the guides' weight alone: no h, no colour)
+ *                  S = S + t;   s1_c = s1_c + t * I_c(q);   s2_c = s2_c + t * (I_c(q) * I_c(q))
+ *                  mu_c = s1_c / S;   m_c = s2_c / S;   s_c = max(m_c - mu_c*mu_c, 0);   e_c = I_c(p) - mu_c      (the centre tap has t = 1: S > 0)
+ *                  Vs  = ((s_r + s_g) + s_b) + ((e_r*e_r + e_g*e_g) + e_b*e_b)
+ *                  V0  = Vs * (mh / max(L_p, 1.0f))                                           (a NaN L_p counts as 1)
+ * From V0 on the filter is pt_film_denoise_variance word for word: the 3 x 3 pre-blur, the iterations with x_c, V' = vnum / den^2,
+ * remodulation and the bgra8 form.
+ * The own-deviation term e is what a restarted pixel among converged neighbours needs: its neighbourhood's variance is small and its own
+ * deviation large.  mh / max(L, 1) is SVGF's 4 / history: the estimate is of one step's variance, the pixel averages L of them, and the
+ * factor errs to the blurry side.  n = min(L * step_frames, n_max) is an approximation: it is exact while 1 / (L + 1) >= alpha, where
+ * pt_film_reproject is a running mean of L steps, and exact in the limit of an exponential average of weight alpha, whose effective sample
+ * count tends to (2 - alpha) / alpha; between the two it is within that range.  DESIGN.md section 17 has the experiment.
+ * Placement, blocking, scratch ownership (the same 48 B per pixel, V in the spare word), budget, device_ms, pt_film_read_denoised and the
+ * caveat about (rank, world) films are those of pt_film_denoise_variance; the film, its planes M and L, the guides and pt_stats stay as they
+ * were.
+ * PT_ERR_INVALID_ARG, nothing written and nothing launched: NULL film or params; a film without guides, without the second-moment plane or
+ * without L; iterations outside 1..8; a sigma that is not finite and > 0; min_history not finite or outside 1..65536; n_max not finite or < 2;
+ * step_frames == 0; min_history * step_frames < 2; a nonzero reserved word.                                                              */
+typedef struct pt_denoise_history_params {
+    uint32_t iterations;       /* 1..8; default 5 */
+    float sigma_normal;        /* default 0.5  */
+    float sigma_depth;         /* default 0.1  */
+    float sigma_color;         /* default 3.0  */
+    float min_history;         /* default 4: pixels with L below it take the spatial estimate; finite, 1..65536 */
+    float n_max;               /* default 9 = (2 - alpha) / alpha at pt_reproject_params_default's alpha: the effective sample count an
+                                  exponential average tends to; finite, >= 2 */
+    uint32_t step_frames;      /* default 1: frames rendered per time step; >= 1; min_history * step_frames >= 2 */
+    uint32_t reserved[1];      /* must be 0 */
+} pt_denoise_history_params;   /* 32 bytes */
+void pt_denoise_history_params_default(pt_denoise_history_params *p);
+pt_status pt_film_denoise_history(pt_film *film, const pt_denoise_history_params *params, void *device_out_rgb_f32, float *device_ms);
+
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {
     uint32_t prim;  /* gl_PrimitiveID, 0xFFFFFFFF = miss                                   */

@@ -107,6 +107,12 @@ class DenoiseVarianceParams(C.Structure):
                 ("frames", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class DenoiseHistoryParams(C.Structure):
+    """include/pt_api.h pt_denoise_history_params: the variance-guided filter with a per-pixel variance, pt_film_denoise_history."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_color", C.c_float),
+                ("min_history", C.c_float), ("n_max", C.c_float), ("step_frames", C.c_uint32), ("reserved", C.c_uint32 * 1)]
+
+
 REPROJECT_MATCH_ID = 1   # include/pt_api.h PT_REPROJECT_MATCH_ID
 
 
@@ -150,7 +156,7 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
                "pt_device_alloc", "pt_device_free", "pt_device_read", "pt_device_write", "pt_ctx_get_tuning", "pt_ctx_set_tuning",
                "pt_scene_snapshot_previous", "pt_film_enable_motion", "pt_film_read_motion", "pt_motion_params_default", "pt_film_motion",
-               "pt_film_reproject_motion"]
+               "pt_film_reproject_motion", "pt_denoise_history_params_default", "pt_film_denoise_history"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium"]
 
@@ -233,6 +239,10 @@ def lib_amd():
             L.pt_motion_params_default.restype = None
             L.pt_film_motion.argtypes = [vp, vp, C.POINTER(MotionParams), C.POINTER(C.c_float)]
             L.pt_film_reproject_motion.argtypes = [vp, vp, C.POINTER(ReprojectParams), C.POINTER(C.c_float)]
+        if hasattr(L, "pt_film_denoise_history"):   # (per-pixel variance for reprojected films; as above)
+            L.pt_denoise_history_params_default.argtypes = [C.POINTER(DenoiseHistoryParams)]
+            L.pt_denoise_history_params_default.restype = None
+            L.pt_film_denoise_history.argtypes = [vp, C.POINTER(DenoiseHistoryParams), vp, C.POINTER(C.c_float)]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -381,6 +391,12 @@ def denoise_default_params():
 def denoise_variance_default_params():
     p = DenoiseVarianceParams()
     lib_amd().pt_denoise_variance_params_default(C.byref(p))
+    return p
+
+
+def denoise_history_default_params():
+    p = DenoiseHistoryParams()
+    lib_amd().pt_denoise_history_params_default(C.byref(p))
     return p
 
 
@@ -628,6 +644,21 @@ class Film:
                 setattr(p, name, v)
         ms = C.c_float(0.0)
         self.ctx._check(lib_amd().pt_film_denoise_variance(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
+        return ms.value
+
+    def denoise_history(self, iterations=None, sigma_normal=None, sigma_depth=None, sigma_color=None, min_history=None, n_max=None, step_frames=None,
+                        device_out=None, params=None):
+        """The variance-guided filter with a per-pixel variance (include/pt_api.h pt_film_denoise_history) over a film that reproject()
+        left: its guide planes, its second-moment plane and its history length -> device ms.  Arguments as in denoise_variance();
+        min_history: pixels whose history is shorter take the spatial estimate; n_max: the cap of the sample count; step_frames: frames
+        rendered per time step.  The film-owned result is read with read_denoised / read_denoised_bgra8."""
+        p = DenoiseHistoryParams.from_buffer_copy(params) if params is not None else denoise_history_default_params()
+        for name, v in (("iterations", iterations), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_color", sigma_color),
+                        ("min_history", min_history), ("n_max", n_max), ("step_frames", step_frames)):
+            if v is not None:
+                setattr(p, name, v)
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_film_denoise_history(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
         return ms.value
 
     def enable_history(self, device_ptr=None):

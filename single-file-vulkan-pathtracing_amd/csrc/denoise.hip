@@ -15,12 +15,24 @@
 //   k_dn_prepare_var   k_dn_prepare, and V0 from the film's second-moment plane (+ 12 B per pixel read) into illum.w
 //   k_dn_var_blur      the 3 x 3 pre-blur of .w, from one ping-pong plane into the other (rgb copied)
 //   k_dn_atrous_var    k_dn_atrous with x_c in the weight, and V' = sum w^2 V_q / den^2 into .w
+//
+// pt_film_denoise_history is pt_film_denoise_variance with V0 made per pixel, for a film that pt_film_reproject left with a history length L
+// of its own in every pixel.  Two kernels in front of the pre-blur, their bodies in denoise_history_kernel.h:
+//   k_dn_prepare_hist  k_dn_prepare_var with n = min(L * step_frames, n_max) from the film's L plane (+ 4 B per pixel read); 0 into .w where
+//                      L < min_history
+//   k_dn_var_spatial   illum[0] -> illum[1].  A lane reads its own L; a wave (one row of 64) in which no lane is short copies its records
+//                      and is done -- one wave-wide vote and a uniform branch.  Otherwise the 5 x 5 window at step 1: per row of taps the ten
+//                      128-bit loads together from clamped addresses, long lanes and taps outside the image dropped by selects.
+// Both take arguments of their own (DhConst, DhPlanes): DnConst and DnPlanes, whose layout the older kernels' scalar loads depend on, stay.
 #include "pt_internal.h"
 #include "pt_math.h"
 
 #include <cmath>
 
 namespace {
+
+#define DH_KEEP(v) asm volatile("" : "+v"(v))  // the value exists in a vector register at this point: its load cannot move below
+#include "denoise_history_kernel.h"  // DhConst, DhPlanes, dh_prepare_pixel, dh_spatial_pixel: the two kernels' bodies
 
 struct DnConst {
     uint32_t w, h, n_bx;  // image, blocks per row of blocks
@@ -96,6 +108,31 @@ __global__ __launch_bounds__(TB) void k_dn_var_blur(DnConst dc, const float4 *__
     }
     rec.w = ptm::fdiv(sum, wsum);
     illum_out[p] = rec;
+}
+
+// pt_film_denoise_history: V0 per pixel from its own history length (the bodies: denoise_history_kernel.h)
+__global__ __launch_bounds__(TB) void k_dn_prepare_hist(uint32_t n_pix, DhConst hc, DhPlanes pl, float4 *__restrict__ illum, float4 *__restrict__ guide)
+{
+    const uint32_t p = blockIdx.x * TB + threadIdx.x;
+    if (p >= n_pix) return;
+    dh_prepare_pixel(hc, pl, p, illum, guide);
+}
+
+__global__ __launch_bounds__(TB) void k_dn_var_spatial(DhConst hc, const float *__restrict__ len, const float4 *__restrict__ guide, const float4 *__restrict__ illum_in,
+                                                       float4 *__restrict__ illum_out)
+{
+    const uint32_t by = blockIdx.x / hc.n_bx, bx = blockIdx.x - by * hc.n_bx;
+    const int x = (int)(bx * DH_BW + (threadIdx.x & (DH_BW - 1))), y = (int)(by * DH_BH + threadIdx.x / DH_BW);
+    if (x >= (int)hc.w || y >= (int)hc.h) return;
+    const size_t p = (size_t)y * hc.w + (uint32_t)x;
+    const float l = len[p];
+    const float4 rec = illum_in[p];
+    // the vote: the lanes of a wave are one row's pixels inside the image; on a steady reprojected film most waves hold no short pixel
+    if (__builtin_amdgcn_ballot_w64(dh_short(l, hc.mh)) == 0) {
+        illum_out[p] = rec;
+        return;
+    }
+    illum_out[p] = dh_spatial_pixel(hc, guide, illum_in, x, y, l, rec);
 }
 
 // k_resolve's clamp and quantise (shade_kernels.hip to_unorm8)
@@ -241,12 +278,18 @@ using DnAtrousVarFn = decltype(&k_dn_atrous_var<false>);
 DnAtrousFn pick_dn_atrous(bool last) { return last ? k_dn_atrous<true> : k_dn_atrous<false>; }
 DnAtrousVarFn pick_dn_atrous_var(bool last) { return last ? k_dn_atrous_var<true> : k_dn_atrous_var<false>; }
 
-// Both filters: the scratch, then prepare (+ the pre-blur), the iterations, the wait.  var: null for pt_film_denoise.
+// The three filters: the scratch, then prepare (+ the spatial estimate, the pre-blur), the iterations, the wait.  var: null for
+// pt_film_denoise.  hist (with var; var->frames unused): pt_film_denoise_history.
 struct DnVariance {
     float sigma_color;
     uint32_t frames;
 };
-pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigma_depth, const DnVariance *var, void *device_out, float *device_ms)
+struct DnHistory {
+    float min_history, n_max;
+    uint32_t step_frames;
+};
+pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigma_depth, const DnVariance *var, void *device_out, float *device_ms,
+                 const DnHistory *hist = nullptr)
 {
     pt_ctx *ctx = f->ctx;
     pt_film::Denoise &d = f->dn;
@@ -275,7 +318,16 @@ pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigm
     const uint32_t n_blocks = dc.n_bx * ((f->h + DN_BH - 1) / DN_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
     PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
     uint32_t in = 0;  // the ping-pong plane the first iteration reads
-    if (var) {
+    if (hist) {
+        DhConst hc{};
+        hc.w = dc.w; hc.h = dc.h; hc.n_bx = dc.n_bx;
+        hc.inv_n = dc.inv_n; hc.sz2 = dc.sz2;
+        hc.mh = hist->min_history; hc.sf = (float)hist->step_frames; hc.n_max = hist->n_max;
+        const DhPlanes hp = { pl.film, pl.albedo, pl.normal, pl.emission, pl.depth, pl.alpha, f->m2.d_m2, f->hist.d_len };
+        k_dn_prepare_hist<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, hc, hp, d.d_illum[0], d.d_guide);
+        k_dn_var_spatial<<<n_blocks, TB, 0, st>>>(hc, f->hist.d_len, d.d_guide, d.d_illum[0], d.d_illum[1]);
+        k_dn_var_blur<<<n_blocks, TB, 0, st>>>(dc, d.d_illum[1], d.d_illum[0]);
+    } else if (var) {
         k_dn_prepare_var<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, f->m2.d_m2, (float)(var->frames - 1), d.d_illum[0], d.d_guide);
         k_dn_var_blur<<<n_blocks, TB, 0, st>>>(dc, d.d_illum[0], d.d_illum[1]);
         in = 1;
@@ -333,4 +385,25 @@ pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, 
     const DnVariance v = { p->sigma_color, p->frames ? p->frames : f->m2.frames };
     if (v.frames < 2) { ctx->err = "pt_film_denoise_variance: a variance estimate needs a film of at least 2 frames (params.frames, or what pt_render recorded)"; return PT_ERR_INVALID_ARG; }
     return dn_run(f, p->iterations, p->sigma_normal, p->sigma_depth, &v, device_out, device_ms);
+}
+
+pt_status ptd_denoise_history(pt_film *f, const pt_denoise_history_params *p, void *device_out, float *device_ms)
+{
+    pt_ctx *ctx = f->ctx;
+    auto bad = [&](const char *msg) { ctx->err = msg; return PT_ERR_INVALID_ARG; };
+    if (!f->aov.enabled) return bad("the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
+    if (!f->m2.d_m2) return bad("the film has no second-moment plane: pt_film_enable_moments before the frames are rendered");
+    if (!f->hist.d_len) return bad("the film has no history-length plane: pt_film_enable_history (and pt_film_reproject) first");
+    if (p->iterations < 1 || p->iterations > 8) return bad("pt_denoise_history_params.iterations must be in 1..8");
+    for (float sg : { p->sigma_normal, p->sigma_depth, p->sigma_color })
+        if (!(std::isfinite(sg) && sg > 0.f)) return bad("pt_denoise_history_params.sigma_normal / sigma_depth / sigma_color must be finite and > 0");
+    if (!(p->min_history >= 1.f && p->min_history <= 65536.f)) return bad("pt_denoise_history_params.min_history must be finite and in 1..65536");
+    if (!(std::isfinite(p->n_max) && p->n_max >= 2.f)) return bad("pt_denoise_history_params.n_max must be finite and >= 2");
+    if (p->step_frames == 0) return bad("pt_denoise_history_params.step_frames must be >= 1");
+    if (p->min_history * (float)p->step_frames < 2.f) return bad("pt_denoise_history_params: min_history * step_frames must be >= 2 (a variance estimate needs two frames)");
+    for (uint32_t r : p->reserved)
+        if (r) return bad("pt_denoise_history_params.reserved must be 0");
+    const DnVariance v = { p->sigma_color, 0 };
+    const DnHistory hs = { p->min_history, p->n_max, p->step_frames };
+    return dn_run(f, p->iterations, p->sigma_normal, p->sigma_depth, &v, device_out, device_ms, &hs);
 }

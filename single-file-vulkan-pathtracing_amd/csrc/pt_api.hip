@@ -513,6 +513,26 @@ pt_status pt_film_denoise_variance(pt_film *f, const pt_denoise_variance_params 
     return guarded(f->ctx, [&] { return ptd_denoise_variance(f, p, device_out_rgb_f32, device_ms); });
 }
 
+void pt_denoise_history_params_default(pt_denoise_history_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->iterations = 5;
+    p->sigma_normal = 0.5f;
+    p->sigma_depth = 0.1f;
+    p->sigma_color = 3.0f;
+    p->min_history = 4.0f;
+    p->n_max = 9.0f;
+    p->step_frames = 1;
+}
+
+pt_status pt_film_denoise_history(pt_film *f, const pt_denoise_history_params *p, void *device_out_rgb_f32, float *device_ms)
+{
+    if (!f || !p) return PT_ERR_INVALID_ARG;
+    PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return guarded(f->ctx, [&] { return ptd_denoise_history(f, p, device_out_rgb_f32, device_ms); });
+}
+
 pt_status pt_film_enable_history(pt_film *f, void *device_len_f32)
 {
     if (!f) return PT_ERR_INVALID_ARG;

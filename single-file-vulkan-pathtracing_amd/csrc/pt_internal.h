@@ -302,6 +302,7 @@ void pta_free(pt_film *f);
 // denoise.hip: the a-trous filter over the film and its guide planes
 pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms);
 pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out, float *device_ms);
+pt_status ptd_denoise_history(pt_film *f, const pt_denoise_history_params *p, void *device_out, float *device_ms);
 void ptd_free(pt_film *f);
 // reproject.hip: temporal accumulation -- `f` takes over the history of `prev` (null: starts a sequence); validates everything but the null checks
 // motion: pt_film_reproject_motion -- the reprojection starts from the film's plane Q

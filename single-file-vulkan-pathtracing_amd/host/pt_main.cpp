@@ -22,7 +22,9 @@
 // (pt_film_enable_moments) and the same files hold the variance-guided filter's result (pt_film_denoise_variance, sigma_color = S).
 // --temporal K --cam-step dx,dy,dz (one rank; --frames is not used): K time steps of one frame each, step k at frame = k with the camera's
 // origin and target moved k times by the step, accumulated across the moves by pt_film_reproject (gain = k + 1; two films, ping-ponged, each
-// cleared before its step; guides at frame 0).  The image written is the last step's film; --denoise [N] filters that film.
+// cleared before its step; guides at frame 0).  The image written is the last step's film; --denoise [N] filters that film.  With
+// --sigma-color S both films get their second-moment plane (pt_film_reproject blends it along) and the denoised files hold the result of
+// pt_film_denoise_history (sigma_color = S, the rest pt_denoise_history_params_default's): the variance-guided filter with a variance per pixel.
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -254,7 +256,8 @@ void run_temporal(const Options &o, const pth_scene &hs, RankResult &res, std::v
         pt_scene_get_info(scene, &res.info);
         bool ok = true;
         for (pt_film *&f : films)
-            if (ok && (pt_film_create(ctx, o.width, o.height, &f) != PT_OK || pt_film_enable_aov(f, nullptr) != PT_OK || pt_film_enable_history(f, nullptr) != PT_OK)) { fail("film set-up"); ok = false; }
+            if (ok && (pt_film_create(ctx, o.width, o.height, &f) != PT_OK || pt_film_enable_aov(f, nullptr) != PT_OK || pt_film_enable_history(f, nullptr) != PT_OK ||
+                       (o.sigma_color > 0.f && pt_film_enable_moments(f, nullptr) != PT_OK))) { fail("film set-up"); ok = false; }  // (M: blended by pt_film_reproject when both films have it)
         if (!ok) break;
         pt_params p;
         pt_params_default(&p);
@@ -300,7 +303,12 @@ void run_temporal(const Options &o, const pth_scene &hs, RankResult &res, std::v
             if (o.denoise > 0) dp.iterations = (uint32_t)o.denoise;
             std::vector<float> plane(3 * np);
             std::vector<uint8_t> bgra(4 * np);
-            if (pt_film_denoise(film, &dp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise"); break; }
+            pt_denoise_history_params hp;   // --sigma-color: the variance-guided form with a variance per pixel (every pixel has its own history), same files
+            pt_denoise_history_params_default(&hp);
+            hp.sigma_color = o.sigma_color;
+            if (o.denoise > 0) hp.iterations = (uint32_t)o.denoise;
+            if (o.sigma_color > 0.f && pt_film_denoise_history(film, &hp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise_history"); break; }
+            if (!(o.sigma_color > 0.f) && pt_film_denoise(film, &dp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise"); break; }
             if (pt_film_read_denoised(film, plane.data(), bgra.data()) != PT_OK) { fail("pt_film_read_denoised"); break; }
             if (!o.ppm.empty() && pth_write_ppm_bgra8(denoised_name(o.ppm).c_str(), bgra.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.ppm); break; }
             if (!o.pfm.empty() && pth_write_pfm(denoised_name(o.pfm).c_str(), plane.data(), o.width, o.height) != 0) { res.error = "cannot write " + denoised_name(o.pfm); break; }
@@ -380,7 +388,7 @@ int main(int argc, char **argv)
     }
     if (o.have_cam_step && !o.temporal) die("--cam-step belongs to --temporal K");
     if (o.temporal && !o.have_cam_step) die("--temporal K needs --cam-step dx,dy,dz (0,0,0 for a camera that stands still)");
-    if (o.temporal && (o.ranks > 1 || !o.aov.empty() || o.sigma_color > 0.f)) die("--temporal accumulates the film of one rank (no --ranks, --aov or --sigma-color)");
+    if (o.temporal && (o.ranks > 1 || !o.aov.empty())) die("--temporal accumulates the film of one rank (no --ranks or --aov)");
     if (o.temporal) o.frames = o.temporal;   // (the JSON line's frame count)
     if (o.sigma_color > 0.f && o.denoise < 0) die("--sigma-color belongs to --denoise (the variance-guided filter)");
     if (o.sigma_color > 0.f && o.ranks > 1) die("--sigma-color filters the film of one rank (no --ranks)");
