@@ -2,7 +2,8 @@
 
 One Cornell film of 1920 x 1080, 32 spp, one frame, with its guides.  Reported (every ms figure: the call's own device events, median of
 --reps alternated repetitions after a warm-up call of each shape, with min and max):
-  denoise_N_iterations    pt_film_denoise with N = 1 .. 5 iterations (k_dn_prepare + N k_dn_atrous launches)
+  denoise_N_iterations    pt_film_denoise with N = 1 .. 5 iterations (k_dn_prepare + N k_dn_atrous launches); wall_median_ms: the blocking call
+                          as the host sees it (what a change of the host code around the kernels can move)
   render_32spp            pt_render of the same frame (PT_PIPELINE_AUTO, depth 8) in the same alternation: what a 5-iteration denoise costs
                           beside the frame it filters
   per_iteration           the differences between consecutive N: the cost of step 2^(N-1), with the algorithmic bytes (W * H * 48 B: two
@@ -23,6 +24,7 @@ import statistics
 import subprocess
 import sys
 import tempfile
+import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -62,11 +64,16 @@ def child(reps):
     legs["render_32spp"] = render
     for fn in legs.values():   # warm-up: every shape once (the first denoise allocates the scratch)
         fn()
-    ms = {k: [] for k in legs}
+    ms, wall = {k: [] for k in legs}, {k: [] for k in legs}
     for _ in range(reps):
         for k, fn in legs.items():
+            t0 = time.perf_counter()
             ms[k].append(fn())
+            wall[k].append((time.perf_counter() - t0) * 1e3)
     out = {k: summary(v) for k, v in ms.items()}
+    for k in legs:
+        if k.startswith("denoise_"):
+            out[k]["wall_median_ms"] = round(statistics.median(wall[k]), 4)
     per = {}
     for n in range(1, 6):
         cur = out[f"denoise_{n}_iterations"]["median_ms"]
@@ -145,7 +152,7 @@ def main():
     for _ in range(args.rounds if len(libs) > 1 else 1):
         for name, path in libs:
             runs[name].append(run_child(path, args.reps))
-            print(name, {k: v["median_ms"] for k, v in runs[name][-1].items() if k.startswith("denoise_") and isinstance(v, dict)}, flush=True)
+            print(name, {k: (v["median_ms"], v["wall_median_ms"]) for k, v in runs[name][-1].items() if k.startswith("denoise_") and isinstance(v, dict)}, flush=True)
     rec.update(runs["in-tree"][0])
     if len(libs) > 1:
         rec["builds"] = {name: [{k: r[k] for k in r if k.startswith("denoise_") and k.endswith("iterations") or k == "per_iteration"} for r in rs]

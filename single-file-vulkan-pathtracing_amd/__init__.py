@@ -382,34 +382,31 @@ def default_params(**kw):
     return p
 
 
-def denoise_default_params():
-    p = DenoiseParams()
-    lib_amd().pt_denoise_params_default(C.byref(p))
+def _default_params(struct, fn):
+    """-> a `struct` as the library's `fn` (a pt_*_params_default) fills it"""
+    p = struct()
+    getattr(lib_amd(), fn)(C.byref(p))
     return p
+
+
+def denoise_default_params():
+    return _default_params(DenoiseParams, "pt_denoise_params_default")
 
 
 def denoise_variance_default_params():
-    p = DenoiseVarianceParams()
-    lib_amd().pt_denoise_variance_params_default(C.byref(p))
-    return p
+    return _default_params(DenoiseVarianceParams, "pt_denoise_variance_params_default")
 
 
 def denoise_history_default_params():
-    p = DenoiseHistoryParams()
-    lib_amd().pt_denoise_history_params_default(C.byref(p))
-    return p
+    return _default_params(DenoiseHistoryParams, "pt_denoise_history_params_default")
 
 
 def reproject_default_params():
-    p = ReprojectParams()
-    lib_amd().pt_reproject_params_default(C.byref(p))
-    return p
+    return _default_params(ReprojectParams, "pt_reproject_params_default")
 
 
 def motion_default_params():
-    p = MotionParams()
-    lib_amd().pt_motion_params_default(C.byref(p))
-    return p
+    return _default_params(MotionParams, "pt_motion_params_default")
 
 
 class Context:
@@ -610,41 +607,44 @@ class Film:
         None take pt_denoise_params_default's values (or `params`, a DenoiseParams, as it stands).  device_out: None for a plane the
         film owns (read_denoised), or a device pointer to width*height*3 floats (a torch tensor's data_ptr())."""
         p = params if params is not None else denoise_default_params()
-        if iterations is not None:
-            p.iterations = iterations
-        if sigma_normal is not None:
-            p.sigma_normal = sigma_normal
-        if sigma_depth is not None:
-            p.sigma_depth = sigma_depth
+        return self._denoise("pt_film_denoise", p, device_out, iterations=iterations, sigma_normal=sigma_normal, sigma_depth=sigma_depth)
+
+    def _denoise(self, fn, p, device_out, **fields):
+        """the library's denoiser `fn` with params `p`, the fields that are not None written into it first -> device ms"""
+        for name, v in fields.items():
+            if v is not None:
+                setattr(p, name, v)
         ms = C.c_float(0.0)
-        self.ctx._check(lib_amd().pt_film_denoise(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
+        self.ctx._check(getattr(lib_amd(), fn)(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
         return ms.value
+
+    def _enable_plane(self, fn, device_ptr):
+        self.ctx._check(getattr(lib_amd(), fn)(self.h, C.c_void_p(device_ptr) if device_ptr else None))
+
+    def _read_plane(self, fn, tail, *more):
+        """-> float32 [H, W] + tail filled by the library's plane reader `fn` (more: its further arguments)"""
+        a = np.zeros((self.height, self.width) + tail, dtype=np.float32)
+        self.ctx._check(getattr(lib_amd(), fn)(self.h, a.ctypes.data, *more))
+        return a
 
     def enable_moments(self, device_ptr=None):
         """Gives the film its second-moment plane (include/pt_api.h pt_film_enable_moments): from now on pt_render blends the squared frame
         colour into it.  device_ptr: None (the film allocates it) or a device pointer to width*height*3 floats of caller-owned memory.
         Call it while the film is empty (before frame 0, or straight after clear())."""
-        self.ctx._check(lib_amd().pt_film_enable_moments(self.h, C.c_void_p(device_ptr) if device_ptr else None))
+        self._enable_plane("pt_film_enable_moments", device_ptr)
 
     def read_moments(self):
         """-> (float32 [H, W, 3], frames): the second-moment plane and the number of frames it and the film average."""
-        a = np.zeros((self.height, self.width, 3), dtype=np.float32)
         n = C.c_uint32(0)
-        self.ctx._check(lib_amd().pt_film_read_moments(self.h, a.ctypes.data, C.byref(n)))
-        return a, n.value
+        return self._read_plane("pt_film_read_moments", (3,), C.byref(n)), n.value
 
     def denoise_variance(self, iterations=None, sigma_normal=None, sigma_depth=None, sigma_color=None, frames=None, device_out=None, params=None):
         """The variance-guided filter of include/pt_api.h pt_film_denoise_variance over the film, its guide planes and its second-moment
         plane -> device ms.  Arguments as in denoise(); frames: how many frames the film averages (None / 0: what pt_render recorded).
         The film-owned result is read with read_denoised / read_denoised_bgra8."""
         p = params if params is not None else denoise_variance_default_params()
-        for name, v in (("iterations", iterations), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_color", sigma_color),
-                        ("frames", frames)):
-            if v is not None:
-                setattr(p, name, v)
-        ms = C.c_float(0.0)
-        self.ctx._check(lib_amd().pt_film_denoise_variance(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
-        return ms.value
+        return self._denoise("pt_film_denoise_variance", p, device_out, iterations=iterations, sigma_normal=sigma_normal, sigma_depth=sigma_depth,
+                             sigma_color=sigma_color, frames=frames)
 
     def denoise_history(self, iterations=None, sigma_normal=None, sigma_depth=None, sigma_color=None, min_history=None, n_max=None, step_frames=None,
                         device_out=None, params=None):
@@ -653,36 +653,27 @@ class Film:
         min_history: pixels whose history is shorter take the spatial estimate; n_max: the cap of the sample count; step_frames: frames
         rendered per time step.  The film-owned result is read with read_denoised / read_denoised_bgra8."""
         p = DenoiseHistoryParams.from_buffer_copy(params) if params is not None else denoise_history_default_params()
-        for name, v in (("iterations", iterations), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_color", sigma_color),
-                        ("min_history", min_history), ("n_max", n_max), ("step_frames", step_frames)):
-            if v is not None:
-                setattr(p, name, v)
-        ms = C.c_float(0.0)
-        self.ctx._check(lib_amd().pt_film_denoise_history(self.h, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
-        return ms.value
+        return self._denoise("pt_film_denoise_history", p, device_out, iterations=iterations, sigma_normal=sigma_normal, sigma_depth=sigma_depth,
+                             sigma_color=sigma_color, min_history=min_history, n_max=n_max, step_frames=step_frames)
 
     def enable_history(self, device_ptr=None):
         """Gives the film its history-length plane L (include/pt_api.h pt_film_enable_history), which pt_film_reproject reads and writes.
         device_ptr: None (the film allocates it) or a device pointer to width*height floats of caller-owned memory."""
-        self.ctx._check(lib_amd().pt_film_enable_history(self.h, C.c_void_p(device_ptr) if device_ptr else None))
+        self._enable_plane("pt_film_enable_history", device_ptr)
 
     def read_history(self):
         """-> float32 [H, W]: the history length of every pixel, in reprojection steps (0 before the first reproject)."""
-        a = np.zeros((self.height, self.width), dtype=np.float32)
-        self.ctx._check(lib_amd().pt_film_read_history(self.h, a.ctypes.data))
-        return a
+        return self._read_plane("pt_film_read_history", ())
 
     def enable_motion(self, device_ptr=None):
         """Gives the film its motion plane Q (include/pt_api.h pt_film_enable_motion), which pt_film_motion writes and
         pt_film_reproject_motion reads.  device_ptr: None (the film allocates it) or a device pointer to width*height*4 floats of
         caller-owned, 16-byte aligned memory."""
-        self.ctx._check(lib_amd().pt_film_enable_motion(self.h, C.c_void_p(device_ptr) if device_ptr else None))
+        self._enable_plane("pt_film_enable_motion", device_ptr)
 
     def read_motion(self):
         """-> float32 [H, W, 4]: per pixel where its surface point was in the previous geometry {x, y, z} and 1, or zeros (none known)."""
-        a = np.zeros((self.height, self.width, 4), dtype=np.float32)
-        self.ctx._check(lib_amd().pt_film_read_motion(self.h, a.ctypes.data))
-        return a
+        return self._read_plane("pt_film_read_motion", (4,))
 
     def motion(self, scene, cam=None, bary_slack=None, params=None):
         """Fills the motion plane from this film's guides, rendered (render_aov) for `scene` as it is now at camera `cam`, and the scene's

@@ -24,6 +24,12 @@
 //                      and is done -- one wave-wide vote and a uniform branch.  Otherwise the 5 x 5 window at step 1: per row of taps the ten
 //                      128-bit loads together from clamped addresses, long lanes and taps outside the image dropped by selects.
 // Both take arguments of their own (DhConst, DhPlanes): DnConst and DnPlanes, whose layout the older kernels' scalar loads depend on, stay.
+//
+// What the kernels share and what they do not, as the device-code comparison (scripts/device_asm_diff.py) decided it: the block (film_pass.h
+// fp_pixel), dn_demod and the guide part of a tap's weight (dn_guide_x, in denoise_history_kernel.h for dn_tap and dh_tap) are one each.
+// dn_tap_var keeps its own copy of the guide weight, k_dn_atrous and k_dn_atrous_var stay two bodies, and the bodies of the five older kernels
+// stay in this file: each of those mergers changed the generated code (registers, schedule) of the a-trous kernels, which are sensitive to
+// their source text.  DESIGN.md section 4, "Film passes", has the list.
 #include "pt_internal.h"
 #include "pt_math.h"
 
@@ -32,7 +38,7 @@
 namespace {
 
 #define DH_KEEP(v) asm volatile("" : "+v"(v))  // the value exists in a vector register at this point: its load cannot move below
-#include "denoise_history_kernel.h"  // DhConst, DhPlanes, dh_prepare_pixel, dh_spatial_pixel: the two kernels' bodies
+#include "denoise_history_kernel.h"  // DhConst, DhPlanes, dh_prepare_pixel, dh_spatial_pixel: the two kernels' bodies; dn_demod, dn_guide_x
 
 struct DnConst {
     uint32_t w, h, n_bx;  // image, blocks per row of blocks
@@ -46,9 +52,6 @@ struct DnOut {
     float *rgb;      // w*h*3
     uchar4 *bgra;    // w*h, or null (a caller-owned output has no bgra8 form)
 };
-constexpr int DN_BW = 64, DN_BH = TB / DN_BW;  // pixels of a block
-
-__device__ __forceinline__ float dn_demod(float a, float alpha) { return fmaxf(a + (1.0f - alpha), 0.001f); }
 
 __global__ __launch_bounds__(TB) void k_dn_prepare(uint32_t n_pix, DnPlanes pl, float4 *__restrict__ illum, float4 *__restrict__ guide)
 {
@@ -85,8 +88,7 @@ __global__ __launch_bounds__(TB) void k_dn_prepare_var(uint32_t n_pix, DnPlanes 
 // V = the 3 x 3 binomial mean of V0 over the taps inside the image (j outer, i inner); the record's rgb goes along
 __global__ __launch_bounds__(TB) void k_dn_var_blur(DnConst dc, const float4 *__restrict__ illum_in, float4 *__restrict__ illum_out)
 {
-    const uint32_t by = blockIdx.x / dc.n_bx, bx = blockIdx.x - by * dc.n_bx;
-    const int x = (int)(bx * DN_BW + (threadIdx.x & (DN_BW - 1))), y = (int)(by * DN_BH + threadIdx.x / DN_BW);
+    int x, y; fp_pixel(dc.n_bx, x, y);
     const int w = (int)dc.w, h = (int)dc.h;
     if (x >= w || y >= h) return;
     const size_t p = (size_t)y * dc.w + (uint32_t)x;
@@ -121,8 +123,7 @@ __global__ __launch_bounds__(TB) void k_dn_prepare_hist(uint32_t n_pix, DhConst 
 __global__ __launch_bounds__(TB) void k_dn_var_spatial(DhConst hc, const float *__restrict__ len, const float4 *__restrict__ guide, const float4 *__restrict__ illum_in,
                                                        float4 *__restrict__ illum_out)
 {
-    const uint32_t by = blockIdx.x / hc.n_bx, bx = blockIdx.x - by * hc.n_bx;
-    const int x = (int)(bx * DH_BW + (threadIdx.x & (DH_BW - 1))), y = (int)(by * DH_BH + threadIdx.x / DH_BW);
+    int x, y; fp_pixel(hc.n_bx, x, y);
     if (x >= (int)hc.w || y >= (int)hc.h) return;
     const size_t p = (size_t)y * hc.w + (uint32_t)x;
     const float l = len[p];
@@ -149,11 +150,7 @@ struct DnSum {
 // one tap: the weight of q seen from p, then the four adds
 __device__ __forceinline__ void dn_tap(DnSum &s, const DnConst &dc, float hh, const float4 gp, const float4 gq, const float4 iq)
 {
-    const float dx = gp.x - gq.x, dy = gp.y - gq.y, dz3 = gp.z - gq.z;
-    const float xn = ((dx * dx + dy * dy) + dz3 * dz3) * dc.inv_n;
-    const float dz = gp.w - gq.w;
-    const float xz = ptm::fdiv(dz * dz, dc.sz2 * (gp.w * gp.w + gq.w * gq.w) + 1e-12f);
-    float t = fmaxf(0.0f, 1.0f - (xn + xz) * 0.0625f);
+    float t = fmaxf(0.0f, 1.0f - dn_guide_x(dc.inv_n, dc.sz2, gp, gq) * 0.0625f);
     t = t * t; t = t * t; t = t * t; t = t * t;
     const float w = hh * t;
     s.r = s.r + w * iq.x;
@@ -207,8 +204,7 @@ template <bool LAST>
 __global__ __launch_bounds__(TB) void k_dn_atrous(DnConst dc, const float4 *__restrict__ guide, const float4 *__restrict__ illum_in,
                                                   float4 *__restrict__ illum_out, DnPlanes pl, DnOut o)
 {
-    const uint32_t by = blockIdx.x / dc.n_bx, bx = blockIdx.x - by * dc.n_bx;
-    const int x = (int)(bx * DN_BW + (threadIdx.x & (DN_BW - 1))), y = (int)(by * DN_BH + threadIdx.x / DN_BW);
+    int x, y; fp_pixel(dc.n_bx, x, y);
     const int w = (int)dc.w, h = (int)dc.h, s = dc.step;
     if (x >= w || y >= h) return;
     const size_t p = (size_t)y * dc.w + (uint32_t)x;
@@ -241,8 +237,7 @@ template <bool LAST>
 __global__ __launch_bounds__(TB) void k_dn_atrous_var(DnConst dc, float sc2, const float4 *__restrict__ guide, const float4 *__restrict__ illum_in,
                                                       float4 *__restrict__ illum_out, DnPlanes pl, DnOut o)  // sc2 = sigma_color * sigma_color
 {
-    const uint32_t by = blockIdx.x / dc.n_bx, bx = blockIdx.x - by * dc.n_bx;
-    const int x = (int)(bx * DN_BW + (threadIdx.x & (DN_BW - 1))), y = (int)(by * DN_BH + threadIdx.x / DN_BW);
+    int x, y; fp_pixel(dc.n_bx, x, y);
     const int w = (int)dc.w, h = (int)dc.h, s = dc.step;
     if (x >= w || y >= h) return;
     const size_t p = (size_t)y * dc.w + (uint32_t)x;
@@ -311,42 +306,47 @@ pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigm
     const DnOut out = { device_out ? static_cast<float *>(device_out) : d.d_out, device_out ? nullptr : reinterpret_cast<uchar4 *>(d.d_out_bgra) };
     DnConst dc{};
     dc.w = f->w; dc.h = f->h;
-    dc.n_bx = (f->w + DN_BW - 1) / DN_BW;
+    const uint32_t n_blocks = fp_grid(f->w, f->h, &dc.n_bx);
     dc.inv_n = 1.0f / (sigma_normal * sigma_normal);
     dc.sz2 = sigma_depth * sigma_depth;
-    hipStream_t st = ctx->stream;
-    const uint32_t n_blocks = dc.n_bx * ((f->h + DN_BH - 1) / DN_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
-    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    uint32_t in = 0;  // the ping-pong plane the first iteration reads
-    if (hist) {
-        DhConst hc{};
-        hc.w = dc.w; hc.h = dc.h; hc.n_bx = dc.n_bx;
-        hc.inv_n = dc.inv_n; hc.sz2 = dc.sz2;
-        hc.mh = hist->min_history; hc.sf = (float)hist->step_frames; hc.n_max = hist->n_max;
-        const DhPlanes hp = { pl.film, pl.albedo, pl.normal, pl.emission, pl.depth, pl.alpha, f->m2.d_m2, f->hist.d_len };
-        k_dn_prepare_hist<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, hc, hp, d.d_illum[0], d.d_guide);
-        k_dn_var_spatial<<<n_blocks, TB, 0, st>>>(hc, f->hist.d_len, d.d_guide, d.d_illum[0], d.d_illum[1]);
-        k_dn_var_blur<<<n_blocks, TB, 0, st>>>(dc, d.d_illum[1], d.d_illum[0]);
-    } else if (var) {
-        k_dn_prepare_var<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, f->m2.d_m2, (float)(var->frames - 1), d.d_illum[0], d.d_guide);
-        k_dn_var_blur<<<n_blocks, TB, 0, st>>>(dc, d.d_illum[0], d.d_illum[1]);
-        in = 1;
-    } else {
-        k_dn_prepare<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, d.d_illum[0], d.d_guide);
-    }
-    for (uint32_t k = 0; k < iterations; k++, in ^= 1u) {
-        dc.step = 1 << k;
-        const bool last = k + 1 == iterations;
-        if (var) hipLaunchKernelGGL(pick_dn_atrous_var(last), dim3(n_blocks), dim3(TB), 0, st, dc, var->sigma_color * var->sigma_color, d.d_guide, d.d_illum[in], d.d_illum[in ^ 1u], pl, out);
-        else hipLaunchKernelGGL(pick_dn_atrous(last), dim3(n_blocks), dim3(TB), 0, st, dc, d.d_guide, d.d_illum[in], d.d_illum[in ^ 1u], pl, out);
-    }
-    PT_HIP(ctx, hipGetLastError());
-    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-    PT_HIP(ctx, hipStreamSynchronize(st));
-    PT_HIP(ctx, hipGetLastError());
-    if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
-    if (!device_out) d.have_out = true;
-    return PT_OK;
+    const pt_status rt = pt_timed_pass(ctx, device_ms, [&](hipStream_t st) {
+        uint32_t in = 0;  // the ping-pong plane the first iteration reads
+        if (hist) {
+            DhConst hc{};
+            hc.w = dc.w; hc.h = dc.h; hc.n_bx = dc.n_bx;
+            hc.inv_n = dc.inv_n; hc.sz2 = dc.sz2;
+            hc.mh = hist->min_history; hc.sf = (float)hist->step_frames; hc.n_max = hist->n_max;
+            const DhPlanes hp = { pl.film, pl.albedo, pl.normal, pl.emission, pl.depth, pl.alpha, f->m2.ptr(), f->hist.ptr() };
+            k_dn_prepare_hist<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, hc, hp, d.d_illum[0], d.d_guide);
+            k_dn_var_spatial<<<n_blocks, TB, 0, st>>>(hc, f->hist.ptr(), d.d_guide, d.d_illum[0], d.d_illum[1]);
+            k_dn_var_blur<<<n_blocks, TB, 0, st>>>(dc, d.d_illum[1], d.d_illum[0]);
+        } else if (var) {
+            k_dn_prepare_var<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, f->m2.ptr(), (float)(var->frames - 1), d.d_illum[0], d.d_guide);
+            k_dn_var_blur<<<n_blocks, TB, 0, st>>>(dc, d.d_illum[0], d.d_illum[1]);
+            in = 1;
+        } else {
+            k_dn_prepare<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, d.d_illum[0], d.d_guide);
+        }
+        for (uint32_t k = 0; k < iterations; k++, in ^= 1u) {
+            dc.step = 1 << k;
+            const bool last = k + 1 == iterations;
+            if (var) hipLaunchKernelGGL(pick_dn_atrous_var(last), dim3(n_blocks), dim3(TB), 0, st, dc, var->sigma_color * var->sigma_color, d.d_guide, d.d_illum[in], d.d_illum[in ^ 1u], pl, out);
+            else hipLaunchKernelGGL(pick_dn_atrous(last), dim3(n_blocks), dim3(TB), 0, st, dc, d.d_guide, d.d_illum[in], d.d_illum[in ^ 1u], pl, out);
+        }
+    });
+    if (rt == PT_OK && !device_out) d.have_out = true;
+    return rt;
+}
+
+// What the three filters refuse alike, in the header's order: a film without the planes they read, iterations, the sigmas.  name: the struct's.
+pt_status dn_checks(pt_film *f, const char *name, bool need_m, bool need_l, uint32_t iterations, std::initializer_list<float> sigmas)
+{
+    pt_ctx *ctx = f->ctx;
+    if (!f->aov.enabled) return pt_bad(ctx, PT_NO_GUIDES_MSG);
+    if (need_m && !f->m2.d) return pt_bad(ctx, PT_NO_M_MSG " before the frames are rendered");
+    if (need_l && !f->hist.d) return pt_bad(ctx, PT_NO_L_MSG " (and pt_film_reproject) first");
+    PT_TRY(pt_check_iterations(ctx, name, iterations));
+    return pt_check_sigmas(ctx, name, sigmas);
 }
 
 }  // namespace
@@ -360,49 +360,29 @@ void ptd_free(pt_film *f)
 
 pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, float *device_ms)
 {
-    pt_ctx *ctx = f->ctx;
-    if (!f->aov.enabled) { ctx->err = "the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first"; return PT_ERR_INVALID_ARG; }
-    if (p->iterations < 1 || p->iterations > 8) { ctx->err = "pt_denoise_params.iterations must be in 1..8"; return PT_ERR_INVALID_ARG; }
-    if (!(std::isfinite(p->sigma_normal) && p->sigma_normal > 0.f) || !(std::isfinite(p->sigma_depth) && p->sigma_depth > 0.f)) {
-        ctx->err = "pt_denoise_params.sigma_normal / sigma_depth must be finite and > 0";
-        return PT_ERR_INVALID_ARG;
-    }
-    for (uint32_t r : p->reserved)
-        if (r) { ctx->err = "pt_denoise_params.reserved must be 0"; return PT_ERR_INVALID_ARG; }
+    PT_TRY(dn_checks(f, "pt_denoise_params", false, false, p->iterations, { p->sigma_normal, p->sigma_depth }));
+    PT_TRY(pt_check_reserved(f->ctx, "pt_denoise_params", p->reserved));
     return dn_run(f, p->iterations, p->sigma_normal, p->sigma_depth, nullptr, device_out, device_ms);
 }
 
 pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out, float *device_ms)
 {
-    pt_ctx *ctx = f->ctx;
-    if (!f->aov.enabled) { ctx->err = "the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first"; return PT_ERR_INVALID_ARG; }
-    if (!f->m2.d_m2) { ctx->err = "the film has no second-moment plane: pt_film_enable_moments before the frames are rendered"; return PT_ERR_INVALID_ARG; }
-    if (p->iterations < 1 || p->iterations > 8) { ctx->err = "pt_denoise_variance_params.iterations must be in 1..8"; return PT_ERR_INVALID_ARG; }
-    for (float sg : { p->sigma_normal, p->sigma_depth, p->sigma_color })
-        if (!(std::isfinite(sg) && sg > 0.f)) { ctx->err = "pt_denoise_variance_params.sigma_normal / sigma_depth / sigma_color must be finite and > 0"; return PT_ERR_INVALID_ARG; }
-    for (uint32_t r : p->reserved)
-        if (r) { ctx->err = "pt_denoise_variance_params.reserved must be 0"; return PT_ERR_INVALID_ARG; }
+    PT_TRY(dn_checks(f, "pt_denoise_variance_params", true, false, p->iterations, { p->sigma_normal, p->sigma_depth, p->sigma_color }));
+    PT_TRY(pt_check_reserved(f->ctx, "pt_denoise_variance_params", p->reserved));
     const DnVariance v = { p->sigma_color, p->frames ? p->frames : f->m2.frames };
-    if (v.frames < 2) { ctx->err = "pt_film_denoise_variance: a variance estimate needs a film of at least 2 frames (params.frames, or what pt_render recorded)"; return PT_ERR_INVALID_ARG; }
+    if (v.frames < 2) return pt_bad(f->ctx, "pt_film_denoise_variance: a variance estimate needs a film of at least 2 frames (params.frames, or what pt_render recorded)");
     return dn_run(f, p->iterations, p->sigma_normal, p->sigma_depth, &v, device_out, device_ms);
 }
 
 pt_status ptd_denoise_history(pt_film *f, const pt_denoise_history_params *p, void *device_out, float *device_ms)
 {
     pt_ctx *ctx = f->ctx;
-    auto bad = [&](const char *msg) { ctx->err = msg; return PT_ERR_INVALID_ARG; };
-    if (!f->aov.enabled) return bad("the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
-    if (!f->m2.d_m2) return bad("the film has no second-moment plane: pt_film_enable_moments before the frames are rendered");
-    if (!f->hist.d_len) return bad("the film has no history-length plane: pt_film_enable_history (and pt_film_reproject) first");
-    if (p->iterations < 1 || p->iterations > 8) return bad("pt_denoise_history_params.iterations must be in 1..8");
-    for (float sg : { p->sigma_normal, p->sigma_depth, p->sigma_color })
-        if (!(std::isfinite(sg) && sg > 0.f)) return bad("pt_denoise_history_params.sigma_normal / sigma_depth / sigma_color must be finite and > 0");
-    if (!(p->min_history >= 1.f && p->min_history <= 65536.f)) return bad("pt_denoise_history_params.min_history must be finite and in 1..65536");
-    if (!(std::isfinite(p->n_max) && p->n_max >= 2.f)) return bad("pt_denoise_history_params.n_max must be finite and >= 2");
-    if (p->step_frames == 0) return bad("pt_denoise_history_params.step_frames must be >= 1");
-    if (p->min_history * (float)p->step_frames < 2.f) return bad("pt_denoise_history_params: min_history * step_frames must be >= 2 (a variance estimate needs two frames)");
-    for (uint32_t r : p->reserved)
-        if (r) return bad("pt_denoise_history_params.reserved must be 0");
+    PT_TRY(dn_checks(f, "pt_denoise_history_params", true, true, p->iterations, { p->sigma_normal, p->sigma_depth, p->sigma_color }));
+    if (!(p->min_history >= 1.f && p->min_history <= 65536.f)) return pt_bad(ctx, "pt_denoise_history_params.min_history must be finite and in 1..65536");
+    if (!(std::isfinite(p->n_max) && p->n_max >= 2.f)) return pt_bad(ctx, "pt_denoise_history_params.n_max must be finite and >= 2");
+    if (p->step_frames == 0) return pt_bad(ctx, "pt_denoise_history_params.step_frames must be >= 1");
+    if (p->min_history * (float)p->step_frames < 2.f) return pt_bad(ctx, "pt_denoise_history_params: min_history * step_frames must be >= 2 (a variance estimate needs two frames)");
+    PT_TRY(pt_check_reserved(ctx, "pt_denoise_history_params", p->reserved));
     const DnVariance v = { p->sigma_color, 0 };
     const DnHistory hs = { p->min_history, p->n_max, p->step_frames };
     return dn_run(f, p->iterations, p->sigma_normal, p->sigma_depth, &v, device_out, device_ms, &hs);

@@ -2,9 +2,11 @@
 // pt_film_denoise_history puts in front of pt_film_denoise_variance's pre-blur and iterations.  In a header of its own, like
 // reproject_kernel.h, so that tests/denoise_history_host.cpp can compile the very same statements for the host (plain IEEE divides stand in
 // for pt_math.h's fdiv, their bitwise equal) and hold them against the numpy restatement without a GPU, under the host's sanitizers.
+// It also holds what the three denoisers share on the device: dn_demod and the guide part of a tap's weight, dn_guide_x.
 // Wants declared before it: ptm::fdiv (pt_math.h), float4, make_float4, min, max, fmaxf, fminf, TB and DH_KEEP(v) (the device: an empty asm
 // that takes v in a vector register; the host: nothing).
 #pragma once
+#include "film_pass.h"
 
 struct DhConst {
     uint32_t w, h, n_bx;    // image, blocks per row of blocks
@@ -15,10 +17,19 @@ struct DhPlanes {
     const float *film, *albedo, *normal, *emission, *depth, *alpha;
     const float *m2, *len;  // M and L
 };
-constexpr int DH_BW = 64, DH_BH = TB / DH_BW;  // pixels of a block: the denoiser's
 
 // pt_film_denoise's D
-__device__ __forceinline__ float dh_demod(float a, float alpha) { return fmaxf(a + (1.0f - alpha), 0.001f); }
+__device__ __forceinline__ float dn_demod(float a, float alpha) { return fmaxf(a + (1.0f - alpha), 0.001f); }
+// the guide part of a tap's weight, x_n + x_z of q seen from p (records {N.xyz, Z}).  dn_tap and dh_tap share it; dn_tap_var (denoise.hip) keeps
+// its own copy of the statements: calling this there re-allocates registers in both k_dn_atrous_var instantiations
+__device__ __forceinline__ float dn_guide_x(float inv_n, float sz2, const float4 gp, const float4 gq)
+{
+    const float dx = gp.x - gq.x, dy = gp.y - gq.y, dz3 = gp.z - gq.z;
+    const float xn = ((dx * dx + dy * dy) + dz3 * dz3) * inv_n;
+    const float dz = gp.w - gq.w;
+    const float xz = ptm::fdiv(dz * dz, sz2 * (gp.w * gp.w + gq.w * gq.w) + 1e-12f);
+    return xn + xz;
+}
 // a pixel takes the spatial estimate unless L >= min_history (a NaN fails: short)
 __device__ __forceinline__ bool dh_short(float len, float mh) { return !(len >= mh); }
 
@@ -32,7 +43,7 @@ __device__ __forceinline__ void dh_prepare_pixel(const DhConst &dc, const DhPlan
     float i3[3], v3[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const float col = pl.film[p3 + c], d = dh_demod(pl.albedo[p3 + c], al);
+        const float col = pl.film[p3 + c], d = dn_demod(pl.albedo[p3 + c], al);
         i3[c] = ptm::fdiv(col - pl.emission[p3 + c], d);
         v3[c] = ptm::fdiv(ptm::fdiv(fmaxf(pl.m2[p3 + c] - col * col, 0.0f), nm1), d * d);
     }
@@ -47,11 +58,7 @@ struct DhSum {
 // one tap of the 5 x 5 window: pt_film_denoise's t^16 of the guides alone (no h), then the seven adds; a tap that does not count leaves the sums
 __device__ __forceinline__ void dh_tap(DhSum &s, const DhConst &dc, bool ok, const float4 gp, const float4 gq, const float4 iq)
 {
-    const float dx = gp.x - gq.x, dy = gp.y - gq.y, dz3 = gp.z - gq.z;
-    const float xn = ((dx * dx + dy * dy) + dz3 * dz3) * dc.inv_n;
-    const float dz = gp.w - gq.w;
-    const float xz = ptm::fdiv(dz * dz, dc.sz2 * (gp.w * gp.w + gq.w * gq.w) + 1e-12f);
-    float t = fmaxf(0.0f, 1.0f - (xn + xz) * 0.0625f);
+    float t = fmaxf(0.0f, 1.0f - dn_guide_x(dc.inv_n, dc.sz2, gp, gq) * 0.0625f);
     t = t * t; t = t * t; t = t * t; t = t * t;
     const float q[3] = { iq.x, iq.y, iq.z };
     const float S1 = s.S + t;

@@ -1,7 +1,8 @@
 // film_work.hip -- the film's wavefront workspace: how many path slots a render gets (frames in flight x sample groups x pixels,
 // RenderShape) and the device buffers behind them (queues, hit records, radiance accumulators or term logs).
 // Buffers only ever grow; a grow that does not fit leaves the film usable (PT_ERR_OOM, AUTO shapes are planned again smaller).
-// Also what every scratch of a film goes through (pt_internal.h): pt_scratch_alloc / pt_scratch_free, the rank's tile list, the camera of a launch.
+// Also what every scratch of a film goes through (pt_internal.h): pt_scratch_alloc / pt_scratch_free, the rank's tile list, the camera of a launch;
+// and the film's optional planes M, L and Q (pt_plane_*).
 #include "wavefront_host.h"
 
 #include <algorithm>
@@ -108,6 +109,64 @@ pt_status pt_scratch_alloc(pt_ctx *ctx, const char *what, const std::vector<pt_b
     }
     if (counter) *counter += total;
     return PT_OK;
+}
+
+namespace {
+struct FilmPlane { pt_plane_any *plane; size_t bytes; };
+// the film's optional planes, in the order they are cleared and freed
+std::vector<FilmPlane> film_planes(pt_film *f)
+{
+    const size_t n_pix = (size_t)f->w * f->h;
+    return { { &f->m2, sizeof(float) * 3 * n_pix }, { &f->hist, sizeof(float) * n_pix }, { &f->mo, sizeof(float4) * n_pix } };
+}
+}  // namespace
+
+pt_status pt_plane_enable(pt_film *f, pt_plane_any &plane, void *user_ptr, size_t bytes, size_t align, const char *entry_name, const char *already_msg)
+{
+    pt_ctx *ctx = f->ctx;
+    if (plane.d) return pt_bad(ctx, already_msg);
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    void *d = user_ptr;
+    if (!d) {
+        const hipError_t e = hipMalloc(&d, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PT_ERR_OOM; }
+    } else if (align && (reinterpret_cast<uintptr_t>(d) & (align - 1))) {
+        return pt_bad(ctx, std::string(entry_name) + ": the plane must be " + std::to_string(align) + "-byte aligned");
+    }
+    // (after the renders already queued, which do not know the plane)
+    hipError_t e = hipMemsetAsync(d, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        if (!user_ptr) (void)hipFree(d);
+        ctx->err = std::string(entry_name) + ": " + hipGetErrorString(e);
+        return PT_ERR_HIP;
+    }
+    plane.d = d;
+    plane.own = user_ptr == nullptr;
+    return PT_OK;
+}
+
+pt_status pt_plane_read(pt_film *f, const pt_plane_any &plane, void *host_out, size_t bytes, const char *missing_msg)
+{
+    pt_ctx *ctx = f->ctx;
+    if (!plane.d) return pt_bad(ctx, missing_msg);
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (host_out) PT_HIP(ctx, hipMemcpy(host_out, plane.d, bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+pt_status pt_planes_clear(pt_film *f, hipStream_t st)
+{
+    for (const FilmPlane &p : film_planes(f))
+        if (p.plane->d) PT_HIP(f->ctx, hipMemsetAsync(p.plane->d, 0, p.bytes, st));
+    f->m2.frames = 0;
+    return PT_OK;
+}
+
+void pt_planes_free(pt_film *f)
+{
+    for (const FilmPlane &p : film_planes(f))
+        if (p.plane->own) (void)hipFree(p.plane->d);
 }
 
 uint64_t pt_rank_tiles(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, std::vector<uint32_t> *tiles, std::vector<uint64_t> *valid)

@@ -26,16 +26,13 @@ namespace {
 template <bool INST>
 __global__ __launch_bounds__(TB) void k_motion(MoConst mc, MoScene sc, MoFilm fl)
 {
-    const uint32_t by_ = blockIdx.x / mc.n_bx, bx_ = blockIdx.x - by_ * mc.n_bx;
-    const int x = (int)(bx_ * MO_BW + (threadIdx.x & (MO_BW - 1))), y = (int)(by_ * MO_BH + threadIdx.x / MO_BW);
+    int x, y; fp_pixel(mc.n_bx, x, y);
     if (x >= (int)mc.w || y >= (int)mc.h) return;
     mo_pixel<INST>(mc, sc, fl, x, y);
 }
 
 using MoFn = decltype(&k_motion<false>);
 MoFn pick_motion(bool inst) { return inst ? k_motion<true> : k_motion<false>; }
-
-bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 }  // namespace
 
@@ -90,36 +87,31 @@ pt_status ptm_snapshot(pt_scene *s)
 pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *device_ms)
 {
     pt_ctx *ctx = s->ctx;
-    auto bad = [&](const char *msg) { ctx->err = msg; return PT_ERR_INVALID_ARG; };
     // every refusal of the header, before anything is written
-    if (f->ctx != ctx) return bad("scene and film belong to different contexts");
-    if (!f->aov.enabled) return bad("the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
-    if (!f->mo.d_q) return bad("the film has no motion plane: pt_film_enable_motion first");
-    if (!s->prev.have) return bad("the scene has no previous geometry: pt_scene_snapshot_previous first");
-    if (!finite3(p->cam_origin) || !finite3(p->cam_target)) return bad("pt_motion_params: the camera must be finite");
-    if (!(std::isfinite(p->bary_slack) && p->bary_slack >= 0.f)) return bad("pt_motion_params.bary_slack must be finite and >= 0");
-    for (uint32_t r : p->reserved)
-        if (r) return bad("pt_motion_params.reserved must be 0");
+    if (f->ctx != ctx) return pt_bad(ctx, "scene and film belong to different contexts");
+    if (!f->aov.enabled) return pt_bad(ctx, PT_NO_GUIDES_MSG);
+    if (!f->mo.d) return pt_bad(ctx, PT_NO_Q_MSG " first");
+    if (!s->prev.have) return pt_bad(ctx, "the scene has no previous geometry: pt_scene_snapshot_previous first");
+    if (!pt_finite3(p->cam_origin) || !pt_finite3(p->cam_target)) return pt_bad(ctx, "pt_motion_params: the camera must be finite");
+    if (!(std::isfinite(p->bary_slack) && p->bary_slack >= 0.f)) return pt_bad(ctx, "pt_motion_params.bary_slack must be finite and >= 0");
+    PT_TRY(pt_check_reserved(ctx, "pt_motion_params", p->reserved));
     const pt_status rb = s->broken ? ptb_repair(s) : PT_OK;
     if (rb != PT_OK) return rb;
     const uint32_t n_inst = s->n_inst;
-    if (n_inst != s->prev.n_inst) return bad("the scene's instance count differs from the snapshot's");
+    if (n_inst != s->prev.n_inst) return pt_bad(ctx, "the scene's instance count differs from the snapshot's");
     if (s->h_xforms.size() != 12 * (size_t)n_inst) { ctx->err = "pt_film_motion: the scene's instance set is incomplete"; return PT_ERR_UNSUPPORTED; }
-    pt_params cp{};
-    for (int k = 0; k < 3; k++) { cp.cam_origin[k] = p->cam_origin[k]; cp.cam_target[k] = p->cam_target[k]; }
-    cp.width = f->w; cp.height = f->h;
     MoConst mc{};
     mc.w = f->w; mc.h = f->h;
-    mc.n_bx = (f->w + MO_BW - 1) / MO_BW;
+    const uint32_t n_blocks = fp_grid(f->w, f->h, &mc.n_bx);
     mc.n_tris = s->n_tris;
     mc.n_inst = n_inst ? n_inst : 1u;
-    mc.cam = ptw_camera(&cp);   // the camera pt_render and pt_render_aov start their rays from
+    mc.cam = ptw_camera_of(p->cam_origin, p->cam_target, f->w, f->h);   // the camera pt_render and pt_render_aov start their rays from
     mc.slack = p->bary_slack;
     const size_t xf_rows = 3 * (size_t)n_inst;
     const MoScene sc = { s->d_tri_orig, s->prev.d_tri, n_inst ? s->prev.d_xf + xf_rows : nullptr, s->prev.d_xf };
     const pt_film::Aov &a = f->aov;
     const MoFilm fl = { static_cast<const float *>(a.plane[PT_AOV_DEPTH]), static_cast<const float *>(a.plane[PT_AOV_ALPHA]),
-                        static_cast<const uint2 *>(a.plane[PT_AOV_ID]), f->mo.d_q };
+                        static_cast<const uint2 *>(a.plane[PT_AOV_ID]), f->mo.ptr() };
     hipStream_t st = ctx->stream;
     // the scene's matrices as they are now, in gl_InstanceID order, into the second half of the snapshot's array
     // (once per pt_scene_set_instances, not once per call; compared as bytes: -0 is not +0 here)
@@ -129,13 +121,5 @@ pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *
         PT_HIP(ctx, hipStreamSynchronize(st));
         s->prev.h_now = s->h_xforms;
     }
-    const uint32_t n_blocks = mc.n_bx * ((f->h + MO_BH - 1) / MO_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
-    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    hipLaunchKernelGGL(pick_motion(n_inst != 0), dim3(n_blocks), dim3(TB), 0, st, mc, sc, fl);
-    PT_HIP(ctx, hipGetLastError());
-    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-    PT_HIP(ctx, hipStreamSynchronize(st));
-    PT_HIP(ctx, hipGetLastError());
-    if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
-    return PT_OK;
+    return pt_timed_pass(ctx, device_ms, [&](hipStream_t ts) { hipLaunchKernelGGL(pick_motion(n_inst != 0), dim3(n_blocks), dim3(TB), 0, ts, mc, sc, fl); });
 }

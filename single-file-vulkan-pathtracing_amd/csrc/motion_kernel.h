@@ -4,6 +4,7 @@
 // Wants declared before it: ptm::Camera, ptm::fdiv, ptm::fsqrt, ptm::primary_target, ptm::div3_dominant (pt_math.h), uint2, float4,
 // make_float4, min, TB and MO_KEEP(v) (the device: an empty asm that takes v in a vector register; the host: nothing).
 #pragma once
+#include "film_pass.h"
 
 struct MoConst {
     uint32_t w, h, n_bx;       // image, blocks per row of blocks
@@ -20,7 +21,6 @@ struct MoFilm {
     const uint2 *id;
     float4 *q;                 // Q: written
 };
-constexpr int MO_BW = 64, MO_BH = TB / MO_BW;  // pixels of a block
 
 struct MoVec { float x, y, z; };
 

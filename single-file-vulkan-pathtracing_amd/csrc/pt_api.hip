@@ -330,10 +330,7 @@ pt_status pt_film_clear(pt_film *f)
     PT_HIP(ctx, hipMemsetAsync(f->d_bgra, 0, 4 * (size_t)f->w * f->h, ctx->stream));
     const pt_status rc = pta_clear(f, ctx->stream);  // the guide buffers, if the film has them
     if (rc != PT_OK) return rc;
-    if (f->m2.d_m2) PT_HIP(ctx, hipMemsetAsync(f->m2.d_m2, 0, sizeof(float) * 3 * (size_t)f->w * f->h, ctx->stream));
-    f->m2.frames = 0;
-    if (f->hist.d_len) PT_HIP(ctx, hipMemsetAsync(f->hist.d_len, 0, sizeof(float) * (size_t)f->w * f->h, ctx->stream));
-    if (f->mo.d_q) PT_HIP(ctx, hipMemsetAsync(f->mo.d_q, 0, sizeof(float4) * (size_t)f->w * f->h, ctx->stream));
+    PT_TRY(pt_planes_clear(f, ctx->stream));  // M, L and Q, where the film has them
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -362,9 +359,7 @@ void pt_film_destroy(pt_film *f)
     ptw_free_work(f);
     pta_free(f);
     ptd_free(f);
-    if (f->m2.own) (void)hipFree(f->m2.d_m2);
-    if (f->hist.own) (void)hipFree(f->hist.d_len);
-    if (f->mo.own) (void)hipFree(f->mo.d_q);
+    pt_planes_free(f);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
     delete f;
@@ -461,39 +456,15 @@ pt_status pt_film_read_denoised(pt_film *f, float *rgb, uint8_t *bgra)
 pt_status pt_film_enable_moments(pt_film *f, void *device_m2_f32)
 {
     if (!f) return PT_ERR_INVALID_ARG;
-    pt_ctx *ctx = f->ctx;
-    if (f->m2.d_m2) { ctx->err = "the film already has a second-moment plane"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    return guarded(ctx, [&]() -> pt_status {
-        const size_t bytes = sizeof(float) * 3 * (size_t)f->w * f->h;
-        void *plane = device_m2_f32;
-        if (!plane) {
-            const hipError_t e = hipMalloc(&plane, bytes);
-            if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PT_ERR_OOM; }
-        }
-        // (after the renders already queued, which do not know the plane)
-        hipError_t e = hipMemsetAsync(plane, 0, bytes, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            if (!device_m2_f32) (void)hipFree(plane);
-            ctx->err = std::string("pt_film_enable_moments: ") + hipGetErrorString(e);
-            return PT_ERR_HIP;
-        }
-        f->m2.d_m2 = static_cast<float *>(plane);
-        f->m2.own = device_m2_f32 == nullptr;
-        return PT_OK;
-    });
+    return guarded(f->ctx, [&] { return pt_plane_enable(f, f->m2, device_m2_f32, sizeof(float) * 3 * (size_t)f->w * f->h, 0, "pt_film_enable_moments", "the film already has a second-moment plane"); });
 }
 
 pt_status pt_film_read_moments(pt_film *f, float *m2, uint32_t *frames)
 {
     if (!f) return PT_ERR_INVALID_ARG;
-    pt_ctx *ctx = f->ctx;
-    if (!f->m2.d_m2) { ctx->err = "the film has no second-moment plane: pt_film_enable_moments first"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (m2) PT_HIP(ctx, hipMemcpy(m2, f->m2.d_m2, sizeof(float) * 3 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
-    if (frames) *frames = f->m2.frames;
-    return PT_OK;
+    const pt_status rc = pt_plane_read(f, f->m2, m2, sizeof(float) * 3 * (size_t)f->w * f->h, PT_NO_M_MSG " first");
+    if (rc == PT_OK && frames) *frames = f->m2.frames;
+    return rc;
 }
 
 void pt_denoise_variance_params_default(pt_denoise_variance_params *p)
@@ -536,38 +507,14 @@ pt_status pt_film_denoise_history(pt_film *f, const pt_denoise_history_params *p
 pt_status pt_film_enable_history(pt_film *f, void *device_len_f32)
 {
     if (!f) return PT_ERR_INVALID_ARG;
-    pt_ctx *ctx = f->ctx;
-    if (f->hist.d_len) { ctx->err = "the film already has a history-length plane"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    return guarded(ctx, [&]() -> pt_status {
-        const size_t bytes = sizeof(float) * (size_t)f->w * f->h;
-        void *plane = device_len_f32;
-        if (!plane) {
-            const hipError_t e = hipMalloc(&plane, bytes);
-            if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PT_ERR_OOM; }
-        }
-        hipError_t e = hipMemsetAsync(plane, 0, bytes, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            if (!device_len_f32) (void)hipFree(plane);
-            ctx->err = std::string("pt_film_enable_history: ") + hipGetErrorString(e);
-            return PT_ERR_HIP;
-        }
-        f->hist.d_len = static_cast<float *>(plane);
-        f->hist.own = device_len_f32 == nullptr;
-        return PT_OK;
-    });
+    return guarded(f->ctx, [&] { return pt_plane_enable(f, f->hist, device_len_f32, sizeof(float) * (size_t)f->w * f->h, 0, "pt_film_enable_history", "the film already has a history-length plane"); });
 }
 
 pt_status pt_film_read_history(pt_film *f, float *len)
 {
     if (!f) return PT_ERR_INVALID_ARG;
-    pt_ctx *ctx = f->ctx;
-    if (!len) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
-    if (!f->hist.d_len) { ctx->err = "the film has no history-length plane: pt_film_enable_history first"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(len, f->hist.d_len, sizeof(float) * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
-    return PT_OK;
+    if (!len) return pt_bad(f->ctx, "null argument");
+    return pt_plane_read(f, f->hist, len, sizeof(float) * (size_t)f->w * f->h, PT_NO_L_MSG " first");
 }
 
 void pt_reproject_params_default(pt_reproject_params *p)
@@ -605,41 +552,14 @@ pt_status pt_scene_snapshot_previous(pt_scene *s)
 pt_status pt_film_enable_motion(pt_film *f, void *device_q_f32x4)
 {
     if (!f) return PT_ERR_INVALID_ARG;
-    pt_ctx *ctx = f->ctx;
-    if (f->mo.d_q) { ctx->err = "the film already has a motion plane"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(ctx, hipSetDevice(ctx->device));
-    return guarded(ctx, [&]() -> pt_status {
-        const size_t bytes = sizeof(float4) * (size_t)f->w * f->h;
-        void *plane = device_q_f32x4;
-        if (!plane) {
-            const hipError_t e = hipMalloc(&plane, bytes);
-            if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return PT_ERR_OOM; }
-        } else if (reinterpret_cast<uintptr_t>(plane) & 15u) {
-            ctx->err = "pt_film_enable_motion: the plane must be 16-byte aligned";
-            return PT_ERR_INVALID_ARG;
-        }
-        hipError_t e = hipMemsetAsync(plane, 0, bytes, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            if (!device_q_f32x4) (void)hipFree(plane);
-            ctx->err = std::string("pt_film_enable_motion: ") + hipGetErrorString(e);
-            return PT_ERR_HIP;
-        }
-        f->mo.d_q = static_cast<float4 *>(plane);
-        f->mo.own = device_q_f32x4 == nullptr;
-        return PT_OK;
-    });
+    return guarded(f->ctx, [&] { return pt_plane_enable(f, f->mo, device_q_f32x4, sizeof(float4) * (size_t)f->w * f->h, 16, "pt_film_enable_motion", "the film already has a motion plane"); });
 }
 
 pt_status pt_film_read_motion(pt_film *f, float *q4)
 {
     if (!f) return PT_ERR_INVALID_ARG;
-    pt_ctx *ctx = f->ctx;
-    if (!q4) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
-    if (!f->mo.d_q) { ctx->err = "the film has no motion plane: pt_film_enable_motion first"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    PT_HIP(ctx, hipMemcpy(q4, f->mo.d_q, sizeof(float4) * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
-    return PT_OK;
+    if (!q4) return pt_bad(f->ctx, "null argument");
+    return pt_plane_read(f, f->mo, q4, sizeof(float4) * (size_t)f->w * f->h, PT_NO_Q_MSG " first");
 }
 
 void pt_motion_params_default(pt_motion_params *p)

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -158,6 +160,16 @@ struct pt_scene {
     } prev;
 };
 
+// An optional plane of a film (M, L, Q below): absent until its pt_film_enable_* call, then the film's own allocation or the caller's memory.
+// pt_plane_enable / pt_plane_read / pt_planes_clear / pt_planes_free (film_work.hip) are all that allocate, zero, read back and free one.
+struct pt_plane_any {
+    void *d = nullptr;                                // null: the film has no such plane
+    bool own = false;
+};
+template <class T> struct pt_plane : pt_plane_any {
+    T *ptr() const { return static_cast<T *>(d); }
+};
+
 struct pt_film {
     pt_ctx *ctx = nullptr;
     uint32_t w = 0, h = 0;
@@ -226,21 +238,13 @@ struct pt_film {
     } dn;
     // pt_film_enable_moments: the running mean of the squared frame colour, blended by the resolve kernel beside the film (shade_kernels.hip
     // k_resolve_m2).  A film plane like the guides, not a workspace.
-    struct Moments {
-        float *d_m2 = nullptr;                        // w*h*3 floats, or null: the film has no such plane
-        bool own = false;
+    struct Moments : pt_plane<float> {                // w*h*3 floats
         uint32_t frames = 0;                          // frame + frame_count of the last pt_render: what the film and the plane average
     } m2;
     // pt_film_enable_history: the history length of pt_film_reproject (reproject.hip), in reprojection steps.  A film plane like M.
-    struct History {
-        float *d_len = nullptr;                       // w*h floats, or null: the film has no such plane
-        bool own = false;
-    } hist;
+    pt_plane<float> hist;                             // w*h floats
     // pt_film_enable_motion: where the surface point of a pixel's first hit was in the previous geometry (motion.hip).  A film plane like L.
-    struct Motion {
-        float4 *d_q = nullptr;                        // w*h float4 {x, y, z, valid}, or null: the film has no such plane
-        bool own = false;
-    } mo;
+    pt_plane<float4> mo;                              // w*h float4 {x, y, z, valid}
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -251,6 +255,51 @@ struct pt_film {
             return PT_ERR_HIP;                                                                    \
         }                                                                                         \
     } while (0)
+
+// ---- what every film pass (denoise.hip, reproject.hip, motion.hip) takes its timing and its refusals from ("Film passes")
+// The timed tail: ev_a, what `launches(stream)` queues, ev_b, the wait; the device time between the events into *device_ms (nullable).
+template <class F>
+inline pt_status pt_timed_pass(pt_ctx *ctx, float *device_ms, F &&launches)
+{
+    hipStream_t st = ctx->stream;
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    launches(st);
+    PT_HIP(ctx, hipGetLastError());
+    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipGetLastError());
+    if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
+    return PT_OK;
+}
+// A refusal: the message into the context, PT_ERR_INVALID_ARG out.  PT_TRY: a check's refusal is the caller's.
+inline pt_status pt_bad(pt_ctx *ctx, const std::string &msg) { ctx->err = msg; return PT_ERR_INVALID_ARG; }
+#define PT_TRY(call) do { const pt_status rc__ = (call); if (rc__ != PT_OK) return rc__; } while (0)
+inline bool pt_finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+// The checks the parameter structs share; `name` is the struct's (pt_denoise_params, ...).
+template <size_t N>
+inline pt_status pt_check_reserved(pt_ctx *ctx, const char *name, const uint32_t (&reserved)[N])
+{
+    for (uint32_t r : reserved)
+        if (r) return pt_bad(ctx, std::string(name) + ".reserved must be 0");
+    return PT_OK;
+}
+inline pt_status pt_check_iterations(pt_ctx *ctx, const char *name, uint32_t n)
+{
+    return n >= 1 && n <= 8 ? PT_OK : pt_bad(ctx, std::string(name) + ".iterations must be in 1..8");
+}
+// sigmas: {sigma_normal, sigma_depth} or {sigma_normal, sigma_depth, sigma_color}
+inline pt_status pt_check_sigmas(pt_ctx *ctx, const char *name, std::initializer_list<float> sigmas)
+{
+    for (float sg : sigmas)
+        if (!(std::isfinite(sg) && sg > 0.f))
+            return pt_bad(ctx, std::string(name) + ".sigma_normal / sigma_depth" + (sigmas.size() > 2 ? " / sigma_color" : "") + " must be finite and > 0");
+    return PT_OK;
+}
+// what a film lacks; the plane messages end in what the refusing entry point wants done (" first", ...)
+#define PT_NO_GUIDES_MSG "the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first"
+#define PT_NO_M_MSG "the film has no second-moment plane: pt_film_enable_moments"
+#define PT_NO_L_MSG "the film has no history-length plane: pt_film_enable_history"
+#define PT_NO_Q_MSG "the film has no motion plane: pt_film_enable_motion"
 
 #define PT_BROKEN_SCENE_MSG "the scene lost its acceleration structure in a failed rebuild (out of memory?): call pt_scene_set_bvh_quality again, or recreate it"
 // lbvh_build.hip
@@ -285,6 +334,14 @@ void pt_scratch_free(const std::vector<pt_buf> &set, size_t *counter, size_t hel
 // PT_ERR_OOM for hipErrorOutOfMemory, PT_ERR_HIP otherwise: the context and the film stay usable.  *counter grows by the set's bytes on success only.
 pt_status pt_scratch_alloc(pt_ctx *ctx, const char *what, const std::vector<pt_buf> &set, size_t *counter, size_t held, size_t others = 0,
                            size_t limit = 0, const char *hint = "");
+// An optional film plane.  enable: refuses with `already_msg` when the film has it; else adopts `user_ptr` (align != 0: refused unless so aligned)
+// or allocates `bytes`, zeroes it on the stream behind the renders already queued (which do not know the plane) and waits; a failure leaves the
+// film without the plane.  `entry_name` is the entry point's, for the messages.  read: the plane into host_out (null: nothing is copied) after a
+// wait for the stream; refuses with `missing_msg` when the film has no such plane.
+pt_status pt_plane_enable(pt_film *f, pt_plane_any &plane, void *user_ptr, size_t bytes, size_t align, const char *entry_name, const char *already_msg);
+pt_status pt_plane_read(pt_film *f, const pt_plane_any &plane, void *host_out, size_t bytes, const char *missing_msg);
+pt_status pt_planes_clear(pt_film *f, hipStream_t st);  // zeroes the planes the film has (queued on st)
+void pt_planes_free(pt_film *f);                        // frees the ones the film owns
 // The 8x8 tiles of rank `rank` of `world` -- tile (tx, ty) belongs to rank (tx + ty) % world -- row by row as tx | ty << 16, appended to *tiles;
 // *valid gets the running count of their pixels inside the w x h image, [n + 1] entries.  Both nullable.  -> that count over all of them.
 uint64_t pt_rank_tiles(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, std::vector<uint32_t> *tiles = nullptr, std::vector<uint64_t> *valid = nullptr);

@@ -456,7 +456,7 @@ pt_status batch_finish(Job &j, int pipes_now, unsigned long long rays_before)
         redo = flag != 0ull;
     }
     if (!redo) {
-        ptw_launch_resolve(j.rc, f->work.d_tiles, j.rad, f->d_rgb, f->d_bgra, st, nullptr, f->m2.d_m2);
+        ptw_launch_resolve(j.rc, f->work.d_tiles, j.rad, f->d_rgb, f->d_bgra, st, nullptr, f->m2.ptr());
         ctx->stats.launches_other++;
         return PT_OK;
     }
@@ -747,7 +747,7 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
         PT_HIP(ctx, hipGetLastError());
         ctx->stats.launches_extend++;
         ctx->stats.rounds++;
-        ptw_launch_resolve(rc, w.d_tiles, rad, f->d_rgb, f->d_bgra, st, sh.bounded ? d_overflow : nullptr, f->m2.d_m2);
+        ptw_launch_resolve(rc, w.d_tiles, rad, f->d_rgb, f->d_bgra, st, sh.bounded ? d_overflow : nullptr, f->m2.ptr());
         ctx->stats.launches_other++;
         bool redo = false;
         if (sh.bounded) {

@@ -29,8 +29,7 @@ namespace {
 template <bool HAS_M>
 __global__ __launch_bounds__(TB) void k_reproject(RpConst rc, RpFilm fl, RpPrev pv)
 {
-    const uint32_t by_ = blockIdx.x / rc.n_bx, bx_ = blockIdx.x - by_ * rc.n_bx;
-    const int x = (int)(bx_ * RP_BW + (threadIdx.x & (RP_BW - 1))), y = (int)(by_ * RP_BH + threadIdx.x / RP_BW);
+    int x, y; fp_pixel(rc.n_bx, x, y);
     if (x >= (int)rc.w || y >= (int)rc.h) return;
     rp_pixel<HAS_M>(rc, fl, pv, x, y);
 }
@@ -43,8 +42,7 @@ RpFn pick_reproject(bool has_m) { return has_m ? k_reproject<true> : k_reproject
 template <bool HAS_M>
 __global__ __launch_bounds__(TB) void k_reproject_motion(RpConst rc, RpFilm fl, RpPrev pv, const float *__restrict__ motion)
 {
-    const uint32_t by_ = blockIdx.x / rc.n_bx, bx_ = blockIdx.x - by_ * rc.n_bx;
-    const int x = (int)(bx_ * RP_BW + (threadIdx.x & (RP_BW - 1))), y = (int)(by_ * RP_BH + threadIdx.x / RP_BW);
+    int x, y; fp_pixel(rc.n_bx, x, y);
     if (x >= (int)rc.w || y >= (int)rc.h) return;
     rp_pixel<HAS_M, true>(rc, fl, pv, x, y, motion);
 }
@@ -52,35 +50,30 @@ __global__ __launch_bounds__(TB) void k_reproject_motion(RpConst rc, RpFilm fl, 
 using RpMotionFn = decltype(&k_reproject_motion<false>);
 RpMotionFn pick_reproject_motion(bool has_m) { return has_m ? k_reproject_motion<true> : k_reproject_motion<false>; }
 
-bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-
 // every refusal of the header, in one place; nothing is written before it returns PT_OK
 pt_status rp_validate(pt_film *f, pt_film *prev, const pt_reproject_params *p, bool motion)
 {
     pt_ctx *ctx = f->ctx;
-    auto bad = [&](const char *msg) { ctx->err = msg; return PT_ERR_INVALID_ARG; };
-    if (prev == f) return bad("pt_film_reproject: prev is the film itself (the history is read while the film is rewritten: two films, ping-ponged)");
-    if (!f->aov.enabled) return bad("the film has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
-    if (!f->hist.d_len) return bad("the film has no history-length plane: pt_film_enable_history first");
-    if (motion && !f->mo.d_q) return bad("the film has no motion plane: pt_film_enable_motion (and pt_film_motion) first");
+    if (prev == f) return pt_bad(ctx, "pt_film_reproject: prev is the film itself (the history is read while the film is rewritten: two films, ping-ponged)");
+    if (!f->aov.enabled) return pt_bad(ctx, PT_NO_GUIDES_MSG);
+    if (!f->hist.d) return pt_bad(ctx, PT_NO_L_MSG " first");
+    if (motion && !f->mo.d) return pt_bad(ctx, PT_NO_Q_MSG " (and pt_film_motion) first");
     if (prev) {
-        if (prev->ctx != ctx) return bad("film and prev belong to different contexts");
-        if (prev->w != f->w || prev->h != f->h) return bad("film and prev differ in size");
-        if (!prev->aov.enabled) return bad("prev has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
-        if (!prev->hist.d_len) return bad("prev has no history-length plane: pt_film_enable_history first");
-        if ((prev->m2.d_m2 != nullptr) != (f->m2.d_m2 != nullptr)) return bad("exactly one of film and prev has a second-moment plane: both or neither");
+        if (prev->ctx != ctx) return pt_bad(ctx, "film and prev belong to different contexts");
+        if (prev->w != f->w || prev->h != f->h) return pt_bad(ctx, "film and prev differ in size");
+        if (!prev->aov.enabled) return pt_bad(ctx, "prev has no guide buffers: pt_film_enable_aov (and pt_render_aov) first");
+        if (!prev->hist.d) return pt_bad(ctx, "prev has no history-length plane: pt_film_enable_history first");
+        if ((prev->m2.d != nullptr) != (f->m2.d != nullptr)) return pt_bad(ctx, "exactly one of film and prev has a second-moment plane: both or neither");
     }
-    if (!finite3(p->cam_origin) || !finite3(p->cam_target) || !finite3(p->prev_cam_origin) || !finite3(p->prev_cam_target))
-        return bad("pt_reproject_params: the cameras must be finite");
-    if (!(std::isfinite(p->gain) && p->gain > 0.f)) return bad("pt_reproject_params.gain must be finite and > 0");
-    if (!(p->alpha >= 0.f && p->alpha <= 1.f)) return bad("pt_reproject_params.alpha must be in [0, 1]");
-    if (!(std::isfinite(p->depth_tol) && p->depth_tol > 0.f)) return bad("pt_reproject_params.depth_tol must be finite and > 0");
-    if (!(p->normal_min >= -1.f && p->normal_min <= 1.f)) return bad("pt_reproject_params.normal_min must be in [-1, 1]");
-    if (p->max_history < 1 || p->max_history > 65535) return bad("pt_reproject_params.max_history must be in 1..65535");
-    if (p->flags & ~(uint32_t)PT_REPROJECT_MATCH_ID) return bad("pt_reproject_params.flags: unknown bits");
-    for (uint32_t r : p->reserved)
-        if (r) return bad("pt_reproject_params.reserved must be 0");
-    return PT_OK;
+    if (!pt_finite3(p->cam_origin) || !pt_finite3(p->cam_target) || !pt_finite3(p->prev_cam_origin) || !pt_finite3(p->prev_cam_target))
+        return pt_bad(ctx, "pt_reproject_params: the cameras must be finite");
+    if (!(std::isfinite(p->gain) && p->gain > 0.f)) return pt_bad(ctx, "pt_reproject_params.gain must be finite and > 0");
+    if (!(p->alpha >= 0.f && p->alpha <= 1.f)) return pt_bad(ctx, "pt_reproject_params.alpha must be in [0, 1]");
+    if (!(std::isfinite(p->depth_tol) && p->depth_tol > 0.f)) return pt_bad(ctx, "pt_reproject_params.depth_tol must be finite and > 0");
+    if (!(p->normal_min >= -1.f && p->normal_min <= 1.f)) return pt_bad(ctx, "pt_reproject_params.normal_min must be in [-1, 1]");
+    if (p->max_history < 1 || p->max_history > 65535) return pt_bad(ctx, "pt_reproject_params.max_history must be in 1..65535");
+    if (p->flags & ~(uint32_t)PT_REPROJECT_MATCH_ID) return pt_bad(ctx, "pt_reproject_params.flags: unknown bits");
+    return pt_check_reserved(ctx, "pt_reproject_params", p->reserved);
 }
 
 }  // namespace
@@ -88,39 +81,28 @@ pt_status rp_validate(pt_film *f, pt_film *prev, const pt_reproject_params *p, b
 pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms, bool motion)
 {
     pt_ctx *ctx = f->ctx;
-    const pt_status rv = rp_validate(f, prev, p, motion);
-    if (rv != PT_OK) return rv;
-    pt_params cp{};
-    for (int k = 0; k < 3; k++) { cp.cam_origin[k] = p->cam_origin[k]; cp.cam_target[k] = p->cam_target[k]; }
-    cp.width = f->w; cp.height = f->h;
+    PT_TRY(rp_validate(f, prev, p, motion));
     RpConst rc{};
     rc.w = f->w; rc.h = f->h;
-    rc.n_bx = (f->w + RP_BW - 1) / RP_BW;
+    const uint32_t n_blocks = fp_grid(f->w, f->h, &rc.n_bx);
     rc.match_id = p->flags & PT_REPROJECT_MATCH_ID;
-    rc.cam = ptw_camera(&cp);   // the camera pt_render and pt_render_aov start their rays from
+    rc.cam = ptw_camera_of(p->cam_origin, p->cam_target, f->w, f->h);   // the camera pt_render and pt_render_aov start their rays from
     rc.pox = p->prev_cam_origin[0]; rc.poy = p->prev_cam_origin[1]; rc.poz = p->prev_cam_origin[2];
     rc.ptx = p->prev_cam_target[0]; rc.pty = p->prev_cam_target[1]; rc.ptz = p->prev_cam_target[2];
     rc.gain = p->gain; rc.alpha = p->alpha; rc.depth_tol = p->depth_tol; rc.normal_min = p->normal_min;
     rc.max_history = (float)p->max_history;
     const pt_film::Aov &a = f->aov;
-    const RpFilm fl = { f->d_rgb, f->m2.d_m2, f->hist.d_len, reinterpret_cast<uchar4 *>(f->d_bgra), static_cast<const float *>(a.plane[PT_AOV_NORMAL]),
+    const RpFilm fl = { f->d_rgb, f->m2.ptr(), f->hist.ptr(), reinterpret_cast<uchar4 *>(f->d_bgra), static_cast<const float *>(a.plane[PT_AOV_NORMAL]),
                         static_cast<const float *>(a.plane[PT_AOV_DEPTH]), static_cast<const float *>(a.plane[PT_AOV_ALPHA]),
                         static_cast<const uint2 *>(a.plane[PT_AOV_ID]) };
     RpPrev pv{};
     if (prev) {
         const pt_film::Aov &b = prev->aov;
-        pv = { prev->d_rgb, prev->m2.d_m2, prev->hist.d_len, static_cast<const float *>(b.plane[PT_AOV_NORMAL]), static_cast<const float *>(b.plane[PT_AOV_DEPTH]),
+        pv = { prev->d_rgb, prev->m2.ptr(), prev->hist.ptr(), static_cast<const float *>(b.plane[PT_AOV_NORMAL]), static_cast<const float *>(b.plane[PT_AOV_DEPTH]),
                static_cast<const float *>(b.plane[PT_AOV_ALPHA]), static_cast<const uint2 *>(b.plane[PT_AOV_ID]) };
     }
-    hipStream_t st = ctx->stream;
-    const uint32_t n_blocks = rc.n_bx * ((f->h + RP_BH - 1) / RP_BH);  // (a film has fewer than 2^28 pixels and sides below 2^19: far fewer than 2^31 blocks)
-    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    if (motion) hipLaunchKernelGGL(pick_reproject_motion(f->m2.d_m2 != nullptr), dim3(n_blocks), dim3(TB), 0, st, rc, fl, pv, reinterpret_cast<const float *>(f->mo.d_q));
-    else hipLaunchKernelGGL(pick_reproject(f->m2.d_m2 != nullptr), dim3(n_blocks), dim3(TB), 0, st, rc, fl, pv);
-    PT_HIP(ctx, hipGetLastError());
-    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-    PT_HIP(ctx, hipStreamSynchronize(st));
-    PT_HIP(ctx, hipGetLastError());
-    if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
-    return PT_OK;
+    return pt_timed_pass(ctx, device_ms, [&](hipStream_t st) {
+        if (motion) hipLaunchKernelGGL(pick_reproject_motion(f->m2.d != nullptr), dim3(n_blocks), dim3(TB), 0, st, rc, fl, pv, reinterpret_cast<const float *>(f->mo.d));
+        else hipLaunchKernelGGL(pick_reproject(f->m2.d != nullptr), dim3(n_blocks), dim3(TB), 0, st, rc, fl, pv);
+    });
 }

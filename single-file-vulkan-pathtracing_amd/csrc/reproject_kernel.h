@@ -4,6 +4,7 @@
 // Wants declared before it: ptm::Camera, ptm::fdiv, ptm::fsqrt, ptm::primary_target, ptm::div3_dominant (pt_math.h), uint2, uchar4,
 // make_uchar4, min, max, TB and RP_KEEP(v) (the device: an empty asm that takes v in a vector register; the host: nothing).
 #pragma once
+#include "film_pass.h"
 
 struct RpConst {
     uint32_t w, h, n_bx;       // image, blocks per row of blocks
@@ -23,7 +24,6 @@ struct RpPrev {
     const float *rgb, *m2, *len, *normal, *depth, *alpha;   // rgb null: no previous film, every pixel takes the no-history path
     const uint2 *id;
 };
-constexpr int RP_BW = 64, RP_BH = TB / RP_BW;  // pixels of a block
 
 // k_resolve's clamp and quantise (shade_kernels.hip to_unorm8)
 __device__ __forceinline__ uint8_t rp_unorm8(float c)

@@ -143,6 +143,14 @@ pt_status ptw_shape_and_work(pt_film *f, const pt_params *p, RenderShape &sh, in
 pt_status ptw_tiles_subject_first(pt_film *f, const int32_t rect[4], hipStream_t st);  // fused pipeline: tiles that can see the scene first (film_work.hip)
 uint64_t ptw_workspace_bytes(const pt_film *f);
 ptm::Camera ptw_camera(const pt_params *p);  // the camera of a launch: pt_render and pt_render_aov start the same rays from it
+// ... of a film pass (reproject.hip, motion.hip), which is given a camera and a film and no pt_params
+inline ptm::Camera ptw_camera_of(const float *origin, const float *target, uint32_t w, uint32_t h)
+{
+    pt_params cp{};
+    for (int k = 0; k < 3; k++) { cp.cam_origin[k] = origin[k]; cp.cam_target[k] = target[k]; }
+    cp.width = w; cp.height = h;
+    return ptw_camera(&cp);
+}
 ptw::RenderConst ptw_render_const(const pt_params *p, const pt_film::Work &w, const RenderShape &sh);
 uint64_t ptw_valid_local_pixels(const pt_film *f, const pt_params *p);
 // render.hip: the pixel rectangle {x0, y0, x1, y1} outside of which no camera ray can reach the scene's box (x1 < x0: no such proof)

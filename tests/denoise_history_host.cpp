@@ -1,31 +1,11 @@
 // denoise_history_host.cpp -- the per-pixel bodies of k_dn_prepare_hist and k_dn_var_spatial (csrc/denoise_history_kernel.h), compiled for the
 // host and run over planes read from files: what tests/test_denoise_history.py holds against its numpy restatement without a GPU, and under
-// the host's sanitizers.  The IEEE divide stands in for pt_math.h's fdiv, its bitwise equal; compile with -ffp-contract=off.
+// the host's sanitizers.  The IEEE divide (kernel_host.h) stands in for pt_math.h's fdiv, its bitwise equal; compile with -ffp-contract=off.
 // usage: denoise_history_host DIR  (DIR/par, film, albedo, normal, emission, depth, alpha, m2, len in; o_illum, o_guide out: the records the
 // pre-blur reads, {I.rgb, V0} and {N.xyz, Z} per pixel; see _run_on_host in the test)
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#include <algorithm>
-#include <string>
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __restrict__
-struct float4 { float x, y, z, w; };
-inline float4 make_float4(float a, float b, float c, float d) { return { a, b, c, d }; }
-constexpr int TB = 256;
-using std::min; using std::max;
-namespace ptm {
-inline float fdiv(float a, float b) { return a / b; }
-}
+#include "kernel_host.h"
 #define DH_KEEP(v) ((void)(v))
 #include "denoise_history_kernel.h"
-template <class T> std::vector<T> rd(const std::string &p, size_t n) { std::vector<T> v(n); FILE *f = fopen(p.c_str(), "rb"); if (!f || fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "read %s\n", p.c_str()); exit(2); } fclose(f); return v; }
-template <class T> void wr(const std::string &p, const std::vector<T> &v) { FILE *f = fopen(p.c_str(), "wb"); if (!f || fwrite(v.data(), sizeof(T), v.size(), f) != v.size() || fclose(f) != 0) { fprintf(stderr, "write %s\n", p.c_str()); exit(2); } }
 int main(int argc, char **argv)
 {
     if (argc != 2) { fprintf(stderr, "usage: denoise_history_host DIR\n"); return 2; }
@@ -35,7 +15,7 @@ int main(int argc, char **argv)
     auto film = rd<float>(d + "/film", 3 * n), albedo = rd<float>(d + "/albedo", 3 * n), normal = rd<float>(d + "/normal", 3 * n), emission = rd<float>(d + "/emission", 3 * n);
     auto depth = rd<float>(d + "/depth", n), alpha = rd<float>(d + "/alpha", n), m2 = rd<float>(d + "/m2", 3 * n), len = rd<float>(d + "/len", n);
     DhConst dc{};
-    dc.w = w; dc.h = h; dc.n_bx = (w + DH_BW - 1) / DH_BW;
+    dc.w = w; dc.h = h; fp_grid(w, h, &dc.n_bx);
     dc.inv_n = 1.0f / (par[2] * par[2]); dc.sz2 = par[3] * par[3];   // (as dn_run computes them)
     dc.mh = par[4]; dc.sf = par[5]; dc.n_max = par[6];
     const DhPlanes pl = { film.data(), albedo.data(), normal.data(), emission.data(), depth.data(), alpha.data(), m2.data(), len.data() };

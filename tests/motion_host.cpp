@@ -1,47 +1,14 @@
 // motion_host.cpp -- k_motion's per-pixel body (csrc/motion_kernel.h) and the MOTION instantiation of k_reproject's (csrc/reproject_kernel.h),
 // compiled for the host and run over planes read from files: what tests/test_motion.py holds against its numpy restatements without a GPU, and
-// under the host's sanitizers.  The stand-ins below are the IEEE operations pt_math.h's helpers are proven equal to; compile with
+// under the host's sanitizers.  The stand-ins (kernel_host.h) are the IEEE operations pt_math.h's helpers are proven equal to; compile with
 // -ffp-contract=off.  usage: motion_host DIR.  DIR/mpar present: Q from DIR/m_* (-> o_Q); DIR/par present: the reprojection of
 // reproject_host.cpp's files plus DIR/c_Q (-> o_C, o_M, o_L, o_bgra).  Every array is read into a vector of exactly its size, so an index
 // that leaves its array is the sanitizer's to find.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#include <algorithm>
-#include <string>
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __restrict__
-struct uint2 { uint32_t x, y; };
-struct uchar4 { uint8_t x, y, z, w; };
-struct alignas(16) float4 { float x, y, z, w; };
-inline uchar4 make_uchar4(uint8_t a, uint8_t b, uint8_t c, uint8_t d) { return { a, b, c, d }; }
-inline float4 make_float4(float a, float b, float c, float d) { return { a, b, c, d }; }
-constexpr int TB = 256;
-using std::min; using std::max;
-namespace ptm {
-struct Camera { float ox, oy, oz, tx, ty, tz, w, h, rw, rh; };
-inline float fdiv(float a, float b) { return a / b; }
-inline float fsqrt(float a) { return sqrtf(a); }
-inline void primary_target(const Camera &cam, uint32_t px, uint32_t py, float jx, float jy, float &vx, float &vy, float &vz)
-{
-    const float sx = (float)px + jx, sy = (float)py + jy;
-    const float qx = fdiv(sx, cam.w), qy = fdiv(sy, cam.h);
-    const float dx = qx * 2.0f - 1.0f, dy = qy * 2.0f - 1.0f;
-    vx = (dx + cam.tx) - cam.ox; vy = (dy + cam.ty) - cam.oy; vz = cam.tz - cam.oz;
-}
-inline void div3_dominant(float a1, float a2, float a3, float b, float &q1, float &q2, float &q3) { q1 = a1 / b; q2 = a2 / b; q3 = a3 / b; }
-}
+#include "kernel_host.h"
 #define RP_KEEP(v) ((void)(v))
 #define MO_KEEP(v) ((void)(v))
 #include "reproject_kernel.h"
 #include "motion_kernel.h"
-template <class T> std::vector<T> rd(const std::string &p, size_t n) { std::vector<T> v(n); FILE *f = fopen(p.c_str(), "rb"); if (!f || fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "read %s\n", p.c_str()); exit(2); } fclose(f); return v; }
-template <class T> void wr(const std::string &p, const std::vector<T> &v) { FILE *f = fopen(p.c_str(), "wb"); if (!f || fwrite(v.data(), sizeof(T), v.size(), f) != v.size() || fclose(f) != 0) { fprintf(stderr, "write %s\n", p.c_str()); exit(2); } }
 static bool have(const std::string &p) { FILE *f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != nullptr; }
 
 static void motion(const std::string &d)
@@ -55,7 +22,7 @@ static void motion(const std::string &d)
     if (n_inst) { xf = rd<float4>(d + "/m_xf", 3 * (size_t)n_inst); xf_prev = rd<float4>(d + "/m_xf_prev", 3 * (size_t)n_inst); }
     std::vector<float4> Q(n, make_float4(9.f, 9.f, 9.f, 9.f));
     MoConst mc{};
-    mc.w = w; mc.h = h; mc.n_bx = (w + 63) / 64; mc.n_tris = n_tris; mc.n_inst = n_inst ? n_inst : 1u;
+    mc.w = w; mc.h = h; fp_grid(w, h, &mc.n_bx); mc.n_tris = n_tris; mc.n_inst = n_inst ? n_inst : 1u;
     mc.cam = { par[4], par[5], par[6], par[7], par[8], par[9], (float)w, (float)h, 0.f, 0.f };
     mc.slack = par[10];
     const MoScene sc = { tri.data(), tri_prev.data(), n_inst ? xf.data() : nullptr, n_inst ? xf_prev.data() : nullptr };
@@ -79,7 +46,7 @@ static void reproject(const std::string &d)
     auto pC = rd<float>(d + "/p_C", 3 * n), pM = rd<float>(d + "/p_M", 3 * n), pN = rd<float>(d + "/p_N", 3 * n), pZ = rd<float>(d + "/p_Z", n), pA = rd<float>(d + "/p_a", n), pL = rd<float>(d + "/p_L", n);
     auto pID = rd<uint2>(d + "/p_ID", n);
     RpConst rc{};
-    rc.w = w; rc.h = h; rc.n_bx = (w + 63) / 64; rc.match_id = (uint32_t)par[3];
+    rc.w = w; rc.h = h; fp_grid(w, h, &rc.n_bx); rc.match_id = (uint32_t)par[3];
     rc.cam = { par[4], par[5], par[6], par[7], par[8], par[9], (float)w, (float)h, 0.f, 0.f };
     rc.pox = par[10]; rc.poy = par[11]; rc.poz = par[12]; rc.ptx = par[13]; rc.pty = par[14]; rc.ptz = par[15];
     rc.gain = par[16]; rc.alpha = par[17]; rc.depth_tol = par[18]; rc.normal_min = par[19]; rc.max_history = par[20];
