@@ -1,16 +1,24 @@
 """dev tool: randomized render parity -- random film sizes (ragged), spp, depth, frame ranges, frames in flight,
-sample groups, tail samples, the cull and the hand-out order on / off, rank/world splits, extend variants, both pipelines, cameras -- GPU film vs the oracle's, bit for bit."""
+sample groups, tail samples, the cull and the hand-out order on / off, rank/world splits, extend variants, both pipelines, cameras -- GPU film vs the oracle's, bit for bit.
+--materials: every configuration draws a family A material table (tests/material_tables.py table_a: zero, -0.0, denormal, tiny, negative and
+ordinary Kd / Ke) instead of the Cornell materials, one of that module's two family A environments, and max_depth <= 6 (nothing can overflow)."""
 import importlib, os, sys, time
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
 pt = importlib.import_module("single-file-vulkan-pathtracing_amd")
 from oracle import pt_oracle as orc
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-SEED0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+MATERIALS = "--materials" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--materials"]
+N = int(argv[0]) if len(argv) > 0 else 30
+SEED0 = int(argv[1]) if len(argv) > 1 else 1
 ctx = pt.Context(0)
 arrays = pt.load_obj(pt.ASSET_CORNELL)
 sc, osc = pt.Scene(ctx, *arrays), orc.Scene(*arrays)
+if MATERIALS:
+    import material_tables as edges
+    owners = importlib.import_module("single-file-vulkan-pathtracing_amd.distributed").owned_mask
 bad = 0
 t0 = time.time()
 for k in range(N):
@@ -32,6 +40,11 @@ for k in range(N):
             q[:, 0] = -q[:, 0]
         inst[i, :, :3] = (q * rng.uniform(0.2, 0.6)).astype(np.float32)
         inst[i, :, 3] = rng.uniform(-1.5, 1.5, 3).astype(np.float32) + np.float32([0, -1, 0])
+    if MATERIALS:  # a table per configuration: new scenes (the table is part of pt_scene_create), family A's depth bound and environments
+        faces = edges.table_a(len(arrays[1]) // 3, SEED0 + k).reshape(-1)
+        sc.close()
+        sc, osc = pt.Scene(ctx, arrays[0], arrays[1], faces), orc.Scene(arrays[0], arrays[1], faces)
+        kw.update(max_depth=min(depth, 6), env=(edges.ENV_MIXED, edges.ENV_TINY)[int(rng.integers(0, 2))])
     sc.set_instances(inst)
     osc.set_instances(inst)
     # oracle: frames f0 .. f0+nf-1 blended onto a film that already holds frames 0 .. f0-1
@@ -61,9 +74,19 @@ for k in range(N):
         if f0:
             pt.render(sc, film, pt.default_params(frame=0, frame_count=f0, **gk))
         pt.render(sc, film, pt.default_params(frame=f0, frame_count=nf, **gk))
-        total += film.read_f32()          # x + 0 == x: shards sum exactly
+        if MATERIALS:                     # put together by ownership: +0 + -0.0 would lose the sign of a -0.0
+            mine = owners(w, h, rank, world)
+            total[mine] = film.read_f32()[mine]
+        else:
+            total += film.read_f32()      # x + 0 == x: shards sum exactly
         film.close()
-    if total.tobytes() != film_o.tobytes():
+    if MATERIALS:                         # the comparison rule of tests/material_tables.py, family A: equal bytes; names pixel, channel and bits
+        try:
+            edges.assert_same(f"configuration {k}", f"{kw} instances {n_inst} world {world}", total, film_o, exact=True)
+        except AssertionError as e:
+            bad += 1
+            print("MISMATCH", e)
+    elif total.tobytes() != film_o.tobytes():
         bad += 1
         print("MISMATCH", k, kw, "instances", n_inst, "world", world, "max abs diff", float(np.abs(total - film_o).max()))
 print(f"render fuzz: {N} configurations, mismatches: {bad}; {time.time() - t0:.1f} s")

@@ -70,15 +70,15 @@ def _oracle_scene(pt, orc, scene, faces=None):
     return osc
 
 
-def _guides(pt, orc, case, frames):
+def _guides(pt, orc, case, frames, faces=None):
     """The definition, with the oracle's bindings: the six planes after `frames` (ascending frame indices, blended one after the
-    other into zeroed planes) -> {name: array}."""
-    key = (case, tuple(frames))
+    other into zeroed planes) -> {name: array}.  faces: a material table [n_tris, 6] in place of the scene's own."""
+    key = (case, tuple(frames), None if faces is None else np.asarray(faces, np.float32).tobytes())
     if key in _cache:
         return _cache[key]
     scene, w, h, spp, cam = CASES[case]
-    faces = np.asarray(_arrays(pt, scene)[2], np.float32).reshape(-1, 6)
-    osc = _oracle_scene(pt, orc, scene)
+    faces = np.asarray(_arrays(pt, scene)[2] if faces is None else faces, np.float32).reshape(-1, 6)
+    osc = _oracle_scene(pt, orc, scene, faces.reshape(-1))
     out = {"albedo": np.zeros((h, w, 3), np.float32), "normal": np.zeros((h, w, 3), np.float32), "emission": np.zeros((h, w, 3), np.float32),
            "depth": np.zeros((h, w), np.float32), "alpha": np.zeros((h, w), np.float32), "id": np.zeros((h, w, 2), np.uint32)}
     normals = {}
