@@ -80,7 +80,9 @@ typedef struct pt_tuning {
     int32_t tlas_ploc;      /* 1: the TLAS of an instanced scene is rebuilt by PLOC like a big scene's binary tree (0: LBVH)   */
     int32_t ploc_adopt_pct; /* a PLOC tree is kept when its area sum is below this percentage of the LBVH's (90; 1000 = always) */
     int32_t fail_rebuild;   /* NOT a speed knob -- failure injection for the tests: > 0 makes the next rebuilds of a scene's tree products fail
-                               after the old ones were freed.  Only pt_ctx_set_tuning sets it; PT_TUNE refuses the name.                      */
+                               after the old ones were freed, and the next allocations of a set of scene buffers (the surface-area tree, the
+                               instance set, the previous geometry, ...) of a scene that has, or has lost, a tree: each failure is PT_ERR_OOM
+                               and takes one off the count.  Only pt_ctx_set_tuning sets it; PT_TUNE refuses the name.                        */
     int32_t fused_tail;     /* fused pipeline, sample_groups left at 0, single-level scenes: S of a pixel's spp samples are traced as one-sample
                                tail slots handed out after every head slot (spp - S samples) -- a launch with few slots per lane ends with short
                                work.  0 = never; -1: by the launch's slots per lane (render.hip fused_tail_samples); clamped to spp - 1.      */

@@ -567,13 +567,6 @@ __global__ __launch_bounds__(TBD) void k_sah_rows(const uint32_t *__restrict__ c
     rows[32 * (size_t)r + 28 + j] = 0u;
 }
 
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, sizeof(T) * (n ? n : 1)); }
-};
-
 }  // namespace
 
 // tlo / thi: HOST arrays of the unpadded triangle boxes (3 floats each), as pt_sah_build_bvh4 takes them.  The rows
@@ -592,11 +585,11 @@ pt_status pt_sah_build_bvh4_device(pt_ctx *ctx, const float *tlo, const float *t
         t += cnt;
     }
     const uint32_t np = (uint32_t)prim_first.size();
-    Buf<float> d_tlo, d_thi;
-    Buf<uint32_t> d_first, d_ids, d_nn, d_rows, d_order, d_counts;
-    Buf<uint8_t> d_tris;
-    Buf<double> d_plo, d_phi;
-    Buf<SahNode> d_nodes;
+    DevBuf<float> d_tlo, d_thi;
+    DevBuf<uint32_t> d_first, d_ids, d_nn, d_rows, d_order, d_counts;
+    DevBuf<uint8_t> d_tris;
+    DevBuf<double> d_plo, d_phi;
+    DevBuf<SahNode> d_nodes;
     PT_HIP(ctx, d_tlo.alloc(3 * (size_t)n)); PT_HIP(ctx, d_thi.alloc(3 * (size_t)n));
     PT_HIP(ctx, d_first.alloc(np)); PT_HIP(ctx, d_tris.alloc(np)); PT_HIP(ctx, d_ids.alloc(np));
     PT_HIP(ctx, d_nn.alloc(1)); PT_HIP(ctx, d_plo.alloc(3 * (size_t)np)); PT_HIP(ctx, d_phi.alloc(3 * (size_t)np));
@@ -608,8 +601,8 @@ pt_status pt_sah_build_bvh4_device(pt_ctx *ctx, const float *tlo, const float *t
     PT_HIP(ctx, hipMemcpyAsync(d_tris.p, prim_tris.data(), np, hipMemcpyHostToDevice, st));
     k_sah_prims<<<(np + TBD - 1) / TBD, TBD, 0, st>>>(d_tlo.p, d_thi.p, d_first.p, d_tris.p, np, d_plo.p, d_phi.p, d_ids.p);
     // (d_nn: the node counter, one node -- the root -- taken; d_nroots: subtrees handed to k_sah_sub)
-    Buf<SahJob> d_roots;
-    Buf<uint32_t> d_nroots;
+    DevBuf<SahJob> d_roots;
+    DevBuf<uint32_t> d_nroots;
     PT_HIP(ctx, d_roots.alloc(np + 1)); PT_HIP(ctx, d_nroots.alloc(1));
     const uint32_t one = 1u;
     PT_HIP(ctx, hipMemcpyAsync(d_nn.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
@@ -620,13 +613,13 @@ pt_status pt_sah_build_bvh4_device(pt_ctx *ctx, const float *tlo, const float *t
     k_sah_top<<<1, TBT, top_smem, st>>>(np, leaf_max > 0 ? leaf_max : 1u, d_plo.p, d_phi.p, d_ids.p, d_nodes.p, d_nn.p, d_roots.p, d_nroots.p);
     // (a child handed over has >= 2 primitives and the ranges are disjoint: <= np / 2 subtrees)
     k_sah_sub<<<std::max(1u, np / 2u), TBD, 0, st>>>(leaf_max > 0 ? leaf_max : 1u, d_plo.p, d_phi.p, d_ids.p, d_nodes.p, d_nn.p, d_roots.p, d_nroots.p);
-    Buf<float> d_nbox;
-    Buf<double> d_narea;
-    Buf<uint32_t> d_ntris;
+    DevBuf<float> d_nbox;
+    DevBuf<double> d_narea;
+    DevBuf<uint32_t> d_ntris;
     PT_HIP(ctx, d_nbox.alloc(6 * (2 * (size_t)np + 1))); PT_HIP(ctx, d_narea.alloc(2 * (size_t)np + 1)); PT_HIP(ctx, d_ntris.alloc(2 * (size_t)np + 1));
     k_sah_node_boxes<<<(2 * np + 1 + TBD - 1) / TBD, TBD, 0, st>>>(d_nodes.p, d_nn.p, d_ids.p, d_first.p, d_tris.p, d_tlo.p, d_thi.p, pad, d_nbox.p,
                                                                    d_narea.p, d_ntris.p);
-    Buf<uint32_t> d_row_kid, d_row_word;
+    DevBuf<uint32_t> d_row_kid, d_row_word;
     PT_HIP(ctx, d_row_kid.alloc(4 * (2 * (size_t)np + 1))); PT_HIP(ctx, d_row_word.alloc(4 * (2 * (size_t)np + 1)));
     const size_t emit_smem = (sizeof(double) + 3 * sizeof(uint32_t) + 3 * sizeof(float) + 1) * (2 * (size_t)np + 1) + sizeof(uint32_t) * (size_t)np + 16;  // <= 143 KB for 2048 primitives
     if (emit_smem > 48 * 1024)

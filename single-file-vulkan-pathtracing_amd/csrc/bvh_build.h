@@ -43,31 +43,24 @@ __device__ __forceinline__ float box_area(const float4 lo, const float4 hi)
 
 constexpr int PLOC_R_MAX = 32;  // PLOC's search radius is a run-time choice (pt_tuning.ploc_radius, default 8) up to this
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, sizeof(T) * (n ? n : 1)); }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
 }  // namespace
 
 // ---- generic part: n boxes (tlo/thi on the device) -> sorted order, binary LBVH, BVH4 ----------
+// The device arrays are the BvhOut's until the caller release()s them: a build that fails at any point leaks nothing.
 struct BvhOut {
-    unsigned long long *d_keys = nullptr;  // sorted Morton keys           (caller owns)
-    uint32_t *d_prim_of = nullptr;         // sorted position -> box id
-    uint32_t *d_prim_q = nullptr;          // PLOC: leaf position of the rebuilt tree -> box id (null: the LBVH is the tree)
-    float4 *d_nodes = nullptr;             // binary nodes, 64 B
-    float4 *d_wide = nullptr;              // BVH4 nodes, 128 B
+    DevBuf<unsigned long long> d_keys;     // sorted Morton keys
+    DevBuf<uint32_t> d_prim_of;            // sorted position -> box id
+    DevBuf<uint32_t> d_prim_q;             // PLOC: leaf position of the rebuilt tree -> box id (null: the LBVH is the tree)
+    DevBuf<float4> d_nodes;                // binary nodes, 64 B
+    DevBuf<float4> d_wide;                 // BVH4 nodes, 128 B
     uint32_t n_nodes = 0, n_wide = 0, height = 0, height_tree = 0;  // height: of the LBVH; height_tree: of the tree the collapses ran on
     uint32_t stack_need = 0;               // most entries a depth-first walk of the BVH4 can have pending
     float bmin[3]{}, bmax[3]{};
     // BVH8 (want8): 128-B nodes, the triangle order that goes with them (position -> sorted position), levels
-    uint4 *d_wide8 = nullptr;
-    uint32_t *d_order8 = nullptr;
+    DevBuf<uint4> d_wide8;
+    DevBuf<uint32_t> d_order8;
     uint32_t n_wide8 = 0, levels8 = 0;
-    uint4 *d_wide16t = nullptr;            // BVH4, 64-B nodes, built top-down with contiguous children (k_w4_emit)
+    DevBuf<uint4> d_wide16t;               // BVH4, 64-B nodes, built top-down with contiguous children (k_w4_emit)
     uint32_t n_wide16t = 0, levels4t = 0;
     float norm_c[3]{}, norm_s[3]{1.f, 1.f, 1.f}, norm_rs[3]{1.f, 1.f, 1.f};
     double area_lbvh = 0.0, area_ploc = 0.0, area_tree = 0.0;  // sums of the internal nodes' surface areas: LBVH, PLOC rebuild (0: not built), the tree kept

@@ -690,9 +690,9 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
     PT_HIP(ctx, d_blo.alloc(2 * (size_t)n));
     PT_HIP(ctx, d_bhi.alloc(2 * (size_t)n));
     out.n_nodes = n > 1 ? n - 1 : 1;
-    PT_HIP(ctx, hipMalloc((void **)&out.d_nodes, sizeof(float4) * 4 * (size_t)out.n_nodes));
-    PT_HIP(ctx, hipMalloc((void **)&out.d_keys, sizeof(unsigned long long) * (size_t)n));
-    PT_HIP(ctx, hipMalloc((void **)&out.d_prim_of, sizeof(uint32_t) * (size_t)n));
+    PT_HIP(ctx, out.d_nodes.alloc(4 * (size_t)out.n_nodes));
+    PT_HIP(ctx, out.d_keys.alloc(n));
+    PT_HIP(ctx, out.d_prim_of.alloc(n));
 
     const uint32_t ord_init[6] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u };
     PT_HIP(ctx, hipMemcpyAsync(d_scene.p, ord_init, sizeof(ord_init), hipMemcpyHostToDevice, st));
@@ -710,15 +710,15 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
                                              d_hist.p, nblocks);
         cur ^= 1;
     }
-    PT_HIP(ctx, hipMemcpyAsync(out.d_keys, d_keys[cur].p, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    PT_HIP(ctx, hipMemcpyAsync(out.d_prim_of, d_vals[cur].p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    PT_HIP(ctx, hipMemcpyAsync(out.d_keys.p, d_keys[cur].p, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    PT_HIP(ctx, hipMemcpyAsync(out.d_prim_of.p, d_vals[cur].p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
 
     if (n > 1) {
-        k_karras<<<(n - 1 + TB - 1) / TB, TB, 0, st>>>(out.d_keys, (int)n, d_topo.p, d_pint.p, d_pleaf.p, d_range.p);
-        k_refit<<<gt, TB, 0, st>>>(d_tlo, d_thi, out.d_prim_of, (int)n, d_topo.p, d_pint.p, d_pleaf.p, d_blo.p, d_bhi.p,
-                                   d_flags.p, d_scene.p, out.d_nodes, d_height.p);
+        k_karras<<<(n - 1 + TB - 1) / TB, TB, 0, st>>>(out.d_keys.p, (int)n, d_topo.p, d_pint.p, d_pleaf.p, d_range.p);
+        k_refit<<<gt, TB, 0, st>>>(d_tlo, d_thi, out.d_prim_of.p, (int)n, d_topo.p, d_pint.p, d_pleaf.p, d_blo.p, d_bhi.p,
+                                   d_flags.p, d_scene.p, out.d_nodes.p, d_height.p);
     } else {
-        k_single<<<1, 1, 0, st>>>(d_tlo, d_thi, d_scene.p, out.d_nodes, d_height.p);
+        k_single<<<1, 1, 0, st>>>(d_tlo, d_thi, d_scene.p, out.d_nodes.p, d_height.p);
     }
     uint32_t ploc_height = 0;
     if (n > 2) {
@@ -727,12 +727,12 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
         out.area_tree = out.area_lbvh;
     }
     if (ploc && n > 2) {
-        PT_HIP(ctx, hipMalloc((void **)&out.d_prim_q, sizeof(uint32_t) * (size_t)n));
+        PT_HIP(ctx, out.d_prim_q.alloc(n));
         double area_ploc = 0.0;
         const pt_status prc = ptb_ploc_refine(ctx, n, pt_tuned(ctx->tune.ploc_radius, 8, 1, PLOC_R_MAX), out.area_lbvh, &area_ploc, d_topo.p, d_range.p,
-                                          d_pint.p, d_pleaf.p, d_blo.p, d_bhi.p, out.d_prim_of, out.d_prim_q, d_sums.p, &ploc_height);
+                                          d_pint.p, d_pleaf.p, d_blo.p, d_bhi.p, out.d_prim_of.p, out.d_prim_q.p, d_sums.p, &ploc_height);
         out.area_ploc = area_ploc;
-        if (prc == PT_ERR_UNSUPPORTED) { (void)hipFree(out.d_prim_q); out.d_prim_q = nullptr; }   // stalled, or no cheaper: the LBVH stands
+        if (prc == PT_ERR_UNSUPPORTED) out.d_prim_q.free();   // stalled, or no cheaper: the LBVH stands
         else if (prc != PT_OK) return prc;
         else out.area_tree = area_ploc;
     }
@@ -749,17 +749,17 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
         PT_HIP(ctx, hipMemcpyAsync(&last_flag, d_wflag.p + (n_int - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         PT_HIP(ctx, hipStreamSynchronize(st));
         n_wide = last_idx + last_flag;
-        PT_HIP(ctx, hipMalloc((void **)&out.d_wide, 128 * (size_t)n_wide));
-        k_wide_emit<<<gi, TB, 0, st>>>((int)n, n_int, d_topo.p, d_range.p, d_wflag.p, d_widx.p, d_blo.p, d_bhi.p, out.d_wide, leaf_max);
+        PT_HIP(ctx, out.d_wide.alloc(8 * (size_t)n_wide));
+        k_wide_emit<<<gi, TB, 0, st>>>((int)n, n_int, d_topo.p, d_range.p, d_wflag.p, d_widx.p, d_blo.p, d_bhi.p, out.d_wide.p, leaf_max);
     } else {
-        PT_HIP(ctx, hipMalloc((void **)&out.d_wide, 128));
-        k_wide_single<<<1, 1, 0, st>>>(out.d_nodes, out.d_wide);
+        PT_HIP(ctx, out.d_wide.alloc(8));
+        k_wide_single<<<1, 1, 0, st>>>(out.d_nodes.p, out.d_wide.p);
     }
     out.n_wide = n_wide;
     out.stack_need = 0xFFFFFFFFu;  // unknown: callers fall back to the height bound
     if (n_wide <= 1024) {
         std::vector<uint32_t> h_wide(32 * (size_t)n_wide);
-        PT_HIP(ctx, hipMemcpyAsync(h_wide.data(), out.d_wide, 128 * (size_t)n_wide, hipMemcpyDeviceToHost, st));
+        PT_HIP(ctx, hipMemcpyAsync(h_wide.data(), out.d_wide.p, 128 * (size_t)n_wide, hipMemcpyDeviceToHost, st));
         PT_HIP(ctx, hipStreamSynchronize(st));
         out.stack_need = pt_wide_stack_need(h_wide);
     }
@@ -767,7 +767,7 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
     PT_HIP(ctx, hipMemcpyAsync(ord, d_scene.p, sizeof(ord), hipMemcpyDeviceToHost, st));
     PT_HIP(ctx, hipMemcpyAsync(&out.height, d_height.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PT_HIP(ctx, hipStreamSynchronize(st));
-    out.height_tree = out.d_prim_q ? ploc_height : out.height;   // (out.height stays the LBVH's: the parity read-back)
+    out.height_tree = out.d_prim_q.p ? ploc_height : out.height;   // (out.height stays the LBVH's: the parity read-back)
     for (int k = 0; k < 3; k++) {
         out.bmin[k] = ord2f(ord[k]);
         out.bmax[k] = ord2f(ord[3 + k]);
@@ -788,8 +788,8 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
         uint32_t count = 1, level_base = 0, tri_run = 0, levels = 0;
         int cf = 0;
         if (want8) {
-        PT_HIP(ctx, hipMalloc((void **)&out.d_wide8, 64 * (size_t)n_int));
-        PT_HIP(ctx, hipMalloc((void **)&out.d_order8, sizeof(uint32_t) * (size_t)n));
+        PT_HIP(ctx, out.d_wide8.alloc(4 * (size_t)n_int));
+        PT_HIP(ctx, out.d_order8.alloc(n));
         PT_HIP(ctx, hipMemsetAsync(d_front[0].p, 0, sizeof(uint32_t), st));  // level 0: the binary root, whose range starts at 0
         PT_HIP(ctx, hipMemsetAsync(d_start[0].p, 0, sizeof(uint32_t), st));
         while (count > 0) {
@@ -809,7 +809,7 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
             if ((uint64_t)next_base + next_count >= (1u << 24) || n >= (1u << 24)) { ctx->err = "the 8-wide nodes hold 24-bit child and triangle bases (scenes up to 16.7 M triangles)"; return PT_ERR_UNSUPPORTED; }
             k_w8_emit<<<g, TB, 0, st>>>(count, level_base, next_base, (int)n, d_kids.p, d_ni.p, d_start[cf].p, d_range.p, d_blo.p, d_bhi.p,
                                         out.norm_c[0], out.norm_c[1], out.norm_c[2], out.norm_rs[0], out.norm_rs[1], out.norm_rs[2],
-                                        out.d_wide8, d_front[cf ^ 1].p, d_start[cf ^ 1].p, out.d_order8);
+                                        out.d_wide8.p, d_front[cf ^ 1].p, d_start[cf ^ 1].p, out.d_order8.p);
             level_base = next_base;
             tri_run += leaves;
             count = next_count;
@@ -822,7 +822,7 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
         }
         if (want4t) {
         // ... and the four-wide tree in the 64-B format, same passes
-        PT_HIP(ctx, hipMalloc((void **)&out.d_wide16t, 64 * (size_t)n_int));
+        PT_HIP(ctx, out.d_wide16t.alloc(4 * (size_t)n_int));
         PT_HIP(ctx, hipMemsetAsync(d_front[0].p, 0, sizeof(uint32_t), st));
         count = 1; level_base = 0; levels = 0; cf = 0;
         while (count > 0) {
@@ -836,7 +836,7 @@ pt_status ptb_build_bvh(pt_ctx *ctx, const float4 *d_tlo, const float4 *d_thi, u
             const uint32_t next_count = tot + last, next_base = level_base + count;
             if ((uint64_t)next_base + next_count > n_int) { ctx->err = "internal: BVH4 (top-down) build overran its bounds"; return PT_ERR_HIP; }
             k_w4_emit<<<g, TB, 0, st>>>(count, level_base, next_base, (int)n, d_kids.p, d_ni.p, d_blo.p, d_bhi.p, out.norm_c[0], out.norm_c[1],
-                                        out.norm_c[2], out.norm_rs[0], out.norm_rs[1], out.norm_rs[2], out.d_wide16t, d_front[cf ^ 1].p,
+                                        out.norm_c[2], out.norm_rs[0], out.norm_rs[1], out.norm_rs[2], out.d_wide16t.p, d_front[cf ^ 1].p,
                                         (top_down & 4) ? 1 : 0);
             level_base = next_base;
             count = next_count;

@@ -38,8 +38,7 @@ MoFn pick_motion(bool inst) { return inst ? k_motion<true> : k_motion<false>; }
 
 void ptm_free_previous(pt_scene *s)
 {
-    (void)hipFree(s->prev.d_tri);
-    (void)hipFree(s->prev.d_xf);
+    pt_scratch_free(ptb_scene_buffers(s, PT_LIFE_PREVIOUS), nullptr, 0);
     s->prev = pt_scene::Previous{};
 }
 
@@ -54,31 +53,25 @@ pt_status ptm_snapshot(pt_scene *s)
     const size_t tri_bytes = sizeof(float4) * 3 * (size_t)s->n_tris, xf_bytes = sizeof(float4) * 3 * (size_t)n_inst;
     // both new copies are made first and swapped in at the end, the old ones freed after them: a call that fails at any point leaves the
     // previous snapshot -- triangles and matrices -- as it was
+    // (so the set is allocated into locals: the allocator frees the set it is given first)
     float4 *d_tri = nullptr, *d_xf = nullptr;
-    auto fail = [&](hipError_t e, pt_status rc) {
-        (void)hipGetLastError();
-        (void)hipFree(d_tri);
-        (void)hipFree(d_xf);
-        ctx->err = std::string("pt_scene_snapshot_previous: ") + hipGetErrorString(e);
-        return rc;
-    };
-    hipError_t e = hipMalloc((void **)&d_tri, tri_bytes);
-    if (e != hipSuccess) { d_tri = nullptr; return fail(e, PT_ERR_OOM); }
-    if (n_inst) {
-        e = hipMalloc((void **)&d_xf, 2 * xf_bytes);
-        if (e != hipSuccess) { d_xf = nullptr; return fail(e, PT_ERR_OOM); }
-    }
+    std::vector<pt_buf> fresh = { pt_buf_of(d_tri, tri_bytes) };
+    if (n_inst) fresh.push_back(pt_buf_of(d_xf, 2 * xf_bytes));
+    PT_TRY(ptb_scene_alloc(s, "the previous geometry", fresh));
     // ordered after the work queued on the stream (an update's gather, a render that still reads the triangles)
-    e = hipMemcpyAsync(d_tri, s->d_tri_orig, tri_bytes, hipMemcpyDeviceToDevice, st);
+    hipError_t e = hipMemcpyAsync(d_tri, s->d_tri_orig, tri_bytes, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && n_inst) e = hipMemcpyAsync(d_xf, s->h_xforms.data(), xf_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(e, PT_ERR_HIP);
-    (void)hipFree(s->prev.d_tri);
-    (void)hipFree(s->prev.d_xf);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        pt_scratch_free(fresh, nullptr, 0);
+        ctx->err = std::string("pt_scene_snapshot_previous: ") + hipGetErrorString(e);
+        return PT_ERR_HIP;
+    }
+    ptm_free_previous(s);
     s->prev.have = true;
     s->prev.d_tri = d_tri;
     s->prev.d_xf = d_xf;
-    s->prev.h_now.clear();  // (the new array's second half holds nothing yet)
     s->prev.n_inst = n_inst;
     s->prev.bytes = tri_bytes + 2 * xf_bytes;
     return PT_OK;

@@ -301,6 +301,19 @@ inline pt_status pt_check_sigmas(pt_ctx *ctx, const char *name, std::initializer
 #define PT_NO_L_MSG "the film has no history-length plane: pt_film_enable_history"
 #define PT_NO_Q_MSG "the film has no motion plane: pt_film_enable_motion"
 
+// A device array that is freed with its scope unless it is release()d to an owner.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { free(); }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, sizeof(T) * (n ? n : 1)); }
+    void free() { if (p) (void)hipFree(p); p = nullptr; }
+    T *release() { T *q = p; p = nullptr; return q; }
+};
+
 #define PT_BROKEN_SCENE_MSG "the scene lost its acceleration structure in a failed rebuild (out of memory?): call pt_scene_set_bvh_quality again, or recreate it"
 // lbvh_build.hip
 pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices,
@@ -324,8 +337,15 @@ pt_status pt_sah_build_bvh4_device(pt_ctx *ctx, const float *tlo, const float *t
 void ptb_free_instances(pt_scene *s);
 // film_work.hip: device scratch that hangs on a film (the wavefront workspace, the guide buffers' ray scratch, the denoiser's planes).
 // A workspace names its buffers in SETS that are allocated and freed together, and keeps one byte counter ("Film scratch").
+// A scene's device arrays go the same way, uncounted (scene_build.hip, DESIGN.md section 5, "Scene buffers").
 struct pt_buf { void **p; size_t bytes; };  // one buffer of a set: where its pointer lives, the bytes it is to have (not read when it is freed)
 template <class T> inline pt_buf pt_buf_of(T *&p, size_t bytes = 0) { return { reinterpret_cast<void **>(&p), bytes }; }
+// scene_build.hip: every device pointer of a scene, named once, by lifetime -- what frees a lifetime is pt_scratch_free over its list
+enum pt_scene_life { PT_LIFE_SOURCE, PT_LIFE_TREE, PT_LIFE_INSTANCES, PT_LIFE_PREVIOUS };
+std::vector<pt_buf> ptb_scene_buffers(pt_scene *s, pt_scene_life life);
+// pt_scratch_alloc for a set of scene buffers (all of them or none; PT_ERR_OOM / PT_ERR_HIP with HIP's sticky error cleared), behind the
+// tests' failure injection (pt_tuning.fail_rebuild)
+pt_status ptb_scene_alloc(pt_scene *s, const char *what, const std::vector<pt_buf> &set);
 // Frees the set's buffers, nulls its pointers and takes `held` (the bytes the set held) off *counter (null: a set nobody counts).
 void pt_scratch_free(const std::vector<pt_buf> &set, size_t *counter, size_t held);
 // Gives every buffer of the set its bytes, or none.  What the set holds now (`held` bytes) is freed FIRST, so that the peak is the new size and not

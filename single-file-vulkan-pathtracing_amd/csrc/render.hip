@@ -905,34 +905,25 @@ pt_status ptw_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, flo
     float2 *d_b = nullptr;
     uint32_t *d_cnt = nullptr, *d_hi = nullptr;
     pt_hit *d_out = nullptr;
+    const std::vector<pt_buf> set = { pt_buf_of(d_a, sizeof(float4) * n), pt_buf_of(d_b, sizeof(float2) * n), pt_buf_of(d_hit, sizeof(float4) * n),
+                                      pt_buf_of(d_out, sizeof(pt_hit) * n), pt_buf_of(d_cnt, sizeof(uint32_t) * 2), pt_buf_of(d_hi, sizeof(uint32_t) * n) };
+    PT_TRY(pt_scratch_alloc(ctx, "the ray and hit buffers of pt_trace", set, nullptr, 0));
     pt_status ret = PT_OK;
-    auto fail = [&](hipError_t e, const char *what) {
-        ctx->err = std::string(what) + ": " + hipGetErrorString(e);
-        ret = PT_ERR_HIP;
-    };
-    hipError_t e;
-    if ((e = hipMalloc((void **)&d_a, sizeof(float4) * n)) != hipSuccess) fail(e, "hipMalloc");
-    if (ret == PT_OK && (e = hipMalloc((void **)&d_b, sizeof(float2) * n)) != hipSuccess) fail(e, "hipMalloc");
-    if (ret == PT_OK && (e = hipMalloc((void **)&d_hit, sizeof(float4) * n)) != hipSuccess) fail(e, "hipMalloc");
-    if (ret == PT_OK && (e = hipMalloc((void **)&d_out, sizeof(pt_hit) * n)) != hipSuccess) fail(e, "hipMalloc");
-    if (ret == PT_OK && (e = hipMalloc((void **)&d_cnt, sizeof(uint32_t) * 2)) != hipSuccess) fail(e, "hipMalloc");
-    if (ret == PT_OK && (e = hipMalloc((void **)&d_hi, sizeof(uint32_t) * n)) != hipSuccess) fail(e, "hipMalloc");
-    if (ret == PT_OK) {
-        (void)hipMemcpyAsync(d_a, a.data(), sizeof(float4) * n, hipMemcpyHostToDevice, st);
-        (void)hipMemcpyAsync(d_b, b.data(), sizeof(float2) * n, hipMemcpyHostToDevice, st);
-        const uint32_t cnt_head[2] = { n, 0u };
-        (void)hipMemcpyAsync(d_cnt, cnt_head, sizeof(cnt_head), hipMemcpyHostToDevice, st);
-        (void)hipEventRecord(ctx->ev_a, st);
-        ptw_launch_extend(pl, s, d_a, d_b, d_hit, d_hi, d_cnt, nullptr, ctx->d_stats, tmin, tmax, false, false, st);
-        (void)hipEventRecord(ctx->ev_b, st);
-        ptw_launch_hits_to_api(d_hit, pl.bvh8 ? s->d_tri4_8 : s->d_tri4, s->n_inst ? d_hi : nullptr, s->d_tlas_prim_of, n, d_out, st);
-        (void)hipMemcpyAsync(hits, d_out, sizeof(pt_hit) * n, hipMemcpyDeviceToHost, st);
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) fail(e, "pt_trace");
-        else if ((e = hipGetLastError()) != hipSuccess) fail(e, "pt_trace");
-        float ms = 0.f;
-        if (ret == PT_OK && hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b) == hipSuccess) ctx->stats.ms_extend += ms;
-        ctx->stats.launches_extend++;
-    }
-    (void)hipFree(d_a); (void)hipFree(d_b); (void)hipFree(d_hit); (void)hipFree(d_out); (void)hipFree(d_cnt); (void)hipFree(d_hi);
+    (void)hipMemcpyAsync(d_a, a.data(), sizeof(float4) * n, hipMemcpyHostToDevice, st);
+    (void)hipMemcpyAsync(d_b, b.data(), sizeof(float2) * n, hipMemcpyHostToDevice, st);
+    const uint32_t cnt_head[2] = { n, 0u };
+    (void)hipMemcpyAsync(d_cnt, cnt_head, sizeof(cnt_head), hipMemcpyHostToDevice, st);
+    (void)hipEventRecord(ctx->ev_a, st);
+    ptw_launch_extend(pl, s, d_a, d_b, d_hit, d_hi, d_cnt, nullptr, ctx->d_stats, tmin, tmax, false, false, st);
+    (void)hipEventRecord(ctx->ev_b, st);
+    ptw_launch_hits_to_api(d_hit, pl.bvh8 ? s->d_tri4_8 : s->d_tri4, s->n_inst ? d_hi : nullptr, s->d_tlas_prim_of, n, d_out, st);
+    (void)hipMemcpyAsync(hits, d_out, sizeof(pt_hit) * n, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { ctx->err = std::string("pt_trace: ") + hipGetErrorString(e); ret = PT_ERR_HIP; }
+    float ms = 0.f;
+    if (ret == PT_OK && hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b) == hipSuccess) ctx->stats.ms_extend += ms;
+    ctx->stats.launches_extend++;
+    pt_scratch_free(set, nullptr, 0);
     return ret;
 }

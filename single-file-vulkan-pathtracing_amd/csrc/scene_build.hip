@@ -121,15 +121,86 @@ __global__ __launch_bounds__(TB) void k_wide_half(const float4 *__restrict__ wid
     o[3] = make_uint4(__float_as_uint(cw.x), __float_as_uint(cw.y), __float_as_uint(cw.z), __float_as_uint(cw.w));
 }
 
+// ---- scene buffers ("Scene buffers") -------------------------------------------------------------------
+// Every device pointer of a scene, once, by lifetime.  d_wide is not among them: it is a view of d_wide_lbvh or d_wide_sah.
+std::vector<pt_buf> ptb_scene_buffers(pt_scene *s, pt_scene_life life)
+{
+    switch (life) {
+    case PT_LIFE_SOURCE:  // live as long as the scene: the kept triangles and materials, the per-triangle tables, the emitters
+        return { pt_buf_of(s->d_tri_orig), pt_buf_of(s->d_faces), pt_buf_of(s->d_tri4), pt_buf_of(s->d_shade4), pt_buf_of(s->d_shade64),
+                 pt_buf_of(s->d_ke4), pt_buf_of(s->d_frame4), pt_buf_of(s->d_lights) };
+    case PT_LIFE_TREE:  // everything that hangs off the binary tree: dropped and made again by a rebuild
+        return { pt_buf_of(s->d_nodes), pt_buf_of(s->d_keys), pt_buf_of(s->d_prim_of), pt_buf_of(s->d_prim_of_sah), pt_buf_of(s->d_wide_lbvh),
+                 pt_buf_of(s->d_wide_sah), pt_buf_of(s->d_wide16), pt_buf_of(s->d_wide16t), pt_buf_of(s->d_wide8), pt_buf_of(s->d_prim_of8),
+                 pt_buf_of(s->d_tri4_8), pt_buf_of(s->d_shade64_8), pt_buf_of(s->d_ke4_8) };
+    case PT_LIFE_INSTANCES:
+        return { pt_buf_of(s->d_inst6), pt_buf_of(s->d_tlas_wide), pt_buf_of(s->d_tlas_prim_of), pt_buf_of(s->d_tlas16), pt_buf_of(s->d_inst_frame),
+                 pt_buf_of(s->d_lights_inst) };
+    default:  // PT_LIFE_PREVIOUS
+        return { pt_buf_of(s->prev.d_tri), pt_buf_of(s->prev.d_xf) };
+    }
+}
+
+// tests: an allocation that is out of memory, without the memory (pt_tuning.fail_rebuild: a scene that has, or has lost, a tree)
+static pt_status injected_failure(pt_scene *s)
+{
+    pt_ctx *ctx = s->ctx;
+    if (!(ctx->tune.fail_rebuild > 0 && (s->broken || s->n_nodes))) return PT_OK;
+    ctx->tune.fail_rebuild--;
+    ctx->err = "hipMalloc: out of memory (pt_tuning.fail_rebuild)";
+    return PT_ERR_OOM;
+}
+
+pt_status ptb_scene_alloc(pt_scene *s, const char *what, const std::vector<pt_buf> &set)
+{
+    const pt_status inj = injected_failure(s);
+    if (inj != PT_OK) { pt_scratch_free(set, nullptr, 0); return inj; }  // (as the allocator leaves a set it could not give its memory)
+    return pt_scratch_alloc(s->ctx, what, set, nullptr, 0);
+}
+
+// A set and the host arrays that fill its first buffers: the set is present only when it is whole, a failed upload frees it again.
+static pt_status alloc_filled(pt_scene *s, const char *what, const std::vector<pt_buf> &set, std::initializer_list<const void *> sources)
+{
+    PT_TRY(ptb_scene_alloc(s, what, set));
+    size_t k = 0;
+    for (const void *src : sources) {
+        const hipError_t e = hipMemcpy(*set[k].p, src, set[k].bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            pt_scratch_free(set, nullptr, 0);
+            s->ctx->err = std::string("hipMemcpy to ") + what + ": " + hipGetErrorString(e);
+            return PT_ERR_HIP;
+        }
+        k++;
+    }
+    return PT_OK;
+}
+
+// leaf_pad() of the device build, same float operations
+static float leaf_pad_of(const float *bmin, const float *bmax)
+{
+    float scale = 0.f;
+    for (int k = 0; k < 3; k++) scale = fmaxf(scale, fmaxf(fabsf(bmin[k]), fabsf(bmax[k])));
+    return scale * 3.814697265625e-06f;
+}
+
+// pt_scene_info.device_bytes / device_bytes8, a formula of the counts and not a counter of allocations: they report what a scene of this
+// size keeps resident for traversal and rebuilds, the read-back arrays (d_keys, d_prim_of, d_nodes) and the lazily built tables left out.
+// BVH4 path: triangle tables (tri4 48 + shade4 48 + shade64 64 + ke4 16 + frames 32 B each), the kept source arrays a rebuild re-packs
+// from (d_tri_orig 48 + d_faces 24) + the 128-B and the two 64-B node arrays; the 8-wide path: its tables + nodes.
+static void set_device_bytes(pt_scene *s)
+{
+    const uint64_t n = s->n_tris;
+    s->device_bytes = n * (48 + 48 + 64 + 16 + 32 + PT_SOURCE_BYTES_PER_TRI) + 128ull * s->n_wide + 64ull * s->n_wide + 64ull * s->n_wide16t;
+    s->device_bytes8 = s->d_wide8 ? n * (48 + 64 + 16 + 4) + 64ull * s->n_wide8 : 0ull;
+}
+
 // (re)builds s->d_wide16 from the BVH4 that is currently traversed
 static pt_status make_wide16(pt_scene *s)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     ptb_norm_box(s->bmin, s->bmax, s->norm_c, s->norm_s, s->norm_rs);
-    (void)hipFree(s->d_wide16);
-    s->d_wide16 = nullptr;
-    PT_HIP(ctx, hipMalloc((void **)&s->d_wide16, 64 * (size_t)s->n_wide));
+    PT_TRY(ptb_scene_alloc(s, "the fp16 BVH4 nodes", { pt_buf_of(s->d_wide16, 64 * (size_t)s->n_wide) }));
     k_wide_half<<<(s->n_wide + TB - 1) / TB, TB, 0, st>>>(s->d_wide, s->n_wide, s->norm_c[0], s->norm_c[1], s->norm_c[2], s->norm_rs[0],
                                                          s->norm_rs[1], s->norm_rs[2], reinterpret_cast<uint4 *>(s->d_wide16));
     PT_HIP(ctx, hipStreamSynchronize(st));
@@ -153,13 +224,8 @@ __global__ __launch_bounds__(TB) void k_tri_boxes(const float4 *__restrict__ tri
 // leaf order -- built (or rebuilt: quality change, first request for the 8-wide nodes) from the kept triangles.
 static void free_tree_products(pt_scene *s)
 {
-    (void)hipFree(s->d_nodes); (void)hipFree(s->d_keys); (void)hipFree(s->d_prim_of); (void)hipFree(s->d_prim_of_sah);
-    (void)hipFree(s->d_wide_lbvh ? s->d_wide_lbvh : s->d_wide); (void)hipFree(s->d_wide_sah);
-    (void)hipFree(s->d_wide16); (void)hipFree(s->d_wide16t);
-    (void)hipFree(s->d_wide8); (void)hipFree(s->d_prim_of8); (void)hipFree(s->d_tri4_8); (void)hipFree(s->d_shade64_8); (void)hipFree(s->d_ke4_8);
-    s->d_nodes = nullptr; s->d_keys = nullptr; s->d_prim_of = s->d_prim_of_sah = nullptr;
-    s->d_wide = s->d_wide_lbvh = s->d_wide_sah = nullptr; s->d_wide16 = nullptr; s->d_wide16t = nullptr;
-    s->d_wide8 = nullptr; s->d_prim_of8 = nullptr; s->d_tri4_8 = s->d_shade64_8 = s->d_ke4_8 = nullptr;
+    pt_scratch_free(ptb_scene_buffers(s, PT_LIFE_TREE), nullptr, 0);
+    s->d_wide = nullptr;
     s->n_wide8 = s->levels8 = 0; s->n_wide16t = s->levels4t = 0;
 }
 
@@ -213,11 +279,7 @@ static pt_status build_tree_products_unguarded(pt_scene *s, uint32_t quality, bo
     hipStream_t st = ctx->stream;
     const uint32_t n = s->n_tris, gt = (n + TB - 1) / TB;
     free_tree_products(s);
-    if (ctx->tune.fail_rebuild > 0 && (s->broken || s->n_nodes)) {  // tests: an out-of-memory rebuild, without the memory
-        ctx->tune.fail_rebuild--;
-        ctx->err = "hipMalloc: out of memory (pt_tuning.fail_rebuild)";
-        return PT_ERR_OOM;
-    }
+    PT_TRY(injected_failure(s));
     DevBuf<float4> d_tlo, d_thi;
     PT_HIP(ctx, d_tlo.alloc(n));
     PT_HIP(ctx, d_thi.alloc(n));
@@ -225,31 +287,27 @@ static pt_status build_tree_products_unguarded(pt_scene *s, uint32_t quality, bo
     k_tri_boxes<<<gt, TB, 0, st>>>(s->d_tri_orig, n, d_tlo.p, d_thi.p);
     const bool ploc = quality == PT_BVH_PREFER_FAST_TRACE && n > PT_SAH_MAX_TRIS;
     BvhOut o;
-    pt_status rc = ptb_build_bvh(ctx, d_tlo.p, d_thi.p, n, PT_BLAS_LEAF_MAX, o, 2 | (want8 ? 1 : 0), ploc);
-    s->d_keys = o.d_keys; s->d_prim_of = o.d_prim_of; s->d_nodes = o.d_nodes; s->d_wide = o.d_wide;  // freed by pt_scene_destroy
-    s->d_prim_of_sah = o.d_prim_q;
-    s->d_wide8 = o.d_wide8; s->n_wide8 = o.n_wide8; s->levels8 = o.levels8;
-    s->d_wide16t = o.d_wide16t; s->n_wide16t = o.n_wide16t; s->levels4t = o.levels4t;
-    DevBuf<uint32_t> d_order8;
-    d_order8.p = o.d_order8;
-    s->d_wide_lbvh = s->d_wide;
-    if (rc != PT_OK) return rc;
+    PT_TRY(ptb_build_bvh(ctx, d_tlo.p, d_thi.p, n, PT_BLAS_LEAF_MAX, o, 2 | (want8 ? 1 : 0), ploc));
+    s->d_keys = o.d_keys.release(); s->d_prim_of = o.d_prim_of.release(); s->d_nodes = o.d_nodes.release();
+    s->d_wide = s->d_wide_lbvh = o.d_wide.release();
+    s->d_prim_of_sah = o.d_prim_q.release();
+    s->d_wide8 = o.d_wide8.release(); s->n_wide8 = o.n_wide8; s->levels8 = o.levels8;
+    s->d_wide16t = o.d_wide16t.release(); s->n_wide16t = o.n_wide16t; s->levels4t = o.levels4t;
     s->n_nodes = o.n_nodes; s->n_wide = o.n_wide; s->height = o.height; s->height_tree = o.height_tree; s->stack_need = o.stack_need;
     s->n_wide_lbvh = s->n_wide; s->stack_need_lbvh = s->stack_need;
     for (int k = 0; k < 3; k++) { s->bmin[k] = o.bmin[k]; s->bmax[k] = o.bmax[k]; }
-    s->bvh4_builder = o.d_prim_q ? 2u : 0u;
+    s->bvh4_builder = s->d_prim_of_sah ? 2u : 0u;
     s->area_lbvh = o.area_lbvh; s->area_ploc = o.area_ploc;
     s->pair_leaves = PT_BLAS_LEAF_MAX == 1u;
-    const uint32_t *order = o.d_prim_q ? o.d_prim_q : s->d_prim_of;   // the traversed leaf order
+    const uint32_t *order = s->d_prim_of_sah ? s->d_prim_of_sah : s->d_prim_of;   // the traversed leaf order
     k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, order, n, s->d_tri4, s->d_shade4, s->d_shade64, s->d_ke4, s->d_frame4);
     if (s->d_wide8) {  // the 8-wide tree's own triangle order: its per-triangle tables (the LDS-sized shade4 is never used with it)
-        PT_HIP(ctx, hipMalloc((void **)&s->d_prim_of8, sizeof(uint32_t) * (size_t)n));
-        PT_HIP(ctx, hipMalloc((void **)&s->d_tri4_8, sizeof(float4) * 3 * (size_t)n));
-        PT_HIP(ctx, hipMalloc((void **)&s->d_shade64_8, sizeof(float4) * 4 * (size_t)n));
-        PT_HIP(ctx, hipMalloc((void **)&s->d_ke4_8, sizeof(float4) * (size_t)n));
+        PT_TRY(ptb_scene_alloc(s, "the 8-wide tree's triangle tables",
+                               { pt_buf_of(s->d_prim_of8, sizeof(uint32_t) * (size_t)n), pt_buf_of(s->d_tri4_8, sizeof(float4) * 3 * (size_t)n),
+                                 pt_buf_of(s->d_shade64_8, sizeof(float4) * 4 * (size_t)n), pt_buf_of(s->d_ke4_8, sizeof(float4) * (size_t)n) }));
         DevBuf<float4> d_shade4_scratch;
         PT_HIP(ctx, d_shade4_scratch.alloc(3 * (size_t)n));
-        k_compose<<<gt, TB, 0, st>>>(d_order8.p, order, n, s->d_prim_of8);
+        k_compose<<<gt, TB, 0, st>>>(o.d_order8.p, order, n, s->d_prim_of8);
         k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, s->d_prim_of8, n, s->d_tri4_8, d_shade4_scratch.p, s->d_shade64_8, s->d_ke4_8);
         PT_HIP(ctx, hipStreamSynchronize(st));
     }
@@ -257,11 +315,7 @@ static pt_status build_tree_products_unguarded(pt_scene *s, uint32_t quality, bo
     PT_HIP(ctx, hipStreamSynchronize(st));
     PT_HIP(ctx, hipGetLastError());
     PT_HIP(ctx, hipEventElapsedTime(&s->build_ms, ctx->ev_a, ctx->ev_b));
-    // resident bytes of the BVH4 path: triangle tables (tri4 48 + shade4 48 + shade64 64 + ke4 16 + frames 32 B each), the kept
-    // source arrays a rebuild re-packs from (d_tri_orig 48 + d_faces 24) + the 128-B and the two 64-B node arrays; of the
-    // 8-wide path: its tables + nodes
-    s->device_bytes = (uint64_t)n * (48 + 48 + 64 + 16 + 32 + PT_SOURCE_BYTES_PER_TRI) + 128ull * s->n_wide + 64ull * s->n_wide + 64ull * s->n_wide16t;
-    s->device_bytes8 = s->d_wide8 ? (uint64_t)n * (48 + 64 + 16 + 4) + 64ull * s->n_wide8 : 0ull;
+    set_device_bytes(s);
     s->quality = quality;
     return make_wide16(s);
 }
@@ -313,41 +367,86 @@ static void find_fan_pairs(const float *h_vertices, const uint32_t *h_indices, u
     }
 }
 
+// The caller's vertices and indices on the device and, after gather(), the de-indexed triangles in d_tri_orig with their boxes here.
+struct GeometryUpload {
+    DevBuf<float> d_vert;
+    DevBuf<uint32_t> d_idx;
+    DevBuf<float4> d_tlo, d_thi;
+    pt_status upload(pt_ctx *ctx, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices, uint32_t n)
+    {
+        hipStream_t st = ctx->stream;
+        PT_HIP(ctx, d_vert.alloc(3 * (size_t)n_verts));
+        PT_HIP(ctx, d_idx.alloc(3 * (size_t)n));
+        PT_HIP(ctx, d_tlo.alloc(n));
+        PT_HIP(ctx, d_thi.alloc(n));
+        PT_HIP(ctx, hipMemcpyAsync(d_vert.p, h_vertices, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, st));
+        PT_HIP(ctx, hipMemcpyAsync(d_idx.p, h_indices, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+        PT_HIP(ctx, hipStreamSynchronize(st));  // pageable host sources are done with
+        return PT_OK;
+    }
+    void gather(pt_scene *s)
+    {
+        k_gather<<<(s->n_tris + TB - 1) / TB, TB, 0, s->ctx->stream>>>(d_vert.p, d_idx.p, s->n_tris, s->d_tri_orig, d_tlo.p, d_thi.p);
+    }
+};
+
+// small scenes: the unpadded triangle boxes a build of the surface-area BVH4 reads, from the device's (gather())
+static pt_status keep_host_boxes(pt_scene *s, const float4 *d_tlo, const float4 *d_thi)
+{
+    pt_ctx *ctx = s->ctx;
+    const uint32_t n = s->n_tris;
+    std::vector<float4> lo(n), hi(n);
+    PT_HIP(ctx, hipMemcpyAsync(lo.data(), d_tlo, sizeof(float4) * n, hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipMemcpyAsync(hi.data(), d_thi, sizeof(float4) * n, hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->h_tlo.resize(3 * (size_t)n);
+    s->h_thi.resize(3 * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        s->h_tlo[3 * i + 0] = lo[i].x; s->h_tlo[3 * i + 1] = lo[i].y; s->h_tlo[3 * i + 2] = lo[i].z;
+        s->h_thi[3 * i + 0] = hi[i].x; s->h_thi[3 * i + 1] = hi[i].y; s->h_thi[3 * i + 2] = hi[i].z;
+    }
+    return PT_OK;
+}
+
+// The tree products as pt_scene_create and a REBUILD make them.  Big scenes: one build at `quality`.  Small scenes: the LBVH, then the
+// BVH4 of `quality` on top of it (ePreferFastTrace: the exact surface-area BVH4), build_ms the two device times added.
+static pt_status build_at_quality(pt_scene *s, uint32_t quality, bool want8)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const bool small = s->n_tris <= PT_SAH_MAX_TRIS;
+    PT_TRY(build_tree_products(s, small ? PT_BVH_PREFER_FAST_TRACE : quality, want8));
+    if (!small) return PT_OK;
+    const float lbvh_ms = s->build_ms;
+    float sah_ms = 0.f;
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    PT_TRY(ptb_set_bvh_quality(s, quality));
+    s->quality = quality;  // (FAST_BUILD: the LBVH just built is already the traversed tree)
+    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipEventElapsedTime(&sah_ms, ctx->ev_a, ctx->ev_b));
+    s->build_ms = lbvh_ms + sah_ms;
+    return PT_OK;
+}
+
 pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices,
                           uint32_t n_tris, const float *h_faces)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     const uint32_t n = n_tris;
-    const uint32_t gt = (n + TB - 1) / TB;
-    DevBuf<float> d_vert;
-    DevBuf<uint32_t> d_idx;
-    DevBuf<float4> d_tlo, d_thi;
-    PT_HIP(ctx, d_vert.alloc(3 * (size_t)n_verts));
-    PT_HIP(ctx, d_idx.alloc(3 * (size_t)n));
-    PT_HIP(ctx, d_tlo.alloc(n));
-    PT_HIP(ctx, d_thi.alloc(n));
     s->n_tris = n;
     // the de-indexed triangles and the per-face materials stay resident (72 B per triangle): a change of the BVH quality,
     // or the first request for the 8-wide nodes, re-packs the tables from them in another leaf order
-    PT_HIP(ctx, hipMalloc((void **)&s->d_tri_orig, sizeof(float4) * 3 * (size_t)n));
-    PT_HIP(ctx, hipMalloc((void **)&s->d_faces, sizeof(float) * 6 * (size_t)n));
-    PT_HIP(ctx, hipMalloc((void **)&s->d_tri4, sizeof(float4) * 3 * (size_t)n));
-    PT_HIP(ctx, hipMalloc((void **)&s->d_shade4, sizeof(float4) * 3 * (size_t)n));
-    PT_HIP(ctx, hipMalloc((void **)&s->d_shade64, sizeof(float4) * 4 * (size_t)n));
-    PT_HIP(ctx, hipMalloc((void **)&s->d_ke4, sizeof(float4) * (size_t)n));
-    PT_HIP(ctx, hipMalloc((void **)&s->d_frame4, sizeof(float4) * 2 * (size_t)n));
-    PT_HIP(ctx, hipMemcpyAsync(d_vert.p, h_vertices, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, st));
-    PT_HIP(ctx, hipMemcpyAsync(d_idx.p, h_indices, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+    PT_TRY(ptb_scene_alloc(s, "the scene's triangle tables",
+                           { pt_buf_of(s->d_tri_orig, sizeof(float4) * 3 * (size_t)n), pt_buf_of(s->d_faces, sizeof(float) * 6 * (size_t)n),
+                             pt_buf_of(s->d_tri4, sizeof(float4) * 3 * (size_t)n), pt_buf_of(s->d_shade4, sizeof(float4) * 3 * (size_t)n),
+                             pt_buf_of(s->d_shade64, sizeof(float4) * 4 * (size_t)n), pt_buf_of(s->d_ke4, sizeof(float4) * (size_t)n),
+                             pt_buf_of(s->d_frame4, sizeof(float4) * 2 * (size_t)n) }));
     PT_HIP(ctx, hipMemcpyAsync(s->d_faces, h_faces, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, st));
-    PT_HIP(ctx, hipStreamSynchronize(st));  // pageable host sources are done with
-    k_gather<<<gt, TB, 0, st>>>(d_vert.p, d_idx.p, n, s->d_tri_orig, d_tlo.p, d_thi.p);
-    // the tree of the default quality (ePreferFastTrace, main.cpp:419): PLOC for big scenes; small scenes get the LBVH
-    // here and the exact surface-area BVH4 below.  The 8-wide nodes only when the context asks AUTO to use them.
-    // (small scenes get the 8-wide nodes at once -- a few KB; big ones on first request: 260 B per triangle nobody else needs)
-    // ... and scenes AUTO walks through them: more than 1 MiB of BVH4 nodes + records, ~96 B per triangle (extend_launch.hip ptw_plan_extend)
-    pt_status rc = build_tree_products(s, PT_BVH_PREFER_FAST_TRACE, ctx->tune.hbm8 == 1 || n <= PT_SAH_MAX_TRIS || (ctx->tune.hbm8 != 0 && 96ull * n > (1ull << 20)));
-    if (rc != PT_OK) return rc;
+    GeometryUpload up;
+    PT_TRY(up.upload(ctx, h_vertices, n_verts, h_indices, n));
+    up.gather(s);
     {   // emitters for the NEE pipeline (push_emitter), and which primitives they are (pt_scene_update recomputes them)
         std::vector<float4> lights;
         float run = 0.f;
@@ -363,35 +462,17 @@ pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts
         s->n_lights = (uint32_t)(lights.size() / 5);
         s->light_area = run;
         s->h_lights = lights;
-        if (s->n_lights) {
-            PT_HIP(ctx, hipMalloc((void **)&s->d_lights, sizeof(float4) * lights.size()));
-            PT_HIP(ctx, hipMemcpy(s->d_lights, lights.data(), sizeof(float4) * lights.size(), hipMemcpyHostToDevice));
-        }
+        if (s->n_lights) PT_TRY(alloc_filled(s, "the emitter table", { pt_buf_of(s->d_lights, sizeof(float4) * lights.size()) }, { lights.data() }));
     }
-    if (n <= PT_SAH_MAX_TRIS) {
-        // small scene: keep what a rebuild of the BVH4 in another leaf order needs, then apply the default
-        // quality (ePreferFastTrace, main.cpp:419)
-        std::vector<float4> lo(n), hi(n);
-        PT_HIP(ctx, hipMemcpy(lo.data(), d_tlo.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
-        PT_HIP(ctx, hipMemcpy(hi.data(), d_thi.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
-        s->h_tlo.resize(3 * (size_t)n);
-        s->h_thi.resize(3 * (size_t)n);
-        for (uint32_t i = 0; i < n; i++) {
-            s->h_tlo[3 * i + 0] = lo[i].x; s->h_tlo[3 * i + 1] = lo[i].y; s->h_tlo[3 * i + 2] = lo[i].z;
-            s->h_thi[3 * i + 0] = hi[i].x; s->h_thi[3 * i + 1] = hi[i].y; s->h_thi[3 * i + 2] = hi[i].z;
-        }
+    if (n <= PT_SAH_MAX_TRIS) {  // small scene: keep what a build of the surface-area BVH4 reads
+        PT_TRY(keep_host_boxes(s, up.d_tlo.p, up.d_thi.p));
         find_fan_pairs(h_vertices, h_indices, n, s->h_pair);
-        const float lbvh_ms = s->build_ms;
-        PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-        const pt_status q = ptb_set_bvh_quality(s, PT_BVH_PREFER_FAST_TRACE);
-        if (q != PT_OK) return q;
-        PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-        PT_HIP(ctx, hipStreamSynchronize(st));
-        float sah_ms = 0.f;
-        PT_HIP(ctx, hipEventElapsedTime(&sah_ms, ctx->ev_a, ctx->ev_b));
-        s->build_ms = lbvh_ms + sah_ms;
     }
-    return PT_OK;
+    // the tree of the default quality (ePreferFastTrace, main.cpp:419): PLOC for big scenes; small scenes get the LBVH and the exact
+    // surface-area BVH4 on top.  The 8-wide nodes only when the context asks AUTO to use them.
+    // (small scenes get the 8-wide nodes at once -- a few KB; big ones on first request: 260 B per triangle nobody else needs)
+    // ... and scenes AUTO walks through them: more than 1 MiB of BVH4 nodes + records, ~96 B per triangle (extend_launch.hip ptw_plan_extend)
+    return build_at_quality(s, PT_BVH_PREFER_FAST_TRACE, ctx->tune.hbm8 == 1 || n <= PT_SAH_MAX_TRIS || (ctx->tune.hbm8 != 0 && 96ull * n > (1ull << 20)));
 }
 
 // Chooses the BVH4 that is traversed (pt_internal.h).  Re-packs the per-triangle tables in its leaf order.
@@ -415,9 +496,7 @@ pt_status ptb_set_bvh_quality(pt_scene *s, uint32_t quality)
     hipStream_t st = ctx->stream;
     const uint32_t n = s->n_tris;
     if (want_sah && !s->d_wide_sah) {
-        float scale = 0.f;  // leaf_pad() of the device build, same float operations
-        for (int k = 0; k < 3; k++) scale = fmaxf(scale, fmaxf(fabsf(s->bmin[k]), fabsf(s->bmax[k])));
-        const float pad = scale * 3.814697265625e-06f;
+        const float pad = leaf_pad_of(s->bmin, s->bmax);
         std::vector<uint32_t> rows, order;
         // one primitive per leaf, a primitive being a triangle or a quad's two halves (pt_tuning.pair_leaves = 0: the former
         // rule, up to PT_SAH_LEAF_MAX independent triangles per leaf where splitting does not pay); built on the device
@@ -425,14 +504,13 @@ pt_status ptb_set_bvh_quality(pt_scene *s, uint32_t quality)
         const pt_status rc8 = pt_sah_build_bvh4_device(ctx, s->h_tlo.data(), s->h_thi.data(), n, pairs ? s->h_pair.data() : nullptr, pad,
                                                        pairs ? 1u : PT_SAH_LEAF_MAX, rows, order);
         if (rc8 != PT_OK) return rc8;
-        s->sah_pair_leaves = pairs;
         if (order.size() != n || rows.empty()) { ctx->err = "internal: SAH build lost triangles"; return PT_ERR_HIP; }
+        // (the scene has the surface-area tree from here on, or nothing of it)
+        PT_TRY(alloc_filled(s, "the surface-area BVH4", { pt_buf_of(s->d_wide_sah, rows.size() * sizeof(uint32_t)), pt_buf_of(s->d_prim_of_sah, sizeof(uint32_t) * n) },
+                            { rows.data(), order.data() }));
+        s->sah_pair_leaves = pairs;
         s->n_wide_sah = (uint32_t)(rows.size() / 32);
         s->stack_need_sah = pt_wide_stack_need(rows);
-        PT_HIP(ctx, hipMalloc((void **)&s->d_wide_sah, rows.size() * sizeof(uint32_t)));
-        PT_HIP(ctx, hipMalloc((void **)&s->d_prim_of_sah, sizeof(uint32_t) * n));
-        PT_HIP(ctx, hipMemcpy(s->d_wide_sah, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        PT_HIP(ctx, hipMemcpy(s->d_prim_of_sah, order.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     }
     PT_HIP(ctx, hipStreamSynchronize(st));  // nothing may still be traversing the old tables
     if (want_sah) {
@@ -446,31 +524,19 @@ pt_status ptb_set_bvh_quality(pt_scene *s, uint32_t quality)
                                            s->d_shade4, s->d_shade64, s->d_ke4, s->d_frame4);
     PT_HIP(ctx, hipStreamSynchronize(st));
     PT_HIP(ctx, hipGetLastError());
-    (void)hipFree(s->d_inst_frame);  // (the triangle order changed: ptb_ensure_inst_frames builds it again on the next render)
-    s->d_inst_frame = nullptr;
-    s->device_bytes = (uint64_t)n * (48 + 48 + 64 + 16 + 32 + PT_SOURCE_BYTES_PER_TRI) + 128ull * s->n_wide + 64ull * s->n_wide + 64ull * s->n_wide16t;
+    pt_scratch_free({ pt_buf_of(s->d_inst_frame) }, nullptr, 0);  // (the triangle order changed: ptb_ensure_inst_frames builds it again on the next render)
+    set_device_bytes(s);
     s->quality = quality;
-    return make_wide16(s);
+    const pt_status rc = make_wide16(s);
+    if (rc != PT_OK) mark_broken(s, quality);  // the tables are the new tree's and its fp16 nodes are missing: nothing to traverse until a repair
+    return rc;
 }
 
 void ptb_free_scene_buffers(pt_scene *s)
 {
-    (void)hipFree(s->d_tri4); (void)hipFree(s->d_shade4); (void)hipFree(s->d_nodes);
-    (void)hipFree(s->d_shade64); (void)hipFree(s->d_ke4); (void)hipFree(s->d_frame4);
-    s->d_shade64 = s->d_ke4 = s->d_frame4 = nullptr;
-    (void)hipFree(s->d_wide_lbvh ? s->d_wide_lbvh : s->d_wide);  // d_wide aliases d_wide_lbvh or d_wide_sah
-    (void)hipFree(s->d_wide_sah); (void)hipFree(s->d_prim_of_sah);
-    (void)hipFree(s->d_keys); (void)hipFree(s->d_prim_of);
-    (void)hipFree(s->d_tri_orig); (void)hipFree(s->d_faces); (void)hipFree(s->d_wide16);
-    s->d_wide16 = nullptr;
-    (void)hipFree(s->d_wide16t);
-    s->d_wide16t = nullptr;
-    (void)hipFree(s->d_lights);
-    s->d_lights = nullptr; s->n_lights = 0;
-    (void)hipFree(s->d_wide8); (void)hipFree(s->d_prim_of8); (void)hipFree(s->d_tri4_8); (void)hipFree(s->d_shade64_8); (void)hipFree(s->d_ke4_8);
-    s->d_wide8 = nullptr; s->d_prim_of8 = nullptr; s->d_tri4_8 = s->d_shade64_8 = s->d_ke4_8 = nullptr;
-    s->d_tri4 = s->d_shade4 = s->d_nodes = s->d_wide = s->d_wide_lbvh = s->d_wide_sah = s->d_tri_orig = nullptr;
-    s->d_prim_of_sah = s->d_prim_of = nullptr; s->d_keys = nullptr; s->d_faces = nullptr;
+    free_tree_products(s);
+    pt_scratch_free(ptb_scene_buffers(s, PT_LIFE_SOURCE), nullptr, 0);
+    s->n_lights = 0;
 }
 
 // ---- instances: TLAS over world boxes of the transformed BLAS root box --------------------------
@@ -558,7 +624,7 @@ pt_status ptb_ensure_inst_frames(pt_scene *s)
     if (!s->n_inst || s->d_inst_frame) return PT_OK;
     const size_t entries = (size_t)s->n_inst * s->n_tris;
     if (entries * 32 > (512ull << 20)) return PT_OK;  // (a table beyond the caches would cost more than it saves: the per-hit transform stays)
-    PT_HIP(ctx, hipMalloc((void **)&s->d_inst_frame, 32 * entries));
+    PT_TRY(ptb_scene_alloc(s, "the instances' frame table", { pt_buf_of(s->d_inst_frame, 32 * entries) }));
     k_inst_frames<<<(unsigned)((entries + TB - 1) / TB), TB, 0, ctx->stream>>>(s->d_inst6, s->d_shade4, s->n_inst, s->n_tris, s->d_inst_frame);
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     PT_HIP(ctx, hipGetLastError());
@@ -592,25 +658,10 @@ pt_status ptb_ensure_inst_lights(pt_scene *s)
                 const float4 v = s->h_lights[5 * (size_t)k + c];
                 for (int r = 0; r < 3; r++) w[c][r] = ((m[4 * r] * v.x + m[4 * r + 1] * v.y) + m[4 * r + 2] * v.z) + m[4 * r + 3];
             }
-            const float e1[3] = { w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2] }, e2[3] = { w[2][0] - w[0][0], w[2][1] - w[0][1], w[2][2] - w[0][2] };
-            const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-            const float len = sqrtf((cx * cx + cy * cy) + cz * cz);
-            run = run + 0.5f * len;
-            wl.push_back(make_float4(w[0][0], w[0][1], w[0][2], run));
-            wl.push_back(make_float4(w[1][0], w[1][1], w[1][2], 0.f));
-            wl.push_back(make_float4(w[2][0], w[2][1], w[2][2], 0.f));
-            wl.push_back(make_float4(-(cx / len), -(cy / len), -(cz / len), 0.f));
-            wl.push_back(s->h_lights[5 * (size_t)k + 4]);
+            push_emitter(w[0], w[1], w[2], s->h_lights[5 * (size_t)k + 4], run, wl);
         }
     }
-    const hipError_t e = hipMalloc((void **)&s->d_lights_inst, sizeof(float4) * wl.size());
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        s->d_lights_inst = nullptr;
-        ctx->err = std::string("hipMalloc of the instanced emitter table: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? PT_ERR_OOM : PT_ERR_HIP;
-    }
-    PT_HIP(ctx, hipMemcpy(s->d_lights_inst, wl.data(), sizeof(float4) * wl.size(), hipMemcpyHostToDevice));
+    PT_TRY(alloc_filled(s, "the instanced emitter table", { pt_buf_of(s->d_lights_inst, sizeof(float4) * wl.size()) }, { wl.data() }));
     s->n_lights_inst = (uint32_t)copies;
     s->light_area_inst = run;
     return PT_OK;
@@ -620,12 +671,9 @@ void ptb_free_instances(pt_scene *s)
 {
     s->h_xforms.clear();
     s->h_xforms.shrink_to_fit();
-    (void)hipFree(s->d_inst_frame);
-    s->d_inst_frame = nullptr;
-    (void)hipFree(s->d_lights_inst);
-    s->d_lights_inst = nullptr; s->n_lights_inst = 0; s->light_area_inst = 0.f;
-    (void)hipFree(s->d_inst6); (void)hipFree(s->d_tlas_wide); (void)hipFree(s->d_tlas_prim_of); (void)hipFree(s->d_tlas16);
-    s->d_inst6 = nullptr; s->d_tlas_wide = nullptr; s->d_tlas_prim_of = nullptr; s->d_tlas16 = nullptr; s->n_tlas16 = 0;
+    pt_scratch_free(ptb_scene_buffers(s, PT_LIFE_INSTANCES), nullptr, 0);
+    s->n_lights_inst = 0; s->light_area_inst = 0.f;
+    s->n_tlas16 = 0;
     s->n_inst = 0; s->n_tlas_wide = 0; s->tlas_height = 0;
 }
 
@@ -651,7 +699,8 @@ pt_status ptb_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n)
                 return PT_ERR_INVALID_ARG;
             }
     }
-    DevBuf<float4> d_in, d_tlo, d_thi;
+    // nothing hangs on the scene before the whole set -- the TLAS and the sorted matrices -- exists: a failure leaves it single-level
+    DevBuf<float4> d_in, d_tlo, d_thi, d_inst6;
     PT_HIP(ctx, d_in.alloc(6 * (size_t)n));
     PT_HIP(ctx, d_tlo.alloc(n));
     PT_HIP(ctx, d_thi.alloc(n));
@@ -661,24 +710,26 @@ pt_status ptb_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n)
     BvhOut o;
     // (n < 32768: also the top-down 64-B TLAS with 16-bit child codes that k_extend_inst16 walks)
     // (pt_tuning.tlas_ploc = 1: the TLAS's binary tree by PLOC, as for big single-level scenes; kept under the same area rule)
-    pt_status rc = ptb_build_bvh(ctx, d_tlo.p, d_thi.p, n, PT_TLAS_LEAF_MAX, o, (n > 1 && n < 32768u && PT_TLAS_LEAF_MAX == 1u) ? 6 : 0,
-                                 ctx->tune.tlas_ploc == 1 && n > 2);
-    (void)hipFree(o.d_keys);
-    (void)hipFree(o.d_nodes);
-    s->d_tlas_wide = o.d_wide;
-    if (o.d_prim_q) { (void)hipFree(o.d_prim_of); s->d_tlas_prim_of = o.d_prim_q; }   // the leaf order of the tree that is walked
-    else s->d_tlas_prim_of = o.d_prim_of;
-    s->tlas_area_lbvh = o.area_lbvh; s->tlas_area_ploc = o.area_ploc;
-    s->d_tlas16 = o.d_wide16t; s->n_tlas16 = o.n_wide16t; s->tlas16_levels = o.levels4t;
-    for (int k = 0; k < 3; k++) { s->tlas_norm_c[k] = o.norm_c[k]; s->tlas_norm_s[k] = o.norm_s[k]; s->tlas_norm_rs[k] = o.norm_rs[k]; }
-    for (int k = 0; k < 3; k++) { s->tlas_bmin[k] = o.bmin[k]; s->tlas_bmax[k] = o.bmax[k]; }
-    if (rc != PT_OK) { ptb_free_instances(s); return rc; }
-    PT_HIP(ctx, hipMalloc((void **)&s->d_inst6, sizeof(float4) * 6 * (size_t)n));
-    // (the emitters' world-space copies for the NEE pipeline are made on that pipeline's first render: ptb_ensure_inst_lights)
-    s->h_xforms.assign(xforms3x4, xforms3x4 + 12 * (size_t)n);
-    k_inst_sort<<<g, TB, 0, st>>>(d_in.p, s->d_tlas_prim_of, n, s->d_inst6);
+    PT_TRY(ptb_build_bvh(ctx, d_tlo.p, d_thi.p, n, PT_TLAS_LEAF_MAX, o, (n > 1 && n < 32768u && PT_TLAS_LEAF_MAX == 1u) ? 6 : 0,
+                         ctx->tune.tlas_ploc == 1 && n > 2));
+    // (a TLAS has no read-back.  Its keys and binary nodes go BEFORE the sorted matrices are allocated: with the matrices allocated first
+    // the call measured 1.13-1.24 ms instead of 0.91-1.07 for 10 000 instances, profiles/scene_buffers_refactor_ab.json)
+    o.d_keys.free();
+    o.d_nodes.free();
+    DevBuf<uint32_t> &prim_of = o.d_prim_q.p ? o.d_prim_q : o.d_prim_of;   // the leaf order of the tree that is walked
+    PT_TRY(ptb_scene_alloc(s, "the instance matrices", { pt_buf_of(d_inst6.p, sizeof(float4) * 6 * (size_t)n) }));
+    k_inst_sort<<<g, TB, 0, st>>>(d_in.p, prim_of.p, n, d_inst6.p);
     PT_HIP(ctx, hipStreamSynchronize(st));
     PT_HIP(ctx, hipGetLastError());
+    s->d_tlas_wide = o.d_wide.release();
+    s->d_tlas_prim_of = prim_of.release();
+    s->d_tlas16 = o.d_wide16t.release(); s->n_tlas16 = o.n_wide16t; s->tlas16_levels = o.levels4t;
+    s->d_inst6 = d_inst6.release();
+    s->tlas_area_lbvh = o.area_lbvh; s->tlas_area_ploc = o.area_ploc;
+    for (int k = 0; k < 3; k++) { s->tlas_norm_c[k] = o.norm_c[k]; s->tlas_norm_s[k] = o.norm_s[k]; s->tlas_norm_rs[k] = o.norm_rs[k]; }
+    for (int k = 0; k < 3; k++) { s->tlas_bmin[k] = o.bmin[k]; s->tlas_bmax[k] = o.bmax[k]; }
+    // (the emitters' world-space copies for the NEE pipeline are made on that pipeline's first render: ptb_ensure_inst_lights)
+    s->h_xforms.assign(xforms3x4, xforms3x4 + 12 * (size_t)n);
     s->n_inst = n;
     s->n_tlas_wide = o.n_wide;
     s->tlas_height = std::max(o.height, o.height_tree);  // (of the tree the TLAS was collapsed from: the stack bound)
@@ -702,9 +753,7 @@ static pt_status refit_tree_products(pt_scene *s, const float4 *d_tlo, const flo
     if (rc != PT_OK) return rc;
     s->area_lbvh = area;
     ptb_norm_box(s->bmin, s->bmax, s->norm_c, s->norm_s, s->norm_rs);
-    float scale = 0.f;  // leaf_pad() of the device build, same float operations
-    for (int k = 0; k < 3; k++) scale = fmaxf(scale, fmaxf(fabsf(s->bmin[k]), fabsf(s->bmax[k])));
-    const float pad = scale * 3.814697265625e-06f;
+    const float pad = leaf_pad_of(s->bmin, s->bmax);
     // leaf positions of the binary tree the collapses ran on: the PLOC tree's (builder 2), else the LBVH's
     const uint32_t *kept = s->bvh4_builder == 2u ? s->d_prim_of_sah : s->d_prim_of;
     rc = ptb_refit_wide(ctx, 0, s->d_wide_lbvh, s->n_wide_lbvh, d_tlo, d_thi, kept, n, pad, s->norm_c, s->norm_rs);
@@ -726,31 +775,13 @@ static pt_status refit_tree_products(pt_scene *s, const float4 *d_tlo, const flo
     return PT_OK;
 }
 
-static void keep_host_boxes(pt_scene *s, const std::vector<float4> &lo, const std::vector<float4> &hi)
-{
-    const uint32_t n = s->n_tris;
-    s->h_tlo.resize(3 * (size_t)n);
-    s->h_thi.resize(3 * (size_t)n);
-    for (uint32_t i = 0; i < n; i++) {
-        s->h_tlo[3 * i + 0] = lo[i].x; s->h_tlo[3 * i + 1] = lo[i].y; s->h_tlo[3 * i + 2] = lo[i].z;
-        s->h_thi[3 * i + 0] = hi[i].x; s->h_thi[3 * i + 1] = hi[i].y; s->h_thi[3 * i + 2] = hi[i].z;
-    }
-}
-
 static pt_status update_tree_products(pt_scene *s, const float4 *d_tlo, const float4 *d_thi, bool refit)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
-    const uint32_t n = s->n_tris;
-    const bool small = n <= PT_SAH_MAX_TRIS;
+    const bool small = s->n_tris <= PT_SAH_MAX_TRIS;
     if (s->n_lights) PT_HIP(ctx, hipMemcpyAsync(s->d_lights, s->h_lights.data(), sizeof(float4) * s->h_lights.size(), hipMemcpyHostToDevice, st));
-    if (small) {  // the unpadded boxes a later surface-area build reads
-        std::vector<float4> lo(n), hi(n);
-        PT_HIP(ctx, hipMemcpyAsync(lo.data(), d_tlo, sizeof(float4) * n, hipMemcpyDeviceToHost, st));
-        PT_HIP(ctx, hipMemcpyAsync(hi.data(), d_thi, sizeof(float4) * n, hipMemcpyDeviceToHost, st));
-        PT_HIP(ctx, hipStreamSynchronize(st));
-        keep_host_boxes(s, lo, hi);
-    }
+    if (small) PT_TRY(keep_host_boxes(s, d_tlo, d_thi));
     if (refit) {
         const pt_status rc = refit_tree_products(s, d_tlo, d_thi);
         if (rc != PT_OK) return rc;
@@ -760,28 +791,14 @@ static pt_status update_tree_products(pt_scene *s, const float4 *d_tlo, const fl
         return PT_OK;
     }
     // REBUILD (or a refit that cannot keep its pair leaves): what pt_scene_create builds, at the scene's quality
-    const uint32_t quality = s->quality;
-    const bool want8 = small || s->d_wide8 != nullptr || ctx->tune.hbm8 == 1;
-    pt_status rc = build_tree_products(s, small ? PT_BVH_PREFER_FAST_TRACE : quality, want8);
-    if (rc != PT_OK || !small) return rc;
-    const float lbvh_ms = s->build_ms;
-    float sah_ms = 0.f;
-    PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    rc = ptb_set_bvh_quality(s, quality);
-    if (rc != PT_OK) return rc;
-    s->quality = quality;  // (FAST_BUILD: the LBVH just built is already the traversed tree)
-    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-    PT_HIP(ctx, hipStreamSynchronize(st));
-    PT_HIP(ctx, hipEventElapsedTime(&sah_ms, ctx->ev_a, ctx->ev_b));
-    s->build_ms = lbvh_ms + sah_ms;
-    return PT_OK;
+    return build_at_quality(s, s->quality, small || s->d_wide8 != nullptr || ctx->tune.hbm8 == 1);
 }
 
 pt_status ptb_update_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices, uint32_t mode)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
-    const uint32_t n = s->n_tris, gt = (n + TB - 1) / TB;
+    const uint32_t n = s->n_tris;
     const bool small = n <= PT_SAH_MAX_TRIS;
     PT_HIP(ctx, hipStreamSynchronize(st));  // after whatever is queued on the scene (a PT_FLAG_ASYNC render included)
     // host-side products first: until the triangles are overwritten below, a failure leaves the scene as it was
@@ -798,28 +815,20 @@ pt_status ptb_update_scene(pt_scene *s, const float *h_vertices, uint32_t n_vert
     for (uint32_t i = 0; i < s->h_pair.size() && i < pair.size(); i++)
         if (s->h_pair[i] && !pair[i]) pairs_hold = false;
     const bool refit = mode == PT_SCENE_UPDATE_REFIT && !s->broken && (pairs_hold || !s->d_wide_sah || !s->sah_pair_leaves);
-    DevBuf<float> d_vert;
-    DevBuf<uint32_t> d_idx;
-    DevBuf<float4> d_tlo, d_thi;
-    PT_HIP(ctx, d_vert.alloc(3 * (size_t)n_verts));
-    PT_HIP(ctx, d_idx.alloc(3 * (size_t)n));
-    PT_HIP(ctx, d_tlo.alloc(n));
-    PT_HIP(ctx, d_thi.alloc(n));
-    PT_HIP(ctx, hipMemcpyAsync(d_vert.p, h_vertices, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, st));
-    PT_HIP(ctx, hipMemcpyAsync(d_idx.p, h_indices, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-    PT_HIP(ctx, hipStreamSynchronize(st));  // pageable host sources are done with
+    GeometryUpload up;
+    PT_TRY(up.upload(ctx, h_vertices, n_verts, h_indices, n));
     PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
     // from here on the scene holds the new triangles: a failure marks it broken (the repair builds from them, never from a mix)
     const uint32_t quality = s->quality;
     const std::vector<float> xforms = s->h_xforms;  // the instance set -- or the one an earlier failed update parked (restore_parked_instances)
     const uint32_t n_inst = (uint32_t)(xforms.size() / 12);
     if (n_inst) ptb_free_instances(s);  // the TLAS, the instances' frames and emitters are made again from the new BLAS below
-    k_gather<<<gt, TB, 0, st>>>(d_vert.p, d_idx.p, n, s->d_tri_orig, d_tlo.p, d_thi.p);
+    up.gather(s);
     // the fan-pair relation a later surface-area build reads: the new arrays' (a pair-leaf tree the refit keeps has only pairs that still hold)
     if (small) s->h_pair = pair;
     s->h_lights = lights;
     s->light_area = run;
-    const pt_status rc = update_tree_products(s, d_tlo.p, d_thi.p, refit);
+    const pt_status rc = update_tree_products(s, up.d_tlo.p, up.d_thi.p, refit);
     if (rc != PT_OK) mark_broken(s, quality);
     if (n_inst) s->h_xforms = xforms;  // parked: set again below, or by the next successful build of the broken scene
     if (rc != PT_OK) return rc;
