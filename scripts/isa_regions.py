@@ -129,8 +129,21 @@ def slow_divide_lines(path):
     return out
 
 
+def function_lines(path, start_re):
+    """(first, last) line of a function or struct of extend_kernel.h whose closing brace stands at the start of a line"""
+    src = open(path).read().splitlines()
+    a = next(i for i, l in enumerate(src, 1) if re.search(start_re, l))
+    b = next(i for i, l in enumerate(src, 1) if i > a and l.startswith("}"))
+    # (the range must be one definition: no second function or struct opens at column 0 inside it, and it is a few dozen lines)
+    if b - a > 60 or any(re.match(r"^(template|struct|__device__|inline|namespace)\b", l) for l in src[a:b - 1]):
+        sys.exit(f"isa_regions: {start_re!r} in {os.path.basename(path)} does not end where expected (lines {a}..{b})")
+    return a, b
+
+
 def classify(body, files, reg_fused, reg_pair, slow_lines=frozenset()):
     """-> {block: Counter(valu, salu, lds, vmem)}, list of basic blocks [(label, majority, n_valu)]"""
+    slab = function_lines(os.path.join(CSRC, "extend_kernel.h"), r"void slab_setup\(")
+    lane_stack = function_lines(os.path.join(CSRC, "extend_kernel.h"), r"^struct LaneStack")
     bbs = [["entry", [], False]]
     cur_loc = None
     for l in body:
@@ -151,7 +164,8 @@ def classify(body, files, reg_fused, reg_pair, slow_lines=frozenset()):
             if f == "fused_kernel.h":
                 blk = reg_fused.get(cur_loc[1])
             elif f == "extend_kernel.h":
-                blk = "NODE" if cur_loc[1] < 132 or cur_loc[1] > 139 else None   # (slab_setup is called from the ray set-up)
+                # (slab_setup is called from the ray set-up, LaneStack's methods from the node step, both pop loops and the shade block)
+                blk = None if slab[0] <= cur_loc[1] <= slab[1] or lane_stack[0] <= cur_loc[1] <= lane_stack[1] else "NODE"
             elif f == "pair_leaf.h":
                 blk = reg_pair.get(cur_loc[1])
         slow = bool(cur_loc) and files.get(cur_loc[0], "") == "pt_math.h" and cur_loc[1] in slow_lines

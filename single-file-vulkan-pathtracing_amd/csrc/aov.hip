@@ -168,8 +168,8 @@ __global__ __launch_bounds__(TB) void k_aov_reduce(AovConst ac, const uint32_t *
 
 // ---- single-kernel form ------------------------------------------------------------------------------------------------------
 // The class of k_extend_lds7 / _lds7p (extend_kernel.h COMPACT: 14-bit child codes, one-dword stack entries, exact stack bound in
-// LDS, tmin > 0).  Dynamic LDS: stack [lds_stack][TB] dwords | nodes (144 B each) | three permuted triangle copies | guide records
-// 3 x float4 per leaf position {n, bits(prim)} {Kd, Ke.r} {Ke.gb, 0, 0}.
+// LDS, tmin > 0).  Dynamic LDS, from byte 0: nodes (160 B each) | three permuted triangle copies | guide records 3 x float4 per leaf
+// position {n, bits(prim)} {Kd, Ke.r} {Ke.gb, 0, 0} | stack (compact_stack_bytes: [lds_stack + 1][TB] dwords, LaneStack).
 // A wave owns one tile at a time (one atomic per 64 pixels x spp x frames rays).  Its lanes run their samples independently -- a lane
 // whose walk ended starts its next sample once AOV_START_IDLE lanes wait, as k_extend refills -- and meet again at the end of a frame.
 constexpr int AOV_START_IDLE = 16;
@@ -183,14 +183,14 @@ template <bool PAIRS>
 __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg, const uint32_t *__restrict__ tiles, uint32_t n_tiles, int32_t frame0, uint32_t n_frames,
                                                   const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
                                                   const float4 *__restrict__ g_shade4, const float *__restrict__ g_faces, uint32_t n_wide,
-                                                  uint32_t n_tris, int lds_stack, AovPlanes planes_arg, uint32_t *next_tile,
+                                                  uint32_t n_tris, AovPlanes planes_arg, uint32_t *next_tile,
                                                   unsigned long long *stats)
 {
     const AovConst ac = ptm::own_sgprs(ac_arg);
     const AovPlanes planes = ptm::own_sgprs(planes_arg);
     constexpr uint32_t LEAF_BIT = C14_LEAF, DONE = C14_DONE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4 *s_wide = reinterpret_cast<float4 *>(smem + (size_t)lds_stack * TB * sizeof(uint32_t));
+    float4 *s_wide = reinterpret_cast<float4 *>(smem);
     float4 *s_tri = s_wide + LDS_NODE_F4 * (size_t)n_wide;
     float4 *s_rec = s_tri + 9 * (size_t)n_tris;
     lds_stage_nodes<TB, true>(s_wide, g_wide, n_wide);
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
     }
     __syncthreads();
     const float4 *wide = s_wide, *tri4 = s_tri;
-    lds_u32 *my_stack32 = (lds_u32 *)reinterpret_cast<uint32_t *>(smem) + threadIdx.x;
+    LaneStack<TB> stk((lds_u32 *)reinterpret_cast<uint32_t *>(s_rec + 3 * (size_t)n_tris) + threadIdx.x);
     const int lane = threadIdx.x & 63;
     const float tmin = ac.tmin, tmax = ac.tmax;
     const float fspp = (float)ac.spp;
@@ -234,11 +234,10 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
             float best_t = tmax, best_V = 0.f, best_W = 0.f, best_det = 1.f;
             uint32_t best_pos = PT_MISS, best_prim = PT_MISS;
             uint32_t cur = DONE;
-            int sp = 0;
+            stk.clear();
             auto pop = [&]() -> uint32_t {
-                while (sp > 0) {
-                    sp--;
-                    const uint32_t e = my_stack32[sp * TB];
+                while (stk.has_entries()) {
+                    const uint32_t e = stk.pop();
                     if (__uint_as_float(e & 0xFFFFC000u) <= best_t) return e & 0x3FFFu;
                 }
                 return DONE;
@@ -255,20 +254,20 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
                     pre = ptm::ray_setup<PAIRS>(org, dir);  // (as extend_body: the per-triangle leaf loop keeps the IEEE expansion)
                     inv = { ptm::safe_inv(dir.x), ptm::safe_inv(dir.y), ptm::safe_inv(dir.z) };
                     slab_setup(org, inv, invf, on, of);
-                    ax = inv.x < 0.f ? 48u : 0u; ay = inv.y < 0.f ? 48u : 0u; az = inv.z < 0.f ? 48u : 0u;
+                    ax = inv.x < 0.f ? LDS_NEG_AXIS : 0u; ay = inv.y < 0.f ? LDS_NEG_AXIS : 0u; az = inv.z < 0.f ? LDS_NEG_AXIS : 0u;
                     tri_base = (uint32_t)pre.kz * 3u * n_tris;
                     orgp = { ptm::sel3(pre.kz, org.y, org.z, org.x), ptm::sel3(pre.kz, org.z, org.x, org.y), ptm::sel3(pre.kz, org.x, org.y, org.z) };
                     best_t = tmax; best_V = 0.f; best_W = 0.f; best_det = 1.f;
                     best_pos = PT_MISS; best_prim = PT_MISS;
                     cur = 0u;  // root
-                    sp = 0;
+                    stk.clear();
                     have = true;
                 }
                 // ---- node phase (k_extend's inner loop and its yield to the lanes that wait with a leaf)
                 bool do_node = have && !(cur & LEAF_BIT);
                 const int n_walk = __popcll(__ballot(have));
                 while (do_node) {
-                    cur = compact_node_step<TB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, my_stack32, sp, pop);
+                    cur = compact_node_step<TB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t) { return pop(); });
                     do_node = !(cur & LEAF_BIT);
                     if (__popcll(__ballot(do_node)) * 6 < n_walk) break;
                 }
@@ -404,7 +403,7 @@ pt_status render_aov_fused(pt_scene *s, pt_film *f, const pt_params *p, const Ex
     PT_HIP(ctx, hipMemsetAsync(a.d_count + AOV_NEXT_TILE, 0, sizeof(uint32_t), st));
     const int grid = (int)std::min<uint32_t>((uint32_t)fp.grid, (a.n_tiles + TB / 64 - 1) / (TB / 64));  // a wave per tile at least
     hipLaunchKernelGGL(pick_aov_fused(fp.pairs), dim3(grid), dim3(TB), (uint32_t)fp.smem, st, ac, a.d_tiles, a.n_tiles, p->frame, p->frame_count, s->d_wide, s->d_tri4,
-                       s->d_shade4, s->d_faces, s->n_wide, s->n_tris, pl.lds_stack, planes_of(f), a.d_count + AOV_NEXT_TILE, ctx->d_stats);
+                       s->d_shade4, s->d_faces, s->n_wide, s->n_tris, planes_of(f), a.d_count + AOV_NEXT_TILE, ctx->d_stats);
     PT_HIP(ctx, hipGetLastError());
     ctx->stats.launches_extend++;
     return PT_OK;

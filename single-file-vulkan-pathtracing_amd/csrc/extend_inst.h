@@ -34,8 +34,8 @@ __global__ __launch_bounds__(TB) void k_extend_inst(const float4 *__restrict__ t
     const float4 *tri4 = g_tri4;
     if (LDS_BLAS) {  // the BLAS is shared by every instance: keep it (and 3 permuted triangle copies) in LDS
         float4 *s_blas = reinterpret_cast<float4 *>(smem + (size_t)LDS_STACK * TB * sizeof(uint2));
-        float4 *s_tri = s_blas + LDS_NODE_F4 * (size_t)n_blas_wide;
-        lds_stage_nodes<TB, false>(s_blas, g_blas, n_blas_wide);
+        float4 *s_tri = s_blas + LDS_NODE128_F4 * (size_t)n_blas_wide;
+        lds_stage_nodes128<TB>(s_blas, g_blas, n_blas_wide);
         lds_stage_tris<TB>(s_tri, g_tri4, n_tris);
         __syncthreads();
         blas = s_blas;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(TB) void k_extend_inst(const float4 *__restrict__ t
         while (have && !(cur & PT_LEAF)) {
             float4 nx, fx, ny, fy, nz, fz, cw;
             if (LDS_BLAS && in_blas) {
-                const char *nd = reinterpret_cast<const char *>(blas + LDS_NODE_F4 * (size_t)cur);
+                const char *nd = reinterpret_cast<const char *>(blas + LDS_NODE128_F4 * (size_t)cur);
                 nx = PT_F4(nd + ax); fx = PT_F4(nd - ax + 48); ny = PT_F4(nd + ay + 16); fy = PT_F4(nd - ay + 64);
                 nz = PT_F4(nd + az + 32); fz = PT_F4(nd - az + 80); cw = PT_F4(nd + 96);
             } else {

@@ -38,15 +38,18 @@ __device__ __forceinline__ unsigned long long stack_entry(uint32_t w, float t)
 }
 
 // Slab test of the 4 children of a BVH4 node with the near/far planes picked by the ray's direction
-// signs THROUGH THE LOAD ADDRESS (ax/ay/az = 48 bytes when the direction component is negative: the near
-// plane of x is then float4 3 instead of 0, its far plane 0 instead of 3 -- one add or sub per load), so no
-// per-child min/max of the two plane distances is needed.  Conservative like ptm::box_test.
+// signs THROUGH THE LOAD ADDRESS, so no per-child min/max of the two plane distances is needed.  The LDS node
+// (lds_scene.h) keeps every axis as lo hi lo: ax/ay/az = 16 bytes when the direction component is negative,
+// the near plane is at node + axis + a?, the far plane 16 bytes behind it -- ONE address per axis, the far
+// plane at its immediate offset.  (The 128-B node in memory -- k_extend_inst -- has near and far 48 bytes apart
+// in opposite directions: a?  = 48, an add and a sub per axis.)  Conservative like ptm::box_test.
 #define PT_F4(P) (*reinterpret_cast<const float4 *>(P))
-#define PT_NODE_LOAD(ND)                                                                                 \
-    const char *nb_ = reinterpret_cast<const char *>(ND);                                                \
-    const float4 nx = PT_F4(nb_ + ax), fx = PT_F4(nb_ - ax + 48), ny = PT_F4(nb_ + ay + 16),             \
-                 fy = PT_F4(nb_ - ay + 64), nz = PT_F4(nb_ + az + 32), fz = PT_F4(nb_ - az + 80),        \
-                 cw = PT_F4(nb_ + 96);
+constexpr uint32_t LDS_NEG_AXIS = 16;  // ax / ay / az of a negative direction component
+#define PT_NODE_LOAD(ND)                                                                                              \
+    const char *nb_ = reinterpret_cast<const char *>(ND);                                                             \
+    const char *px_ = nb_ + ax, *py_ = nb_ + ay + 16 * LDS_NODE_AXIS_F4, *pz_ = nb_ + az + 32 * LDS_NODE_AXIS_F4;     \
+    const float4 nx = PT_F4(px_), fx = PT_F4(px_ + 16), ny = PT_F4(py_), fy = PT_F4(py_ + 16), nz = PT_F4(pz_),       \
+                 fz = PT_F4(pz_ + 16), cw = PT_F4(nb_ + 16 * LDS_NODE_CW_F4);
 // Plane distances are ONE fma each, n * inv + (-org * inv), instead of (n - org) * inv: 6 VALU
 // instructions less per child.  The rounding of the folded origin term and of the scaled far-plane
 // reciprocal (absolute error <= 2^-22 |org*inv| in total) is covered by moving the origin term
@@ -79,6 +82,38 @@ __device__ __forceinline__ float min_raw(float a, float b)
     return r;
 }
 
+// The stack of one lane of the compact walk: one-dword entries in LDS, [level][thread], held as the ADDRESS of the lane's top entry instead
+// of a level number -- a push is an add and a store, a pop a read and a subtract, and no access forms
+// level * STRIDE + lane.  In front of level 0 lies one level more, "level -1", that no push writes: the pointer of an empty stack rests there,
+// and a read of the top entry (k_fused reads it with every node, ahead of the pop that may want it) needs no compare for the empty case.
+// STRIDE: threads per block.  compact_stack_bytes: what a plan gives the stack of `levels` entries per lane.
+template <int STRIDE>
+struct LaneStack {
+    lds_u32 *top;    // the top entry; `under` while the stack is empty
+    lds_u32 *under;  // the lane's level -1
+    // lane_base: the lane's dword of the stack's first bytes, i.e. of level -1
+    __device__ __forceinline__ explicit LaneStack(lds_u32 *lane_base) : top(lane_base), under(lane_base) {}
+    __device__ __forceinline__ bool empty() const { return top <= under; }
+    __device__ __forceinline__ bool has_entries() const { return top > under; }
+    __device__ __forceinline__ void clear() { top = under; }
+    __device__ __forceinline__ void push(uint32_t e) { top += STRIDE; *top = e; }
+    __device__ __forceinline__ uint32_t peek() const { return *top; }
+    __device__ __forceinline__ uint32_t pop() { const uint32_t e = *top; top -= STRIDE; return e; }
+    __device__ __forceinline__ void drop() { top -= STRIDE; }
+    // k_fused keeps a BOTTOM entry under level 0 instead of asking "empty?" at every pop: key -inf (no best_t is below it) | the DONE code, so the
+    // pop that runs out of entries takes it like any other and returns DONE.  It is written once per lane (arm_bottom) at the plan's level -1;
+    // `under` of such a kernel is the address one level BELOW that (other LDS of the kernel: never accessed through the stack): a cleared stack
+    // rests ON the bottom entry, a stack whose bottom entry was popped at `under`.
+    static constexpr uint32_t BOTTOM = 0xFF800000u | C14_DONE;
+    __device__ __forceinline__ void arm_bottom() { under[STRIDE] = BOTTOM; }
+    __device__ __forceinline__ void clear_to_bottom() { top = under + STRIDE; }
+    // k_fused: a lane that owns no path at all holds a pointer below `under`, where a level number held -1 (one dword below: never read or
+    // written through, and not below LDS byte 0 -- the scene's tables lie in front of every stack and are never empty: fused_lds asserts it)
+    __device__ __forceinline__ void park() { top = under - 1; }
+    __device__ __forceinline__ bool parked() const { return top < under; }
+};
+__host__ __device__ constexpr size_t compact_stack_bytes(size_t threads, size_t levels) { return sizeof(uint32_t) * threads * (levels + 1); }
+
 // ONE source of the compact node step of the scenes that live in LDS (k_extend_lds7 / _lds7p and k_fused instantiate it with their block
 // sizes): the BVH4 node's planes through the direction-sign offsets (PT_NODE_LOAD), four slab tests (PT_SLAB4), the children ordered as
 // one-dword keys -- entry distance truncated to its top 18 bits | 14-bit child word; formed BEFORE the sort they order like the distances
@@ -86,17 +121,22 @@ __device__ __forceinline__ float min_raw(float a, float b)
 // v_max_u32 instead of a compare and four selects: 14 VALU for the network instead of 25, and the pushes store the key as it is.
 // Children closer together than 2^-9 of their distance may swap places -- the visit order is not part of the result (closest t, lowest
 // primitive id).  The host runs these kernels for tmin > 0 only (entry distances >= tmin: no -0, whose bit pattern would sort last).
-// -> the nearest child's code, or what `pop` returns when the ray misses all four.  STRIDE: threads per block (the stack is [level][thread]).
+// -> the nearest child's code, or what `pop(e_top)` returns when the ray misses all four; e_top: the stack's top entry as it was BEFORE the step's
+// pushes, read with the node's planes -- a step whose four children all miss pushed nothing, so that entry is what its pop looks at first (k_fused
+// takes it from this register instead of behind an LDS round trip; a caller that ignores it does not pay for the read).
+// STRIDE: threads per block (the stack is [level][thread]).
+// wide: the callers stage the nodes at LDS byte 0, so the node's address is cur * stride and nothing else.
 template <int STRIDE, class Pop>
 __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32_t cur, const ptm::f3 &inv, const ptm::f3 &invf, const ptm::f3 &on,
                                                       const ptm::f3 &of, uint32_t ax, uint32_t ay, uint32_t az, float tmin, float best_t,
-                                                      lds_u32 *my_stack32, int &sp, Pop &&pop)
+                                                      LaneStack<STRIDE> &stk, Pop &&pop)
 {
     const float INF = __builtin_inff();
     float t0, t1, t2, t3;
     // (a 24-bit multiply-add forms the node's LDS address: the child codes are below 2^14)
     const float4 *nd = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(wide) + __umul24(cur, 16u * LDS_NODE_F4));
     PT_NODE_LOAD(nd)
+    const uint32_t e_top = stk.peek();
     const uint32_t w0 = __float_as_uint(cw.x), w1 = __float_as_uint(cw.y), w2 = __float_as_uint(cw.z), w3 = __float_as_uint(cw.w);
     PT_SLAB4(t0, x)
     PT_SLAB4(t1, y)
@@ -112,10 +152,10 @@ __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32
     PT_KSWAP(k1, k2)
 #undef PT_KSWAP
     constexpr uint32_t KINF = 0x7F800000u;
-    if (k3 < KINF) { my_stack32[sp * STRIDE] = k3; sp++; }  // farthest first, so the nearest pending pops first
-    if (k2 < KINF) { my_stack32[sp * STRIDE] = k2; sp++; }
-    if (k1 < KINF) { my_stack32[sp * STRIDE] = k1; sp++; }
-    return k0 < KINF ? (k0 & 0x3FFFu) : pop();
+    if (k3 < KINF) stk.push(k3);  // farthest first, so the nearest pending pops first
+    if (k2 < KINF) stk.push(k2);
+    if (k1 < KINF) stk.push(k1);
+    return k0 < KINF ? (k0 & 0x3FFFu) : pop(e_top);
 }
 __device__ __forceinline__ void slab_setup(const ptm::f3 org, const ptm::f3 inv, ptm::f3 &invf, ptm::f3 &on, ptm::f3 &of)
 {
@@ -217,11 +257,12 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
     constexpr uint32_t DONE = COMPACT ? C14_DONE : SENTINEL;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint2 *stack = reinterpret_cast<uint2 *>(smem);  // [LDS_STACK][TB]
+    // LDS_SCENE: nodes | three triangle copies from LDS byte 0, the stack behind them (COMPACT: compact_stack_bytes, level -1 first); else the stack alone
+    uint2 *stack = reinterpret_cast<uint2 *>(smem + (LDS_SCENE ? lds_scene_bytes(n_wide, n_tris) : 0));  // [lds_stack][TB]
     const float4 *wide = g_wide;
     const float4 *tri4 = g_tri4;
     if (LDS_SCENE) {
-        float4 *s_wide = reinterpret_cast<float4 *>(smem + (size_t)lds_stack * TB * (COMPACT ? sizeof(uint32_t) : sizeof(uint2)));
+        float4 *s_wide = reinterpret_cast<float4 *>(smem);
         float4 *s_tri = s_wide + LDS_NODE_F4 * (size_t)n_wide;
         lds_stage_nodes<TB, COMPACT>(s_wide, g_wide, n_wide);
         lds_stage_tris<TB>(s_tri, g_tri4, n_tris);
@@ -235,7 +276,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
         if (stats) atomicAdd(stats, (unsigned long long)n);  // exact ray count
     }
     lds_u64 *my_stack = (lds_u64 *)reinterpret_cast<unsigned long long *>(stack) + threadIdx.x;
-    lds_u32 *my_stack32 = (lds_u32 *)reinterpret_cast<uint32_t *>(stack) + threadIdx.x;
+    LaneStack<TB> stk((lds_u32 *)reinterpret_cast<uint32_t *>(stack) + threadIdx.x);  // (COMPACT)
     unsigned long long *my_spill = reinterpret_cast<unsigned long long *>(spill) + (size_t)blockIdx.x * TB + threadIdx.x;
     const float INF = __builtin_inff();
     const int lane = threadIdx.x & 63;
@@ -249,7 +290,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
     uint32_t cursor = 0;
     ptm::f3 inv{}, invf{}, on{}, of{}, orgp{};  // slab_setup: near/far reciprocals and folded origin terms
     ptm::RayPre pre{};
-    uint32_t ax = 0, ay = 0, az = 0;  // 48 where the direction component is negative (PT_NODE_LOAD)
+    uint32_t ax = 0, ay = 0, az = 0;  // LDS_NEG_AXIS (fp16 nodes: any non-zero value) where the direction component is negative (PT_NODE_LOAD)
     uint32_t tri_base = 0;           // LDS_SCENE: start of the triangle copy for this ray's kz
     float best_t = tmax, best_V = 0.f, best_W = 0.f, best_det = 1.f;
     uint32_t best_pos = PT_MISS, best_prim = PT_MISS;
@@ -264,8 +305,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
 
     auto push = [&](uint32_t w, float t) {
         if (COMPACT) {
-            my_stack32[sp * TB] = (__float_as_uint(t) & 0xFFFFC000u) | w;
-            sp++;
+            stk.push((__float_as_uint(t) & 0xFFFFC000u) | w);
             return;
         }
         const unsigned long long e = stack_entry(w, t);
@@ -273,13 +313,16 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
         else my_spill[(size_t)(sp - lds_stack) * spill_stride] = e;
         sp++;
     };
+    auto clear_stack = [&] {
+        if (COMPACT) stk.clear();
+        else sp = 0;
+    };
     auto pop = [&]() -> uint32_t {  // next subtree that can still contain the closest hit
         if (COMPACT) {
-            while (sp > 0) {
+            while (stk.has_entries()) {
                 PT_COUNT_WAVE(c_pops);
                 if (COUNT) c_pop_lanes++;
-                sp--;
-                const uint32_t e = my_stack32[sp * TB];
+                const uint32_t e = stk.pop();
                 if (__uint_as_float(e & 0xFFFFC000u) <= best_t) return e & 0x3FFFu;
             }
             return DONE;
@@ -325,10 +368,10 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                         inv = { inv.x * nb.sx, inv.y * nb.sy, inv.z * nb.sz };
                         slab_setup(orgn, inv, invf, on, of);
                     }
-                    // byte offset of the near planes inside a node: 3 planes of 16 B (fp32 node) or 8 B (fp16 node)
-                    ax = inv.x < 0.f ? (LDS_SCENE ? 48u : 24u) : 0u;
-                    ay = inv.y < 0.f ? (LDS_SCENE ? 48u : 24u) : 0u;
-                    az = inv.z < 0.f ? (LDS_SCENE ? 48u : 24u) : 0u;
+                    // byte offset of the near planes: one plane within the axis' lo hi lo (LDS node); the fp16 node in memory only asks "negative?"
+                    ax = inv.x < 0.f ? (LDS_SCENE ? LDS_NEG_AXIS : 24u) : 0u;
+                    ay = inv.y < 0.f ? (LDS_SCENE ? LDS_NEG_AXIS : 24u) : 0u;
+                    az = inv.z < 0.f ? (LDS_SCENE ? LDS_NEG_AXIS : 24u) : 0u;
                     if (LDS_SCENE) {
                         tri_base = (uint32_t)pre.kz * 3u * n_tris;
                         orgp = { ptm::sel3(pre.kz, org.y, org.z, org.x), ptm::sel3(pre.kz, org.z, org.x, org.y),
@@ -337,7 +380,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                     best_t = ray_tmax ? ray_tmax[q] : tmax; best_V = 0.f; best_W = 0.f; best_det = 1.f;
                     best_pos = PT_MISS; best_prim = PT_MISS;
                     cur = 0u;  // wide root
-                    sp = 0;
+                    clear_stack();
                     have = true;
                 }
             }
@@ -364,7 +407,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                 if (lane == __ffsll((long long)__ballot(1)) - 1) c_node_steps++;  // one lane per wave step
             }
             if constexpr (LDS_SCENE && COMPACT) {
-                cur = compact_node_step<TB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, my_stack32, sp, pop);
+                cur = compact_node_step<TB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t) { return pop(); });
             } else {
             float t0, t1, t2, t3;
             uint32_t w0, w1, w2, w3;
@@ -438,7 +481,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                     ptl::pair_leaf_test(tri4, (size_t)tri_base + 3 * (size_t)first, two, first, pre, orgp, tmin, tmax,
                                         [&](float t, float V, float W, float det, uint32_t pos, uint32_t) {
                                             if (ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos) && ray_tmax)
-                                                sp = 0;  // any hit will do: nothing pending any more
+                                                clear_stack();  // any hit will do: nothing pending any more
                                         },
                                         [&] {
                                             PT_COUNT_WAVE(c_hit_blocks);
@@ -473,13 +516,13 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                                          __float_as_uint(g_tri4[3 * (size_t)pos].w) < __float_as_uint(g_tri4[3 * (size_t)best_pos].w);
                             if (closer) {
                                 best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos;
-                                if (ray_tmax) sp = 0;
+                                if (ray_tmax) clear_stack();
                             }
                         } else {
                         const uint32_t prim = __float_as_uint(a.w);
                         if (t < best_t || (t == best_t && prim < best_prim)) {
                             best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos; best_prim = prim;
-                            if (ray_tmax) sp = 0;
+                            if (ray_tmax) clear_stack();
                         }
                         }
                     }

@@ -77,7 +77,7 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
     if (s->n_inst) {  // two-level scenes: one kernel variant (BVH4s read through L1/L2)
         if (want == PT_EXTEND_LDS) { ctx->err = "instanced scenes only have the HBM extend variant"; return PT_ERR_UNSUPPORTED; }
         pl.variant = PT_EXTEND_HBM;
-        const size_t blas_bytes = lds_scene_bytes(s->n_wide, s->n_tris);
+        const size_t blas_bytes = lds_scene128_bytes(s->n_wide, s->n_tris);  // (k_extend_inst keeps the 128-B node: lds_scene.h)
         pl.lds_scene = blas_bytes <= 24 * 1024;  // here: the BLAS (shared by all instances) is staged in LDS
         pl.smem = (size_t)LDS_STACK * TB * sizeof(uint2) + (pl.lds_scene ? blas_bytes : 0);
         int per_cu_i = 0;
@@ -125,10 +125,12 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
         pl.spill_levels = bound_i > (uint32_t)LDS_STACK ? bound_i - (uint32_t)LDS_STACK : 0u;  // (sized for the 8-entry fallback kernel)
         return ptw_reserve_spill(ctx, PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)std::max(pl.grid, pl.grid_inst_fallback) * TB * sizeof(uint2));
     }
-    const size_t scene_bytes = lds_scene_bytes(s->n_wide, s->n_tris);
+    // scene_bytes: the image in LDS (160-B nodes); class_bytes: what the class limits below are drawn in (144-B nodes, as they were measured:
+    // lds_scene.h) -- the wider node moved no scene across a limit
+    const size_t scene_bytes = lds_scene_bytes(s->n_wide, s->n_tris), class_bytes = lds_class_bytes(s->n_wide, s->n_tris);
     // (round 2's 128-B eight-wide node with fp16 planes visited 26 % fewer nodes and fetched as many 128-B LINES -- two 64-B
     // BVH4 siblings share one -- and lost: 458 vs 395 ms of kernel time per 4 frames of C5; the 64-B node above is its successor)
-    const bool auto8 = want == PT_EXTEND_AUTO && scene_bytes > 24 * 1024 && s->d_wide8 && (ctx->tune.hbm8 == 1 || auto8_big);
+    const bool auto8 = want == PT_EXTEND_AUTO && class_bytes > 24 * 1024 && s->d_wide8 && (ctx->tune.hbm8 == 1 || auto8_big);
     if (want == PT_EXTEND_HBM8 || auto8) {
         pl.variant = PT_EXTEND_HBM8;
         pl.bvh8 = true;
@@ -155,8 +157,8 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
         pl.spill_levels = bound8 > (uint32_t)pl.lds_stack ? bound8 - (uint32_t)pl.lds_stack : 0u;
         return ptw_reserve_spill(ctx, PT_MAX_PIPES * (size_t)std::max(pl.spill_levels, 1u) * (size_t)pl.grid * TB * sizeof(uint2));
     }
-    if (want == PT_EXTEND_LDS && scene_bytes > 96 * 1024) { ctx->err = "scene does not fit LDS"; return PT_ERR_UNSUPPORTED; }
-    pl.lds_scene = want == PT_EXTEND_LDS || (want == PT_EXTEND_AUTO && scene_bytes <= 24 * 1024);
+    if (want == PT_EXTEND_LDS && class_bytes > 96 * 1024) { ctx->err = "scene does not fit LDS"; return PT_ERR_UNSUPPORTED; }
+    pl.lds_scene = want == PT_EXTEND_LDS || (want == PT_EXTEND_AUTO && class_bytes <= 24 * 1024);
     pl.variant = pl.lds_scene ? PT_EXTEND_LDS : PT_EXTEND_HBM;
     // deep trees of big scenes: 12 LDS entries measured best on the 1M-triangle soup (4: -15 %, 8: -3 %,
     // 16: -5 %, 24: -16 %: beyond 12 the extra LDS costs occupancy; 9/10/11, which would admit a 7th block per CU: -2.4 %)
@@ -168,7 +170,7 @@ pt_status ptw_plan_extend(pt_scene *s, uint32_t want, ExtendPlan &pl)
     if (!pl.spill) pl.lds_stack = (int)std::max(s->stack_need, 1u);
     pl.pairs = !pl.spill && s->pair_leaves && ctx->tune.pair_kernel != 0;
     pl.smem_wide_entries = (size_t)pl.lds_stack * TB * sizeof(uint2) + (pl.lds_scene ? scene_bytes : 0);
-    pl.smem = pl.spill ? pl.smem_wide_entries : (size_t)pl.lds_stack * TB * sizeof(uint32_t) + scene_bytes;
+    pl.smem = pl.spill ? pl.smem_wide_entries : compact_stack_bytes(TB, pl.lds_stack) + scene_bytes;  // (one-dword entries, level -1 in front: LaneStack)
     // every kernel ptw_launch_extend can take for this plan, with the LDS size it would be launched with: the 8-byte-entry kernels of a
     // compact plan (tmin <= 0), the instrumented twin, the shadow-ray twin of a compact kernel (NEE pipeline), the product kernel --
     // whose occupancy makes the grid of them all

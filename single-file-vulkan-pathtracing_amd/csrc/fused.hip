@@ -130,11 +130,9 @@ pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPla
                    "kernels' class: <= 2047 triangles in <= 24 KB, stack bound <= 16, tmin > 0)";
         return PT_ERR_UNSUPPORTED;
     }
-    // (one stack level more than the walk needs: level -1, never written, is what the node step's read of the stack's top entry lands on when the stack is
-    // empty -- fused_kernel.h)
-    fp.lds_stack = pl.lds_stack + 1;
-    fp.smem = (size_t)fp.lds_stack * FTB * sizeof(uint32_t) + lds_scene_bytes(s->n_wide, s->n_tris) + tables +
-              sizeof(uint32_t) * FS_FIELDS * FTB + sizeof(uint32_t) * (FTB / 64) * PT_FUSED_WTILES;
+    // (the plan gives the stack one level in front of level 0: the BOTTOM entry every pop may take -- fused_lds)
+    fp.lds_stack = pl.lds_stack;
+    fp.smem = fused_lds(s->n_wide, s->n_tris, (uint32_t)fp.lds_stack).extra;
     fp.pairs = pl.pairs;
     fp.block = FTB;
     int per_cu = 0;

@@ -55,8 +55,11 @@ __global__ __launch_bounds__(FITB, PT_FUSEDI_WAVES) void k_fused_inst(
     uint32_t *s_stack = reinterpret_cast<uint32_t *>(smem);  // [lds_stack][FITB]
     uint32_t *s_blas = s_stack + (size_t)lds_stack * FITB;    // [n_blas_wide + n_tlas_lds][I16_NODE_DW]
     float4 *s_tri = reinterpret_cast<float4 *>(s_blas + (size_t)I16_NODE_DW * (n_blas_wide + n_tlas_lds));
-    float4 *s_shade = s_tri + 9 * (size_t)n_tris;
-    lds_u32 *my_state = (lds_u32 *)reinterpret_cast<uint32_t *>(s_shade + 3 * (size_t)n_tris) + threadIdx.x;
+    // (the shade table directly behind the triangle copies, three float4 per triangle: pair_leaf_test<LOAD_D_FIRST> reads that far past them)
+    constexpr size_t SHADE_F4 = 3;
+    static_assert(lds_tris_bytes(1) == 9 * sizeof(float4) && SHADE_F4 >= ptl::D_FIRST_OVERREAD_F4, "k_fused_inst: s_shade directly behind s_tri (pair_leaf.h LOAD_D_FIRST)");
+    float4 *s_shade = s_tri + lds_tris_bytes(n_tris) / sizeof(float4);
+    lds_u32 *my_state = (lds_u32 *)reinterpret_cast<uint32_t *>(s_shade + SHADE_F4 * (size_t)n_tris) + threadIdx.x;
     // lds_stage_nodes16 and lds_stage_tris (lds_scene.h) restated: through the shared helpers this kernel's register allocation changes
     for (uint32_t i = threadIdx.x; i < 4 * n_tlas_lds; i += FITB)
         *reinterpret_cast<uint4 *>(s_blas + (size_t)(n_blas_wide + (i >> 2)) * I16_NODE_DW + 4 * (i & 3u)) = tlas16[i];

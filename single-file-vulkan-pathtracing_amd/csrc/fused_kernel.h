@@ -75,6 +75,41 @@ enum : int { FS_NEE_POS = 0, FS_NEE_R, FS_NEE_G, FS_NEE_B, FS_NEE_FIELDS };
 #define PT_FUSED_WAVES_NEE 4
 #endif
 
+// ---- the LDS plan, in bytes from LDS byte 0: fused.hip sizes the launch with it, the kernel takes its pointers from it.
+// nodes | three permuted triangle copies | shade4 | tangent frames || path state | the waves' tile words | stack (the BOTTOM entry's level, then
+// level 0 ...: LaneStack) | extra
+// The path state lies IN FRONT of the stack: LaneStack's `under`, one level below the BOTTOM entry, is an address inside it -- compared with, never
+// read or written through -- so the stack costs no level of its own for it (one more 2-KB level is the third block per CU).
+// The scene's tables come FIRST: the kernel has no static LDS, so they start at LDS address 0 and a node's address is its number times the
+// stride -- no base register in the node step.  What a run-time count places (the stack, the state) is reached through per-lane pointers anyway.
+// extra: the shadow ray's state (NEE) or the block counters (COUNT), never both.
+struct FusedLds { uint32_t wide, tri, shade, frame, stack, state, wtile, extra; };
+__host__ __device__ constexpr FusedLds fused_lds(uint32_t n_wide, uint32_t n_tris, uint32_t stack_levels)
+{
+    FusedLds l{};
+    l.wide = 0u;
+    l.tri = l.wide + (uint32_t)lds_nodes_bytes(n_wide);
+    l.shade = l.tri + (uint32_t)lds_tris_bytes(n_tris);
+    l.frame = l.shade + (uint32_t)sizeof(float4) * 3u * n_tris;
+    l.state = l.frame + (uint32_t)sizeof(float4) * 2u * n_tris;
+    l.wtile = l.state + (uint32_t)sizeof(uint32_t) * FS_FIELDS * FTB;
+    l.stack = l.wtile + (uint32_t)sizeof(uint32_t) * (FTB / 64) * PT_FUSED_WTILES;
+    l.extra = l.stack + (uint32_t)compact_stack_bytes(FTB, stack_levels);  // (its extra level is the BOTTOM entry's)
+    return l;
+}
+// pair_leaf_test<LOAD_D_FIRST> reads the record five float4 behind a leaf's first: for a single triangle at the last position of the last copy
+// that is ptl::D_FIRST_OVERREAD_F4 float4 past the triangle copies -- the shade table must start right there and be at least that long
+constexpr bool fused_lds_covers_leaf_read(uint32_t n_wide, uint32_t n_tris)
+{
+    const FusedLds l = fused_lds(n_wide, n_tris, 1u);
+    // (... and more than one stack level of other LDS in front of the stack: `under` and a parked pointer, a level and a dword below the BOTTOM
+    // entry, are no wrapped addresses)
+    return l.shade == l.tri + lds_tris_bytes(n_tris) && l.frame - l.shade >= sizeof(float4) * ptl::D_FIRST_OVERREAD_F4 && l.wide == 0u &&
+           l.stack >= l.state + sizeof(uint32_t) * FTB + 4u;
+}
+static_assert(fused_lds_covers_leaf_read(1, 1) && fused_lds_covers_leaf_read(1, 2) && fused_lds_covers_leaf_read(21, 36) && fused_lds_covers_leaf_read(85, 85),
+              "k_fused: s_shade directly behind s_tri (pair_leaf.h LOAD_D_FIRST), tables at LDS byte 0");
+
 // PAIRS: every leaf is one triangle or one fan pair (k_extend_lds7p's trees); else leaves of up to four triangles (k_extend_lds7's)
 // MODE 0: one sample group (a slot is a pixel's whole frame; radiance added in LDS); 1: several groups (every slot logs its radiance terms);
 // 2: HEAD + TAIL (wavefront_types.h RenderConst::tail) -- head slots like mode 0 for samples [0, head_samples), handed out first, then one-sample tail
@@ -156,12 +191,13 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
         light_area = ptm::own_sgprs(light_area_arg);
     }
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // ---- LDS: stack | BVH4 nodes | three permuted triangle copies | shade4 | tangent frames | path state
-    float4 *s_wide = reinterpret_cast<float4 *>(smem + (size_t)lds_stack * FTB * sizeof(uint32_t));
-    float4 *s_tri = s_wide + LDS_NODE_F4 * (size_t)n_wide;
-    float4 *s_shade = s_tri + 9 * (size_t)n_tris;
-    float4 *s_frame = s_shade + 3 * (size_t)n_tris;
-    lds_u32 *my_state = (lds_u32 *)reinterpret_cast<uint32_t *>(s_frame + 2 * (size_t)n_tris) + threadIdx.x;
+    // ---- LDS: BVH4 nodes | three permuted triangle copies | shade4 | tangent frames | stack | path state (fused_lds)
+    const FusedLds lds = fused_lds(n_wide, n_tris, (uint32_t)lds_stack);
+    float4 *s_wide = reinterpret_cast<float4 *>(smem + lds.wide);
+    float4 *s_tri = reinterpret_cast<float4 *>(smem + lds.tri);
+    float4 *s_shade = reinterpret_cast<float4 *>(smem + lds.shade);
+    float4 *s_frame = reinterpret_cast<float4 *>(smem + lds.frame);
+    lds_u32 *my_state = (lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.state) + threadIdx.x;
     lds_stage_nodes<FTB, true>(s_wide, g_wide, n_wide);  // (child words -> 14-bit codes: extend_kernel.h COMPACT)
     lds_stage_tris<FTB, true>(s_tri, g_tri4, n_tris, s_shade, g_shade4);  // (the kz = 2 copy is also what the shade block reads)
     for (uint32_t i = threadIdx.x; i < 2 * n_tris; i += FTB) s_frame[i] = g_frame4[i];
@@ -169,27 +205,30 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     const float4 *wide = s_wide, *tri4 = s_tri;
     const float4 *verts = s_tri + 6 * (size_t)n_tris;
 
-    // (the stack's level 0 is the SECOND of the lds_stack levels: the first, never written, is where the node step's read of the top entry lands
-    // when the stack is empty -- an address without a compare and a select)
-    lds_u32 *my_stack32 = (lds_u32 *)reinterpret_cast<uint32_t *>(smem) + FTB + threadIdx.x;
+    // (the lane's stack as the address of its top entry, over a BOTTOM entry (-inf | DONE) that every pop may take: the node step's read of the top
+    // entry and both pop loops need no "empty?" compare -- LaneStack, extend_kernel.h.  Each lane writes and reads its own: no barrier)
+    LaneStack<FTB> stk((lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.stack) - FTB + threadIdx.x);  // (`under`: a level below the BOTTOM entry, in the path state)
+    stk.arm_bottom();
+    stk.park();  // (no path yet)
     const int lane = threadIdx.x & 63;
 
     FusedDev dev;  // (fused_dev.h: empty in the product build)
     dev.kernel_begin();
     // COUNT: {wave executions, lanes inside} of every block, kept per wave in LDS behind the product kernel's plan (no registers: the walk keeps
     // its allocation) and added by the first active lane of the moment
-    lds_u32 *s_fb = (lds_u32 *)reinterpret_cast<uint32_t *>(s_frame + 2 * (size_t)n_tris) + FS_FIELDS * FTB + (FTB / 64) * PT_FUSED_WTILES + (threadIdx.x >> 6) * (2 * FB_N);
+    // (the wave's counters are addressed where they are used, not through a pointer kept across the loop: the twin has no register to spare for it)
+    auto fb_of_wave = [&]() -> lds_u32 * { return (lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.extra) + (threadIdx.x >> 6) * (2 * FB_N); };
     if constexpr (COUNT) {
-        if (lane < 2 * FB_N) s_fb[lane] = 0u;
+        if (lane < 2 * FB_N) fb_of_wave()[lane] = 0u;
     }
 #define PT_FB(B)                                                                                        \
     if constexpr (COUNT) {                                                                              \
         const unsigned long long m_fb = __ballot(1);                                                    \
-        if (lane == __ffsll((long long)m_fb) - 1) { s_fb[2 * (B)] += 1u; s_fb[2 * (B) + 1] += (uint32_t)__popcll(m_fb); } \
+        if (lane == __ffsll((long long)m_fb) - 1) { lds_u32 *s_fb = fb_of_wave(); s_fb[2 * (B)] += 1u; s_fb[2 * (B) + 1] += (uint32_t)__popcll(m_fb); } \
     }
     // (a lane traces a ray <=> cur != DONE: the shade block sets cur = 0 with the new ray, the walk ends with cur == DONE.  No flag is kept: a
     // loop-carried bool lives in a lane mask, and every ballot of one costs a v_cndmask + v_cmp to clear its inactive lanes -- a compare does not)
-    // (the lane owns a live path -- its state is in LDS; not tracing: a hit record awaits shading -- <=> sp >= 0: a lane without a path holds sp = -1.
+    // (the lane owns a live path -- its state is in LDS; not tracing: a hit record awaits shading -- <=> its stack pointer is not parked.
     // No flag for that either: the loop's head asks for three wave masks of it per pass, and a ballot of a flag is two vector instructions, of a
     // compare one; the masks are combined as 64-bit integers on the scalar unit)
     bool out_of_slots = false;  // wave-uniform: the slot counter ran past the end
@@ -206,15 +245,14 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     // world 8 is not helped (its loss is elsewhere), 16 frames on one device are: 39.76 -> 40.8 Grays/s, two of two rounds; K = 8 +-0, K = 4 +2 %; the two-level
     // kernel loses 1 % with it and keeps the frame-major order (profiles/r04ag_ab_fused_tilemajor.log).  (Slot numbers, and with them the radiance arrays, are frame-major as before.)
     const uint32_t part_len = ((n_slots + PT_FUSED_PARTS - 1) / PT_FUSED_PARTS + 63u) & ~63u;  // (several groups)
-    lds_u32 *s_wtile = (lds_u32 *)reinterpret_cast<uint32_t *>(s_frame + 2 * (size_t)n_tris) + FS_FIELDS * FTB + (threadIdx.x >> 6) * PT_FUSED_WTILES;
-    lds_u32 *my_nee = (lds_u32 *)reinterpret_cast<uint32_t *>(s_frame + 2 * (size_t)n_tris) + FS_FIELDS * FTB + (FTB / 64) * PT_FUSED_WTILES + threadIdx.x;  // (NEE)
+    lds_u32 *s_wtile = (lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.wtile) + (threadIdx.x >> 6) * PT_FUSED_WTILES;
+    lds_u32 *my_nee = (lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.extra) + threadIdx.x;  // (NEE)
     ptm::f3 inv{}, invf{}, on{}, of{}, orgp{};
     ptm::RayPre pre{};
     uint32_t ax = 0, ay = 0, az = 0, tri_base = 0;
     float best_t = tmax, best_V = 0.f, best_W = 0.f, best_det = 1.f;
     uint32_t best_pos = PT_MISS;
     uint32_t cur = DONE;
-    int sp = -1;
 
     // The stack's pop with the cull against best_t: a loop on the WAVE's condition -- the lanes that are served sit out behind one exec mask (see the
     // node loop) -- with selects inside, not branches (two more vector instructions for eight fewer scalar ones per pass).  r: PENDING for the lanes
@@ -224,29 +262,28 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
         while (__ballot(r == PENDING)) {
             if (r == PENDING) {
                 PT_FB(FB_POP)
-                sp--;
-                const uint32_t e = my_stack32[sp * FTB];
-                const uint32_t miss = sp == 0 ? DONE : PENDING;
-                r = __uint_as_float(e & 0xFFFFC000u) <= best_t ? (e & 0x3FFFu) : miss;
+                const uint32_t e = stk.pop();  // (the BOTTOM entry ends the search: never behind best_t, its code is DONE)
+                r = !(__uint_as_float(e & 0xFFFFC000u) > best_t) ? (e & 0x3FFFu) : PENDING;
             }
         }
         return r;
     };
-    auto pop = [&]() -> uint32_t { return pop_pending(sp > 0 ? PENDING : DONE); };
+    auto pop = [&]() -> uint32_t { return pop_pending(PENDING); };
 
     for (;;) {
         PT_FB(FB_ITER)
         // ---- shade block: the lanes that wait with a hit (or with nothing, while slots are left) -- once enough of them do
-        const bool have = cur != DONE, path = sp >= 0;
+        const bool have = cur != DONE, path = !stk.parked();
         const unsigned long long m_have = __ballot(have), m_path = __ballot(path);
         const unsigned long long m_in_blk = ~m_have & (out_of_slots ? m_path : ~0ull);  // (waves are whole: FTB is a multiple of 64)
-        const bool in_blk = !have && (path || !out_of_slots);
         const int n_work = __popcll(m_in_blk);
         if (n_work && n_work * 64 >= refill * (n_work + __popcll(m_have))) {  // (refill <= 64: a wave without a tracing lane always passes)
             uint32_t slot = 0, ctr = 0, seed = 0, pxy = 0;
             float wr = 0.f, wg = 0.f, wb = 0.f;
             ptm::f3 org{}, dir{};
+            const bool in_blk = !have && (path || !out_of_slots);
             bool got_ray = false, need_primary = false, bounce = false;
+            bool freed = false;   // the lane's slot was completed in step (1): it has no path any more (what stk.parked() says, without a second compare)
             bool shadow = false;  // NEE: the lane's next ray is the shadow ray of a light sample (org, dir = the hit, wi; tmax nc.w)
             uint32_t bpos = 0u;   // NEE: the hit whose bounce step (3) draws (its position is in org)
             float4 nc{};          // NEE: the light sample's contribution | the shadow ray's tmax
@@ -352,7 +389,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         if (!logs) rad.color[slot] = make_float4(__uint_as_float(my_state[FS_A * FTB]), __uint_as_float(my_state[FS_B * FTB]),
                                                                    __uint_as_float(my_state[FS_C * FTB]), 0.f);
                         else if (!dbg_no_nterm) rad.nterm[lslot] = my_state[FS_A * FTB];
-                        sp = -1;  // (no path)
+                        stk.park();  // (no path)
+                        freed = true;
                         dev.slot_end(slot);
                     }
                 }
@@ -361,9 +399,10 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
             // (2) new slots for the lanes without a path (wave-uniform part).  A wave draws PT_FUSED_BATCH consecutive slots per
             // atomic and the tile words that give them their pixels with it: the two dependent round trips to memory (~3 us) are
             // paid once per batch -- per lane and shade block, as the first version did, they were 3/4 of the kernel's time.
-            const unsigned long long m_want = __ballot(in_blk && sp < 0);
+            const bool wants = in_blk && (!path || freed);  // (a lane in the block without a path: it asks for a slot)
+            const unsigned long long m_want = __ballot(wants);
             if (m_want && !out_of_slots) {
-                if (in_blk && sp < 0) { PT_FB(FB_HANDOUT) }
+                if (wants) { PT_FB(FB_HANDOUT) }
                 if (w_next >= w_end) {
                     PT_FB(FB_DRAW)
                     // The slots are cut into PT_FUSED_PARTS contiguous parts with a counter each, 128 B apart; a wave starts on part
@@ -419,7 +458,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 const uint32_t take = min((uint32_t)__popcll(m_want), w_end - w_next);
                 const uint32_t rank = (uint32_t)__popcll(m_want & ((1ull << lane) - 1ull));
                 uint32_t cull_n = 0u;  // samples of a slot that is finished here: its pixel cannot see the scene (RenderConst::cull)
-                if (in_blk && sp < 0 && rank < take) {
+                if (wants && rank < take) {
                     PT_FB(FB_TAKE)
                     const uint32_t mine = w_next + rank;
                     uint32_t f, g, local;
@@ -457,7 +496,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         my_state[FS_A * FTB] = 0u;  // colour.r = +0.0f | term count = 0
                         if (!GROUPED) { my_state[FS_B * FTB] = 0u; my_state[FS_C * FTB] = 0u; }
                         my_state[FS_MB * FTB] = (uint32_t)((int32_t)rc.spp * (rc.frame_base + (int32_t)f)) + 1u;
-                        sp = 0;  // (a path)
+                        stk.clear_to_bottom();  // (a path)
                         need_primary = true;
                         dev.slot_begin();
                     } else if (GROUPED) {
@@ -542,16 +581,16 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 pre = ptm::ray_setup<true>(org, dir);
                 inv = { ptm::safe_inv(dir.x), ptm::safe_inv(dir.y), ptm::safe_inv(dir.z) };
                 slab_setup(org, inv, invf, on, of);
-                ax = inv.x < 0.f ? 48u : 0u;
-                ay = inv.y < 0.f ? 48u : 0u;
-                az = inv.z < 0.f ? 48u : 0u;
+                ax = inv.x < 0.f ? LDS_NEG_AXIS : 0u;
+                ay = inv.y < 0.f ? LDS_NEG_AXIS : 0u;
+                az = inv.z < 0.f ? LDS_NEG_AXIS : 0u;
                 tri_base = (uint32_t)pre.kz * 3u * n_tris;
                 orgp = { ptm::sel3(pre.kz, org.y, org.z, org.x), ptm::sel3(pre.kz, org.z, org.x, org.y), ptm::sel3(pre.kz, org.x, org.y, org.z) };
                 best_t = (NEE && shadow) ? nc.w : tmax;  // (a shadow ray: its own tmax, k_extend's ray_tmax)
                 best_V = 0.f; best_W = 0.f; best_det = 1.f;
                 best_pos = PT_MISS;
                 cur = 0u;
-                sp = 0;
+                stk.clear_to_bottom();
             }
             const uint32_t n_started = (uint32_t)__popcll(__ballot(got_ray));  // (wave-uniform control flow here: every lane keeps the same count)
             n_rays_wave += n_started;
@@ -562,7 +601,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
         // phase, and the compiler copied the five of them at every block boundary of it -- ~30 v_mov per pass (profiles/r06x_one_latch.log)
         const bool tracing = cur != DONE;
         const unsigned long long m_tracing = __ballot(tracing);
-        if (m_tracing == 0ull && __ballot(sp >= 0) == 0ull && out_of_slots) break;
+        if (m_tracing == 0ull && __ballot(!stk.parked()) == 0ull && out_of_slots) break;
 
         // ---- node phase (extend_body, LDS_SCENE && COMPACT): every lane descends until it holds a leaf
         const int n_have = __popcll(m_tracing);
@@ -579,18 +618,15 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 do {
                     if (dn) {
                         PT_FB(FB_NODE)
-                        // (the stack's top entry, read WITH the node's planes: a step whose four children all miss pushed nothing, so that entry is what
-                        // its pop looks at first -- from a register instead of behind an LDS round trip: -1.8 %, profiles/r06r_speculative_pop.log.  Level -1,
-                        // never written, is what the read lands on at an empty stack)
-                        const uint32_t e_top = my_stack32[(sp - 1) * FTB];
-                        cur = compact_node_step<FTB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, my_stack32, sp, [&]() -> uint32_t {
+                        // (e_top, the stack's top entry read WITH the node's planes: a step whose four children all miss pushed nothing, so that entry is what
+                        // its pop looks at first -- from a register instead of behind an LDS round trip: -1.8 %, profiles/r06r_speculative_pop.log.  At an
+                        // empty stack the read lands on the BOTTOM entry)
+                        cur = compact_node_step<FTB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t e_top) -> uint32_t {
                             PT_FB(FB_POPTOP)
-                            // (the top entry as the pop's first candidate, by selects: empty stack -> DONE; entry within best_t -> taken; else the loop)
-                            const bool any = sp > 0;
-                            sp -= any ? 1 : 0;
-                            const uint32_t below = sp > 0 ? PENDING : DONE;
-                            const uint32_t top = __uint_as_float(e_top & 0xFFFFC000u) <= best_t ? (e_top & 0x3FFFu) : below;
-                            return pop_pending(any ? top : DONE);
+                            // (the top entry as the pop's first candidate: within best_t -> taken -- the BOTTOM entry of an empty stack always is, and says
+                            // DONE; else the loop)
+                            stk.drop();
+                            return pop_pending(!(__uint_as_float(e_top & 0xFFFFC000u) > best_t) ? (e_top & 0x3FFFu) : PENDING);
                         });
                     }
                     dn = cur < LEAF_BIT;
@@ -609,7 +645,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                                             [[maybe_unused]] const bool closer =
                                                 ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos);
                                             if constexpr (NEE) {  // a shadow ray: any hit below its tmax will do, nothing pending any more
-                                                if (closer && my_nee[FS_NEE_POS * FTB] != PT_MISS) sp = 0;
+                                                if (closer && my_nee[FS_NEE_POS * FTB] != PT_MISS) stk.clear_to_bottom();
                                             }
                                         },
                                         [&] { PT_FB(FB_DIV) });
@@ -626,7 +662,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                                 closer = best_pos == PT_MISS || __float_as_uint(a.w) < __float_as_uint(tri4[(size_t)tri_base + 3 * (size_t)best_pos].w);
                             if (closer) {
                                 best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos;
-                                if (NEE && my_nee[FS_NEE_POS * FTB] != PT_MISS) sp = 0;  // (a shadow ray: any hit will do)
+                                if (NEE && my_nee[FS_NEE_POS * FTB] != PT_MISS) stk.clear_to_bottom();  // (a shadow ray: any hit will do)
                             }
                         }
                     }
@@ -642,7 +678,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     if (lane == 0 && n_cull_wave) atomicAdd(stats + 19, (unsigned long long)n_cull_wave);  // (pt_stats.rays_culled)
     dev.kernel_end(lane, n_rays_wave, FTB);
     if constexpr (COUNT) {  // (pt_get_block_counts: stats[PT_N_STATS + 2 * block] wave executions, [+ 1] lanes inside them)
-        if (lane < 2 * FB_N) atomicAdd(stats + PT_N_STATS + lane, (unsigned long long)s_fb[lane]);
+        if (lane < 2 * FB_N) atomicAdd(stats + PT_N_STATS + lane, (unsigned long long)fb_of_wave()[lane]);
     }
 #undef PT_FB
 }

@@ -13,6 +13,8 @@ namespace ptl {
 // tri4: the permuted triangle records in LDS -- {v0, id} {v1} {v2} per triangle, a pair's second triangle behind the first, so the pair's
 // fourth vertex is record 5 (.w = the second triangle's gl_PrimitiveID); ti: index of the first record; first: the leaf's first position.
 // accept(t, V, W, det, pos, prim_bits): a hit inside the range, in primitive order (first half first); hit_block(): once per divide block.
+// LOAD_D_FIRST: how far past a single triangle's record (three float4) the step reads: records ti + 3 .. ti + 5
+constexpr unsigned D_FIRST_OVERREAD_F4 = 3;
 template <bool LOAD_D_FIRST = false, class Accept, class HitBlock>
 __device__ __forceinline__ void pair_leaf_test(const float4 *tri4, size_t ti, bool two, uint32_t first, const ptm::RayPre &pre,
                                                const ptm::f3 &orgp, float tmin, float tmax, Accept &&accept, HitBlock &&hit_block)
