@@ -144,6 +144,11 @@ def classify(body, files, reg_fused, reg_pair, slow_lines=frozenset()):
     """-> {block: Counter(valu, salu, lds, vmem)}, list of basic blocks [(label, majority, n_valu)]"""
     slab = function_lines(os.path.join(CSRC, "extend_kernel.h"), r"void slab_setup\(")
     lane_stack = function_lines(os.path.join(CSRC, "extend_kernel.h"), r"^struct LaneStack")
+    ek = open(os.path.join(CSRC, "extend_kernel.h")).read().splitlines()
+    # (the cut-key helpers: one-liners called from the node step and from both pop loops)
+    cut_keys = [i for i, l in enumerate(ek, 1) if re.match(r"^__device__ __forceinline__ \w+ (pop_cut|push_cut|entry_within)\(", l)]
+    if len(cut_keys) != 3:
+        sys.exit("isa_regions: the cut-key helpers of extend_kernel.h are not where expected")
     bbs = [["entry", [], False]]
     cur_loc = None
     for l in body:
@@ -164,8 +169,9 @@ def classify(body, files, reg_fused, reg_pair, slow_lines=frozenset()):
             if f == "fused_kernel.h":
                 blk = reg_fused.get(cur_loc[1])
             elif f == "extend_kernel.h":
-                # (slab_setup is called from the ray set-up, LaneStack's methods from the node step, both pop loops and the shade block)
-                blk = None if slab[0] <= cur_loc[1] <= slab[1] or lane_stack[0] <= cur_loc[1] <= lane_stack[1] else "NODE"
+                # (slab_setup is called from the ray set-up, LaneStack's methods and the cut-key helpers from the node step, both pop loops and
+                # the shade block)
+                blk = None if slab[0] <= cur_loc[1] <= slab[1] or lane_stack[0] <= cur_loc[1] <= lane_stack[1] or cur_loc[1] in cut_keys else "NODE"
             elif f == "pair_leaf.h":
                 blk = reg_pair.get(cur_loc[1])
         slow = bool(cur_loc) and files.get(cur_loc[0], "") == "pt_math.h" and cur_loc[1] in slow_lines

@@ -235,10 +235,10 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
             uint32_t best_pos = PT_MISS, best_prim = PT_MISS;
             uint32_t cur = DONE;
             stk.clear();
-            auto pop = [&]() -> uint32_t {
+            auto pop = [&](uint32_t cut) -> uint32_t {  // (cut: the cut key of best_t, extend_kernel.h)
                 while (stk.has_entries()) {
                     const uint32_t e = stk.pop();
-                    if (__uint_as_float(e & 0xFFFFC000u) <= best_t) return e & 0x3FFFu;
+                    if (entry_within(e, cut)) return e & 0x3FFFu;
                 }
                 return DONE;
             };
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
                 bool do_node = have && !(cur & LEAF_BIT);
                 const int n_walk = __popcll(__ballot(have));
                 while (do_node) {
-                    cur = compact_node_step<TB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t) { return pop(); });
+                    cur = compact_node_step<TB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t, uint32_t kcut) { return pop(kcut); });
                     do_node = !(cur & LEAF_BIT);
                     if (__popcll(__ballot(do_node)) * 6 < n_walk) break;
                 }
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
                                 }
                             }
                         }
-                        cur = pop();
+                        cur = pop(pop_cut(best_t));
                     }
                     if (cur == DONE) {  // the sample's first hit is known
                         Guide v = {};

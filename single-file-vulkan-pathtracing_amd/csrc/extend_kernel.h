@@ -69,6 +69,16 @@ constexpr uint32_t LDS_NEG_AXIS = 16;  // ax / ay / az of a negative direction c
                                min_raw(__builtin_fmaf(fz.C, invf.z, of.z), best_t));                             \
         T = tn <= tf ? tn : INF;                                                                                 \
     }
+// PT_SLAB4 without best_t on the far side, for the one-dword keys of compact_node_step: there a child that starts behind the best hit is culled
+// by its KEY, at the push (cut keys, below), so the far distance only has to say whether the ray meets the box at all.
+#define PT_SLAB4_KEYED(T, C)                                                                                     \
+    {                                                                                                            \
+        const float tn = fmaxf(fmaxf(__builtin_fmaf(nx.C, inv.x, on.x), __builtin_fmaf(ny.C, inv.y, on.y)),      \
+                               max_raw_s(__builtin_fmaf(nz.C, inv.z, on.z), tmin));                              \
+        const float tf = fminf(fminf(__builtin_fmaf(fx.C, invf.x, of.x), __builtin_fmaf(fy.C, invf.y, of.y)),    \
+                               __builtin_fmaf(fz.C, invf.z, of.z));                                              \
+        T = tn <= tf ? tn : INF;                                                                                 \
+    }
 __device__ __forceinline__ float max_raw_s(float a, float uniform_b)
 {
     float r;
@@ -81,6 +91,20 @@ __device__ __forceinline__ float min_raw(float a, float b)
     asm("v_min_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+
+// Cut keys of the compact walk.  A one-dword entry is (bits(t) & 0xFFFFC000) | 14-bit child word, t a non-negative float: entries order like
+// their truncated distances as UNSIGNED integers, so "not behind the best hit", !(float(e & 0xFFFFC000) > best_t), is e <= bits(best_t) | 0x3FFF
+// on the raw entry -- no mask, no float compare (best_t >= +0 and never a NaN: the host runs these kernels for tmin > 0 only).  The cull is <=:
+// equal-t candidates survive for the lowest-primitive-id rule.
+//  * pop_cut: what a popped entry is compared with.  The BOTTOM entry's key is +0: within every cut.
+//  * push_cut: ... a child's key before it is pushed or entered.  Capped at FLT_MAX | 0x3FFF: a miss key (+inf | word) is above it whatever
+//    best_t is, +inf included, so one compare says "hit by the ray and not behind the best hit" and no miss is ever pushed.
+//    A stacked entry is within the cap, so entry_within(e, push_cut) == entry_within(e, pop_cut): a step may use its push_cut for both.
+// Against the exact `far = min(far, best_t)` of PT_SLAB4 the truncated compare lets through children that start within 2^-9 of best_t
+// behind it: visits, never hits.
+__device__ __forceinline__ uint32_t pop_cut(float best_t) { return __float_as_uint(best_t) | 0x3FFFu; }
+__device__ __forceinline__ uint32_t push_cut(float best_t) { return min(pop_cut(best_t), 0x7F7FFFFFu); }
+__device__ __forceinline__ bool entry_within(uint32_t e, uint32_t cut) { return e <= cut; }
 
 // The stack of one lane of the compact walk: one-dword entries in LDS, [level][thread], held as the ADDRESS of the lane's top entry instead
 // of a level number -- a push is an add and a store, a pop a read and a subtract, and no access forms
@@ -96,15 +120,17 @@ struct LaneStack {
     __device__ __forceinline__ bool empty() const { return top <= under; }
     __device__ __forceinline__ bool has_entries() const { return top > under; }
     __device__ __forceinline__ void clear() { top = under; }
+    // (the compiler forms the new pointer beside the old one and stores at an offset of the old: an add and a move.  An add in place -- the stride
+    // in a scalar register the compiler cannot see through -- was measured and left out: DESIGN.md section 6, "The cut key")
     __device__ __forceinline__ void push(uint32_t e) { top += STRIDE; *top = e; }
     __device__ __forceinline__ uint32_t peek() const { return *top; }
     __device__ __forceinline__ uint32_t pop() { const uint32_t e = *top; top -= STRIDE; return e; }
     __device__ __forceinline__ void drop() { top -= STRIDE; }
-    // k_fused keeps a BOTTOM entry under level 0 instead of asking "empty?" at every pop: key -inf (no best_t is below it) | the DONE code, so the
+    // k_fused keeps a BOTTOM entry under level 0 instead of asking "empty?" at every pop: key +0 (within every cut key) | the DONE code, so the
     // pop that runs out of entries takes it like any other and returns DONE.  It is written once per lane (arm_bottom) at the plan's level -1;
     // `under` of such a kernel is the address one level BELOW that (other LDS of the kernel: never accessed through the stack): a cleared stack
     // rests ON the bottom entry, a stack whose bottom entry was popped at `under`.
-    static constexpr uint32_t BOTTOM = 0xFF800000u | C14_DONE;
+    static constexpr uint32_t BOTTOM = 0x00000000u | C14_DONE;
     __device__ __forceinline__ void arm_bottom() { under[STRIDE] = BOTTOM; }
     __device__ __forceinline__ void clear_to_bottom() { top = under + STRIDE; }
     // k_fused: a lane that owns no path at all holds a pointer below `under`, where a level number held -1 (one dword below: never read or
@@ -117,16 +143,17 @@ __host__ __device__ constexpr size_t compact_stack_bytes(size_t threads, size_t 
 // ONE source of the compact node step of the scenes that live in LDS (k_extend_lds7 / _lds7p and k_fused instantiate it with their block
 // sizes): the BVH4 node's planes through the direction-sign offsets (PT_NODE_LOAD), four slab tests (PT_SLAB4), the children ordered as
 // one-dword keys -- entry distance truncated to its top 18 bits | 14-bit child word; formed BEFORE the sort they order like the distances
-// (non-negative floats compare like their bit patterns; a miss is +inf | word, above every hit), so a compare-exchange is v_min_u32 +
+// (non-negative floats compare like their bit patterns; a miss is +inf | word, above every hit and above the cut key), so a compare-exchange is v_min_u32 +
 // v_max_u32 instead of a compare and four selects: 14 VALU for the network instead of 25, and the pushes store the key as it is.
 // Children closer together than 2^-9 of their distance may swap places -- the visit order is not part of the result (closest t, lowest
 // primitive id).  The host runs these kernels for tmin > 0 only (entry distances >= tmin: no -0, whose bit pattern would sort last).
-// -> the nearest child's code, or what `pop(e_top)` returns when the ray misses all four; e_top: the stack's top entry as it was BEFORE the step's
+// -> the nearest child's code, or what `pop(e_top, kcut)` returns when the ray misses all four or all are behind the best hit (kcut: the step's
+// cut key, good for the pop test too); e_top: the stack's top entry as it was BEFORE the step's
 // pushes, read with the node's planes -- a step whose four children all miss pushed nothing, so that entry is what its pop looks at first (k_fused
 // takes it from this register instead of behind an LDS round trip; a caller that ignores it does not pay for the read).
 // STRIDE: threads per block (the stack is [level][thread]).
 // wide: the callers stage the nodes at LDS byte 0, so the node's address is cur * stride and nothing else.
-template <int STRIDE, class Pop>
+template <int STRIDE, bool CUT_PER_STEP = false, class Pop>
 __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32_t cur, const ptm::f3 &inv, const ptm::f3 &invf, const ptm::f3 &on,
                                                       const ptm::f3 &of, uint32_t ax, uint32_t ay, uint32_t az, float tmin, float best_t,
                                                       LaneStack<STRIDE> &stk, Pop &&pop)
@@ -138,10 +165,10 @@ __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32
     PT_NODE_LOAD(nd)
     const uint32_t e_top = stk.peek();
     const uint32_t w0 = __float_as_uint(cw.x), w1 = __float_as_uint(cw.y), w2 = __float_as_uint(cw.z), w3 = __float_as_uint(cw.w);
-    PT_SLAB4(t0, x)
-    PT_SLAB4(t1, y)
-    PT_SLAB4(t2, z)
-    PT_SLAB4(t3, w)
+    PT_SLAB4_KEYED(t0, x)
+    PT_SLAB4_KEYED(t1, y)
+    PT_SLAB4_KEYED(t2, z)
+    PT_SLAB4_KEYED(t3, w)
     uint32_t k0 = (__float_as_uint(t0) & 0xFFFFC000u) | w0, k1 = (__float_as_uint(t1) & 0xFFFFC000u) | w1,
              k2 = (__float_as_uint(t2) & 0xFFFFC000u) | w2, k3 = (__float_as_uint(t3) & 0xFFFFC000u) | w3;
 #define PT_KSWAP(A, B) { const uint32_t lo_ = min(A, B), hi_ = max(A, B); A = lo_; B = hi_; }
@@ -151,11 +178,17 @@ __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32
     PT_KSWAP(k1, k3)
     PT_KSWAP(k1, k2)
 #undef PT_KSWAP
-    constexpr uint32_t KINF = 0x7F800000u;
-    if (k3 < KINF) stk.push(k3);  // farthest first, so the nearest pending pops first
-    if (k2 < KINF) stk.push(k2);
-    if (k1 < KINF) stk.push(k1);
-    return k0 < KINF ? (k0 & 0x3FFFu) : pop(e_top);
+    // (a child behind the cut sorts behind every child within it: the order of those that are visited is what it was.  best_t does not change
+    // while a wave descends, so the cut is formed once per pass of the caller's node loop)
+    // CUT_PER_STEP (a kernel without a register to spare for it: k_extend_lds7 at seven waves): the cut is formed here in every step, behind
+    // the slab tests, instead of being held across the loop -- two instructions per step for a register
+    float cut_t = best_t;
+    if constexpr (CUT_PER_STEP) asm("" : "+v"(cut_t) : "v"(k3));
+    const uint32_t kcut = push_cut(cut_t);
+    if (entry_within(k3, kcut)) stk.push(k3);  // farthest first, so the nearest pending pops first
+    if (entry_within(k2, kcut)) stk.push(k2);
+    if (entry_within(k1, kcut)) stk.push(k1);
+    return entry_within(k0, kcut) ? (k0 & 0x3FFFu) : pop(e_top, kcut);
 }
 __device__ __forceinline__ void slab_setup(const ptm::f3 org, const ptm::f3 inv, ptm::f3 &invf, ptm::f3 &on, ptm::f3 &of)
 {
@@ -317,16 +350,18 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
         if (COMPACT) stk.clear();
         else sp = 0;
     };
-    auto pop = [&]() -> uint32_t {  // next subtree that can still contain the closest hit
-        if (COMPACT) {
-            while (stk.has_entries()) {
-                PT_COUNT_WAVE(c_pops);
-                if (COUNT) c_pop_lanes++;
-                const uint32_t e = stk.pop();
-                if (__uint_as_float(e & 0xFFFFC000u) <= best_t) return e & 0x3FFFu;
-            }
-            return DONE;
+    // next subtree that can still contain the closest hit.  COMPACT: one-dword entries, compared raw with `cut`, the cut key of best_t (a node
+    // step hands over its own); the other kernels: 64-bit entries, the distance compared as a float
+    auto pop_compact = [&](uint32_t cut) -> uint32_t {
+        while (stk.has_entries()) {
+            PT_COUNT_WAVE(c_pops);
+            if (COUNT) c_pop_lanes++;
+            const uint32_t e = stk.pop();
+            if (entry_within(e, cut)) return e & 0x3FFFu;
         }
+        return DONE;
+    };
+    auto pop_wide = [&]() -> uint32_t {
         while (sp > 0) {
             PT_COUNT_WAVE(c_pops);
             if (COUNT) c_pop_lanes++;
@@ -337,6 +372,10 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
             if (__uint_as_float((uint32_t)(e >> 32)) <= best_t) return (uint32_t)e;
         }
         return DONE;
+    };
+    auto pop = [&]() -> uint32_t {  // (behind a leaf step: best_t may have changed there, so the cut key is formed here)
+        if constexpr (COMPACT) return pop_compact(pop_cut(best_t));
+        else return pop_wide();
     };
 
     for (;;) {
@@ -407,7 +446,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                 if (lane == __ffsll((long long)__ballot(1)) - 1) c_node_steps++;  // one lane per wave step
             }
             if constexpr (LDS_SCENE && COMPACT) {
-                cur = compact_node_step<TB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t) { return pop(); });
+                cur = compact_node_step<TB, true>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t, uint32_t kcut) { return pop_compact(kcut); });
             } else {
             float t0, t1, t2, t3;
             uint32_t w0, w1, w2, w3;
@@ -458,7 +497,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
             if (t3 < INF) push(w3, t3);  // farthest first, so the nearest pending pops first
             if (t2 < INF) push(w2, t2);
             if (t1 < INF) push(w1, t1);
-            cur = t0 < INF ? w0 : pop();
+            cur = t0 < INF ? w0 : pop_wide();
             }
             }
             do_node = !VOTE && !(cur & LEAF_BIT);

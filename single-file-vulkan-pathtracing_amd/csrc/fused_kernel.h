@@ -205,7 +205,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     const float4 *wide = s_wide, *tri4 = s_tri;
     const float4 *verts = s_tri + 6 * (size_t)n_tris;
 
-    // (the lane's stack as the address of its top entry, over a BOTTOM entry (-inf | DONE) that every pop may take: the node step's read of the top
+    // (the lane's stack as the address of its top entry, over a BOTTOM entry (+0 | DONE) that every pop may take: the node step's read of the top
     // entry and both pop loops need no "empty?" compare -- LaneStack, extend_kernel.h.  Each lane writes and reads its own: no barrier)
     LaneStack<FTB> stk((lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.stack) - FTB + threadIdx.x);  // (`under`: a level below the BOTTOM entry, in the path state)
     stk.arm_bottom();
@@ -258,17 +258,19 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     // node loop) -- with selects inside, not branches (two more vector instructions for eight fewer scalar ones per pass).  r: PENDING for the lanes
     // that still look for an entry
     constexpr uint32_t PENDING = 0xFFFFFFFFu;
-    auto pop_pending = [&](uint32_t r) -> uint32_t {
+    // kcut: the cut key of the moment's best_t (pop_cut or push_cut, extend_kernel.h), compared with the raw entry
+    auto pop_pending = [&](uint32_t r, uint32_t kcut) -> uint32_t {
         while (__ballot(r == PENDING)) {
             if (r == PENDING) {
                 PT_FB(FB_POP)
-                const uint32_t e = stk.pop();  // (the BOTTOM entry ends the search: never behind best_t, its code is DONE)
-                r = !(__uint_as_float(e & 0xFFFFC000u) > best_t) ? (e & 0x3FFFu) : PENDING;
+                const uint32_t e = stk.pop();  // (the BOTTOM entry ends the search: within every cut key, its code is DONE)
+                r = entry_within(e, kcut) ? (e & 0x3FFFu) : PENDING;
             }
         }
         return r;
     };
-    auto pop = [&]() -> uint32_t { return pop_pending(PENDING); };
+    // (after a leaf step: its accept may have changed best_t, so the cut key is formed here)
+    auto pop = [&]() -> uint32_t { return pop_pending(PENDING, pop_cut(best_t)); };
 
     for (;;) {
         PT_FB(FB_ITER)
@@ -359,7 +361,9 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                                 rr.spill[idx] = make_float4(er, eg, eb, __uint_as_float(k == rc.term_cap ? SPILL_NONE : rr.spill_head[lslot]));
                                 rr.spill_head[lslot] = (uint32_t)idx;
                             } else {
-                                *rr.overflow = 1ull;
+                                // (not `= 1ull`: hipcc of ROCm 7.2 (AMD clang 22.0.0git), gfx950, kept that stored constant in a register pair across the whole loop, or, where
+                                // it had none, in 12 B of scratch; the atomic's operand is formed here.  k_fused_inst has registers to spare and keeps the store)
+                                atomicOr(rr.overflow, 1ull);
                             }
                         }
                         my_state[FS_A * FTB] = k + 1u;
@@ -621,12 +625,12 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         // (e_top, the stack's top entry read WITH the node's planes: a step whose four children all miss pushed nothing, so that entry is what
                         // its pop looks at first -- from a register instead of behind an LDS round trip: -1.8 %, profiles/r06r_speculative_pop.log.  At an
                         // empty stack the read lands on the BOTTOM entry)
-                        cur = compact_node_step<FTB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t e_top) -> uint32_t {
+                        cur = compact_node_step<FTB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t e_top, uint32_t kcut) -> uint32_t {
                             PT_FB(FB_POPTOP)
-                            // (the top entry as the pop's first candidate: within best_t -> taken -- the BOTTOM entry of an empty stack always is, and says
+                            // (the top entry as the pop's first candidate: within the cut key -> taken -- the BOTTOM entry of an empty stack always is, and says
                             // DONE; else the loop)
                             stk.drop();
-                            return pop_pending(!(__uint_as_float(e_top & 0xFFFFC000u) > best_t) ? (e_top & 0x3FFFu) : PENDING);
+                            return pop_pending(entry_within(e_top, kcut) ? (e_top & 0x3FFFu) : PENDING, kcut);
                         });
                     }
                     dn = cur < LEAF_BIT;
