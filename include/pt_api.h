@@ -691,7 +691,9 @@ enum pt_fused_block {
     PT_FB_ITER = 0,  /* one pass of the outer loop                                              */
     PT_FB_SHADE,     /* the shade block ran (lanes: with a finished ray, or asking for a slot)  */
     PT_FB_HIT,       /* ... state loads of the lanes with a hit record                          */
-    PT_FB_MISS,      /* ... miss.rmiss:8-12                                                     */
+    PT_FB_MISS,      /* ... miss.rmiss:8-12: counted lanes only -- the product kernel has no    */
+                     /*     code of its own for it (a miss is a record of the shade table, run  */
+                     /*     by PT_FB_SURFACE's instructions)                                    */
     PT_FB_SURFACE,   /* ... closesthit.rchit:33-41, 50-53: material, emission                   */
     PT_FB_ADD,       /* ... raygen.rgen:76 color += weight * emission                           */
     PT_FB_BOUNCE,    /* ... closesthit.rchit:56-57 + raygen.rgen:77-80                          */

@@ -23,7 +23,10 @@
 //   * control flow is written for the CU's ONE scalar unit (round 6: it was as busy as the vector units -- DESIGN.md section 6): the loops inside
 //     the persistent loop (node steps, pops) run on the WAVE's condition, with the lanes that are served behind one exec mask; no `continue`
 //     (one way back to the loop's head); selects instead of short-circuit branches where the wave runs both sides anyway; no loop-carried
-//     flag where a register says the same (`cur != DONE`); every kernel argument in a scalar register of its own (ptm::own_sgprs).
+//     flag where a register says the same (`cur != DONE`); every kernel argument in a scalar register of its own (ptm::own_sgprs).  The shade
+//     block's step (1) follows the same rule: a pass of ~45 lanes holds misses and surface hits, emitters and others, ended and continuing paths
+//     all at once, so a miss is one more record of the shade table (no miss / surface split), one sample group adds its term without a vote
+//     (adding +-0 keeps an accumulator's bits), and a path's end is selects -- only a complete slot, which stores, is a branch.
 //
 // Radiance goes where the wavefront pipeline puts it (struct Radiance): one accumulator per slot written when the slot is
 // complete (one sample group), or the ordered term logs that k_resolve replays (several groups) -- k_resolve is shared.
@@ -76,7 +79,7 @@ enum : int { FS_NEE_POS = 0, FS_NEE_R, FS_NEE_G, FS_NEE_B, FS_NEE_FIELDS };
 #endif
 
 // ---- the LDS plan, in bytes from LDS byte 0: fused.hip sizes the launch with it, the kernel takes its pointers from it.
-// nodes | three permuted triangle copies | shade4 | tangent frames || path state | the waves' tile words | stack (the BOTTOM entry's level, then
+// nodes | three permuted triangle copies | shade4, then the miss record | tangent frames || path state | the waves' tile words | stack (the BOTTOM entry's level, then
 // level 0 ...: LaneStack) | extra
 // The path state lies IN FRONT of the stack: LaneStack's `under`, one level below the BOTTOM entry, is an address inside it -- compared with, never
 // read or written through -- so the stack costs no level of its own for it (one more 2-KB level is the third block per CU).
@@ -90,7 +93,7 @@ __host__ __device__ constexpr FusedLds fused_lds(uint32_t n_wide, uint32_t n_tri
     l.wide = 0u;
     l.tri = l.wide + (uint32_t)lds_nodes_bytes(n_wide);
     l.shade = l.tri + (uint32_t)lds_tris_bytes(n_tris);
-    l.frame = l.shade + (uint32_t)sizeof(float4) * 3u * n_tris;
+    l.frame = l.shade + (uint32_t)sizeof(float4) * 3u * (n_tris + 1u);  // (record n_tris: the miss -- weight * env as the Ke of a hit that ends its path)
     l.state = l.frame + (uint32_t)sizeof(float4) * 2u * n_tris;
     l.wtile = l.state + (uint32_t)sizeof(uint32_t) * FS_FIELDS * FTB;
     l.stack = l.wtile + (uint32_t)sizeof(uint32_t) * (FTB / 64) * PT_FUSED_WTILES;
@@ -132,8 +135,8 @@ enum FusedBlock : int {
     FB_ITER = 0,   // one pass of the outer loop (its head: the ballots that decide what runs)
     FB_SHADE,      // the shade block ran (lanes: those inside it, with a hit or asking for a slot)
     FB_HIT,        // (1) state loads of the lanes with a hit record
-    FB_MISS,       // ... miss.rmiss: weight * env
-    FB_SURFACE,    // ... closesthit.rchit: the triangle's shading record, weight * Ke
+    FB_MISS,       // ... miss.rmiss: weight * env -- the lanes are counted; the product kernel has no code of its own for it (FB_SURFACE's runs it; NEE has)
+    FB_SURFACE,    // ... closesthit.rchit: the shading record (a triangle's, or the miss record), weight * Ke (lanes: the surface hits)
     FB_ADD,        // ... color += (LDS accumulator or term log)
     FB_BOUNCE,     // ... position, tangent frame, direction, brdf * cos / pdf (raygen.rgen:77-80)
     FB_NEXT,       // ... path ended: next sample of the slot, or the slot is complete
@@ -201,6 +204,13 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     lds_stage_nodes<FTB, true>(s_wide, g_wide, n_wide);  // (child words -> 14-bit codes: extend_kernel.h COMPACT)
     lds_stage_tris<FTB, true>(s_tri, g_tri4, n_tris, s_shade, g_shade4);  // (the kz = 2 copy is also what the shade block reads)
     for (uint32_t i = threadIdx.x; i < 2 * n_tris; i += FTB) s_frame[i] = g_frame4[i];
+    // (a miss is record n_tris of the shade table: env where a triangle's record has its Ke -- step (1) reads it through min(pos, n_tris), PT_MISS
+    // being all ones.  Its other words are never used: a miss does not bounce)
+    if (threadIdx.x == 0) {
+        s_shade[3 * n_tris + 0] = make_float4(0.f, 0.f, 0.f, 0.f);
+        s_shade[3 * n_tris + 1] = make_float4(0.f, 0.f, rc.env[0], rc.env[1]);
+        s_shade[3 * n_tris + 2] = make_float4(rc.env[2], 0.f, 0.f, 0.f);
+    }
     __syncthreads();
     const float4 *wide = s_wide, *tri4 = s_tri;
     const float4 *verts = s_tri + 6 * (size_t)n_tris;
@@ -225,6 +235,12 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     if constexpr (COUNT) {                                                                              \
         const unsigned long long m_fb = __ballot(1);                                                    \
         if (lane == __ffsll((long long)m_fb) - 1) { lds_u32 *s_fb = fb_of_wave(); s_fb[2 * (B)] += 1u; s_fb[2 * (B) + 1] += (uint32_t)__popcll(m_fb); } \
+    }
+    // (the twin's count of a block that the product kernel runs as selects inside another block's code: the lanes for which C holds.  No region of
+    // its own for scripts/isa_regions.py, which reads the markers spelled PT_FB( outside of #define lines)
+#define PT_FB_IF(C, B)                                                                                  \
+    if constexpr (COUNT) {                                                                              \
+        if (C) { PT_FB(B) }                                                                             \
     }
     // (a lane traces a ray <=> cur != DONE: the shade block sets cur = 0 with the new ray, the walk ends with cur == DONE.  No flag is kept: a
     // loop-carried bool lives in a lane mask, and every ballot of one costs a v_cndmask + v_cmp to clear its inactive lanes -- a compare does not)
@@ -310,7 +326,21 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     bpos = npos;
                     // (the hit's position was the shadow ray's origin: the permuted copy the walk kept, put back in order -- selects, same bits)
                     org = { ptm::sel3(pre.kz, orgp.z, orgp.y, orgp.x), ptm::sel3(pre.kz, orgp.x, orgp.z, orgp.y), ptm::sel3(pre.kz, orgp.y, orgp.x, orgp.z) };
-                } else if (pos == PT_MISS) {  // miss.rmiss:10-11 then raygen.rgen:76, 81-83
+                } else if (!NEE) {
+                    // miss.rmiss:10-11 / closesthit.rchit:50-65, then raygen.rgen:76: ONE sequence for both kinds of lanes.  A pass holds miss lanes and
+                    // surface lanes nearly always, so a miss / surface split would run both sides and pay the masks between them; a miss reads record
+                    // n_tris of the shade table (env where a triangle has its Ke: `wr * env[0]` has the same bits from LDS as from a scalar register) and
+                    // ends its path by a select.  The product kernel has no miss block of its own; the twin counts the two kinds of lanes
+                    if (pos != PT_MISS) { PT_FB(FB_SURFACE) }
+                    PT_FB_IF(pos == PT_MISS, FB_MISS)
+                    const bool miss = pos == PT_MISS;
+                    const uint32_t rec = min(pos, n_tris);  // (PT_MISS is all ones)
+                    const float4 s1 = s_shade[3 * rec + 1], s2 = s_shade[3 * rec + 2];
+                    er = wr * s1.z; eg = wg * s1.w; eb = wb * s2.x;
+                    add = miss | !(er == 0.f && eg == 0.f && eb == 0.f);  // (a miss always adds: env = 0 is a logged term too)
+                    depth++;  // (a miss: its depth is set to 0 below, like that of every ended path)
+                    terminated = miss | (depth >= rc.max_depth);  // raygen.rgen:62, 81-83
+                } else if (pos == PT_MISS) {  // (from here: NEE) miss.rmiss:10-11 then raygen.rgen:76, 81-83
                     PT_FB(FB_MISS)
                     er = wr * rc.env[0]; eg = wg * rc.env[1]; eb = wb * rc.env[2];
                     add = true;
@@ -342,7 +372,14 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 const bool logs = GROUPED || (HYB && slot >= rc.n_head);  // (a slot whose radiance goes through the term log)
                 const uint32_t lslot = HYB ? slot - rc.n_head : slot;     // ... its place in the log arrays
                 const uint32_t lstride = HYB ? rc.n_tail : rc.n_slots;
-                if (add) {
+                if constexpr (MODE == 0 && !NEE) {
+                    // one sample group: every lane adds, without the vote.  An accumulator starts at +0 and a sum is -0 only when both terms are, so it
+                    // is never -0 and `acc + (+-0)` keeps its bits: the same film as with the skip, and `add` with its three compares is dead here
+                    if (add) { PT_FB(FB_ADD) }
+                    my_state[FS_A * FTB] = __float_as_uint(__uint_as_float(my_state[FS_A * FTB]) + er);
+                    my_state[FS_B * FTB] = __float_as_uint(__uint_as_float(my_state[FS_B * FTB]) + eg);
+                    my_state[FS_C * FTB] = __float_as_uint(__uint_as_float(my_state[FS_C * FTB]) + eb);
+                } else if (add) {  // (a logged term changes nterm: modes 1 and 2 keep the vote)
                     PT_FB(FB_ADD)
                     if (!logs) {
                         my_state[FS_A * FTB] = __float_as_uint(__uint_as_float(my_state[FS_A * FTB]) + er);
@@ -369,7 +406,26 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         my_state[FS_A * FTB] = k + 1u;
                     }
                 }
-                if (!terminated) {
+                if constexpr (!GROUPED && !NEE) {
+                    // the path's end as selects: a pass holds ended and continuing paths nearly always.  Only a complete slot stays a branch (its
+                    // store).  (Several groups keep the branch below: their `more` costs two divisions by run-time constants)
+                    if (terminated) { PT_FB(FB_NEXT) }
+                    bounce = !terminated;  // (the bounce itself: step (3), beside the camera rays)
+                    sample += terminated ? 1u : 0u;
+                    depth = terminated ? 0u : depth;
+                    const bool more = HYB ? (!logs && sample < rc.head_samples)  // (a tail slot is one sample)
+                                          : sample < rc.spp;                      // (one group: the slot is the pixel's whole frame)
+                    need_primary = terminated & more;  // the slot's next sample: raygen.rgen:45-60
+                    if (terminated & !more) {  // the slot is complete
+                        PT_FB(FB_DONE)
+                        if (!logs) rad.color[slot] = make_float4(__uint_as_float(my_state[FS_A * FTB]), __uint_as_float(my_state[FS_B * FTB]),
+                                                                   __uint_as_float(my_state[FS_C * FTB]), 0.f);
+                        else if (!dbg_no_nterm) rad.nterm[lslot] = my_state[FS_A * FTB];
+                        stk.park();  // (no path)
+                        freed = true;
+                        dev.slot_end(slot);
+                    }
+                } else if (!terminated) {
                     bounce = !shadow;  // (the bounce itself: step (3), beside the camera rays -- NEE: after the shadow ray, if there is one)
                     got_ray = shadow;
                 } else {
@@ -377,10 +433,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     sample++;
                     depth = 0;
                     bool more;
-                    if (HYB) {
-                        more = !logs && sample < rc.head_samples;  // (a tail slot is one sample)
-                    } else if (!GROUPED) {
-                        more = sample < rc.spp;  // (one group: the slot is the pixel's whole frame)
+                    if (!GROUPED) {
+                        more = sample < rc.spp;  // (NEE, one group: the slot is the pixel's whole frame)
                     } else {
                         const uint32_t lane_slot = rc.div_spl.div(slot);  // = frame lane * groups + sample group (slot_pixel)
                         const uint32_t g = lane_slot - rc.div_groups.div(lane_slot) * rc.groups;
@@ -684,6 +738,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     if constexpr (COUNT) {  // (pt_get_block_counts: stats[PT_N_STATS + 2 * block] wave executions, [+ 1] lanes inside them)
         if (lane < 2 * FB_N) atomicAdd(stats + PT_N_STATS + lane, (unsigned long long)fb_of_wave()[lane]);
     }
+#undef PT_FB_IF
 #undef PT_FB
 }
 
