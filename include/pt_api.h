@@ -595,6 +595,62 @@ typedef struct pt_denoise_history_params {
 void pt_denoise_history_params_default(pt_denoise_history_params *p);
 pt_status pt_film_denoise_history(pt_film *film, const pt_denoise_history_params *params, void *device_out_rgb_f32, float *device_ms);
 
+/* ---- guide-driven upsampling of a low-resolution film -----------------------------------------------------------------------------------
+ * pt_film_upsample(film, lo, params, device_out_rgb_f32, device_ms) brings the radiance of `lo` (w' x h', w' <= w, h' <= h) to the size of
+ * `film` (w x h).  Only the guides of `film` are read (pt_render_aov at the camera); `lo` holds radiance (pt_render) and guides of its own
+ * (pt_render_aov), rendered at the same (cam_origin, cam_target): primary_target maps a pixel to ((x + jitter) / width) * 2 - 1 with no
+ * aspect term, so a film of any size at one camera sees the same view.  All arithmetic is binary32, every operation rounded on its own, no
+ * contraction, denormals kept, operation order as written; NaN planes are outside the contract.  A, N, E, Z, a are the full-size guides as
+ * stored; primed names are lo's; S' is the plane params.source names (lo's film C', or the film-owned result of lo's last
+ * pt_film_denoise*); inv_n and the 1e-12f of x_z are pt_film_denoise's.
+ *   per lo pixel q:
+ *                  D'_c = max(A'_c + (1 - a'), 0.001f);   I'_c(q) = (S'_c - E'_c) / D'_c        (pt_film_denoise's demodulation of S')
+ *   once:          sx = (float)w' / (float)w;   sy = (float)h' / (float)h                        (one correctly rounded division each)
+ *   per full-size pixel p = (x, y):
+ *                  D_c = max(A_c + (1 - a), 0.001f)
+ *                  fx = ((float)x + 0.5f) * sx - 0.5f;   x0 = floor(fx);   bx = fx - x0;        fy, y0, by likewise with y and sy
+ *   FIRST RING     num_c = den = 0; for j = 0, 1 (outer), i = 0, 1 (inner), q = (x0 + i, y0 + j), taps outside lo's image skipped:
+ *                  wq  = (i ? bx : 1 - bx) * (j ? by : 1 - by)
+ *                  dn  = N_p - N'_q;   x_n = ((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) * inv_n
+ *                  dz  = Z_p - Z'_q;   x_z = (dz*dz) / ((sigma_depth*sigma_depth) * (Z_p*Z_p + Z'_q*Z'_q) + 1e-12f)
+ *                  t   = max(0, 1 - (x_n + x_z) * 0.0625f);   t = t*t, four times
+ *                  wt  = wq * t;   num_c = num_c + wt * I'_c(q);   den = den + wt
+ *                  if den >= 0.01f:  I_c = num_c / den
+ *   SECOND RING    otherwise (a NaN den included): num_c = den = 0; for j = -1 .. 2 (outer), i = -1 .. 2 (inner), the same q, taps outside
+ *                  lo's image skipped, t as above:
+ *                  num_c = num_c + t * I'_c(q);   den = den + t                                  (the guides' weight alone)
+ *                  if den >= 0.01f:  I_c = num_c / den
+ *   NEAREST        otherwise:  qn = (min(max((int)floor(fx + 0.5f), 0), w' - 1), likewise y);   I_c = I'_c(qn)
+ *   remodulation   out_c = I_c * D_c + E_c
+ * Demodulating with lo's albedo and remodulating with the full-size one carries albedo and emission edges at full resolution; a miss pixel
+ * has D = 1, and the depth stop separates it from a surface.  The second ring serves silhouettes and thin features whose four taps all lie
+ * on the other surface; the nearest tap is the last resort, so that every pixel has a defined value.  With w' = w / 2 the bilinear weights
+ * are exactly {0.25, 0.75}; with w' = w, fx = x and bx = 0.  The defaults (1.0, 0.2) are the best of a 3 x 3 grid around the denoiser's
+ * (0.5, 0.1) on the Cornell box at 128 x 96 from 64 x 48; nobody has tuned them at 1080p.
+ * The output goes to device_out_rgb_f32: caller-owned DEVICE memory of w*h*3 floats (a torch tensor's data_ptr()), which has no bgra8
+ * form; with NULL it goes to a plane `film` owns, with its bgra8 form by k_resolve's clamp and quantise rule (pt_film_denoise's text above),
+ * read through pt_film_read_upsampled.  Blocking; runs on the context's stream, ordered after the work already queued there; device_ms (may
+ * be NULL): device time from the first kernel to the last.  The call writes only the output and scratch: both films' C, bgra8, guides, M,
+ * L, Q, lo's denoised plane and pt_stats stay as they were.  The scratch is lo's denoiser scratch (the records {I'.rgb, 0} and {N'.xyz, Z'}
+ * of its pixels, 48 B per lo pixel, made here if lo never denoised) and the film-owned output (16 B per pixel of `film`, on first need);
+ * both count against the context's memory budget with their film's other workspaces and are freed by pt_film_destroy.
+ * PT_ERR_INVALID_ARG, nothing written and nothing launched: NULL film, lo or params; lo == film; films of different contexts; w' > w or
+ * h' > h; either film without guides; an unknown source; PT_UPSAMPLE_SRC_DENOISED when lo has no film-owned denoised result; a sigma that
+ * is not finite and > 0; a nonzero reserved word.  PT_ERR_OOM: the scratch does not fit pt_tuning.mem_budget_mb (both films are left as
+ * they were).  The caveat about (rank, world) films is pt_film_denoise's.                                                              */
+enum { PT_UPSAMPLE_SRC_FILM = 0, PT_UPSAMPLE_SRC_DENOISED = 1 };
+typedef struct pt_upsample_params {
+    float    sigma_normal;     /* default 1.0  */
+    float    sigma_depth;      /* default 0.2  */
+    uint32_t source;          /* PT_UPSAMPLE_SRC_*: lo's film C', or the film-owned result of lo's last pt_film_denoise*; default _SRC_FILM */
+    uint32_t reserved[5];      /* must be 0 */
+} pt_upsample_params;          /* 32 bytes */
+void pt_upsample_params_default(pt_upsample_params *p);
+pt_status pt_film_upsample(pt_film *film, pt_film *lo, const pt_upsample_params *params, void *device_out_rgb_f32, float *device_ms);
+/* The film-owned result of the last pt_film_upsample(..., NULL, ...): rgb width*height*3 floats, bgra width*height*4 bytes; either may be
+ * NULL.  PT_ERR_INVALID_ARG before any upsample into the film's own plane.                                                             */
+pt_status pt_film_read_upsampled(pt_film *film, float *rgb, uint8_t *bgra);
+
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {
     uint32_t prim;  /* gl_PrimitiveID, 0xFFFFFFFF = miss                                   */

@@ -113,6 +113,14 @@ class DenoiseHistoryParams(C.Structure):
                 ("min_history", C.c_float), ("n_max", C.c_float), ("step_frames", C.c_uint32), ("reserved", C.c_uint32 * 1)]
 
 
+UPSAMPLE_SRC_FILM, UPSAMPLE_SRC_DENOISED = 0, 1   # include/pt_api.h PT_UPSAMPLE_SRC_*
+
+
+class UpsampleParams(C.Structure):
+    """include/pt_api.h pt_upsample_params: the guide-driven upsampling of pt_film_upsample."""
+    _fields_ = [("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("source", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
 REPROJECT_MATCH_ID = 1   # include/pt_api.h PT_REPROJECT_MATCH_ID
 
 
@@ -156,7 +164,8 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
                "pt_device_alloc", "pt_device_free", "pt_device_read", "pt_device_write", "pt_ctx_get_tuning", "pt_ctx_set_tuning",
                "pt_scene_snapshot_previous", "pt_film_enable_motion", "pt_film_read_motion", "pt_motion_params_default", "pt_film_motion",
-               "pt_film_reproject_motion", "pt_denoise_history_params_default", "pt_film_denoise_history"]
+               "pt_film_reproject_motion", "pt_denoise_history_params_default", "pt_film_denoise_history",
+               "pt_upsample_params_default", "pt_film_upsample", "pt_film_read_upsampled"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium"]
 
@@ -243,6 +252,11 @@ def lib_amd():
             L.pt_denoise_history_params_default.argtypes = [C.POINTER(DenoiseHistoryParams)]
             L.pt_denoise_history_params_default.restype = None
             L.pt_film_denoise_history.argtypes = [vp, C.POINTER(DenoiseHistoryParams), vp, C.POINTER(C.c_float)]
+        if hasattr(L, "pt_film_upsample"):   # (guide-driven upsampling; as above)
+            L.pt_upsample_params_default.argtypes = [C.POINTER(UpsampleParams)]
+            L.pt_upsample_params_default.restype = None
+            L.pt_film_upsample.argtypes = [vp, vp, C.POINTER(UpsampleParams), vp, C.POINTER(C.c_float)]
+            L.pt_film_read_upsampled.argtypes = [vp, vp, vp]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -399,6 +413,10 @@ def denoise_variance_default_params():
 
 def denoise_history_default_params():
     return _default_params(DenoiseHistoryParams, "pt_denoise_history_params_default")
+
+
+def upsample_default_params():
+    return _default_params(UpsampleParams, "pt_upsample_params_default")
 
 
 def reproject_default_params():
@@ -719,6 +737,31 @@ class Film:
         ms = C.c_float(0.0)
         self.ctx._check(getattr(lib_amd(), fn)(self.h, prev.h if prev is not None else None, C.byref(p), C.byref(ms)))
         return ms.value
+
+    def upsample(self, lo, sigma_normal=None, sigma_depth=None, source=None, device_out=None, params=None):
+        """Guide-driven upsampling (include/pt_api.h pt_film_upsample): the radiance of `lo`, a smaller film with guides of its own rendered
+        at the same camera, brought to this film's size by this film's guides -> device ms.  Arguments left at None take
+        pt_upsample_params_default's values (or those of `params`, an UpsampleParams, which is not modified).  source: UPSAMPLE_SRC_FILM
+        (lo's film) or UPSAMPLE_SRC_DENOISED (the film-owned result of lo's last denoise).  device_out: None for a plane this film owns
+        (read_upsampled / read_upsampled_bgra8), or a device pointer to width*height*3 floats (a torch tensor's data_ptr())."""
+        p = UpsampleParams.from_buffer_copy(params) if params is not None else upsample_default_params()
+        for name, v in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("source", source)):
+            if v is not None:
+                setattr(p, name, v)
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_film_upsample(self.h, lo.h if lo is not None else None, C.byref(p), C.c_void_p(device_out) if device_out else None, C.byref(ms)))
+        return ms.value
+
+    def read_upsampled(self):
+        """-> float32 [H, W, 3]: the film-owned result of the last upsample(device_out=None)."""
+        a = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        self.ctx._check(lib_amd().pt_film_read_upsampled(self.h, a.ctypes.data, None))
+        return a
+
+    def read_upsampled_bgra8(self):
+        a = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self.ctx._check(lib_amd().pt_film_read_upsampled(self.h, None, a.ctypes.data))
+        return a
 
     def read_denoised(self):
         """-> float32 [H, W, 3]: the film-owned result of the last denoise(device_out=None)."""

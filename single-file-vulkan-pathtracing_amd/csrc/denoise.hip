@@ -290,11 +290,8 @@ pt_status dn_run(pt_film *f, uint32_t iterations, float sigma_normal, float sigm
     pt_film::Denoise &d = f->dn;
     const size_t n_pix = (size_t)f->w * f->h;
     // each set whole or not at all, so that a refused call leaves the film as it was; all of the film's workspaces count against the budget
-    const size_t others = f->work.bytes + f->aov.bytes, px4 = sizeof(float4) * n_pix;
-    pt_status rc = PT_OK;
-    if (!d.d_guide)
-        rc = pt_scratch_alloc(ctx, "denoiser workspace", { pt_buf_of(d.d_guide, px4), pt_buf_of(d.d_illum[0], px4), pt_buf_of(d.d_illum[1], px4) }, &d.bytes, 0, others,
-                              ctx->mem_budget);
+    const size_t others = f->work.bytes + f->aov.bytes + f->up.bytes;
+    pt_status rc = ptd_scratch(f);
     if (rc == PT_OK && !device_out && !d.d_out)
         rc = pt_scratch_alloc(ctx, "denoiser workspace", { pt_buf_of(d.d_out, sizeof(float) * 3 * n_pix), pt_buf_of(d.d_out_bgra, 4 * n_pix) }, &d.bytes, 0, others,
                               ctx->mem_budget);
@@ -350,6 +347,27 @@ pt_status dn_checks(pt_film *f, const char *name, bool need_m, bool need_l, uint
 }
 
 }  // namespace
+
+// the records' planes (48 B per pixel), made by the first call that needs them and kept
+pt_status ptd_scratch(pt_film *f)
+{
+    pt_film::Denoise &d = f->dn;
+    if (d.d_guide) return PT_OK;
+    const size_t px4 = sizeof(float4) * (size_t)f->w * f->h;
+    return pt_scratch_alloc(f->ctx, "denoiser workspace", { pt_buf_of(d.d_guide, px4), pt_buf_of(d.d_illum[0], px4), pt_buf_of(d.d_illum[1], px4) }, &d.bytes, 0,
+                            f->work.bytes + f->aov.bytes + f->up.bytes, f->ctx->mem_budget);
+}
+
+// pt_film_upsample's records of a low-resolution film: k_dn_prepare over f with `src` (f's film or its denoised plane) as the film plane
+void ptd_prepare_records(pt_film *f, const float *src, hipStream_t st)
+{
+    const pt_film::Aov &a = f->aov;
+    const DnPlanes pl = { src, static_cast<const float *>(a.plane[PT_AOV_ALBEDO]), static_cast<const float *>(a.plane[PT_AOV_NORMAL]),
+                          static_cast<const float *>(a.plane[PT_AOV_EMISSION]), static_cast<const float *>(a.plane[PT_AOV_DEPTH]),
+                          static_cast<const float *>(a.plane[PT_AOV_ALPHA]) };
+    const size_t n_pix = (size_t)f->w * f->h;
+    k_dn_prepare<<<(uint32_t)((n_pix + TB - 1) / TB), TB, 0, st>>>((uint32_t)n_pix, pl, f->dn.d_illum[0], f->dn.d_guide);
+}
 
 void ptd_free(pt_film *f)
 {

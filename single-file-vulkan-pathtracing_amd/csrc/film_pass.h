@@ -1,4 +1,4 @@
-// film_pass.h -- the launch shape of every per-pixel film pass (denoise.hip, reproject.hip, motion.hip): a block is 64 x 4 pixels, a wave
+// film_pass.h -- the launch shape of every per-pixel film pass (denoise.hip, reproject.hip, motion.hip, upsample.hip): a block is 64 x 4 pixels, a wave
 // one row of 64, so that a wave's loads of a row are consecutive records and a row test is wave-uniform.  The constants and fp_grid compile
 // for the host too (the *_kernel.h headers and the tests/*_host.cpp programs read them); fp_pixel is the device's.
 // Wants declared before it: TB (pt_internal.h; tests/kernel_host.h).

@@ -359,6 +359,7 @@ void pt_film_destroy(pt_film *f)
     ptw_free_work(f);
     pta_free(f);
     ptd_free(f);
+    ptu_free(f);
     pt_planes_free(f);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
@@ -584,6 +585,33 @@ pt_status pt_film_reproject_motion(pt_film *f, pt_film *prev, const pt_reproject
     if (!f || !p) return PT_ERR_INVALID_ARG;
     PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
     return guarded(f->ctx, [&] { return ptr_reproject(f, prev, p, device_ms, true); });
+}
+
+void pt_upsample_params_default(pt_upsample_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->sigma_normal = 1.0f;   // the best of the grid of DESIGN.md section 18
+    p->sigma_depth = 0.2f;
+    p->source = PT_UPSAMPLE_SRC_FILM;
+}
+
+pt_status pt_film_upsample(pt_film *f, pt_film *lo, const pt_upsample_params *p, void *device_out_rgb_f32, float *device_ms)
+{
+    if (!f || !lo || !p) return PT_ERR_INVALID_ARG;
+    PT_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return guarded(f->ctx, [&] { return ptu_upsample(f, lo, p, device_out_rgb_f32, device_ms); });
+}
+
+pt_status pt_film_read_upsampled(pt_film *f, float *rgb, uint8_t *bgra)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = f->ctx;
+    if (!f->up.have_out) { ctx->err = "no upsampled image: pt_film_upsample with a NULL output first"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rgb) PT_HIP(ctx, hipMemcpy(rgb, f->up.d_out, sizeof(float) * 3 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
+    if (bgra) PT_HIP(ctx, hipMemcpy(bgra, f->up.d_out_bgra, 4 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)

@@ -236,6 +236,13 @@ struct pt_film {
         bool have_out = false;                        // a denoise has written d_out / d_out_bgra
         size_t bytes = 0;                             // device bytes of all of the above
     } dn;
+    // pt_film_upsample (upsample.hip): the film-owned result of the full-size film, made by the first call that asks for it and kept.
+    struct Upsample {
+        float *d_out = nullptr;                       // w*h*3 floats ...
+        uint8_t *d_out_bgra = nullptr;                // ... and its bgra8 form
+        bool have_out = false;                        // an upsample has written d_out / d_out_bgra
+        size_t bytes = 0;                             // device bytes of both
+    } up;
     // pt_film_enable_moments: the running mean of the squared frame colour, blended by the resolve kernel beside the film (shade_kernels.hip
     // k_resolve_m2).  A film plane like the guides, not a workspace.
     struct Moments : pt_plane<float> {                // w*h*3 floats
@@ -256,7 +263,7 @@ struct pt_film {
         }                                                                                         \
     } while (0)
 
-// ---- what every film pass (denoise.hip, reproject.hip, motion.hip) takes its timing and its refusals from ("Film passes")
+// ---- what every film pass (denoise.hip, reproject.hip, motion.hip, upsample.hip) takes its timing and its refusals from ("Film passes")
 // The timed tail: ev_a, what `launches(stream)` queues, ev_b, the wait; the device time between the events into *device_ms (nullable).
 template <class F>
 inline pt_status pt_timed_pass(pt_ctx *ctx, float *device_ms, F &&launches)
@@ -381,6 +388,11 @@ pt_status ptd_denoise(pt_film *f, const pt_denoise_params *p, void *device_out, 
 pt_status ptd_denoise_variance(pt_film *f, const pt_denoise_variance_params *p, void *device_out, float *device_ms);
 pt_status ptd_denoise_history(pt_film *f, const pt_denoise_history_params *p, void *device_out, float *device_ms);
 void ptd_free(pt_film *f);
+pt_status ptd_scratch(pt_film *f);  // the records' planes d_guide / d_illum of the film, if it has none yet (counted against the budget)
+void ptd_prepare_records(pt_film *f, const float *src, hipStream_t st);  // k_dn_prepare over f into them, `src` standing in for the film plane
+// upsample.hip: `lo`'s radiance to the size of `f` by f's guides (everything but the null checks is validated there)
+pt_status ptu_upsample(pt_film *f, pt_film *lo, const pt_upsample_params *p, void *device_out, float *device_ms);
+void ptu_free(pt_film *f);
 // reproject.hip: temporal accumulation -- `f` takes over the history of `prev` (null: starts a sequence); validates everything but the null checks
 // motion: pt_film_reproject_motion -- the reprojection starts from the film's plane Q
 pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p, float *device_ms, bool motion = false);

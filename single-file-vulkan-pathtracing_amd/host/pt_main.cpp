@@ -7,7 +7,7 @@
 //           [--frames 1] [--spp 32] [--depth 8] [--device 0] [--batch N]
 //           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--denoise [N] [--sigma-color S]] [--pipeline auto|wavefront|fused|nee] [--nee]
 //           [--ranks N [--devices 0,1,...] [--selftest]]
-//           [--temporal K --cam-step dx,dy,dz]
+//           [--temporal K --cam-step dx,dy,dz] [--render-scale S]
 // --ranks N renders with N GPUs: one host thread and one context per GPU, the 8x8 pixel tiles interleaved over the
 // ranks (pt_params.rank/world), and ONE RCCL gather of the packed tiles to rank 0 per presented image
 // (pt_film_present); the image written is the presented one.  --selftest: before rendering, every rank presents a film whose own tiles
@@ -25,6 +25,10 @@
 // cleared before its step; guides at frame 0).  The image written is the last step's film; --denoise [N] filters that film.  With
 // --sigma-color S both films get their second-moment plane (pt_film_reproject blends it along) and the denoised files hold the result of
 // pt_film_denoise_history (sigma_color = S, the rest pt_denoise_history_params_default's): the variance-guided filter with a variance per pixel.
+// --render-scale S (an integer >= 2; one rank, no --temporal, --aov or --sigma-color): the radiance and a set of guides are rendered at
+// ceil(width / S) x ceil(height / S), the full-size guides at width x height, and pt_film_upsample brings the radiance to full size;
+// --denoise [N] filters the low-resolution film first and the upsample takes that result (PT_UPSAMPLE_SRC_DENOISED).  --ppm / --pfm hold the
+// upsampled image.
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -62,6 +66,7 @@ struct Options {
     uint32_t temporal = 0;       // --temporal K: K time steps accumulated by pt_film_reproject (0: off)
     float cam_step[3] = { 0.f, 0.f, 0.f };   // --cam-step dx,dy,dz: the camera's move per time step
     bool have_cam_step = false;
+    uint32_t render_scale = 0;   // --render-scale S: radiance at 1 / S of the size, brought back by pt_film_upsample (0: off)
 };
 
 // out.ppm -> out.denoised.ppm
@@ -326,6 +331,58 @@ void run_temporal(const Options &o, const pth_scene &hs, RankResult &res, std::v
     pt_scene_destroy(scene);
     pt_ctx_destroy(ctx);
 }
+
+// --render-scale S: radiance at ceil(width / S) x ceil(height / S), guides at both sizes, and pt_film_upsample brings the image to full size.
+void run_scaled(const Options &o, const pth_scene &hs, RankResult &res, std::vector<float> *image_f32, std::vector<uint8_t> *image_bgra8)
+{
+    pt_ctx *ctx = nullptr;
+    pt_scene *scene = nullptr;
+    pt_film *film = nullptr, *lo = nullptr;
+    auto fail = [&](const char *what) { res.error = std::string(what) + ": " + (ctx ? pt_last_error(ctx) : pt_last_error(nullptr)); };
+    const uint32_t lw = (o.width + o.render_scale - 1) / o.render_scale, lh = (o.height + o.render_scale - 1) / o.render_scale;
+    do {
+        if (pt_ctx_create(o.device, nullptr, &ctx) != PT_OK) { fail("pt_ctx_create"); break; }
+        if (pt_scene_create(ctx, hs.vertices, hs.n_verts, hs.indices, hs.n_tris, hs.faces, &scene) != PT_OK) { fail("pt_scene_create"); break; }
+        pt_scene_get_info(scene, &res.info);
+        if (pt_film_create(ctx, o.width, o.height, &film) != PT_OK || pt_film_enable_aov(film, nullptr) != PT_OK || pt_film_create(ctx, lw, lh, &lo) != PT_OK ||
+            pt_film_enable_aov(lo, nullptr) != PT_OK) { fail("film set-up"); break; }
+        pt_params p;
+        pt_params_default(&p);
+        p.width = lw; p.height = lh; p.spp_per_frame = o.spp; p.max_depth = o.depth;
+        p.frames_in_flight = o.batch;
+        p.pipeline = o.pipeline;
+        if (o.nee) p.flags |= PT_FLAG_NEE;
+        p.frame = 0; p.frame_count = o.frames;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (pt_render(scene, lo, &p) != PT_OK) { fail("pt_render"); break; }
+        res.render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pt_get_stats(ctx, &res.st);
+        pt_params g = p;   // the guides of the same frames at both sizes: no estimator flags
+        g.flags = 0;
+        if (g.pipeline == PT_PIPELINE_WAVEFRONT_NEE) g.pipeline = PT_PIPELINE_AUTO;
+        if (pt_render_aov(scene, lo, &g) != PT_OK) { fail("pt_render_aov"); break; }
+        g.width = o.width; g.height = o.height;
+        if (pt_render_aov(scene, film, &g) != PT_OK) { fail("pt_render_aov"); break; }
+        pt_upsample_params up;
+        pt_upsample_params_default(&up);
+        if (o.denoise >= 0) {   // the low film is filtered first, and the upsample takes that result
+            pt_denoise_params dp;
+            pt_denoise_params_default(&dp);
+            if (o.denoise > 0) dp.iterations = (uint32_t)o.denoise;
+            if (pt_film_denoise(lo, &dp, nullptr, nullptr) != PT_OK) { fail("pt_film_denoise"); break; }
+            up.source = PT_UPSAMPLE_SRC_DENOISED;
+        }
+        if (pt_film_upsample(film, lo, &up, nullptr, nullptr) != PT_OK) { fail("pt_film_upsample"); break; }
+        const size_t np = (size_t)o.width * o.height;
+        if (image_f32) image_f32->resize(3 * np);
+        if (image_bgra8) image_bgra8->resize(4 * np);
+        if (pt_film_read_upsampled(film, image_f32 ? image_f32->data() : nullptr, image_bgra8 ? image_bgra8->data() : nullptr) != PT_OK) { fail("pt_film_read_upsampled"); break; }
+    } while (false);
+    pt_film_destroy(lo);
+    pt_film_destroy(film);
+    pt_scene_destroy(scene);
+    pt_ctx_destroy(ctx);
+}
 }  // namespace
 
 int main(int argc, char **argv)
@@ -379,6 +436,11 @@ int main(int argc, char **argv)
             o.temporal = (uint32_t)std::max(0, std::atoi(val()));
             if (o.temporal == 0) die("--temporal needs a number of time steps >= 1");
         }
+        else if (a == "--render-scale") {
+            const int s = std::atoi(val());
+            if (s < 2) die("--render-scale needs an integer >= 2");
+            o.render_scale = (uint32_t)s;
+        }
         else if (a == "--cam-step") {
             char tail = 0;
             if (std::sscanf(val(), "%f,%f,%f%c", &o.cam_step[0], &o.cam_step[1], &o.cam_step[2], &tail) != 3) die("--cam-step needs dx,dy,dz");
@@ -392,6 +454,8 @@ int main(int argc, char **argv)
     if (o.temporal) o.frames = o.temporal;   // (the JSON line's frame count)
     if (o.sigma_color > 0.f && o.denoise < 0) die("--sigma-color belongs to --denoise (the variance-guided filter)");
     if (o.sigma_color > 0.f && o.ranks > 1) die("--sigma-color filters the film of one rank (no --ranks)");
+    if (o.render_scale && (o.ranks > 1 || o.temporal || !o.aov.empty() || o.sigma_color > 0.f))
+        die("--render-scale upsamples the film of one rank (no --ranks, --temporal, --aov or --sigma-color)");
     if (o.ranks > 1) {
         if (o.devices.empty()) for (uint32_t r = 0; r < o.ranks; r++) o.devices.push_back((int)r);
         if (o.devices.size() != o.ranks) die("--devices needs one ordinal per rank");
@@ -410,7 +474,9 @@ int main(int argc, char **argv)
     std::vector<uint8_t> image_bgra8;
     const bool want_f32 = !o.pfm.empty() || (o.ranks > 1 && !o.ppm.empty());
     const auto t2 = std::chrono::steady_clock::now();
-    if (o.temporal) {
+    if (o.render_scale) {
+        run_scaled(o, hs, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr);
+    } else if (o.temporal) {
         run_temporal(o, hs, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr);
     } else if (o.ranks == 1) {
         run_rank(o, hs, 0, nullptr, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr, nullptr);
