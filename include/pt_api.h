@@ -202,7 +202,7 @@ pt_status pt_film_create(pt_ctx *ctx, uint32_t width, uint32_t height, pt_film *
  * a torch tensor's data_ptr(), so a collective can reduce it in place.                      */
 pt_status pt_film_create_external(pt_ctx *ctx, uint32_t width, uint32_t height,
                                   void *device_rgb_f32, pt_film **out);
-pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov and the planes of pt_film_enable_moments / pt_film_enable_history / pt_film_enable_motion) */
+pt_status pt_film_clear(pt_film *film);  /* (also zeroes the guide buffers of pt_film_enable_aov and the planes of pt_film_enable_moments / pt_film_enable_history / pt_film_enable_motion / pt_film_enable_counts) */
 /* rgb: width*height*3 floats, row-major, linear radiance mean over all frames so far.       */
 pt_status pt_film_read_f32(pt_film *film, float *rgb);
 /* bgra: width*height*4 bytes = what main.cpp:661-667 copies to the swapchain.               */
@@ -650,6 +650,68 @@ pt_status pt_film_upsample(pt_film *film, pt_film *lo, const pt_upsample_params 
 /* The film-owned result of the last pt_film_upsample(..., NULL, ...): rgb width*height*3 floats, bgra width*height*4 bytes; either may be
  * NULL.  PT_ERR_INVALID_ARG before any upsample into the film's own plane.                                                             */
 pt_status pt_film_read_upsampled(pt_film *film, float *rgb, uint8_t *bgra);
+
+/* ---- adaptive sampling: the film's variance decides which 8x8 tiles are traced ------------------------------------------------------------
+ * pt_film_enable_counts gives the film a plane K of width*height floats, zeroed: the frames each pixel holds.  device_k_f32 NULL for a plane
+ * the film owns, or caller-owned DEVICE memory of that size (a torch tensor's data_ptr()).  Once per film: a second call is
+ * PT_ERR_INVALID_ARG.  A film plane like L (pt_film_enable_history): not counted against pt_tuning.mem_budget_mb, zeroed by pt_film_clear,
+ * and pt_render does not know it.  Precondition: a film that has K is filled by pt_render_adaptive only, starting empty -- enable K (and M,
+ * pt_film_enable_moments) before the film's first frame or straight after pt_film_clear.  The calls do not look at what the film holds: after
+ * a pt_render into such a film K says 0 frames beside a C that holds some, and the next adaptive blend overwrites them.
+ * pt_film_read_counts: k (width*height floats); PT_ERR_INVALID_ARG on a film without the plane.
+ *
+ * pt_render_adaptive(scene, film, params, ap, result) renders frames [frame, frame + frame_count) for the tiles a selection pass keeps, and
+ * blends each of their pixels by the pixel's own count.  All arithmetic is binary32, every operation rounded on its own, no contraction,
+ * denormals kept, sqrt and / correctly rounded; NaN planes are outside the contract.  C is the film, M its second-moment plane, K the counts.
+ * SELECTION, once per call, before anything is traced.  For every tile T of the film's (params.rank, params.world) tile list, lane l = 0 .. 63
+ * stands for pixel (8*tx + (l & 7), 8*ty + (l >> 3)); a lane is valid if that pixel is inside the image; n_valid counts the valid lanes.
+ *   short  = some valid pixel has !(K_p >= (float)min_frames)
+ *   capped = max_frames > 0 and every valid pixel has K_p >= (float)max_frames
+ *   e_l    = 0 for an invalid lane or !(K_p >= 2); otherwise
+ *            v_c = max(M_c - C_c*C_c, 0) / (K_p - 1)
+ *            e_l = sqrt((v_r + v_g) + v_b) / (((C_r + C_g) + C_b) + rel_floor)
+ *   sum    : x = e; for k = 0 .. 5: x[l] = x[l] + x[l ^ (1 << k)]        (a butterfly: every lane ends with the same value)
+ *   e_T    = sum / (float)n_valid
+ *   selected = !capped && (short || e_T > threshold)                     (a NaN e_T is not "greater")
+ * RENDER.  Pipeline, estimator, cull, frames in flight and sample groups are planned as pt_render plans them for the whole list; the frame
+ * colour c of a pixel is pt_render's, bit for bit (a sample's seed depends on pixel, sample, frame and spp only).
+ * BLEND.  Each valid pixel of a selected tile, in ascending frame order, starting with n = K_p:
+ *   C = (c + C*n) / (n + 1);   M = (c*c + M*n) / (n + 1)                 (old values not read when n == 0)
+ *   bgra8: pt_render's byte blend with n in place of the frame (old byte / 255, blend, clamp and quantise; A from 1.0)
+ *   n = n + 1
+ * and K_p = n at the end.  Pixels of unselected tiles are not touched in any plane.  With every tile selected in every call and frames
+ * 0, 1, 2, ... the film, M and the bgra8 image are pt_render's.  The `frames` pt_film_read_moments reports is pt_render's record and is
+ * not advanced: the pixels of such a film hold different numbers of frames, and K says how many.
+ * pt_stats.rays grows by exactly the rays those pixels trace, paths by pixels_selected * spp_per_frame * frame_count; rays_culled follows
+ * pt_render's rule; pipeline reports what ran.  frame_count == 0 is a dry run: the call selects, fills `result` and writes nothing -- the
+ * caller's convergence query.  tiles_selected == 0 launches nothing after the selection and is PT_OK.  The caller uses distinct `frame`
+ * values across calls (two calls with the same frame add the same samples twice: the note of pt_film_reproject).
+ * Pipelines: PT_PIPELINE_WAVEFRONT, _WAVEFRONT_NEE, _FUSED and _AUTO with pt_render's support rules and fall-backs, instanced scenes
+ * included; PT_FLAG_NEE, PT_FLAG_SORT_RAYS and PT_FLAG_NO_SORT_RAYS are accepted.  PT_FLAG_ASYNC, PT_FLAG_PROFILE and PT_FLAG_COUNT_VISITS
+ * are PT_ERR_UNSUPPORTED: the call is blocking, it reads the count of selected tiles back.  The selection's scratch (a few words per tile of
+ * the list) is the film's, counts against the context's memory budget and is freed by pt_film_destroy.
+ * PT_ERR_INVALID_ARG, nothing written and nothing launched: NULL scene, film, params or ap; a film without M or without K; params whose size
+ * differs from the film's (and pt_render's other refusals); threshold not finite or < 0; rel_floor not finite or <= 0; min_frames outside
+ * 2..65535; a nonzero reserved word.                                                                                                  */
+pt_status pt_film_enable_counts(pt_film *film, void *device_k_f32);
+pt_status pt_film_read_counts(pt_film *film, float *k);
+typedef struct pt_adaptive_params {
+    float    threshold;    /* default 0.05: a tile is traced while its mean relative standard error exceeds it; finite, >= 0 */
+    float    rel_floor;    /* default 0.01: added to the colour sum in the denominator; finite, > 0 */
+    uint32_t min_frames;   /* default 4: a tile with a pixel below it is always traced; 2..65535 */
+    uint32_t max_frames;   /* default 0 = none: a tile whose valid pixels all hold >= this many frames is never traced */
+    uint32_t reserved[4];  /* must be 0 */
+} pt_adaptive_params;      /* 32 bytes */
+typedef struct pt_adaptive_result {
+    uint32_t tiles_total, tiles_selected;
+    uint64_t pixels_selected;       /* valid pixels of the selected tiles */
+    float    max_error;             /* max e_T over the tiles without a short pixel (0 if none) */
+    float    select_ms;             /* device time of the selection pass */
+    uint32_t reserved[2];
+} pt_adaptive_result;               /* 32 bytes */
+void pt_adaptive_params_default(pt_adaptive_params *p);
+pt_status pt_render_adaptive(pt_scene *scene, pt_film *film, const pt_params *params,
+                             const pt_adaptive_params *ap, pt_adaptive_result *result /* may be NULL */);
 
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {

@@ -121,6 +121,17 @@ class UpsampleParams(C.Structure):
     _fields_ = [("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("source", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+class AdaptiveParams(C.Structure):
+    """include/pt_api.h pt_adaptive_params: which tiles pt_render_adaptive traces."""
+    _fields_ = [("threshold", C.c_float), ("rel_floor", C.c_float), ("min_frames", C.c_uint32), ("max_frames", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class AdaptiveResult(C.Structure):
+    """include/pt_api.h pt_adaptive_result: what the selection pass of pt_render_adaptive found."""
+    _fields_ = [("tiles_total", C.c_uint32), ("tiles_selected", C.c_uint32), ("pixels_selected", C.c_uint64), ("max_error", C.c_float),
+                ("select_ms", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 REPROJECT_MATCH_ID = 1   # include/pt_api.h PT_REPROJECT_MATCH_ID
 
 
@@ -165,7 +176,8 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_device_alloc", "pt_device_free", "pt_device_read", "pt_device_write", "pt_ctx_get_tuning", "pt_ctx_set_tuning",
                "pt_scene_snapshot_previous", "pt_film_enable_motion", "pt_film_read_motion", "pt_motion_params_default", "pt_film_motion",
                "pt_film_reproject_motion", "pt_denoise_history_params_default", "pt_film_denoise_history",
-               "pt_upsample_params_default", "pt_film_upsample", "pt_film_read_upsampled"]
+               "pt_upsample_params_default", "pt_film_upsample", "pt_film_read_upsampled",
+               "pt_film_enable_counts", "pt_film_read_counts", "pt_adaptive_params_default", "pt_render_adaptive"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium"]
 
@@ -257,6 +269,12 @@ def lib_amd():
             L.pt_upsample_params_default.restype = None
             L.pt_film_upsample.argtypes = [vp, vp, C.POINTER(UpsampleParams), vp, C.POINTER(C.c_float)]
             L.pt_film_read_upsampled.argtypes = [vp, vp, vp]
+        if hasattr(L, "pt_render_adaptive"):   # (adaptive sampling; as above)
+            L.pt_film_enable_counts.argtypes = [vp, vp]
+            L.pt_film_read_counts.argtypes = [vp, vp]
+            L.pt_adaptive_params_default.argtypes = [C.POINTER(AdaptiveParams)]
+            L.pt_adaptive_params_default.restype = None
+            L.pt_render_adaptive.argtypes = [vp, vp, C.POINTER(Params), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveResult)]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -417,6 +435,10 @@ def denoise_history_default_params():
 
 def upsample_default_params():
     return _default_params(UpsampleParams, "pt_upsample_params_default")
+
+
+def adaptive_default_params():
+    return _default_params(AdaptiveParams, "pt_adaptive_params_default")
 
 
 def reproject_default_params():
@@ -683,6 +705,16 @@ class Film:
         """-> float32 [H, W]: the history length of every pixel, in reprojection steps (0 before the first reproject)."""
         return self._read_plane("pt_film_read_history", ())
 
+    def enable_counts(self, device_ptr=None):
+        """Gives the film its frame-count plane K (include/pt_api.h pt_film_enable_counts), which render_adaptive blends by and advances.
+        device_ptr: None (the film allocates it) or a device pointer to width*height floats of caller-owned memory.  Call it while the
+        film is empty; a film that has K is filled by render_adaptive only."""
+        self._enable_plane("pt_film_enable_counts", device_ptr)
+
+    def read_counts(self):
+        """-> float32 [H, W]: the frames every pixel holds."""
+        return self._read_plane("pt_film_read_counts", ())
+
     def enable_motion(self, device_ptr=None):
         """Gives the film its motion plane Q (include/pt_api.h pt_film_enable_motion), which pt_film_motion writes and
         pt_film_reproject_motion reads.  device_ptr: None (the film allocates it) or a device pointer to width*height*4 floats of
@@ -867,6 +899,21 @@ def render(scene, film, params):
     """pushConstants(frame) + traceRaysKHR(W,H,1) + waitIdle (main.cpp:656-659, 683), for
     params.frame_count consecutive frames."""
     scene.ctx._check(lib_amd().pt_render(scene.h, film.h, C.byref(params)))
+
+
+def render_adaptive(scene, film, params, adaptive_params=None, **adaptive):
+    """params' frames for the 8x8 tiles whose error is still above the threshold, blended by each pixel's own frame count (include/pt_api.h
+    pt_render_adaptive) -> AdaptiveResult.  The film has M and K (Film.enable_moments, Film.enable_counts).  adaptive: fields of
+    AdaptiveParams (threshold, rel_floor, min_frames, max_frames) over pt_adaptive_params_default's values, or over those of
+    `adaptive_params`, which is not modified.  params.frame_count == 0 is a dry run: the selection alone."""
+    ap = AdaptiveParams.from_buffer_copy(adaptive_params) if adaptive_params is not None else adaptive_default_params()
+    for k, v in adaptive.items():
+        if not hasattr(ap, k):
+            raise AttributeError(k)
+        setattr(ap, k, v)
+    res = AdaptiveResult()
+    scene.ctx._check(lib_amd().pt_render_adaptive(scene.h, film.h, C.byref(params), C.byref(ap), C.byref(res)))
+    return res
 
 
 def render_aov(scene, film, params):

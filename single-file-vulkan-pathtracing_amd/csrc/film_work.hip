@@ -2,7 +2,7 @@
 // RenderShape) and the device buffers behind them (queues, hit records, radiance accumulators or term logs).
 // Buffers only ever grow; a grow that does not fit leaves the film usable (PT_ERR_OOM, AUTO shapes are planned again smaller).
 // Also what every scratch of a film goes through (pt_internal.h): pt_scratch_alloc / pt_scratch_free, the rank's tile list, the camera of a launch;
-// and the film's optional planes M, L and Q (pt_plane_*).
+// and the film's optional planes M, L, Q and K (pt_plane_*).
 #include "wavefront_host.h"
 
 #include <algorithm>
@@ -117,7 +117,8 @@ struct FilmPlane { pt_plane_any *plane; size_t bytes; };
 std::vector<FilmPlane> film_planes(pt_film *f)
 {
     const size_t n_pix = (size_t)f->w * f->h;
-    return { { &f->m2, sizeof(float) * 3 * n_pix }, { &f->hist, sizeof(float) * n_pix }, { &f->mo, sizeof(float4) * n_pix } };
+    return { { &f->m2, sizeof(float) * 3 * n_pix }, { &f->hist, sizeof(float) * n_pix }, { &f->mo, sizeof(float4) * n_pix },
+             { &f->cnt, sizeof(float) * n_pix } };
 }
 }  // namespace
 
@@ -434,23 +435,24 @@ ptm::Camera ptw_camera(const pt_params *p)
              p->width <= (1u << 20) ? 1.0f / (float)p->width : 0.0f, p->height <= (1u << 20) ? 1.0f / (float)p->height : 0.0f };
 }
 
-ptw::RenderConst ptw_render_const(const pt_params *p, const pt_film::Work &w, const RenderShape &sh)
+ptw::RenderConst ptw_render_const(const pt_params *p, uint32_t n_tiles, const RenderShape &sh)
 {
+    const uint32_t n_slots = sh.lanes * sh.groups * n_tiles * 64u;  // (the film's own list: pt_film::Work::n_slots, below 2^31 by ptw_ensure_work)
     ptw::RenderConst rc{};
     rc.cam = ptw_camera(p);
     for (int k = 0; k < 3; k++) rc.env[k] = p->env[k];
     rc.tmin = p->tmin; rc.tmax = p->tmax;
     rc.width = p->width; rc.height = p->height; rc.tiles_x = (p->width + 7) / 8;
     rc.spp = p->spp_per_frame; rc.max_depth = p->max_depth;
-    rc.slots_per_lane = w.n_tiles * 64u;
+    rc.slots_per_lane = n_tiles * 64u;
     rc.groups = sh.groups; rc.group_size = sh.group_size; rc.term_cap = sh.term_cap;
     rc.div_spl.init(std::max(rc.slots_per_lane, 1u)); rc.div_groups.init(std::max(sh.groups, 1u));
     rc.term_pcap = sh.term_pcap;
-    rc.n_slots = w.n_slots;
+    rc.n_slots = n_slots;
     rc.tail = sh.tail;
     rc.head_samples = p->spp_per_frame - std::min(sh.tail, p->spp_per_frame);
-    rc.n_head = sh.tail ? w.n_slots : 0u;
-    rc.n_tail = sh.tail ? w.n_slots * sh.tail : 0u;
+    rc.n_head = sh.tail ? n_slots : 0u;
+    rc.n_tail = sh.tail ? n_slots * sh.tail : 0u;
     rc.div_tail.init(std::max(sh.tail, 1u));
     return rc;
 }

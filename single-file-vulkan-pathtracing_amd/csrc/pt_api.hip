@@ -330,7 +330,7 @@ pt_status pt_film_clear(pt_film *f)
     PT_HIP(ctx, hipMemsetAsync(f->d_bgra, 0, 4 * (size_t)f->w * f->h, ctx->stream));
     const pt_status rc = pta_clear(f, ctx->stream);  // the guide buffers, if the film has them
     if (rc != PT_OK) return rc;
-    PT_TRY(pt_planes_clear(f, ctx->stream));  // M, L and Q, where the film has them
+    PT_TRY(pt_planes_clear(f, ctx->stream));  // M, L, Q and K, where the film has them
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -360,6 +360,7 @@ void pt_film_destroy(pt_film *f)
     pta_free(f);
     ptd_free(f);
     ptu_free(f);
+    ptad_free(f);
     pt_planes_free(f);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
@@ -612,6 +613,36 @@ pt_status pt_film_read_upsampled(pt_film *f, float *rgb, uint8_t *bgra)
     if (rgb) PT_HIP(ctx, hipMemcpy(rgb, f->up.d_out, sizeof(float) * 3 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
     if (bgra) PT_HIP(ctx, hipMemcpy(bgra, f->up.d_out_bgra, 4 * (size_t)f->w * f->h, hipMemcpyDeviceToHost));
     return PT_OK;
+}
+
+pt_status pt_film_enable_counts(pt_film *f, void *device_k_f32)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    return guarded(f->ctx, [&] { return pt_plane_enable(f, f->cnt, device_k_f32, sizeof(float) * (size_t)f->w * f->h, 0, "pt_film_enable_counts", "the film already has a frame-count plane"); });
+}
+
+pt_status pt_film_read_counts(pt_film *f, float *k)
+{
+    if (!f) return PT_ERR_INVALID_ARG;
+    if (!k) return pt_bad(f->ctx, "null argument");
+    return pt_plane_read(f, f->cnt, k, sizeof(float) * (size_t)f->w * f->h, PT_NO_K_MSG " first");
+}
+
+void pt_adaptive_params_default(pt_adaptive_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->threshold = 0.05f;
+    p->rel_floor = 0.01f;
+    p->min_frames = 4;
+}
+
+pt_status pt_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p, const pt_adaptive_params *ap, pt_adaptive_result *result)
+{
+    if (!s || !f || !p || !ap) return PT_ERR_INVALID_ARG;
+    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return ptw_render_adaptive(s, f, p, ap, result); });
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)

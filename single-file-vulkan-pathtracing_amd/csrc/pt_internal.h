@@ -252,6 +252,18 @@ struct pt_film {
     pt_plane<float> hist;                             // w*h floats
     // pt_film_enable_motion: where the surface point of a pixel's first hit was in the previous geometry (motion.hip).  A film plane like L.
     pt_plane<float4> mo;                              // w*h float4 {x, y, z, valid}
+    // pt_film_enable_counts: the frames each pixel holds, as pt_render_adaptive blends them (adaptive.hip).  A film plane like L.
+    pt_plane<float> cnt;                              // w*h floats
+    // pt_render_adaptive's selection (adaptive.hip): the film's scratch, made by the first call and kept; it grows with the rank's tile list.
+    struct Adapt {
+        uint32_t *d_sel = nullptr;                    // the selected tile words, in the source list's order
+        uint32_t *d_off = nullptr;                    // [cap + 1] a flag per tile of the source list, then its exclusive scan
+        uint32_t *d_err = nullptr;                    // a word per tile: the bits of its e_T (0 for a short tile)
+        uint32_t *d_sums = nullptr;                   // the scan's block sums (device_scan.h)
+        void *d_rec = nullptr;                        // the record the host reads once per call: count, max error, pixels
+        size_t cap = 0;                               // tiles the arrays hold
+        size_t bytes = 0;                             // device bytes of all of the above
+    } ad;
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -307,6 +319,7 @@ inline pt_status pt_check_sigmas(pt_ctx *ctx, const char *name, std::initializer
 #define PT_NO_M_MSG "the film has no second-moment plane: pt_film_enable_moments"
 #define PT_NO_L_MSG "the film has no history-length plane: pt_film_enable_history"
 #define PT_NO_Q_MSG "the film has no motion plane: pt_film_enable_motion"
+#define PT_NO_K_MSG "the film has no frame-count plane: pt_film_enable_counts"
 
 // A device array that is freed with its scope unless it is release()d to an owner.
 template <typename T>
@@ -400,3 +413,6 @@ pt_status ptr_reproject(pt_film *f, pt_film *prev, const pt_reproject_params *p,
 pt_status ptm_snapshot(pt_scene *s);
 void ptm_free_previous(pt_scene *s);
 pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *device_ms);
+// render.hip: pt_render_adaptive (validates everything but the null checks); adaptive.hip: the selection's scratch
+pt_status ptw_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p, const pt_adaptive_params *ap, pt_adaptive_result *result);
+void ptad_free(pt_film *f);

@@ -88,6 +88,7 @@ struct Pipe {
 // What one pt_render call (wavefront pipelines) decides once and every batch uses.
 struct Job {
     pt_scene *s; pt_film *f; const pt_params *p; pt_ctx *ctx;
+    const TileView *sel = nullptr;  // pt_render_adaptive: the selected tiles (null: the film's own list)
     ExtendPlan pl;
     RenderShape sh;
     RenderConst rc;
@@ -175,7 +176,7 @@ pt_status job_setup(Job &j)
     j.spill_cap = j.sh.bounded ? SPILL_POOL_ENTRIES : 0u;  // worst-case logs never reach the pool
     if (ctx->tune.term_spill >= 0) j.spill_cap = std::min<uint32_t>(j.spill_cap, (uint32_t)ctx->tune.term_spill);  // tests
     j.rad = job_radiance(j);
-    j.rc = ptw_render_const(p, w, j.sh);
+    j.rc = ptw_render_const(p, ptw_tile_view(f, j.sel).n_tiles, j.sh);
     {
         int32_t rect[4];
         subject_rect(s, p, rect);
@@ -301,7 +302,7 @@ pt_status batch_begin(Job &j, Pipe *pipe, int &pipes_now, unsigned long long &ra
     }
     for (int k = 0; k < pipes_now; k++) {
         Pipe &pp = pipe[k];
-        ptw_launch_generate(j.rc, w.d_tiles, pp.slot_begin, pp.n_slots, j.rad, pp.qv[0], &pp.count[0], ctx->d_stats, ctx->num_cus, pp.st);
+        ptw_launch_generate(j.rc, ptw_tile_view(j.f, j.sel).d_tiles, pp.slot_begin, pp.n_slots, j.rad, pp.qv[0], &pp.count[0], ctx->d_stats, ctx->num_cus, pp.st);
         ctx->stats.launches_other++;
     }
     return PT_OK;
@@ -347,7 +348,7 @@ pt_status pipe_round(Job &j, Pipe *pipe, int k, int pipes_now, uint32_t round, b
     const int ahead = (k + 1) % pipes_now;
     if (shade_rule && shade_recorded[ahead]) PT_HIP(ctx, hipStreamWaitEvent(pp.st, ctx->ev_shade[ahead], 0));
     ShadeLaunch sl;
-    sl.rc = j.rc; sl.tiles = w.d_tiles; sl.scene = s; sl.bvh8 = j.pl.bvh8; sl.lds_tables = j.shade_lds; sl.nee = j.nee;
+    sl.rc = j.rc; sl.tiles = ptw_tile_view(j.f, j.sel).d_tiles; sl.scene = s; sl.bvh8 = j.pl.bvh8; sl.lds_tables = j.shade_lds; sl.nee = j.nee;
     sl.grid = j.shade_grid; sl.smem = j.shade_smem; sl.rad = j.rad; sl.hit = pp.hit; sl.hit_inst = pp.hit_inst;
     sl.in = pp.qv[cur]; sl.out = pp.qv[cur ^ 1]; sl.count_in = &pp.count[cur]; sl.count_out = &pp.count[cur ^ 1];
     sl.inst_frame = j.inst_frame; sl.lights = j.nee_lights; sl.n_lights = j.nee_n_lights; sl.light_area = j.nee_light_area;
@@ -437,7 +438,14 @@ void drain_side_streams(pt_ctx *ctx, int pipes_now)
     (void)hipGetLastError();
 }
 
-pt_status render_wavefront(pt_scene *s, pt_film *f, const pt_params *p, const ExtendPlan &pl, bool nested);
+pt_status render_wavefront(pt_scene *s, pt_film *f, const pt_params *p, const ExtendPlan &pl, bool nested, const TileView *sel = nullptr,
+                           AdaptCall *ad = nullptr);
+// the blend of a batch's frames into the film: k_resolve over the film's own list, k_resolve_adapt over a selection
+void launch_resolve(pt_film *f, const RenderConst &rc, const TileView &tv, const Radiance &rad, hipStream_t st, const unsigned long long *skip_if_set)
+{
+    if (tv.counts) ptw_launch_resolve_adapt(rc, tv.d_tiles, rad, f->d_rgb, f->d_bgra, st, skip_if_set, f->m2.ptr(), tv.counts);
+    else ptw_launch_resolve(rc, tv.d_tiles, rad, f->d_rgb, f->d_bgra, st, skip_if_set, f->m2.ptr());
+}
 
 // ---- per batch: join, term-log overflow check, resolve (or the same frames once more with one sample group) -----------------
 pt_status batch_finish(Job &j, int pipes_now, unsigned long long rays_before)
@@ -456,7 +464,7 @@ pt_status batch_finish(Job &j, int pipes_now, unsigned long long rays_before)
         redo = flag != 0ull;
     }
     if (!redo) {
-        ptw_launch_resolve(j.rc, f->work.d_tiles, j.rad, f->d_rgb, f->d_bgra, st, nullptr, f->m2.ptr());
+        launch_resolve(f, j.rc, ptw_tile_view(f, j.sel), j.rad, st, nullptr);
         ctx->stats.launches_other++;
         return PT_OK;
     }
@@ -472,7 +480,7 @@ pt_status batch_finish(Job &j, int pipes_now, unsigned long long rays_before)
     q.frame_count = j.rc.lanes_active;
     q.frames_in_flight = j.rc.lanes_active;
     q.sample_groups = 1;
-    pt_status rc = render_wavefront(j.s, f, &q, j.pl, true);
+    pt_status rc = render_wavefront(j.s, f, &q, j.pl, true, j.sel);
     if (rc != PT_OK) return rc;
     rc = ptw_ensure_work(f, p->rank, p->world, j.sh.lanes, j.sh.groups, j.sh.term_cap, j.sh.term_pcap);
     if (rc != PT_OK) return rc;
@@ -481,18 +489,28 @@ pt_status batch_finish(Job &j, int pipes_now, unsigned long long rays_before)
 }
 
 // ---- the wavefront pipelines (PT_PIPELINE_WAVEFRONT, _NEE) ---------------------------------------------------------------
-pt_status render_wavefront(pt_scene *s, pt_film *f, const pt_params *p, const ExtendPlan &pl, bool nested)
+pt_status render_wavefront(pt_scene *s, pt_film *f, const pt_params *p, const ExtendPlan &pl, bool nested, const TileView *sel, AdaptCall *ad)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     Job j{};
-    j.s = s; j.f = f; j.p = p; j.ctx = ctx; j.pl = pl; j.nested = nested;
+    j.s = s; j.f = f; j.p = p; j.ctx = ctx; j.pl = pl; j.nested = nested; j.sel = sel;
     pt_status rc = ptw_shape_and_work(f, p, j.sh, launch_class(s, pl));
     if (rc != PT_OK) return rc;
+    TileView picked;
+    if (ad) {  // pt_render_adaptive: the work is planned for the full list; the selection over it, then nothing but the selection
+        rc = ptad_select(f, ad->ap, ptw_tile_view(f, nullptr), &picked, &ad->res);
+        if (rc != PT_OK) return rc;
+        ctx->stats.frames_in_flight = j.sh.lanes;
+        ctx->stats.sample_groups = j.sh.groups;
+        ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
+        if (ad->dry || picked.n_tiles == 0) return PT_OK;
+        j.sel = &picked;
+    }
     rc = job_setup(j);
     if (rc != PT_OK) return rc;
     if (!nested) PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    for (uint32_t done = 0; f->work.n_slots > 0 && done < p->frame_count; done += j.sh.lanes) {
+    for (uint32_t done = 0; j.rc.n_slots > 0 && done < p->frame_count; done += j.sh.lanes) {
         j.rc.frame_base = p->frame + (int32_t)done;
         j.rc.lanes_active = std::min(j.sh.lanes, p->frame_count - done);
         Pipe pipe[PT_MAX_PIPES];
@@ -518,7 +536,7 @@ pt_status render_wavefront(pt_scene *s, pt_film *f, const pt_params *p, const Ex
     }
     if (!nested) {
         ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
-        ctx->stats.paths += ptw_valid_local_pixels(f, p) * p->spp_per_frame * p->frame_count;  // samples started
+        ctx->stats.paths += (j.sel ? j.sel->pixels : ptw_valid_local_pixels(f, p)) * p->spp_per_frame * p->frame_count;  // samples started
     }
     if (j.profile) {
         for (size_t i = 0; i + 1 < j.ev_extend.size(); i += 2) {
@@ -614,7 +632,8 @@ uint32_t fused_tail_samples(const pt_ctx *ctx, const pt_film *f, const pt_params
     return (uint32_t)std::max(0, std::min<int>(t, (int)spp - 1));
 }
 
-pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const ExtendPlan &pl, bool nested, bool prepare_only)
+pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const ExtendPlan &pl, bool nested, bool prepare_only, const TileView *sel = nullptr,
+                       AdaptCall *ad = nullptr)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
@@ -691,10 +710,17 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
     }
     ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
     if (prepare_only) return PT_OK;
-    {
+    if (!sel) {  // (a selection inherits the order of the list it was made from)
         const int32_t none[4] = { 0, 0, -1, -1 };
         rc_ = ptw_tiles_subject_first(f, ctx->tune.fused_subject == 0 ? none : rect, st);
         if (rc_ != PT_OK) return rc_;
+    }
+    TileView picked;
+    if (ad) {  // pt_render_adaptive: the work is planned for the full list; the selection over it, then nothing but the selection
+        rc_ = ptad_select(f, ad->ap, ptw_tile_view(f, nullptr), &picked, &ad->res);
+        if (rc_ != PT_OK) return rc_;
+        if (ad->dry || picked.n_tiles == 0) return PT_OK;
+        sel = &picked;
     }
     pt_film::Work &w = f->work;
     unsigned long long *const d_overflow = ctx->d_stats + 6, *const d_spill_count = ctx->d_stats + 7;
@@ -713,7 +739,7 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
     };
     rc_ = set_rad();
     if (rc_ != PT_OK) return rc_;
-    RenderConst rc = ptw_render_const(p, w, sh);
+    RenderConst rc = ptw_render_const(p, ptw_tile_view(f, sel).n_tiles, sh);
     apply_cull(ctx, p, rect, rc);
     const bool profile = !nested && (p->flags & PT_FLAG_PROFILE) != 0;
     ctx->stats.extend_variant = pl.variant;
@@ -721,7 +747,8 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
     if (!nested) PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
     std::vector<hipEvent_t> evs;
     size_t ev_used = 0;
-    for (uint32_t done = 0; w.n_slots > 0 && done < p->frame_count; done += sh.lanes) {
+    for (uint32_t done = 0; rc.n_slots > 0 && done < p->frame_count; done += sh.lanes) {
+        const TileView tv = ptw_tile_view(f, sel);
         rc.frame_base = p->frame + (int32_t)done;
         rc.lanes_active = std::min(sh.lanes, p->frame_count - done);
         // A launch whose term logs are bounded can overflow them (scenes where most surfaces emit): k_fused raises d_overflow, k_resolve then
@@ -743,11 +770,11 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
             e0 = ctx->ev_pool[ev_used++]; e1 = ctx->ev_pool[ev_used++];
             evs.push_back(e0); evs.push_back(e1);
         }
-        ptw_launch_fused(fp, sh.groups > 1, rc, w.d_tiles, rad, s, n_slots, w.d_count, ctx->d_stats, p->tmin, p->tmax, st, e0, e1);  // (rc.tail != 0: the head + tail kernel)
+        ptw_launch_fused(fp, sh.groups > 1, rc, tv.d_tiles, rad, s, n_slots, w.d_count, ctx->d_stats, p->tmin, p->tmax, st, e0, e1);  // (rc.tail != 0: the head + tail kernel)
         PT_HIP(ctx, hipGetLastError());
         ctx->stats.launches_extend++;
         ctx->stats.rounds++;
-        ptw_launch_resolve(rc, w.d_tiles, rad, f->d_rgb, f->d_bgra, st, sh.bounded ? d_overflow : nullptr, f->m2.ptr());
+        launch_resolve(f, rc, tv, rad, st, sh.bounded ? d_overflow : nullptr);
         ctx->stats.launches_other++;
         bool redo = false;
         if (sh.bounded) {
@@ -763,7 +790,7 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
             ctx->stats.redone_batches++;
             pt_params r = *p;
             r.frame = rc.frame_base; r.frame_count = rc.lanes_active; r.frames_in_flight = rc.lanes_active; r.sample_groups = 1;
-            rc_ = render_fused(s, f, &r, pl, true, false);
+            rc_ = render_fused(s, f, &r, pl, true, false, sel);
             if (rc_ != PT_OK) return rc_;
             rc_ = ptw_ensure_work(f, p->rank, p->world, sh.lanes, sh.groups, sh.term_cap, sh.term_pcap, false, sh.tail);
             if (rc_ != PT_OK) return rc_;
@@ -779,7 +806,7 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
         PT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
         ctx->stats.ms_total += ms;
         ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
-        ctx->stats.paths += ptw_valid_local_pixels(f, p) * p->spp_per_frame * p->frame_count;
+        ctx->stats.paths += (sel ? sel->pixels : ptw_valid_local_pixels(f, p)) * p->spp_per_frame * p->frame_count;
     }
     for (size_t i = 0; i + 1 < evs.size(); i += 2) {
         float a = 0.f;
@@ -880,6 +907,41 @@ pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p_in)
     s->ctx->stats.pipeline = p->pipeline;
     rc_ = p->pipeline == PT_PIPELINE_FUSED ? render_fused(s, f, p, pl, false, false) : render_wavefront(s, f, p, pl, false);
     if (rc_ == PT_OK) f->m2.frames = (uint32_t)p->frame + p->frame_count;  // what the film and its second-moment plane now average
+    return rc_;
+}
+
+// pt_render_adaptive: pt_render's plan over the tiles the selection pass keeps (adaptive.hip; include/pt_api.h has the definition).  Every
+// refusal comes before anything is allocated, launched or written.
+pt_status ptw_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p_in, const pt_adaptive_params *ap, pt_adaptive_result *result)
+{
+    pt_ctx *ctx = s->ctx;
+    if (result) *result = pt_adaptive_result{};
+    if (!f->m2.d) return pt_bad(ctx, PT_NO_M_MSG " first");
+    if (!f->cnt.d) return pt_bad(ctx, PT_NO_K_MSG " first");
+    if (!(std::isfinite(ap->threshold) && ap->threshold >= 0.f)) return pt_bad(ctx, "pt_adaptive_params.threshold must be finite and >= 0");
+    if (!(std::isfinite(ap->rel_floor) && ap->rel_floor > 0.f)) return pt_bad(ctx, "pt_adaptive_params.rel_floor must be finite and > 0");
+    if (ap->min_frames < 2u || ap->min_frames > 0xFFFFu) return pt_bad(ctx, "pt_adaptive_params.min_frames must be in 2..65535");
+    PT_TRY(pt_check_reserved(ctx, "pt_adaptive_params", ap->reserved));
+    pt_params p_res = *p_in;
+    AdaptCall ad;
+    ad.ap = ap;
+    ad.dry = p_in->frame_count == 0;
+    if (ad.dry) p_res.frame_count = 1;  // (a dry run plans one frame's work: it needs the rank's tile list and nothing else)
+    pt_status rc_ = check_params(s, f, &p_res);
+    if (rc_ != PT_OK) return rc_;
+    if (p_in->flags & (PT_FLAG_ASYNC | PT_FLAG_PROFILE | PT_FLAG_COUNT_VISITS)) {
+        ctx->err = "pt_render_adaptive: not with PT_FLAG_ASYNC, PT_FLAG_PROFILE or PT_FLAG_COUNT_VISITS (the call reads the selection's count back)";
+        return PT_ERR_UNSUPPORTED;
+    }
+    rc_ = s->broken ? ptb_repair(s) : PT_OK;
+    if (rc_ != PT_OK) return rc_;
+    ExtendPlan pl;
+    rc_ = ptw_plan_extend(s, p_in->extend, pl);
+    if (rc_ != PT_OK) return rc_;
+    p_res.pipeline = resolve_pipeline(s, &p_res, pl);
+    ctx->stats.pipeline = p_res.pipeline;
+    rc_ = p_res.pipeline == PT_PIPELINE_FUSED ? render_fused(s, f, &p_res, pl, false, false, nullptr, &ad) : render_wavefront(s, f, &p_res, pl, false, nullptr, &ad);
+    if (rc_ == PT_OK && result) *result = ad.res;
     return rc_;
 }
 

@@ -5,6 +5,7 @@
 //   extend_hbm.hip      the closest-hit kernels that walk a scene out of L2 / MALL / HBM (their own instruction scheduler)
 //   fused.hip           PT_PIPELINE_FUSED: k_fused (fused_kernel.h), its plan and its launcher
 //   aov.hip             pt_render_aov: the guide buffers' kernels, plan and launch
+//   adaptive.hip        pt_render_adaptive: the selection of the tiles a render runs over, and the resolve that blends by a pixel's own count
 //   film_work.hip       the film's workspace: how many slots a render gets (RenderShape) and the buffers behind them
 //   render.hip          pt_render / pt_render_prepare / pt_trace: batches, pipelines on streams, rounds, polls, redo
 //
@@ -110,6 +111,37 @@ void ptw_launch_resolve(const ptw::RenderConst &rc, const uint32_t *tiles, const
 void ptw_launch_hits_to_api(const float4 *hit, const float4 *tri4, const uint32_t *hit_inst, const uint32_t *inst_id, uint32_t n, pt_hit *out,
                             hipStream_t st);
 
+// ---- the tile list a render runs over ------------------------------------------------------------------------------------------
+// Every kernel finds its pixels through a list of 8x8 tiles (wavefront_types.h slot_pixel) and does not care which tiles are listed: pt_render
+// runs over the film's own (rank, world) list, pt_render_adaptive over a selection of it.
+struct TileView {
+    const uint32_t *d_tiles = nullptr;  // tile x | tile y << 16
+    uint32_t n_tiles = 0;
+    uint64_t pixels = 0;                // pixels of them inside the image (what pt_stats.paths counts)
+    float *counts = nullptr;            // a selection: the film's plane K, which its resolve blends by and advances (adaptive.hip)
+};
+// What pt_render_adaptive hands down to the pipeline that serves it: the pipeline plans its work as for pt_render, then -- its tile list in its
+// final order, nothing traced yet -- has the selection made (ptad_select) and renders that.
+struct AdaptCall {
+    const pt_adaptive_params *ap = nullptr;
+    pt_adaptive_result res{};
+    bool dry = false;                   // frame_count == 0: select, render nothing
+};
+// the list a launch uses: the selection, or the film's own as it stands now (a workspace grow or another hand-out order rebuilds it)
+inline TileView ptw_tile_view(const pt_film *f, const TileView *sel)
+{
+    if (sel) return *sel;
+    return { f->work.d_tiles, f->work.n_tiles, 0, nullptr };
+}
+
+// ---- adaptive.hip ------------------------------------------------------------------------------------------------------------------
+// The selection of pt_render_adaptive over the list `src`: the selected tile words compacted in src's order into the film's scratch (-> *out),
+// the record read back once (-> *res: tiles_total, tiles_selected, pixels_selected, max_error, select_ms).  Blocking.
+pt_status ptad_select(pt_film *f, const pt_adaptive_params *ap, const TileView &src, TileView *out, pt_adaptive_result *res);
+// k_resolve_adapt: ptw_launch_resolve with the blend by the pixel's own count (the film has M and K)
+void ptw_launch_resolve_adapt(const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, float *film, uint8_t *bgra, hipStream_t st,
+                              const unsigned long long *skip_if_set, float *m2, float *counts);
+
 constexpr size_t PTW_COUNT_WORDS = 16 * 32;  // pt_film::Work::d_count: the wavefront's queue sizes (2 per pipeline) | eight slot counters of the fused kernel, one 128-B line each (sixteen with head + tail slots)
 
 // ---- fused.hip ---------------------------------------------------------------------------------------------------------
@@ -151,7 +183,8 @@ inline ptm::Camera ptw_camera_of(const float *origin, const float *target, uint3
     cp.width = w; cp.height = h;
     return ptw_camera(&cp);
 }
-ptw::RenderConst ptw_render_const(const pt_params *p, const pt_film::Work &w, const RenderShape &sh);
+// (n_tiles: of the list the render runs over -- the slot numbering follows from it, the buffers are the full list's)
+ptw::RenderConst ptw_render_const(const pt_params *p, uint32_t n_tiles, const RenderShape &sh);
 uint64_t ptw_valid_local_pixels(const pt_film *f, const pt_params *p);
 // render.hip: the pixel rectangle {x0, y0, x1, y1} outside of which no camera ray can reach the scene's box (x1 < x0: no such proof)
 void ptw_subject_rect(const pt_scene *s, const pt_params *p, int32_t rect[4]);

@@ -8,6 +8,7 @@
 //           [--ppm out.ppm] [--pfm out.pfm] [--aov PREFIX] [--denoise [N] [--sigma-color S]] [--pipeline auto|wavefront|fused|nee] [--nee]
 //           [--ranks N [--devices 0,1,...] [--selftest]]
 //           [--temporal K --cam-step dx,dy,dz] [--render-scale S]
+//           [--adaptive THRESH [--steps N] [--passes N] [--min-frames N] [--max-frames N]]
 // --ranks N renders with N GPUs: one host thread and one context per GPU, the 8x8 pixel tiles interleaved over the
 // ranks (pt_params.rank/world), and ONE RCCL gather of the packed tiles to rank 0 per presented image
 // (pt_film_present); the image written is the presented one.  --selftest: before rendering, every rank presents a film whose own tiles
@@ -29,6 +30,10 @@
 // ceil(width / S) x ceil(height / S), the full-size guides at width x height, and pt_film_upsample brings the radiance to full size;
 // --denoise [N] filters the low-resolution film first and the upsample takes that result (PT_UPSAMPLE_SRC_DENOISED).  --ppm / --pfm hold the
 // upsampled image.
+// --adaptive THRESH (one rank; no --temporal, --render-scale, --aov or --denoise; --frames is not used): the film gets its planes M and K and
+// pt_render_adaptive renders passes of --steps frames (default 4) over the 8x8 tiles whose mean relative standard error is above THRESH, until a dry
+// run (frame_count = 0) selects nothing or --passes passes (default 32) have run.  --min-frames / --max-frames: pt_adaptive_params' fields.  One line
+// per pass on stderr: tiles selected of the total, the worst tile error, the pass's rays.  The JSON line's frames are the frames of all passes.
 // Prints one JSON line with ray count, ms/frame and Mrays/s.
 #include <algorithm>
 #include <atomic>
@@ -67,6 +72,8 @@ struct Options {
     float cam_step[3] = { 0.f, 0.f, 0.f };   // --cam-step dx,dy,dz: the camera's move per time step
     bool have_cam_step = false;
     uint32_t render_scale = 0;   // --render-scale S: radiance at 1 / S of the size, brought back by pt_film_upsample (0: off)
+    float adaptive = -1.f;       // --adaptive THRESH: pt_render_adaptive in passes until nothing is selected (< 0: off)
+    uint32_t steps = 4, passes = 32, min_frames = 0, max_frames = 0;   // --steps, --passes, --min-frames (0: the library's default), --max-frames
 };
 
 // out.ppm -> out.denoised.ppm
@@ -383,6 +390,60 @@ void run_scaled(const Options &o, const pth_scene &hs, RankResult &res, std::vec
     pt_scene_destroy(scene);
     pt_ctx_destroy(ctx);
 }
+
+// --adaptive THRESH: passes of o.steps frames over the tiles still above the threshold, until a dry run selects nothing.
+void run_adaptive(Options &o, const pth_scene &hs, RankResult &res, std::vector<float> *image_f32, std::vector<uint8_t> *image_bgra8)
+{
+    pt_ctx *ctx = nullptr;
+    pt_scene *scene = nullptr;
+    pt_film *film = nullptr;
+    auto fail = [&](const char *what) { res.error = std::string(what) + ": " + (ctx ? pt_last_error(ctx) : pt_last_error(nullptr)); };
+    do {
+        if (pt_ctx_create(o.device, nullptr, &ctx) != PT_OK) { fail("pt_ctx_create"); break; }
+        if (pt_scene_create(ctx, hs.vertices, hs.n_verts, hs.indices, hs.n_tris, hs.faces, &scene) != PT_OK) { fail("pt_scene_create"); break; }
+        pt_scene_get_info(scene, &res.info);
+        if (pt_film_create(ctx, o.width, o.height, &film) != PT_OK || pt_film_enable_moments(film, nullptr) != PT_OK ||
+            pt_film_enable_counts(film, nullptr) != PT_OK) { fail("film set-up"); break; }
+        pt_params p;
+        pt_params_default(&p);
+        p.width = o.width; p.height = o.height; p.spp_per_frame = o.spp; p.max_depth = o.depth;
+        p.frames_in_flight = o.batch;
+        p.pipeline = o.pipeline;
+        if (o.nee) p.flags |= PT_FLAG_NEE;
+        pt_adaptive_params ap;
+        pt_adaptive_params_default(&ap);
+        ap.threshold = o.adaptive;
+        if (o.min_frames) ap.min_frames = o.min_frames;
+        ap.max_frames = o.max_frames;
+        bool ok = true;
+        unsigned long long rays_before = 0;
+        uint32_t frame = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t pass = 0; pass < o.passes; pass++) {
+            pt_adaptive_result r{};
+            p.frame = (int32_t)frame; p.frame_count = 0;   // the convergence query
+            if (pt_render_adaptive(scene, film, &p, &ap, &r) != PT_OK) { fail("pt_render_adaptive"); ok = false; break; }
+            if (r.tiles_selected == 0) break;
+            p.frame_count = o.steps;
+            if (pt_render_adaptive(scene, film, &p, &ap, &r) != PT_OK) { fail("pt_render_adaptive"); ok = false; break; }
+            frame += o.steps;
+            pt_get_stats(ctx, &res.st);
+            std::fprintf(stderr, "pass %u: %u of %u tiles, worst tile error %.4f, %llu rays\n", pass, r.tiles_selected, r.tiles_total, (double)r.max_error,
+                         (unsigned long long)res.st.rays - rays_before);
+            rays_before = res.st.rays;
+        }
+        if (!ok) break;
+        res.render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pt_get_stats(ctx, &res.st);
+        o.frames = std::max(frame, 1u);   // (the JSON line's frame count)
+        const size_t np = (size_t)o.width * o.height;
+        if (image_f32) { image_f32->resize(3 * np); if (pt_film_read_f32(film, image_f32->data()) != PT_OK) { fail("pt_film_read_f32"); break; } }
+        if (image_bgra8) { image_bgra8->resize(4 * np); if (pt_film_read_bgra8(film, image_bgra8->data()) != PT_OK) { fail("pt_film_read_bgra8"); break; } }
+    } while (false);
+    pt_film_destroy(film);
+    pt_scene_destroy(scene);
+    pt_ctx_destroy(ctx);
+}
 }  // namespace
 
 int main(int argc, char **argv)
@@ -441,6 +502,14 @@ int main(int argc, char **argv)
             if (s < 2) die("--render-scale needs an integer >= 2");
             o.render_scale = (uint32_t)s;
         }
+        else if (a == "--adaptive") {
+            o.adaptive = (float)std::atof(val());
+            if (!(o.adaptive >= 0.f)) die("--adaptive needs a threshold >= 0");
+        }
+        else if (a == "--steps") o.steps = (uint32_t)std::max(1, std::atoi(val()));
+        else if (a == "--passes") o.passes = (uint32_t)std::max(1, std::atoi(val()));
+        else if (a == "--min-frames") o.min_frames = (uint32_t)std::max(0, std::atoi(val()));
+        else if (a == "--max-frames") o.max_frames = (uint32_t)std::max(0, std::atoi(val()));
         else if (a == "--cam-step") {
             char tail = 0;
             if (std::sscanf(val(), "%f,%f,%f%c", &o.cam_step[0], &o.cam_step[1], &o.cam_step[2], &tail) != 3) die("--cam-step needs dx,dy,dz");
@@ -456,6 +525,8 @@ int main(int argc, char **argv)
     if (o.sigma_color > 0.f && o.ranks > 1) die("--sigma-color filters the film of one rank (no --ranks)");
     if (o.render_scale && (o.ranks > 1 || o.temporal || !o.aov.empty() || o.sigma_color > 0.f))
         die("--render-scale upsamples the film of one rank (no --ranks, --temporal, --aov or --sigma-color)");
+    if (o.adaptive >= 0.f && (o.ranks > 1 || o.temporal || o.render_scale || !o.aov.empty() || o.denoise >= 0))
+        die("--adaptive samples the film of one rank (no --ranks, --temporal, --render-scale, --aov or --denoise)");
     if (o.ranks > 1) {
         if (o.devices.empty()) for (uint32_t r = 0; r < o.ranks; r++) o.devices.push_back((int)r);
         if (o.devices.size() != o.ranks) die("--devices needs one ordinal per rank");
@@ -474,7 +545,9 @@ int main(int argc, char **argv)
     std::vector<uint8_t> image_bgra8;
     const bool want_f32 = !o.pfm.empty() || (o.ranks > 1 && !o.ppm.empty());
     const auto t2 = std::chrono::steady_clock::now();
-    if (o.render_scale) {
+    if (o.adaptive >= 0.f) {
+        run_adaptive(o, hs, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr);
+    } else if (o.render_scale) {
         run_scaled(o, hs, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr);
     } else if (o.temporal) {
         run_temporal(o, hs, res[0], want_f32 ? &image_f32 : nullptr, !o.ppm.empty() ? &image_bgra8 : nullptr);
