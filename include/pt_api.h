@@ -713,6 +713,43 @@ void pt_adaptive_params_default(pt_adaptive_params *p);
 pt_status pt_render_adaptive(pt_scene *scene, pt_film *film, const pt_params *params,
                              const pt_adaptive_params *ap, pt_adaptive_result *result /* may be NULL */);
 
+/* ---- film and guides of one camera in one pass ------------------------------------------------------------------
+ * Every film pass wants the radiance film and the first-hit guides of the same camera; pt_render followed by pt_render_aov walks the camera
+ * rays twice.  pt_render_guided(scene, film, params, gp, result) walks them once: pt_render's fused kernels store the first hit of every
+ * camera ray in a log, and a reduce kernel folds the log into the guide planes with pt_render_aov's arithmetic.
+ * CONTRACT: after the call the film holds exactly what pt_render(scene, film, params) followed by pt_render_aov(scene, film, params) leaves,
+ * bit for bit: C, bgra8, M if enabled, the recorded `frames`, and the six guide planes, film-owned or external.
+ * mode  PT_GUIDED_AUTO         the single pass wherever pt_render would run a fused kernel for these params (single-level and instanced scenes
+ *                              that live in LDS, with or without PT_FLAG_NEE, PT_PIPELINE_AUTO or _FUSED, params.extend = PT_EXTEND_AUTO) and the
+ *                              log fits; everywhere else the two existing calls one after the other -- never an error they would not give
+ *       PT_GUIDED_SINGLE_PASS  PT_ERR_UNSUPPORTED where AUTO would take the two calls
+ *       PT_GUIDED_TWO_CALLS    the two calls, always
+ * pt_stats: the single pass adds pt_render's rays, paths and rays_culled alone (no second trace happened), the two calls both calls'; `pipeline`
+ * is what rendered.  result: single_pass says which form ran; launches is the number of fused launches of the single pass (0 in the two-call
+ * form); guide_ms is the device time of the reduce launches, in the two-call form that of the pt_render_aov part.
+ * The log is the film's scratch: 8 bytes x pixels of the rank's 8x8 tiles x spp x frames per launch (0.53 GB for one 1080p frame at 32 spp).  It only
+ * grows, counts against pt_tuning.mem_budget_mb beside the render workspace and is freed by pt_film_destroy.  The call may render its frames in
+ * more launches than pt_render would so that the log fits (the film does not depend on the frames in flight); if not even one frame fits,
+ * AUTO takes the two calls.
+ * Blocking: any flag but PT_FLAG_NEE -- PT_FLAG_ASYNC, PT_FLAG_PROFILE, PT_FLAG_COUNT_VISITS, and the ray-sort flags pt_render_aov refuses -- and
+ * PT_PIPELINE_WAVEFRONT_NEE (pt_render_aov's refusal) are PT_ERR_UNSUPPORTED, before anything is launched.
+ * PT_ERR_INVALID_ARG, nothing written and nothing launched: NULL scene, film, params or gp; a film without guides; an unknown mode; a nonzero
+ * reserved word; every refusal of pt_render.                                                                                            */
+enum { PT_GUIDED_AUTO = 0, PT_GUIDED_SINGLE_PASS = 1, PT_GUIDED_TWO_CALLS = 2 };
+typedef struct pt_guided_params {
+    uint32_t mode;         /* PT_GUIDED_*; default PT_GUIDED_AUTO */
+    uint32_t reserved[7];  /* must be 0 */
+} pt_guided_params;        /* 32 bytes */
+typedef struct pt_guided_result {
+    uint32_t single_pass;  /* 1: the single pass ran; 0: pt_render then pt_render_aov */
+    uint32_t launches;     /* fused launches of the single pass */
+    float    guide_ms;     /* device time of the guides' part */
+    uint32_t reserved[5];
+} pt_guided_result;        /* 32 bytes */
+void pt_guided_params_default(pt_guided_params *p);
+pt_status pt_render_guided(pt_scene *scene, pt_film *film, const pt_params *params,
+                           const pt_guided_params *gp, pt_guided_result *result /* may be NULL */);
+
 /* ---- closest-hit query alone: traceRayEXT (raygen.rgen:63-75) -------------------------- */
 typedef struct pt_hit {
     uint32_t prim;  /* gl_PrimitiveID, 0xFFFFFFFF = miss                                   */

@@ -132,6 +132,21 @@ class AdaptiveResult(C.Structure):
                 ("select_ms", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+GUIDED_AUTO = 0          # include/pt_api.h PT_GUIDED_*: which form pt_render_guided takes
+GUIDED_SINGLE_PASS = 1
+GUIDED_TWO_CALLS = 2
+
+
+class GuidedParams(C.Structure):
+    """include/pt_api.h pt_guided_params: the form of pt_render_guided."""
+    _fields_ = [("mode", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class GuidedResult(C.Structure):
+    """include/pt_api.h pt_guided_result: which form ran, its fused launches, the device time of the guides' part."""
+    _fields_ = [("single_pass", C.c_uint32), ("launches", C.c_uint32), ("guide_ms", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 REPROJECT_MATCH_ID = 1   # include/pt_api.h PT_REPROJECT_MATCH_ID
 
 
@@ -177,7 +192,8 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_scene_snapshot_previous", "pt_film_enable_motion", "pt_film_read_motion", "pt_motion_params_default", "pt_film_motion",
                "pt_film_reproject_motion", "pt_denoise_history_params_default", "pt_film_denoise_history",
                "pt_upsample_params_default", "pt_film_upsample", "pt_film_read_upsampled",
-               "pt_film_enable_counts", "pt_film_read_counts", "pt_adaptive_params_default", "pt_render_adaptive"]
+               "pt_film_enable_counts", "pt_film_read_counts", "pt_adaptive_params_default", "pt_render_adaptive",
+               "pt_guided_params_default", "pt_render_guided"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium"]
 
@@ -275,6 +291,10 @@ def lib_amd():
             L.pt_adaptive_params_default.argtypes = [C.POINTER(AdaptiveParams)]
             L.pt_adaptive_params_default.restype = None
             L.pt_render_adaptive.argtypes = [vp, vp, C.POINTER(Params), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveResult)]
+        if hasattr(L, "pt_render_guided"):   # (film and guides in one pass; as above)
+            L.pt_guided_params_default.argtypes = [C.POINTER(GuidedParams)]
+            L.pt_guided_params_default.restype = None
+            L.pt_render_guided.argtypes = [vp, vp, C.POINTER(Params), C.POINTER(GuidedParams), C.POINTER(GuidedResult)]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
@@ -439,6 +459,10 @@ def upsample_default_params():
 
 def adaptive_default_params():
     return _default_params(AdaptiveParams, "pt_adaptive_params_default")
+
+
+def guided_default_params():
+    return _default_params(GuidedParams, "pt_guided_params_default")
 
 
 def reproject_default_params():
@@ -913,6 +937,19 @@ def render_adaptive(scene, film, params, adaptive_params=None, **adaptive):
         setattr(ap, k, v)
     res = AdaptiveResult()
     scene.ctx._check(lib_amd().pt_render_adaptive(scene.h, film.h, C.byref(params), C.byref(ap), C.byref(res)))
+    return res
+
+
+def render_guided(scene, film, params, mode=GUIDED_AUTO, guided_params=None):
+    """pt_render and pt_render_aov of the same params in one call (include/pt_api.h pt_render_guided) -> GuidedResult: the film and its guide
+    planes (Film.enable_aov) end up as the two calls leave them, bit for bit; where a fused kernel renders, the camera rays are walked once.
+    mode: GUIDED_AUTO, GUIDED_SINGLE_PASS (PtError where AUTO would take the two calls) or GUIDED_TWO_CALLS; guided_params, if given, is used
+    as it is."""
+    gp = guided_params if guided_params is not None else guided_default_params()
+    if guided_params is None:
+        gp.mode = mode
+    res = GuidedResult()
+    scene.ctx._check(lib_amd().pt_render_guided(scene.h, film.h, C.byref(params), C.byref(gp), C.byref(res)))
     return res
 
 

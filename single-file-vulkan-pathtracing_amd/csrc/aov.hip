@@ -22,6 +22,7 @@
 
 namespace {
 using namespace ptw;
+#include "guided_kernel.h"  // AovPlanes, Guide, guide_add / guide_blend / guide_load / guide_store: shared with pt_render_guided's reduce (guided.hip)
 
 struct AovConst {
     ptm::Camera cam;
@@ -33,10 +34,6 @@ struct AovConst {
     uint32_t cull_on;
     int32_t cull[4];
 };
-struct AovPlanes {
-    float *albedo, *normal, *emission, *depth, *alpha;
-    uint2 *id;
-};
 constexpr size_t AOV_RAY_BYTES = sizeof(float4) + sizeof(float2) + sizeof(float4) + sizeof(uint32_t);  // rayA, rayB, hit, hit_inst
 constexpr size_t AOV_MAX_CHUNK_RAYS = (size_t)1 << 26;                                                  // 2.75 GB of them at most, whatever the budget
 constexpr uint32_t AOV_NEXT_TILE = 32;  // word of Aov::d_count the single-kernel form hands tiles out of (a line of its own)
@@ -46,48 +43,6 @@ __device__ __forceinline__ void tile_pixel(const uint32_t *__restrict__ tiles, u
     const uint32_t g = tiles[pix >> 6];  // tile x | tile y << 16
     px = (g & 0xFFFFu) * 8u + (pix & 7u);
     py = (g >> 16) * 8u + ((pix >> 3) & 7u);
-}
-
-// the eleven running sums of a pixel: one frame's, or the plane values
-struct Guide {
-    float ar, ag, ab, nx, ny, nz, er, eg, eb, d, a;
-};
-__device__ __forceinline__ void guide_add(Guide &g, const Guide &v)
-{
-    g.ar = g.ar + v.ar; g.ag = g.ag + v.ag; g.ab = g.ab + v.ab;
-    g.nx = g.nx + v.nx; g.ny = g.ny + v.ny; g.nz = g.nz + v.nz;
-    g.er = g.er + v.er; g.eg = g.eg + v.eg; g.eb = g.eb + v.eb;
-    g.d = g.d + v.d; g.a = g.a + v.a;
-}
-// raygen.rgen:86, 88-90 per channel: sum / spp, then (value + old * frame) / (frame + 1)
-__device__ __forceinline__ float blend1(float sum, float spp, float old, bool first, float ff, float f1)
-{
-    return ptm::fdiv(ptm::fdiv(sum, spp) + (first ? 0.f : old) * ff, f1);
-}
-__device__ __forceinline__ void guide_blend(Guide &acc, const Guide &sum, float spp, int32_t frame)
-{
-    const float ff = (float)frame, f1 = (float)(frame + 1);
-    const bool first = frame == 0;
-    acc.ar = blend1(sum.ar, spp, acc.ar, first, ff, f1); acc.ag = blend1(sum.ag, spp, acc.ag, first, ff, f1); acc.ab = blend1(sum.ab, spp, acc.ab, first, ff, f1);
-    acc.nx = blend1(sum.nx, spp, acc.nx, first, ff, f1); acc.ny = blend1(sum.ny, spp, acc.ny, first, ff, f1); acc.nz = blend1(sum.nz, spp, acc.nz, first, ff, f1);
-    acc.er = blend1(sum.er, spp, acc.er, first, ff, f1); acc.eg = blend1(sum.eg, spp, acc.eg, first, ff, f1); acc.eb = blend1(sum.eb, spp, acc.eb, first, ff, f1);
-    acc.d = blend1(sum.d, spp, acc.d, first, ff, f1); acc.a = blend1(sum.a, spp, acc.a, first, ff, f1);
-}
-__device__ __forceinline__ Guide guide_load(const AovPlanes &pl, size_t pix)
-{
-    Guide g;
-    g.ar = pl.albedo[3 * pix + 0]; g.ag = pl.albedo[3 * pix + 1]; g.ab = pl.albedo[3 * pix + 2];
-    g.nx = pl.normal[3 * pix + 0]; g.ny = pl.normal[3 * pix + 1]; g.nz = pl.normal[3 * pix + 2];
-    g.er = pl.emission[3 * pix + 0]; g.eg = pl.emission[3 * pix + 1]; g.eb = pl.emission[3 * pix + 2];
-    g.d = pl.depth[pix]; g.a = pl.alpha[pix];
-    return g;
-}
-__device__ __forceinline__ void guide_store(const AovPlanes &pl, size_t pix, const Guide &g)
-{
-    pl.albedo[3 * pix + 0] = g.ar; pl.albedo[3 * pix + 1] = g.ag; pl.albedo[3 * pix + 2] = g.ab;
-    pl.normal[3 * pix + 0] = g.nx; pl.normal[3 * pix + 1] = g.ny; pl.normal[3 * pix + 2] = g.nz;
-    pl.emission[3 * pix + 0] = g.er; pl.emission[3 * pix + 1] = g.eg; pl.emission[3 * pix + 2] = g.eb;
-    pl.depth[pix] = g.d; pl.alpha[pix] = g.a;
 }
 
 // ---- queue form ------------------------------------------------------------------------------------------------------------

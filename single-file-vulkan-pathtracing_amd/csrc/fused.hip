@@ -28,6 +28,7 @@ extern "C" int pt_debug_fused_hist(void *device_u32_2x8192x16)
 
 namespace {
 using namespace ptw;
+#include "guided_kernel.h"  // (the first-hit log's index: the kernels with LOG are fused_guided.hip's)
 #include "fused_dev.h"
 #include "fused_kernel.h"
 #include "fused_inst_kernel.h"

@@ -25,16 +25,34 @@
 #endif
 constexpr int FITB = PT_FUSEDI_TB;
 
+// PT_FUSEDI_LOG (fused_guided.hip defines it to 1 before it includes this header; pt_render_guided): the kernel below is k_fused_inst_log, takes the
+// launch's first-hit log as one more argument and stores the first hit of every camera ray in it, as fused_kernel.h's LOG does; its first word
+// packs the instance's TLAS leaf position with the triangle's (gd_pack_inst, guided_kernel.h).  By the preprocessor and not by a template flag:
+// wrapped into a body that two __global__ functions share, this kernel's register allocation changes, and k_fused_inst is to stay what it was.
+#ifndef PT_FUSEDI_LOG
+#define PT_FUSEDI_LOG 0
+#endif
+#if PT_FUSEDI_LOG
+#define PT_FUSEDI_KERNEL k_fused_inst_log
+#define PT_FUSEDI_LOG_ARG , uint2 *log_arg
+#else
+#define PT_FUSEDI_KERNEL k_fused_inst
+#define PT_FUSEDI_LOG_ARG
+#endif
+
 // PAIRS: every BLAS leaf is one triangle or one fan pair (tested with shared vertex work); else leaves of up to four triangles
 template <bool GROUPED, bool PAIRS>
-__global__ __launch_bounds__(FITB, PT_FUSEDI_WAVES) void k_fused_inst(
+__global__ __launch_bounds__(FITB, PT_FUSEDI_WAVES) void PT_FUSEDI_KERNEL(
     RenderConst rc_arg, const uint32_t *__restrict__ tiles_arg, Radiance rad_arg, const uint4 *__restrict__ tlas16_arg, NormBox nbt_arg,
     const uint4 *__restrict__ g_blas16, NormBox nbb_arg, const float4 *__restrict__ g_tri4, const float4 *__restrict__ g_shade4,
     uint32_t n_blas_wide, uint32_t n_tris, const float4 *__restrict__ inst6_arg, const uint32_t *__restrict__ inst_id_arg,
     const float4 *__restrict__ inst_frame_arg, uint32_t slot_base_arg, uint32_t n_slots_arg, uint32_t *next_slot_arg, unsigned long long *stats_arg,
     uint32_t *__restrict__ spill_arg, uint32_t spill_stride_arg, int refill_arg, float tmin_arg, float tmax_arg, int lds_stack, int enter_min_arg,
-    int leaf_min_arg, int node_yield_arg, uint32_t n_tlas_lds_arg)
+    int leaf_min_arg, int node_yield_arg, uint32_t n_tlas_lds_arg PT_FUSEDI_LOG_ARG)
 {
+#if PT_FUSEDI_LOG
+    uint2 *log = ptm::own_sgprs(log_arg);
+#endif
     // (everything the persistent loop reads: a scalar register of its own -- ptm::own_sgprs)
     const RenderConst rc = ptm::own_sgprs(rc_arg);
     const Radiance rad = ptm::own_sgprs(rad_arg);
@@ -171,6 +189,15 @@ __global__ __launch_bounds__(FITB, PT_FUSEDI_WAVES) void k_fused_inst(
                 float er, eg, eb;
                 bool terminated, add;
                 const uint32_t pos = best_pos;
+#if PT_FUSEDI_LOG
+                if (depth == 0u) {  // a camera ray ended: its record at (frame of the launch, sample, pixel of the tile list)
+                    const uint32_t mine = slot - slot_base;
+                    const uint32_t lane_slot = rc.div_spl.div(mine);  // = frame | frame * groups + group
+                    const uint32_t local = mine - lane_slot * rc.slots_per_lane;
+                    const uint32_t f = GROUPED ? rc.div_groups.div(lane_slot) : lane_slot;
+                    ptm::st_stream<true>(log + gd_log_index(f, local, sample, rc.slots_per_lane, rc.spp), make_uint2(gd_pack_inst(pos, best_ipos), __float_as_uint(best_t)));
+                }
+#endif
                 if (pos == PT_MISS) {  // miss.rmiss:10-11 then raygen.rgen:76, 81-83
                     er = wr * rc.env[0]; eg = wg * rc.env[1]; eb = wb * rc.env[2];
                     add = true;
@@ -485,3 +512,5 @@ __global__ __launch_bounds__(FITB, PT_FUSEDI_WAVES) void k_fused_inst(
     if (lane == 0 && n_rays_wave) atomicAdd(stats, (unsigned long long)n_rays_wave);
     if (lane == 0 && n_cull_wave) atomicAdd(stats + 19, (unsigned long long)n_cull_wave);  // (pt_stats.rays_culled)
 }
+#undef PT_FUSEDI_KERNEL
+#undef PT_FUSEDI_LOG_ARG

@@ -163,18 +163,23 @@ enum FusedBlock : int {
 // one light sample (ptn::nee_sample, three random numbers before the bounce's two) whose shadow ray this lane walks next -- an any-hit walk up to
 // the sample's own tmax -- then the bounce.  Per sample the adds are the depth-0 emission, the light samples hit by hit, env at the miss: the
 // oracle's order.  One sample group only (MODE 0).
-template <int MODE, bool PAIRS, bool COUNT, bool NEE = false>
+// LOG (pt_render_guided, fused_guided.hip): the shade block stores the first hit of every camera ray -- {best_pos, bits(best_t)}, a miss as PT_MISS --
+// at gd_log_index (guided_kernel.h): k_aov_reduce's input order per frame of the launch.  No LDS, no accumulator; the instantiations with LOG =
+// false carry none of it.
+template <int MODE, bool PAIRS, bool COUNT, bool NEE = false, bool LOG = false>
 __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *__restrict__ tiles_arg, Radiance rad_arg,
                                            const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
                                            const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
                                            uint32_t n_wide, uint32_t n_tris, uint32_t slot_base_arg, uint32_t n_slots_arg,
                                            uint32_t *next_slot_arg, unsigned long long *stats_arg, int refill_arg, float tmin_arg,
                                            float tmax_arg, int lds_stack, FastDiv div_frames_arg,
-                                           const float4 *__restrict__ lights_arg = nullptr, uint32_t n_lights_arg = 0u, float light_area_arg = 0.f)
+                                           const float4 *__restrict__ lights_arg = nullptr, uint32_t n_lights_arg = 0u, float light_area_arg = 0.f,
+                                           uint2 *log_arg = nullptr)
 {
     constexpr uint32_t LEAF_BIT = C14_LEAF, DONE = C14_DONE;
     constexpr bool GROUPED = MODE == 1, HYB = MODE == 2;
     static_assert(!NEE || (MODE == 0 && !COUNT), "NEE: one sample group, no instrumented twin");
+    static_assert(!LOG || !COUNT, "the first-hit log: no instrumented twin");
     // (everything the persistent loop reads: a scalar register of its own -- own_sgprs)
     const RenderConst rc = ptm::own_sgprs(rc_arg);
     const Radiance rad = ptm::own_sgprs(rad_arg);
@@ -193,6 +198,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
         n_lights = ptm::own_sgprs(n_lights_arg);
         light_area = ptm::own_sgprs(light_area_arg);
     }
+    uint2 *log = nullptr;  // LOG: the first-hit log of the launch
+    if constexpr (LOG) log = ptm::own_sgprs(log_arg);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // ---- LDS: BVH4 nodes | three permuted triangle copies | shade4 | tangent frames | stack | path state (fused_lds)
     const FusedLds lds = fused_lds(n_wide, n_tris, (uint32_t)lds_stack);
@@ -319,6 +326,18 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 bool terminated, add;
                 const uint32_t pos = best_pos;
                 const uint32_t npos = NEE ? (uint32_t)my_nee[FS_NEE_POS * FTB] : PT_MISS;
+                if constexpr (LOG) {
+                    // a camera ray ended (depth 0: a NEE shadow ray returns at depth >= 1): its record, at (frame of the launch, sample, pixel of the
+                    // tile list) -- the slot number decoded as the hand-out encodes it
+                    if (depth == 0u) {
+                        const bool tail_slot = HYB && slot >= rc.n_head;
+                        const uint32_t mine = tail_slot ? slot - rc.n_head : slot - slot_base;
+                        const uint32_t lane_slot = rc.div_spl.div(mine);  // = frame (one group, head slots) | frame * groups + group | frame * tail + tail j
+                        const uint32_t local = mine - lane_slot * rc.slots_per_lane;
+                        const uint32_t f = GROUPED ? rc.div_groups.div(lane_slot) : tail_slot ? rc.div_tail.div(lane_slot) : lane_slot;
+                        ptm::st_stream<true>(log + gd_log_index(f, local, sample, rc.slots_per_lane, rc.spp), make_uint2(pos, __float_as_uint(best_t)));
+                    }
+                }
                 if (NEE && npos != PT_MISS) {  // NEE: the shadow ray of hit npos ended -- its light sample counts if nothing was in the way; then that hit's bounce
                     er = __uint_as_float(my_nee[FS_NEE_R * FTB]); eg = __uint_as_float(my_nee[FS_NEE_G * FTB]); eb = __uint_as_float(my_nee[FS_NEE_B * FTB]);
                     add = pos == PT_MISS;
@@ -779,4 +798,28 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES) void k_fused_count(RenderConst
 {
     fused_body<MODE, PAIRS, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill, tmin,
                                   tmax, lds_stack, div_frames);
+}
+// the kernels above with the first-hit log (LOG): pt_render_guided's launches.  No instrumented twin.
+template <int MODE, bool PAIRS>
+__global__ __launch_bounds__(FTB, PT_FUSED_WAVES) void k_fused_log(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad,
+                                                                  const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
+                                                                  const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
+                                                                  uint32_t n_wide, uint32_t n_tris, uint32_t slot_base, uint32_t n_slots,
+                                                                  uint32_t *next_slot, unsigned long long *stats, int refill, float tmin,
+                                                                  float tmax, int lds_stack, FastDiv div_frames, uint2 *log)
+{
+    fused_body<MODE, PAIRS, false, false, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill,
+                                                tmin, tmax, lds_stack, div_frames, nullptr, 0u, 0.f, log);
+}
+template <bool PAIRS>
+__global__ __launch_bounds__(FTB, PT_FUSED_WAVES_NEE) void k_fused_nee_log(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad,
+                                                                          const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
+                                                                          const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
+                                                                          uint32_t n_wide, uint32_t n_tris, uint32_t slot_base, uint32_t n_slots,
+                                                                          uint32_t *next_slot, unsigned long long *stats, int refill, float tmin,
+                                                                          float tmax, int lds_stack, FastDiv div_frames,
+                                                                          const float4 *__restrict__ lights, uint32_t n_lights, float light_area, uint2 *log)
+{
+    fused_body<0, PAIRS, false, true, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill,
+                                            tmin, tmax, lds_stack, div_frames, lights, n_lights, light_area, log);
 }

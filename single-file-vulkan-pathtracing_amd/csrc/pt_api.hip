@@ -361,6 +361,7 @@ void pt_film_destroy(pt_film *f)
     ptd_free(f);
     ptu_free(f);
     ptad_free(f);
+    ptg_free(f);
     pt_planes_free(f);
     if (f->own_rgb) (void)hipFree(f->d_rgb);
     (void)hipFree(f->d_bgra);
@@ -643,6 +644,21 @@ pt_status pt_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p, const 
     if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
     PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
     return guarded(s->ctx, [&] { return ptw_render_adaptive(s, f, p, ap, result); });
+}
+
+void pt_guided_params_default(pt_guided_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->mode = PT_GUIDED_AUTO;
+}
+
+pt_status pt_render_guided(pt_scene *s, pt_film *f, const pt_params *p, const pt_guided_params *gp, pt_guided_result *result)
+{
+    if (!s || !f || !p || !gp) return PT_ERR_INVALID_ARG;
+    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return ptw_render_guided(s, f, p, gp, result); });
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)

@@ -264,6 +264,13 @@ struct pt_film {
         size_t cap = 0;                               // tiles the arrays hold
         size_t bytes = 0;                             // device bytes of all of the above
     } ad;
+    // pt_render_guided's first-hit log (guided.hip): the film's scratch, made by the first single-pass call; it only grows and counts against the
+    // memory budget beside the render workspace.
+    struct Guided {
+        uint2 *d_log = nullptr;                       // 8 B per (frame of a launch, pixel of the tile list, sample): guided_kernel.h
+        size_t cap = 0;                               // records it holds
+        size_t bytes = 0;                             // its device bytes
+    } gd;
 };
 
 #define PT_HIP(ctx, call)                                                                         \
@@ -416,3 +423,7 @@ pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *
 // render.hip: pt_render_adaptive (validates everything but the null checks); adaptive.hip: the selection's scratch
 pt_status ptw_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p, const pt_adaptive_params *ap, pt_adaptive_result *result);
 void ptad_free(pt_film *f);
+// render.hip: pt_render_guided (validates everything but the null checks); guided.hip: the first-hit log and the reduce that folds it into the guides
+pt_status ptw_render_guided(pt_scene *s, pt_film *f, const pt_params *p, const pt_guided_params *gp, pt_guided_result *result);
+pt_status ptg_ensure_log(pt_film *f, size_t records);  // the film's log holds at least `records` records (PT_ERR_OOM: not within the budget / the device)
+void ptg_free(pt_film *f);

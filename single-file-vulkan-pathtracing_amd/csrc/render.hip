@@ -632,8 +632,10 @@ uint32_t fused_tail_samples(const pt_ctx *ctx, const pt_film *f, const pt_params
     return (uint32_t)std::max(0, std::min<int>(t, (int)spp - 1));
 }
 
+// gd (pt_render_guided): every launch also writes the film's first-hit log (fused_guided.hip), and the reduce behind it folds the log into the
+// guide planes (guided.hip).  The caller has sized the log for the frames in flight it passes.
 pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const ExtendPlan &pl, bool nested, bool prepare_only, const TileView *sel = nullptr,
-                       AdaptCall *ad = nullptr)
+                       AdaptCall *ad = nullptr, GuidedCall *gd = nullptr)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
@@ -747,6 +749,10 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
     if (!nested) PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
     std::vector<hipEvent_t> evs;
     size_t ev_used = 0;
+    if (gd && (size_t)sh.lanes * rc.slots_per_lane * rc.spp > f->gd.cap) {  // (never: ptw_render_guided sized the log for this shape)
+        ctx->err = "pt_render_guided: the first-hit log is smaller than the launch";
+        return PT_ERR_OOM;
+    }
     for (uint32_t done = 0; rc.n_slots > 0 && done < p->frame_count; done += sh.lanes) {
         const TileView tv = ptw_tile_view(f, sel);
         rc.frame_base = p->frame + (int32_t)done;
@@ -770,12 +776,33 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
             e0 = ctx->ev_pool[ev_used++]; e1 = ctx->ev_pool[ev_used++];
             evs.push_back(e0); evs.push_back(e1);
         }
-        ptw_launch_fused(fp, sh.groups > 1, rc, tv.d_tiles, rad, s, n_slots, w.d_count, ctx->d_stats, p->tmin, p->tmax, st, e0, e1);  // (rc.tail != 0: the head + tail kernel)
+        if (gd) {
+            rc_ = ptw_launch_fused_log(fp, sh.groups > 1, rc, tv.d_tiles, rad, s, n_slots, w.d_count, ctx->d_stats, p->tmin, p->tmax, f->gd.d_log, st);
+            if (rc_ != PT_OK) return rc_;
+            gd->launches++;
+        } else {
+            ptw_launch_fused(fp, sh.groups > 1, rc, tv.d_tiles, rad, s, n_slots, w.d_count, ctx->d_stats, p->tmin, p->tmax, st, e0, e1);  // (rc.tail != 0: the head + tail kernel)
+        }
         PT_HIP(ctx, hipGetLastError());
         ctx->stats.launches_extend++;
         ctx->stats.rounds++;
         launch_resolve(f, rc, tv, rad, st, sh.bounded ? d_overflow : nullptr);
         ctx->stats.launches_other++;
+        if (gd) {
+            // The launch's frames into the guide planes, timed by a pair of pooled events (the call is not profiled).  Queued here, before the overflow
+            // flag is looked at: a launch whose term log overflows still walks every path to its end, so its log is complete, and the redo below --
+            // which numbers its slots by the one-group tile order, another list than a grouped launch's (film_work.hip) -- neither writes nor needs it.
+            rc_ = grow_event_pool(ctx, ev_used + 2);
+            if (rc_ != PT_OK) return rc_;
+            hipEvent_t g0 = ctx->ev_pool[ev_used++], g1 = ctx->ev_pool[ev_used++];
+            evs.push_back(g0); evs.push_back(g1);
+            PT_HIP(ctx, hipEventRecord(g0, st));
+            const uint32_t last = p->frame_count - 1u - done;  // the call's last frame, counted from this launch's first
+            ptg_launch_reduce(s, f, rc, tv.d_tiles, last, fp.inst_frame, st);
+            PT_HIP(ctx, hipGetLastError());
+            PT_HIP(ctx, hipEventRecord(g1, st));
+            ctx->stats.launches_other++;
+        }
         bool redo = false;
         if (sh.bounded) {
             unsigned long long flag = 0;
@@ -792,6 +819,7 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
             r.frame = rc.frame_base; r.frame_count = rc.lanes_active; r.frames_in_flight = rc.lanes_active; r.sample_groups = 1;
             rc_ = render_fused(s, f, &r, pl, true, false, sel);
             if (rc_ != PT_OK) return rc_;
+            if (gd) gd->launches++;
             rc_ = ptw_ensure_work(f, p->rank, p->world, sh.lanes, sh.groups, sh.term_cap, sh.term_pcap, false, sh.tail);
             if (rc_ != PT_OK) return rc_;
             rc_ = set_rad();
@@ -810,7 +838,9 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
     }
     for (size_t i = 0; i + 1 < evs.size(); i += 2) {
         float a = 0.f;
-        if (hipEventElapsedTime(&a, evs[i], evs[i + 1]) == hipSuccess) ctx->stats.ms_extend += a;
+        if (hipEventElapsedTime(&a, evs[i], evs[i + 1]) != hipSuccess) continue;
+        if (gd) gd->guide_ms += a;  // (a guided call is not profiled: the pairs are its reduce launches')
+        else ctx->stats.ms_extend += a;
     }
     return PT_OK;
 }
@@ -942,6 +972,87 @@ pt_status ptw_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p_in, co
     ctx->stats.pipeline = p_res.pipeline;
     rc_ = p_res.pipeline == PT_PIPELINE_FUSED ? render_fused(s, f, &p_res, pl, false, false, nullptr, &ad) : render_wavefront(s, f, &p_res, pl, false, nullptr, &ad);
     if (rc_ == PT_OK && result) *result = ad.res;
+    return rc_;
+}
+
+// pt_render_guided (include/pt_api.h has the contract): pt_render with the guides written from its own camera rays where a fused kernel renders,
+// pt_render followed by pt_render_aov everywhere else.  Every refusal comes before anything is allocated, launched or written.
+pt_status ptw_render_guided(pt_scene *s, pt_film *f, const pt_params *p_in, const pt_guided_params *gp, pt_guided_result *result)
+{
+    pt_ctx *ctx = s->ctx;
+    if (result) *result = pt_guided_result{};
+    if (!f->aov.enabled) return pt_bad(ctx, "the film has no guide buffers: pt_film_enable_aov first");
+    if (gp->mode > PT_GUIDED_TWO_CALLS) return pt_bad(ctx, "pt_guided_params.mode is none of PT_GUIDED_AUTO, _SINGLE_PASS, _TWO_CALLS");
+    PT_TRY(pt_check_reserved(ctx, "pt_guided_params", gp->reserved));
+    pt_status rc_ = check_params(s, f, p_in);
+    if (rc_ != PT_OK) return rc_;
+    if (p_in->flags & ~(uint32_t)PT_FLAG_NEE) {
+        ctx->err = "pt_render_guided takes no flag but PT_FLAG_NEE: blocking, not instrumented (pt_render_aov's rule)";
+        return PT_ERR_UNSUPPORTED;
+    }
+    if (p_in->pipeline == PT_PIPELINE_WAVEFRONT_NEE) {
+        ctx->err = "pt_render_guided: PT_FLAG_NEE names the estimator (pt_render_aov takes PT_PIPELINE_WAVEFRONT, _FUSED or _AUTO)";
+        return PT_ERR_UNSUPPORTED;
+    }
+    rc_ = s->broken ? ptb_repair(s) : PT_OK;
+    if (rc_ != PT_OK) return rc_;
+    ExtendPlan pl;
+    rc_ = ptw_plan_extend(s, p_in->extend, pl);
+    if (rc_ != PT_OK) return rc_;
+    pt_params p_res = *p_in;
+    p_res.pipeline = resolve_pipeline(s, p_in, pl);
+    // the single pass: where a fused kernel renders these params and pt_render_aov's fused or queue form would serve them too
+    bool single = gp->mode != PT_GUIDED_TWO_CALLS && p_res.pipeline == PT_PIPELINE_FUSED && p_in->extend == PT_EXTEND_AUTO && p_in->width <= 0xFFFFu &&
+                  p_in->height <= 0xFFFFu;
+    const char *why = "pt_render would not run a fused kernel for these params (PT_GUIDED_AUTO takes the two calls)";
+    if (single) {  // (PT_PIPELINE_FUSED by name: the scene has to be of the fused kernels' class)
+        FusedPlan fp;
+        const std::string keep = ctx->err;
+        single = ptw_plan_fused(s, pl, p_in->tmin, fp, (p_in->flags & PT_FLAG_NEE) != 0) == PT_OK;
+        ctx->err = keep;
+    }
+    // the log: the frames per launch pt_render would take, or as many as fit beside its workspace (planned again for fewer: at most twice)
+    bool have_log = false;
+    for (int pass = 0; single && !have_log && pass < 4; pass++) {
+        rc_ = render_fused(s, f, &p_res, pl, false, true);
+        if (rc_ != PT_OK) return rc_;
+        const uint32_t lanes = std::max(ctx->stats.frames_in_flight, 1u);
+        const size_t per_frame = (size_t)f->work.n_tiles * 64 * p_in->spp_per_frame;  // records
+        if (per_frame == 0) { have_log = true; break; }  // (a rank without tiles: nothing is launched)
+        size_t fit = lanes;
+        if (ctx->mem_budget) fit = std::min<size_t>(fit, (ctx->mem_budget > f->work.bytes ? ctx->mem_budget - f->work.bytes : 0) / (per_frame * sizeof(uint2)));
+        if (fit == 0) { single = false; why = "pt_render_guided: not one frame of the first-hit log fits the memory budget"; break; }
+        if (fit < lanes) {  // (equal launches, as pt_render batches its frames: 16 frames where 15 fit are 8 + 8)
+            const size_t batches = (p_in->frame_count + fit - 1) / fit;
+            p_res.frames_in_flight = (uint32_t)std::min<size_t>(fit, (p_in->frame_count + batches - 1) / batches);
+            continue;
+        }
+        const std::string keep = ctx->err;
+        if (ptg_ensure_log(f, per_frame * lanes) != PT_OK) {  // (the device has no room: the two calls need none)
+            ctx->err = keep;
+            single = false;
+            why = "pt_render_guided: no room for the first-hit log";
+        }
+        have_log = single;
+    }
+    if (single && !have_log) { single = false; why = "pt_render_guided: the first-hit log does not fit beside the render workspace"; }
+    if (!single && gp->mode == PT_GUIDED_SINGLE_PASS) { ctx->err = why; return PT_ERR_UNSUPPORTED; }
+    if (single) {
+        ctx->stats.pipeline = PT_PIPELINE_FUSED;
+        GuidedCall gd;
+        rc_ = render_fused(s, f, &p_res, pl, false, false, nullptr, nullptr, &gd);
+        if (rc_ != PT_OK) return rc_;
+        f->m2.frames = (uint32_t)p_in->frame + p_in->frame_count;
+        if (result) { result->single_pass = 1; result->launches = gd.launches; result->guide_ms = gd.guide_ms; }
+        return PT_OK;
+    }
+    rc_ = ptw_render(s, f, p_in);
+    if (rc_ != PT_OK) return rc_;
+    const uint32_t rendered_by = ctx->stats.pipeline;
+    const float ms_before = ctx->stats.ms_total;
+    rc_ = pta_render(s, f, p_in);
+    ctx->stats.pipeline = rendered_by;
+    if (rc_ == PT_OK && result) result->guide_ms = ctx->stats.ms_total - ms_before;
     return rc_;
 }
 

@@ -160,6 +160,17 @@ pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPla
 void ptw_launch_fused(const FusedPlan &fp, bool grouped, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad,
                       const pt_scene *s, uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax,
                       hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+// fused_guided.hip: the same launch by the kernels that also write the first-hit log (pt_render_guided; guided_kernel.h has the log's layout)
+pt_status ptw_launch_fused_log(const FusedPlan &fp, bool grouped, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, const pt_scene *s,
+                               uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax, uint2 *log, hipStream_t st);
+// guided.hip: the records of the launch's frames folded into the film's guide planes (id_frame: the frame of the launch that is the call's last, or
+// >= rc.lanes_active); inst_frame: FusedPlan::inst_frame
+void ptg_launch_reduce(const pt_scene *s, pt_film *f, const ptw::RenderConst &rc, const uint32_t *tiles, uint32_t id_frame, const float4 *inst_frame, hipStream_t st);
+// What pt_render_guided hands down to render_fused (render.hip): every launch writes the film's log and is followed by the reduce.
+struct GuidedCall {
+    uint32_t launches = 0;              // fused launches of the call
+    float guide_ms = 0.f;               // device time of the reduce launches
+};
 
 // ---- film_work.hip -----------------------------------------------------------------------------------------------------
 struct RenderShape {
