@@ -64,6 +64,15 @@ int pth_make_soup(uint32_t n_tris, uint32_t seed, pth_scene *out);
  * (384, 160) = 396 706 triangles: the tests' and the probe's scene; (640, 224) = 1.02 M.                            */
 int pth_make_stadium(uint32_t floor_side, uint32_t sphere_seg, pth_scene *out);
 
+/* The self-leaf rule of the fused kernel (csrc/self_leaf.h), as the scene packer and the kernel evaluate it -- the same
+ * functions, for tests that check the rule on the CPU.  A bounce ray that starts on triangle (e0, own, e1) of a leaf -- `other`: the apex of the
+ * leaf's second triangle (e0, e1, other), or NULL -- leaves that leaf out of its walk when dir . n >= max(thr, c1 * g).
+ * pth_self_leaf_rule: thr (+inf: never) and the bits of g (low 14 mantissa bits zero: the packer puts the leaf's code there);
+ * pth_self_leaf_c1: the launch's factor for its tmin; pth_self_leaf_skip: code[i] = g_word's low 14 bits where dt[i] passes, else 0.          */
+void pth_self_leaf_rule(const float *e0, const float *e1, const float *own, const float *other, float scene_e, float *thr, uint32_t *g_bits);
+float pth_self_leaf_c1(float tmin);
+void pth_self_leaf_skip(const float *dt, uint32_t n, float thr, uint32_t g_word, float c1, uint32_t *code);
+
 #ifdef __cplusplus
 }
 #endif

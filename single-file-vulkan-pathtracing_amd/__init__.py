@@ -169,7 +169,7 @@ class HostScene(C.Structure):
 
 # include/pt_api.h pt_fused_block, in order
 FUSED_BLOCKS = ["ITER", "SHADE", "HIT", "MISS", "SURFACE", "ADD", "BOUNCE", "NEXT", "DONE", "HANDOUT", "DRAW", "TAKE", "CULLED", "PRIMARY", "SETUP",
-                "NODE", "POP", "LEAF", "DIV", "FINISH", "TRACE", "SPAWN", "PTARGET", "PDIR", "POPTOP"]
+                "NODE", "POP", "LEAF", "DIV", "FINISH", "TRACE", "SPAWN", "PTARGET", "PDIR", "POPTOP", "SKIP"]
 # include/pt_api.h PT_AOV_*: the guide planes of pt_render_aov and their (trailing shape, dtype)
 AOV_ALBEDO, AOV_NORMAL, AOV_EMISSION, AOV_DEPTH, AOV_ALPHA, AOV_ID, AOV_COUNT = 0, 1, 2, 3, 4, 5, 6
 AOV_SHAPES = {AOV_ALBEDO: ((3,), np.float32), AOV_NORMAL: ((3,), np.float32), AOV_EMISSION: ((3,), np.float32),
@@ -195,7 +195,7 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_film_enable_counts", "pt_film_read_counts", "pt_adaptive_params_default", "pt_render_adaptive",
                "pt_guided_params_default", "pt_render_guided"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
-                "pth_make_stadium"]
+                "pth_make_stadium", "pth_self_leaf_rule", "pth_self_leaf_c1", "pth_self_leaf_skip"]
 
 _amd = None
 _host = None
@@ -333,11 +333,40 @@ def lib_host():
         L.pth_write_soup_obj.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32]
         L.pth_make_soup.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(HostScene)]
         L.pth_make_stadium.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(HostScene)]
+        L.pth_self_leaf_rule.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
+        L.pth_self_leaf_rule.restype = None
+        L.pth_self_leaf_c1.argtypes = [C.c_float]
+        L.pth_self_leaf_c1.restype = C.c_float
+        L.pth_self_leaf_skip.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_float, C.c_void_p]
+        L.pth_self_leaf_skip.restype = None
         _host = L
     return _host
 
 
 # ---- host side: scene ingest / image output ---------------------------------------------------
+def self_leaf_rule(e0, e1, own, other=None, scene_e=1.0):
+    """csrc/self_leaf.h leaf_rule for triangle (e0, own, e1) of a leaf whose second triangle is (e0, e1, other), or a single triangle
+    -> (thr f32, bits of g u32); thr = inf: a ray from this triangle never leaves its leaf out"""
+    a = [np.ascontiguousarray(x, np.float32) for x in (e0, e1, own)]
+    o = None if other is None else np.ascontiguousarray(other, np.float32)
+    thr, g = C.c_float(), C.c_uint32()
+    lib_host().pth_self_leaf_rule(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, None if o is None else o.ctypes.data, scene_e, C.byref(thr), C.byref(g))
+    return np.float32(thr.value), int(g.value)
+
+
+def self_leaf_c1(tmin):
+    """csrc/self_leaf.h launch_c1: the launch's factor of the self-leaf rule"""
+    return np.float32(lib_host().pth_self_leaf_c1(tmin))
+
+
+def self_leaf_skip(dt, thr, g_word, c1):
+    """csrc/self_leaf.h skip_code per element of dt -> u32 array: g_word's low 14 bits (the leaf's code) where the ray leaves its leaf out, else 0"""
+    dt = np.ascontiguousarray(dt, np.float32)
+    out = np.zeros(dt.size, np.uint32)
+    lib_host().pth_self_leaf_skip(dt.ctypes.data, dt.size, thr, g_word, c1, out.ctypes.data)
+    return out
+
+
 QUAD_SHORTER_DIAGONAL = 1
 SMALL_CHUNKS = 2  # test hook of the loader (include/pt_host.h)
 

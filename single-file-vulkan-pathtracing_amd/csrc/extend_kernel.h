@@ -153,10 +153,14 @@ __host__ __device__ constexpr size_t compact_stack_bytes(size_t threads, size_t 
 // takes it from this register instead of behind an LDS round trip; a caller that ignores it does not pay for the read).
 // STRIDE: threads per block (the stack is [level][thread]).
 // wide: the callers stage the nodes at LDS byte 0, so the node's address is cur * stride and nothing else.
-template <int STRIDE, bool CUT_PER_STEP = false, class Pop>
+// SKIP (k_fused): is_skip(key) says whether a key's child is the one leaf this lane's ray must not enter (self_leaf.h).  Such a child is pushed
+// like any other -- the pops leave it out -- but never returned: when it is the nearest child the step's pop runs instead, as pop(top, kcut, true),
+// and `top` is then the entry the step pushed last (k1, if any was pushed: the keys are sorted), not the stale e_top.
+struct NoSkip { __device__ __forceinline__ bool operator()(uint32_t) const { return false; } };
+template <int STRIDE, bool CUT_PER_STEP = false, bool SKIP = false, class Pop, class IsSkip = NoSkip>
 __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32_t cur, const ptm::f3 &inv, const ptm::f3 &invf, const ptm::f3 &on,
                                                       const ptm::f3 &of, uint32_t ax, uint32_t ay, uint32_t az, float tmin, float best_t,
-                                                      LaneStack<STRIDE> &stk, Pop &&pop)
+                                                      LaneStack<STRIDE> &stk, Pop &&pop, [[maybe_unused]] IsSkip &&is_skip = IsSkip())
 {
     const float INF = __builtin_inff();
     float t0, t1, t2, t3;
@@ -188,7 +192,13 @@ __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32
     if (entry_within(k3, kcut)) stk.push(k3);  // farthest first, so the nearest pending pops first
     if (entry_within(k2, kcut)) stk.push(k2);
     if (entry_within(k1, kcut)) stk.push(k1);
-    return entry_within(k0, kcut) ? (k0 & 0x3FFFu) : pop(e_top, kcut);
+    if constexpr (SKIP) {
+        const uint32_t c0 = k0 & 0x3FFFu;
+        const bool in0 = entry_within(k0, kcut), self0 = is_skip(k0);
+        return (in0 & !self0) ? c0 : pop((self0 & entry_within(k1, kcut)) ? k1 : e_top, kcut, bool(self0 & in0));
+    } else {
+        return entry_within(k0, kcut) ? (k0 & 0x3FFFu) : pop(e_top, kcut);
+    }
 }
 __device__ __forceinline__ void slab_setup(const ptm::f3 org, const ptm::f3 inv, ptm::f3 &invf, ptm::f3 &on, ptm::f3 &of)
 {

@@ -25,6 +25,7 @@ extern "C" int pt_debug_fused_hist(void *device_u32_2x8192x16)
 
 #include "fused_cull.h"
 #include "nee_sample.h"  // the light sample of k_fused_nee (shared with k_shade)
+#include "self_leaf.h"   // which bounce rays leave out the leaf they start on (the per-triangle part: scene_build.hip)
 
 namespace {
 using namespace ptw;
@@ -193,5 +194,5 @@ void ptw_launch_fused(const FusedPlan &fp, bool grouped, const ptw::RenderConst 
     }
     hipExtLaunchKernelGGL(pick_fused(mode, fp.pairs, fp.count), dim3(fp.grid), dim3(FTB), (uint32_t)(fp.smem + (fp.count ? FUSED_COUNT_LDS : 0)), st, ev0, ev1, 0u, rc, tiles,
                           rad, s->d_wide, s->d_tri4, s->d_shade4, s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots, next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack,
-                          div_frames);
+                          div_frames, ptsl::launch_c1(tmin));
 }

@@ -10,6 +10,7 @@
 #include "extend_inst16.h"
 #include "fused_cull.h"
 #include "nee_sample.h"
+#include "self_leaf.h"
 
 namespace {
 using namespace ptw;
@@ -61,6 +62,6 @@ pt_status ptw_launch_fused_log(const FusedPlan &fp, bool grouped, const ptw::Ren
     const FusedLogFn fn = pick_fused_log(mode, fp.pairs);
     PT_TRY(ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(fn), FTB, fp.smem));
     hipLaunchKernelGGL(fn, dim3(fp.grid), dim3(FTB), (uint32_t)fp.smem, st, rc, tiles, rad, s->d_wide, s->d_tri4, s->d_shade4, s->d_frame4, s->n_wide, s->n_tris, 0u, n_slots,
-                       next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack, div_frames, log);
+                       next_slot, stats, fp.refill, tmin, tmax, fp.lds_stack, div_frames, ptsl::launch_c1(tmin), log);
     return PT_OK;
 }

@@ -157,6 +157,7 @@ enum FusedBlock : int {
     FB_PTARGET,    // camera ray: pixel + jitter -> target - origin, its squared length (raygen.rgen:51-56)
     FB_PDIR,       // camera ray: the normalisation's three quotients (raygen.rgen:57)
     FB_POPTOP,     // a node step whose four children all missed takes the stack's top entry, read with the node, from a register
+    FB_SKIP,       // (no code of its own) lanes whose walk left out the leaf of the triangle their ray started on (self_leaf.h): once per such ray
     FB_N
 };
 // NEE: next-event estimation (the oracle's `nee` mode, k_shade<.., NEE>): emission at the camera ray's hit only; at every hit before the last
@@ -172,12 +173,18 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                                            const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
                                            uint32_t n_wide, uint32_t n_tris, uint32_t slot_base_arg, uint32_t n_slots_arg,
                                            uint32_t *next_slot_arg, unsigned long long *stats_arg, int refill_arg, float tmin_arg,
-                                           float tmax_arg, int lds_stack, FastDiv div_frames_arg,
+                                           float tmax_arg, int lds_stack, FastDiv div_frames_arg, float self_c1_arg = 0.f,
                                            const float4 *__restrict__ lights_arg = nullptr, uint32_t n_lights_arg = 0u, float light_area_arg = 0.f,
                                            uint2 *log_arg = nullptr)
 {
     constexpr uint32_t LEAF_BIT = C14_LEAF, DONE = C14_DONE;
     constexpr bool GROUPED = MODE == 1, HYB = MODE == 2;
+    // SKIP: a bounce ray leaves out the leaf of the triangle it starts on when self_leaf.h's rule says that leaf cannot yield a hit: pair-leaf trees
+    // (the rule is per triangle or fan pair); the NEE instantiations, whose shadow rays start on a triangle too, stay as they were
+    // ... and so does the kernel of several sample groups (MODE 1), which has no register left for the code (with it: 12 B of scratch)
+    constexpr bool SKIP = PAIRS && !NEE && !GROUPED;
+    static_assert(ptsl::leaf_code14(0x155u, 2u) == (C14_LEAF | (1u << 11) | 0x155u) && ptsl::CODE_BITS == C14_DONE && ptsl::CODE_NONE == 0u,
+                  "self_leaf.h names leaves as the staged nodes do; the root's code stands for `none`");
     static_assert(!NEE || (MODE == 0 && !COUNT), "NEE: one sample group, no instrumented twin");
     static_assert(!LOG || !COUNT, "the first-hit log: no instrumented twin");
     // (everything the persistent loop reads: a scalar register of its own -- own_sgprs)
@@ -210,7 +217,17 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     lds_u32 *my_state = (lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.state) + threadIdx.x;
     lds_stage_nodes<FTB, true>(s_wide, g_wide, n_wide);  // (child words -> 14-bit codes: extend_kernel.h COMPACT)
     lds_stage_tris<FTB, true>(s_tri, g_tri4, n_tris, s_shade, g_shade4);  // (the kz = 2 copy is also what the shade block reads)
-    for (uint32_t i = threadIdx.x; i < 2 * n_tris; i += FTB) s_frame[i] = g_frame4[i];
+    // (SKIP: the spare words of a frame record's second float4 hold the triangle's self-leaf rule {thr, g | code}: staged as {the launch's limit
+    // max(thr, c1 * g) for dt, the code} -- self_c1_arg, ptsl::launch_c1 of the launch's tmin, is read here and nowhere in the loop)
+    for (uint32_t i = threadIdx.x; i < 2 * n_tris; i += FTB) {
+        float4 v = g_frame4[i];
+        if (i & 1u) {
+            const uint32_t gw = __float_as_uint(v.w);
+            v.z = ptsl::skip_limit(v.z, gw, self_c1_arg);
+            v.w = __uint_as_float(gw & ptsl::CODE_BITS);
+        }
+        s_frame[i] = v;
+    }
     // (a miss is record n_tris of the shade table: env where a triangle's record has its Ke -- step (1) reads it through min(pos, n_tris), PT_MISS
     // being all ones.  Its other words are never used: a miss does not bounce)
     if (threadIdx.x == 0) {
@@ -276,6 +293,12 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     float best_t = tmax, best_V = 0.f, best_W = 0.f, best_det = 1.f;
     uint32_t best_pos = PT_MISS;
     uint32_t cur = DONE;
+    // SKIP: the code of the leaf this lane's ray leaves out -- the leaf of the triangle a bounce ray starts on, where the rule allows it -- or
+    // CODE_NONE (camera rays; a ray too flat for the rule).  A leaf with this code never becomes `cur`: the node step's nearest child and both pops
+    // (pop_pending, the POPTOP candidate) compare with it
+    // (a register of its own: riding in tri_base's spare high bits instead it cost the head + tail kernel 12 B of scratch -- DESIGN.md section 6)
+    [[maybe_unused]] uint32_t self_leaf = ptsl::CODE_NONE;
+    auto is_self = [&](uint32_t e) -> bool { return (e & 0x3FFFu) == self_leaf; };
 
     // The stack's pop with the cull against best_t: a loop on the WAVE's condition -- the lanes that are served sit out behind one exec mask (see the
     // node loop) -- with selects inside, not branches (two more vector instructions for eight fewer scalar ones per pass).  r: PENDING for the lanes
@@ -287,7 +310,13 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
             if (r == PENDING) {
                 PT_FB(FB_POP)
                 const uint32_t e = stk.pop();  // (the BOTTOM entry ends the search: within every cut key, its code is DONE)
-                r = entry_within(e, kcut) ? (e & 0x3FFFu) : PENDING;
+                if constexpr (SKIP) {
+                    const bool within = entry_within(e, kcut), self = is_self(e);
+                    PT_FB_IF(within & self, FB_SKIP)
+                    r = (within & !self) ? (e & 0x3FFFu) : PENDING;
+                } else {
+                    r = entry_within(e, kcut) ? (e & 0x3FFFu) : PENDING;
+                }
             }
         }
         return r;
@@ -618,6 +647,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 // (V, W) / det (closesthit.rchit:56 through the hit record's undivided numerators) -- div3_dominant serves both (the bounce's third
                 // numerator is its second once more: same guard, same bits).  -1.5 %, profiles/r06w_merged_division.log
                 float q1, q2, q3;
+                [[maybe_unused]] uint32_t skip = ptsl::CODE_NONE;  // SKIP: the leaf the new ray leaves out (a camera ray starts on no triangle: none)
                 ptm::div3_dominant(need_primary ? vx : best_V, need_primary ? vy : best_W, need_primary ? vz : best_W, need_primary ? sq : best_det, q1, q2, q3);
                 if (need_primary) {
                     PT_FB(FB_PDIR)
@@ -631,6 +661,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     const float4 f0 = s_frame[2 * pos + 0], f1 = s_frame[2 * pos + 1];
                     dir = ptm::sample_direction_frame_sq(r1, r2, sq, nrm, { f0.x, f0.y, f0.z }, { f0.w, f1.x, f1.y });
                     const float dt = (dir.x * nrm.x + dir.y * nrm.y) + dir.z * nrm.z;
+                    // (the triangle's rule rides in the two spare words of its tangent-frame record: no LDS read of its own)
+                    if constexpr (SKIP) skip = dt >= f1.z ? __float_as_uint(f1.w) : ptsl::CODE_NONE;  // (ptsl::skip_code with the staged limit)
                     float fr = s0.w * dt, fg = s1.x * dt, fb = s1.y * dt;
                     ptm::div3_by_pdf(fr, fg, fb);
                     wr = wr * fr; wg = wg * fg; wb = wb * fb;
@@ -641,6 +673,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         org = { (a.x * b0 + b.x * hu) + c.x * hv, (a.y * b0 + b.y * hu) + c.y * hv, (a.z * b0 + b.z * hu) + c.z * hv };
                     }
                 }
+                if constexpr (SKIP) self_leaf = skip;
                 got_ray = true;
             }
             // (4) state back to LDS, ray set-up (the refill block of extend_body<true, false, false, true>)
@@ -698,13 +731,19 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         // (e_top, the stack's top entry read WITH the node's planes: a step whose four children all miss pushed nothing, so that entry is what
                         // its pop looks at first -- from a register instead of behind an LDS round trip: -1.8 %, profiles/r06r_speculative_pop.log.  At an
                         // empty stack the read lands on the BOTTOM entry)
-                        cur = compact_node_step<FTB>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t e_top, uint32_t kcut) -> uint32_t {
+                        cur = compact_node_step<FTB, false, SKIP>(wide, cur, inv, invf, on, of, ax, ay, az, tmin, best_t, stk, [&](uint32_t e_top, uint32_t kcut, [[maybe_unused]] bool skipped = false) -> uint32_t {
                             PT_FB(FB_POPTOP)
                             // (the top entry as the pop's first candidate: within the cut key -> taken -- the BOTTOM entry of an empty stack always is, and says
-                            // DONE; else the loop)
+                            // DONE; else the loop.  SKIP: the lane's own leaf is no candidate; `skipped`: it was this step's nearest child)
                             stk.drop();
-                            return pop_pending(entry_within(e_top, kcut) ? (e_top & 0x3FFFu) : PENDING, kcut);
-                        });
+                            if constexpr (SKIP) {
+                                const bool within = entry_within(e_top, kcut), self = is_self(e_top);
+                                PT_FB_IF(skipped | (within & self), FB_SKIP)
+                                return pop_pending((within & !self) ? (e_top & 0x3FFFu) : PENDING, kcut);
+                            } else {
+                                return pop_pending(entry_within(e_top, kcut) ? (e_top & 0x3FFFu) : PENDING, kcut);
+                            }
+                        }, is_self);
                     }
                     dn = cur < LEAF_BIT;
                     n_cont = __popcll(__ballot(dn));
@@ -767,10 +806,10 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES) void k_fused(RenderConst rc, c
                                                               const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
                                                               uint32_t n_wide, uint32_t n_tris, uint32_t slot_base, uint32_t n_slots,
                                                               uint32_t *next_slot, unsigned long long *stats, int refill, float tmin,
-                                                              float tmax, int lds_stack, FastDiv div_frames)
+                                                              float tmax, int lds_stack, FastDiv div_frames, float self_c1)
 {
     fused_body<MODE, PAIRS, false>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill, tmin,
-                                   tmax, lds_stack, div_frames);
+                                   tmax, lds_stack, div_frames, self_c1);
 }
 // PT_FLAG_NEE: next-event estimation, one sample group; the emitter table beside the scene's (pt_scene::d_lights).  Its own LDS plan (FS_NEE_*)
 // and occupancy (fused.hip); the instantiations above do not carry any of it
@@ -784,7 +823,7 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES_NEE) void k_fused_nee(RenderCon
                                                                       const float4 *__restrict__ lights, uint32_t n_lights, float light_area)
 {
     fused_body<0, PAIRS, false, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill,
-                                      tmin, tmax, lds_stack, div_frames, lights, n_lights, light_area);
+                                      tmin, tmax, lds_stack, div_frames, 0.f, lights, n_lights, light_area);
 }
 // the instrumented twin (PT_FLAG_COUNT_VISITS): the same LDS plan and block size, so a wave holds what it holds in the timed kernel; the counters
 // cost registers (spills), so it is slower and never timed
@@ -794,10 +833,10 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES) void k_fused_count(RenderConst
                                                                     const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
                                                                     uint32_t n_wide, uint32_t n_tris, uint32_t slot_base, uint32_t n_slots,
                                                                     uint32_t *next_slot, unsigned long long *stats, int refill, float tmin,
-                                                                    float tmax, int lds_stack, FastDiv div_frames)
+                                                                    float tmax, int lds_stack, FastDiv div_frames, float self_c1)
 {
     fused_body<MODE, PAIRS, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill, tmin,
-                                  tmax, lds_stack, div_frames);
+                                  tmax, lds_stack, div_frames, self_c1);
 }
 // the kernels above with the first-hit log (LOG): pt_render_guided's launches.  No instrumented twin.
 template <int MODE, bool PAIRS>
@@ -806,10 +845,10 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES) void k_fused_log(RenderConst r
                                                                   const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
                                                                   uint32_t n_wide, uint32_t n_tris, uint32_t slot_base, uint32_t n_slots,
                                                                   uint32_t *next_slot, unsigned long long *stats, int refill, float tmin,
-                                                                  float tmax, int lds_stack, FastDiv div_frames, uint2 *log)
+                                                                  float tmax, int lds_stack, FastDiv div_frames, float self_c1, uint2 *log)
 {
     fused_body<MODE, PAIRS, false, false, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill,
-                                                tmin, tmax, lds_stack, div_frames, nullptr, 0u, 0.f, log);
+                                                tmin, tmax, lds_stack, div_frames, self_c1, nullptr, 0u, 0.f, log);
 }
 template <bool PAIRS>
 __global__ __launch_bounds__(FTB, PT_FUSED_WAVES_NEE) void k_fused_nee_log(RenderConst rc, const uint32_t *__restrict__ tiles, Radiance rad,
@@ -821,5 +860,5 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES_NEE) void k_fused_nee_log(Rende
                                                                           const float4 *__restrict__ lights, uint32_t n_lights, float light_area, uint2 *log)
 {
     fused_body<0, PAIRS, false, true, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill,
-                                            tmin, tmax, lds_stack, div_frames, lights, n_lights, light_area, log);
+                                            tmin, tmax, lds_stack, div_frames, 0.f, lights, n_lights, light_area, log);
 }

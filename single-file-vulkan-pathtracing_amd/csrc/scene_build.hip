@@ -4,6 +4,7 @@
 // normal of closesthit.rchit:43-48, brdf = Kd / pi, the tangent frame of raygen.rgen:14-21 -- evaluated once with the
 // per-hit operations), and for instanced scenes the TLAS, the per-instance matrices and the world-space emitter / frame tables.
 #include "bvh_build.h"
+#include "self_leaf.h"
 
 #include <hip/hip_fp16.h>
 
@@ -70,7 +71,8 @@ __global__ __launch_bounds__(TB) void k_pack(const float4 *__restrict__ tri_orig
         ptm::f3 T, B;
         ptm::tangent_frame(nrm, T, B);
         frame4[2 * (size_t)pos + 0] = make_float4(T.x, T.y, T.z, B.x);
-        frame4[2 * (size_t)pos + 1] = make_float4(B.y, B.z, 0.f, 0.f);
+        // (.z, .w: the self-leaf rule of this triangle -- k_self_leaf, which knows the leaves, writes it; until then: never skip)
+        frame4[2 * (size_t)pos + 1] = make_float4(B.y, B.z, INFINITY, 0.f);
     }
     // the same values regrouped for scenes whose tables stay in HBM (k_shade<.., false>): one 64-B record instead of
     // two 48-B ones (4 divergent 16-B loads per hit instead of 6, 1 instead of 3 for a path that ends at this hit),
@@ -84,6 +86,37 @@ __global__ __launch_bounds__(TB) void k_pack(const float4 *__restrict__ tri_orig
 }
 
 
+// 6b. the self-leaf rule (self_leaf.h) of every triangle of the traversed BVH4, beside its tangent frame: frame4[2 * pos + 1] = {.., .., thr,
+// g | the leaf's 14-bit code}.  One thread per child word; a leaf that is no single triangle or fan pair of a pair-leaf tree, or that the compact
+// codes cannot name, keeps k_pack's "never".  Runs wherever k_pack runs (pack_tables), so a refit or rebuild recomputes it from the moved vertices.
+__global__ __launch_bounds__(TB) void k_self_leaf(const float4 *__restrict__ wide, uint32_t n_wide, const float4 *__restrict__ tri4, uint32_t n, float scene_e,
+                                                  float4 *__restrict__ frame4)
+{
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= 4u * n_wide) return;
+    const uint32_t w = reinterpret_cast<const uint32_t *>(wide + 8 * (size_t)(i >> 2) + 6)[i & 3u];
+    if (w == SENTINEL || !(w & PT_LEAF)) return;
+    const uint32_t cnt = ((w >> 28) & 7u) + 1u, first = w & 0x0FFFFFFFu;
+    if (cnt > 2u || first + cnt > n || first + cnt > 0x7FFu) return;
+    const float4 a = tri4[3 * (size_t)first + 0], b = tri4[3 * (size_t)first + 1], c = tri4[3 * (size_t)first + 2];
+    const float v0[3] = { a.x, a.y, a.z }, v1[3] = { b.x, b.y, b.z }, v2[3] = { c.x, c.y, c.z };
+    float *out = reinterpret_cast<float *>(frame4 + 2 * (size_t)first + 1);
+    const uint32_t code = ptsl::leaf_code14(first, cnt);
+    auto put = [&](float *o, const ptsl::Rule r) {  // (a triangle that never skips carries no code)
+        o[2] = r.thr;
+        o[3] = r.thr < INFINITY ? __uint_as_float(__float_as_uint(r.g) | code) : 0.f;
+    };
+    if (cnt == 1u) {
+        put(out, ptsl::leaf_rule(v0, v2, v1, nullptr, scene_e));
+        return;
+    }
+    const float4 d = tri4[3 * (size_t)first + 5];  // the fan pair (v0, v1, v2) + (v0, v2, v3): the second half's apex (pair_leaf.h)
+    const float v3[3] = { d.x, d.y, d.z };
+    put(out, ptsl::leaf_rule(v0, v2, v1, v3, scene_e));
+    put(out + 8, ptsl::leaf_rule(v0, v2, v3, v1, scene_e));  // (the second half's record: two float4 on)
+}
+
+
 __global__ __launch_bounds__(TB) void k_compose(const uint32_t *__restrict__ order8, const uint32_t *__restrict__ prim_of, uint32_t n,
                                                 uint32_t *__restrict__ out)
 {
@@ -91,6 +124,15 @@ __global__ __launch_bounds__(TB) void k_compose(const uint32_t *__restrict__ ord
     if (i < n) out[i] = prim_of[order8[i]];
 }
 
+
+// behind every k_pack of the traversed tree's tables (d_wide, pair_leaves, bmin / bmax are the new tree's by then)
+void pack_self_leaf(pt_scene *s, hipStream_t st)
+{
+    if (!s->pair_leaves || !s->d_frame4 || !s->n_wide) return;  // (leaves of several independent triangles: k_pack's "never" stands)
+    float e = 0.f;
+    for (int k = 0; k < 3; k++) e = std::max(e, std::max(std::fabs(s->bmin[k]), std::fabs(s->bmax[k])));
+    k_self_leaf<<<(4 * s->n_wide + TB - 1) / TB, TB, 0, st>>>(s->d_wide, s->n_wide, s->d_tri4, s->n_tris, e, s->d_frame4);
+}
 
 }  // namespace
 
@@ -301,6 +343,7 @@ static pt_status build_tree_products_unguarded(pt_scene *s, uint32_t quality, bo
     s->pair_leaves = PT_BLAS_LEAF_MAX == 1u;
     const uint32_t *order = s->d_prim_of_sah ? s->d_prim_of_sah : s->d_prim_of;   // the traversed leaf order
     k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, order, n, s->d_tri4, s->d_shade4, s->d_shade64, s->d_ke4, s->d_frame4);
+    pack_self_leaf(s, st);
     if (s->d_wide8) {  // the 8-wide tree's own triangle order: its per-triangle tables (the LDS-sized shade4 is never used with it)
         PT_TRY(ptb_scene_alloc(s, "the 8-wide tree's triangle tables",
                                { pt_buf_of(s->d_prim_of8, sizeof(uint32_t) * (size_t)n), pt_buf_of(s->d_tri4_8, sizeof(float4) * 3 * (size_t)n),
@@ -522,6 +565,7 @@ pt_status ptb_set_bvh_quality(pt_scene *s, uint32_t quality)
     }
     k_pack<<<(n + TB - 1) / TB, TB, 0, st>>>(s->d_tri_orig, s->d_faces, want_sah ? s->d_prim_of_sah : s->d_prim_of, n, s->d_tri4,
                                            s->d_shade4, s->d_shade64, s->d_ke4, s->d_frame4);
+    pack_self_leaf(s, st);
     PT_HIP(ctx, hipStreamSynchronize(st));
     PT_HIP(ctx, hipGetLastError());
     pt_scratch_free({ pt_buf_of(s->d_inst_frame) }, nullptr, 0);  // (the triangle order changed: ptb_ensure_inst_frames builds it again on the next render)
@@ -768,6 +812,7 @@ static pt_status refit_tree_products(pt_scene *s, const float4 *d_tlo, const flo
     if (s->d_wide8)  // (d_shade4 is scratch here: the k_pack below writes it)
         k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, s->d_prim_of8, n, s->d_tri4_8, s->d_shade4, s->d_shade64_8, s->d_ke4_8);
     k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, order, n, s->d_tri4, s->d_shade4, s->d_shade64, s->d_ke4, s->d_frame4);
+    pack_self_leaf(s, st);
     k_wide_half<<<(s->n_wide + TB - 1) / TB, TB, 0, st>>>(s->d_wide, s->n_wide, s->norm_c[0], s->norm_c[1], s->norm_c[2], s->norm_rs[0],
                                                          s->norm_rs[1], s->norm_rs[2], reinterpret_cast<uint4 *>(s->d_wide16));
     PT_HIP(ctx, hipGetLastError());
