@@ -299,6 +299,12 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     // (a register of its own: riding in tri_base's spare high bits instead it cost the head + tail kernel 12 B of scratch -- DESIGN.md section 6)
     [[maybe_unused]] uint32_t self_leaf = ptsl::CODE_NONE;
     auto is_self = [&](uint32_t e) -> bool { return (e & 0x3FFFu) == self_leaf; };
+    // UNDEF: values that every path writes before it reads them are declared without a fill (ptm::undef: no instruction) -- the pair-leaf kernels
+    // without NEE.  The kernels of leaves of up to four and the NEE ones keep their zeros: they are short of registers where such a value has to
+    // be kept (with it: 8 - 20 B more scratch in k_fused<1 | 2, false>, two to four more VGPRs in k_fused_nee)
+    constexpr bool UNDEF = PAIRS && !NEE;
+    auto undef_u = [] { return ptm::undef_if<UNDEF>(0u); };
+    auto undef_f = [](float fill) { return ptm::undef_if<UNDEF>(fill); };
 
     // The stack's pop with the cull against best_t: a loop on the WAVE's condition -- the lanes that are served sit out behind one exec mask (see the
     // node loop) -- with selects inside, not branches (two more vector instructions for eight fewer scalar ones per pass).  r: PENDING for the lanes
@@ -332,9 +338,22 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
         const unsigned long long m_in_blk = ~m_have & (out_of_slots ? m_path : ~0ull);  // (waves are whole: FTB is a multiple of 64)
         const int n_work = __popcll(m_in_blk);
         if (n_work && n_work * 64 >= refill * (n_work + __popcll(m_have))) {  // (refill <= 64: a wave without a tracing lane always passes)
-            uint32_t slot = 0, ctr = 0, seed = 0, pxy = 0;
-            float wr = 0.f, wg = 0.f, wb = 0.f;
-            ptm::f3 org{}, dir{};
+            // The path state of the pass: declared here, DEFINED by the step that a lane comes through -- no zero-fill for the lanes of the other steps
+            // (ptm::undef: a register as it is, for no instruction).  Who writes what before which read, per lane:
+            //   slot   (1) loads it (a lane with a path); (2) sets it in every branch of a lane that takes a slot.  Read by (1) itself (LOG's record,
+            //          `logs` / `lslot`, rad.color / rad.nterm, the spill chain), by (2) behind its own write (finish_group / finish_plain,
+            //          rad.nterm), and by (4)'s store under got_ray: a lane has got_ray only through (1) or through (2)'s in-image branch
+            //   ctr    (1) loads it and rewrites it at its end; (2)'s in-image branch sets it.  Read by (3) under need_primary -- which only those two
+            //          set -- and by (4)'s store
+            //   pxy    (1) loads it, (2)'s in-image branch sets it; read by (3) under need_primary and by (4)'s store
+            //   seed   (1) loads it; (3) sets it under need_primary BEFORE the two rnd of the spawn steps.  A bounce lane (and NEE's light sample)
+            //          comes from (1).  Read by those rnd and by (4)'s store
+            //   wr, wg, wb   as seed: (1) loads them, (3) sets them to 1 under need_primary; read by (1) (weight * Ke), the bounce and (4)'s store
+            //   org, dir     (3) sets both for a camera ray; for a bounce it sets dir, and org (NEE: org is (1)'s, at the hit that draws the light sample
+            //          or from the returning shadow ray; a shadow ray's dir is (1)'s `wi`).  Read by (4) under got_ray only
+            uint32_t slot = undef_u(), ctr = undef_u(), seed = undef_u(), pxy = undef_u();
+            float wr = undef_f(0.f), wg = undef_f(0.f), wb = undef_f(0.f);
+            ptm::f3 org = { undef_f(0.f), undef_f(0.f), undef_f(0.f) }, dir = { undef_f(0.f), undef_f(0.f), undef_f(0.f) };
             const bool in_blk = !have && (path || !out_of_slots);
             bool got_ray = false, need_primary = false, bounce = false;
             bool freed = false;   // the lane's slot was completed in step (1): it has no path any more (what stk.parked() says, without a second compare)
@@ -634,7 +653,9 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 PT_FB(FB_SPAWN)
                 const float r1 = ptm::rnd(seed);  // bounce: cos(theta) first, azimuth second; camera ray: x jitter first, then y
                 const float r2 = ptm::rnd(seed);
-                float vx = 0.f, vy = 0.f, vz = 0.f, sq_arg;
+                // (vx, vy, vz: primary_target writes them for the camera lanes, and only those lanes' selects below take them -- a bounce lane's
+                // quotient, and the guard of div3_dominant, which branches per lane, see best_V / best_W / best_det of its hit)
+                float vx = undef_f(0.f), vy = undef_f(0.f), vz = undef_f(0.f), sq_arg;
                 if (need_primary) {
                     PT_FB(FB_PTARGET)
                     ptm::primary_target(rc.cam, pxy & 0xFFFFu, pxy >> 16, r1, r2, vx, vy, vz);
@@ -646,6 +667,9 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 // ... and one set of quotients by a common divisor: the camera ray's direction (target - origin) / length, the bounce's barycentrics
                 // (V, W) / det (closesthit.rchit:56 through the hit record's undivided numerators) -- div3_dominant serves both (the bounce's third
                 // numerator is its second once more: same guard, same bits).  -1.5 %, profiles/r06w_merged_division.log
+                // (The selects cost three copies: the compiler moves best_V, best_W, best_W into the operand registers for all lanes, then the camera
+                // lanes overwrite them.  Camera lanes writing vx, vy straight into best_V, best_W -- their hit record is spent -- removes two of the
+                // three in the listing and was 0.35 % SLOWER on the box: profiles/fused_moves_ab.json.  Left as it is.)
                 float q1, q2, q3;
                 [[maybe_unused]] uint32_t skip = ptsl::CODE_NONE;  // SKIP: the leaf the new ray leaves out (a camera ray starts on no triangle: none)
                 ptm::div3_dominant(need_primary ? vx : best_V, need_primary ? vy : best_W, need_primary ? vz : best_W, need_primary ? sq : best_det, q1, q2, q3);
@@ -697,7 +721,11 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 tri_base = (uint32_t)pre.kz * 3u * n_tris;
                 orgp = { ptm::sel3(pre.kz, org.y, org.z, org.x), ptm::sel3(pre.kz, org.z, org.x, org.y), ptm::sel3(pre.kz, org.x, org.y, org.z) };
                 best_t = (NEE && shadow) ? nc.w : tmax;  // (a shadow ray: its own tmax, k_extend's ray_tmax)
-                best_V = 0.f; best_W = 0.f; best_det = 1.f;
+                // (best_V, best_W, best_det get no value of their own: the bounce of a hit -- step (3) -- and NEE's div2_dominant at a hit are their only
+                // readers, both behind best_pos != PT_MISS, and the accept that sets best_pos writes all three with it -- closer_single_level's two
+                // places and the loop of the leaves of up to four.  A ray that hits nothing leaves them without a value and nobody looks.  The
+                // kernels without UNDEF keep the reset)
+                best_V = undef_f(0.f); best_W = undef_f(0.f); best_det = undef_f(1.f);
                 best_pos = PT_MISS;
                 cur = 0u;
                 stk.clear_to_bottom();
@@ -756,7 +784,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 PT_FB(FB_LEAF)
                 if (PAIRS) {
                     const uint32_t first = cur & 0x7FFu;
-                    ptl::pair_leaf_test<true>(tri4, (size_t)tri_base + 3 * (size_t)first, ((cur >> 11) & 3u) != 0u, first, pre, orgp, tmin, tmax,
+                    ptl::pair_leaf_test<true, true>(tri4, (size_t)tri_base + 3 * (size_t)first, ((cur >> 11) & 3u) != 0u, first, pre, orgp, tmin, tmax,
                                         [&](float t, float V, float W, float det, uint32_t pos, uint32_t) {
                                             [[maybe_unused]] const bool closer =
                                                 ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos);

@@ -15,7 +15,7 @@ namespace ptl {
 // accept(t, V, W, det, pos, prim_bits): a hit inside the range, in primitive order (first half first); hit_block(): once per divide block.
 // LOAD_D_FIRST: how far past a single triangle's record (three float4) the step reads: records ti + 3 .. ti + 5
 constexpr unsigned D_FIRST_OVERREAD_F4 = 3;
-template <bool LOAD_D_FIRST = false, class Accept, class HitBlock>
+template <bool LOAD_D_FIRST = false, bool PIN_BY_USE = false, class Accept, class HitBlock>
 __device__ __forceinline__ void pair_leaf_test(const float4 *tri4, size_t ti, bool two, uint32_t first, const ptm::RayPre &pre,
                                                const ptm::f3 &orgp, float tmin, float tmax, Accept &&accept, HitBlock &&hit_block)
 {
@@ -26,7 +26,12 @@ __device__ __forceinline__ void pair_leaf_test(const float4 *tri4, size_t ti, bo
     float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
     if (LOAD_D_FIRST) {
         d = tri4[ti + 5];
-        asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));  // (keeps the load here: the compiler sinks it back behind the branch)
+        // (keeps the load here: the compiler sinks it back behind the branch)
+        // PIN_BY_USE: the pin is a USE of the loaded registers, not a tie ("+v").  A tied operand is a new value per component, and the compiler
+        // copies three of the four out of the load's register tuple to make them: three v_mov_b32 per leaf step (k_fused; k_fused_inst keeps
+        // the tie until its own listing is read)
+        if (PIN_BY_USE) asm volatile("" :: "v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w));
+        else asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
     }
     // the sheared vertices and the products of the edge v0-v2 serve both halves (ptm::tri_test_perm, same operands in the same order:
     // bit-identical numerators)

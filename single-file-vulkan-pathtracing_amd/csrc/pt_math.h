@@ -56,6 +56,34 @@ __device__ __forceinline__ T own_sgprs(const T &x)
     return r;
 }
 
+// A value that is DEFINED but whose content nobody may rely on: a vector register as it happens to be, for no instruction.  For a variable that
+// every path writes before it reads -- per lane -- but that the source has to declare ahead of those writes: `= 0` there is a v_mov_b32 for the lanes
+// that never read it.  This is not an uninitialised read (undefined behaviour, which lets the compiler drop whatever depends on it): the empty
+// asm's output is an ordinary value, selects and stores of it are well defined, only its bits are anybody's guess.
+// -DPT_UNDEF_POISON: a fixed pattern instead -- a quiet NaN for floats, a wild index for integers -- so that a value that does reach a film, a
+// ray count or a slot index shows (tests/test_fused_undef.py builds that twin).
+template <class T>
+__device__ __forceinline__ T undef()
+{
+    static_assert(sizeof(T) == 4 && (__is_same(T, float) || __is_same(T, uint32_t)), "one dword: a float or a uint32_t");
+#ifdef PT_UNDEF_POISON
+    if constexpr (__is_same(T, float)) return __builtin_bit_cast(float, 0x7FC0DEADu);
+    else return 0xDEADBEEFu;
+#else
+    T r;
+    asm volatile("" : "=v"(r));  // (volatile: two plain ones are ONE value to the compiler, which then copies it into the registers of both variables)
+    return r;
+#endif
+}
+// ... for the instantiations of a template that gain by it; the others keep their fill.  (A zero can be made again wherever it is wanted; the asm's
+// value has to be KEPT from its definition to its last use, and a kernel that is short of registers there pays for that with a spill.)
+template <bool ON, class T>
+__device__ __forceinline__ T undef_if(T fill)
+{
+    if constexpr (ON) return undef<T>();
+    else return fill;
+}
+
 // x / (1/(2 pi)) for three values at once (raygen.rgen:79-80 divides by the pdf as a true division).
 // For THIS divisor, q0 = x*rc, r = fma(-q0, c, x), q = fma(r, rc, q0) with rc = RN(1/c) equals the
 // correctly rounded quotient for every float with 2^-100 <= |x| <= 2^120: proven by enumerating all of
