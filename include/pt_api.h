@@ -360,9 +360,9 @@ void pt_denoise_params_default(pt_denoise_params *p);
  * the first kernel to the last.
  * PT_ERR_INVALID_ARG: NULL film or params; a film without guides (pt_film_enable_aov); iterations outside 1..8; a sigma that is not
  * finite and > 0; a nonzero reserved word.  PT_ERR_OOM: the scratch does not fit the budget (the film renders on as before).
- * A film rendered as (rank, world) holds only its own tiles: the filter would read zeros from the other ranks' pixels.  Filtering a
- * gathered image means a film over external planes (pt_film_create_external + pt_film_enable_aov with caller memory) on the rank
- * that holds it; gathering the guides across ranks is not part of this library.                                                */
+ * A film rendered as (rank, world) holds only its own tiles: the filter would read zeros from the other ranks' pixels.  Filter the
+ * film that pt_film_present_planes assembles on the root instead: it gathers the radiance, the guides and the planes M, L, K, Q of all
+ * ranks into a film (the multi-GPU section below), and this call runs on that film unchanged.                                   */
 pt_status pt_film_denoise(pt_film *film, const pt_denoise_params *params, void *device_out_rgb_f32, float *device_ms);
 /* The film-owned result of the last pt_film_denoise(..., NULL, ...): rgb width*height*3 floats, bgra width*height*4 bytes; either may
  * be NULL.  PT_ERR_INVALID_ARG before any denoise into the film's own plane.                                                     */
@@ -402,7 +402,8 @@ pt_status pt_film_read_moments(pt_film *film, float *m2, uint32_t *frames);
  * An infinite x_c gives weight 0; NaN inputs are outside the contract.  sigma_color is in standard deviations of the difference of two
  * pixels: 1 keeps the noise, 8 oversmooths (DESIGN.md section 14 has the experiment the default comes from).  Placement, blocking,
  * scratch ownership (V rides in the spare word of the illumination records: the same 48 B per pixel), budget, device_ms and the caveat
- * about (rank, world) films are those of pt_film_denoise; the film-owned result is read through pt_film_read_denoised.
+ * about (rank, world) films are those of pt_film_denoise (gather with pt_film_present_planes, PT_PLANES_MOMENTS in the set: the
+ * gathered film takes over `frames`); the film-owned result is read through pt_film_read_denoised.
  * PT_ERR_INVALID_ARG: NULL film or params; a film without guides or without the second-moment plane; frames resolving below 2;
  * iterations outside 1..8; a sigma that is not finite and > 0; a nonzero reserved word.  A refused call writes no result.        */
 typedef struct pt_denoise_variance_params {
@@ -468,7 +469,7 @@ pt_status pt_film_denoise_variance(pt_film *film, const pt_denoise_variance_para
  * is homogeneous in their scale (Z / a, and both sides of the depth and the normal test carry a_p * a'_q or a'_q).
  * alpha is the least weight of the new frames: 0 makes a static sequence the running mean of its steps up to max_history, 1 keeps no history.
  * After pt_scene_update the validation simply rejects what moved (pt_film_reproject_motion below follows it); a (rank, world) film holds only its own tiles,
- * the caveat of pt_film_denoise.  DESIGN.md section 15 has the experiment the defaults were run on.
+ * the caveat of pt_film_denoise: reproject the films pt_film_present_planes gathers (PT_PLANES_HISTORY carries L).  DESIGN.md section 15 has the experiment the defaults were run on.
  * PT_ERR_INVALID_ARG: NULL film or params; prev == film; prev of another size or context; film or prev without guides or without L; exactly
  * one of the two with a second-moment plane; a camera component, gain or depth_tol that is not finite, gain or depth_tol not > 0, alpha outside
  * [0, 1], normal_min outside [-1, 1], max_history outside 1..65535; unknown flag bits; a nonzero reserved word.  A refused call writes nothing. */
@@ -637,7 +638,7 @@ pt_status pt_film_denoise_history(pt_film *film, const pt_denoise_history_params
  * PT_ERR_INVALID_ARG, nothing written and nothing launched: NULL film, lo or params; lo == film; films of different contexts; w' > w or
  * h' > h; either film without guides; an unknown source; PT_UPSAMPLE_SRC_DENOISED when lo has no film-owned denoised result; a sigma that
  * is not finite and > 0; a nonzero reserved word.  PT_ERR_OOM: the scratch does not fit pt_tuning.mem_budget_mb (both films are left as
- * they were).  The caveat about (rank, world) films is pt_film_denoise's.                                                              */
+ * they were).  The caveat about (rank, world) films is pt_film_denoise's: upsample films that pt_film_present_planes gathered.          */
 enum { PT_UPSAMPLE_SRC_FILM = 0, PT_UPSAMPLE_SRC_DENOISED = 1 };
 typedef struct pt_upsample_params {
     float    sigma_normal;     /* default 1.0  */
@@ -786,6 +787,61 @@ pt_status pt_film_present(pt_film *film, pt_comm *comm, uint32_t root, float *d_
 pt_status pt_film_tile_count(const pt_film *film, uint32_t rank, uint32_t world, uint32_t *n_tiles);
 pt_status pt_film_pack_tiles(pt_film *film, uint32_t rank, uint32_t world, float *d_packed);
 pt_status pt_film_unpack_tiles(pt_film *film, uint32_t rank, uint32_t world, const float *d_packed, float *d_image);
+
+/* ---- multi-GPU: gathering a film's planes into a FILM on the root, so that the film passes run on a sharded render ----------------------
+ * pt_film_present moves the radiance plane into a bare image.  pt_film_present_planes moves any set of the planes a film can have -- the
+ * radiance C, the six guide planes of pt_film_enable_aov, M, L, K, Q -- and lands them in the planes of another film, `dst`, on the root:
+ * dst is then a film like one rendered on a single device, and pt_film_denoise, _denoise_variance, _denoise_history, pt_film_reproject,
+ * _reproject_motion, pt_film_upsample and pt_render_adaptive's convergence query run on it unchanged.
+ *
+ * THE PACKED LAYOUT (the contract of the three calls below, and of distributed.py's numpy mirrors):
+ *   - Data moves as 32-bit words and no arithmetic touches a value: NaN payloads, -0.0, denormals and the id plane's 0xFFFFFFFF arrive as
+ *     they left.
+ *   - The buffer holds the tiles of rank `rank` of `world` -- tile (tx, ty) belongs to rank (tx + ty) % world -- row by row over the tile
+ *     grid, the order of pt_film_pack_tiles; pt_film_tile_count gives their number.
+ *   - Per tile there is ONE record of 64 * S words, S the words per pixel of the named set (pt_film_planes_words: 3 .. 25).
+ *   - Inside a record the named planes come in this fixed order: C, albedo, normal, emission, depth, alpha, id, M, L, K, Q.
+ *   - Each plane is a block [64 pixels][channels]; pixel p of tile (tx, ty) is (8*tx + (p & 7), 8*ty + (p >> 3)).
+ *   - A pixel outside the image packs as zero words; unpack skips it.
+ *   - With planes == PT_PLANES_FILM the buffer equals pt_film_pack_tiles's output byte for byte.
+ *
+ * pt_film_pack_planes: the named planes of `film`'s tiles of (rank, world) into d_packed, DEVICE memory of tiles * 64 * S words.  Blocking.
+ * pt_film_unpack_planes: such a buffer into dst's own planes, film-owned or caller-owned alike.  It writes exactly the pixels of that rank's
+ * tiles and touches nothing else; when PT_PLANES_FILM is named it also writes those pixels' bgra8 from the new C by k_resolve's clamp and
+ * quantise rule with A = 255 (the rule pt_film_reproject states).  Blocking.
+ *
+ * pt_film_present_planes(film, comm, root, planes, dst, device_ms): every rank of the communicator calls it with the film it rendered as
+ * (rank, world) of the communicator and the same root and planes.  One pack launch per rank, ONE RCCL group of ncclSend / ncclRecv of the
+ * packed buffers (the group shape of pt_film_present), one unpack launch on the root over all ranks' records.  On the root every named plane
+ * of dst is overwritten completely -- every pixel belongs to exactly one rank -- and dst gets its bgra8 as under unpack; with
+ * PT_PLANES_MOMENTS dst also takes over the `frames` record of the root's film, so that pt_film_denoise_variance(frames = 0) works on it.
+ * `film` on every rank, the planes of dst that are not named and pt_stats stay as they were.  dst is read on the root only and ignored
+ * elsewhere.  Blocking; runs on the context's stream, ordered after the work already queued there.  device_ms (may be NULL): the device time
+ * on this rank's stream from the pack to the last unpack; on a rank that is not the root, from the pack to the send.
+ * The staging buffers (a rank's records, on the root all ranks' records, and the tile lists) belong to the communicator, are keyed by
+ * (film size, root, planes), are replaced only when that key changes and are freed by pt_comm_destroy: a second call with the same key
+ * allocates nothing.  They are NOT counted against pt_tuning.mem_budget_mb.
+ *
+ * PT_ERR_INVALID_ARG -- nothing is launched and no collective is joined: NULL film or comm; planes == 0 or with bits outside
+ * PT_PLANES_ALL; root >= the communicator's world; a film of another context than the communicator's; a film rendered as another
+ * (rank, world) than the communicator's (pt_film_present's rule); a film that lacks a named plane (no guide buffers, no M, L, K or Q);
+ * and on the root a dst that is NULL, is `film` itself, has another size or context, or lacks a named plane.  The standalone pack and
+ * unpack refuse the same argument errors (and a NULL buffer, world == 0, rank >= world).
+ * As with pt_film_present, THE RANKS MUST AGREE ON SUCCESS BEFORE THE CALL: a rank that refuses, or that failed earlier, while the others
+ * send leaves them waiting in the collective.  Check on every rank what can be checked (the planes exist, dst on the root) and exchange the
+ * outcome first; host/pt_main.cpp's Agreement is the pattern.                                                                          */
+enum { PT_PLANES_FILM = 1u,      /* C: 3 words per pixel */
+       PT_PLANES_GUIDES = 2u,    /* the six planes of pt_film_enable_aov: albedo 3, normal 3, emission 3, depth 1, alpha 1, id 2 */
+       PT_PLANES_MOMENTS = 4u,   /* M: 3 */
+       PT_PLANES_HISTORY = 8u,   /* L: 1 */
+       PT_PLANES_COUNTS = 16u,   /* K: 1 */
+       PT_PLANES_MOTION = 32u,   /* Q: 4 */
+       PT_PLANES_ALL = 63u };
+pt_status pt_film_planes_words(const pt_film *film, uint32_t planes, uint32_t *words_per_pixel);   /* S: 3 .. 25; a function of `planes` alone */
+pt_status pt_film_pack_planes(pt_film *film, uint32_t rank, uint32_t world, uint32_t planes, void *d_packed);
+pt_status pt_film_unpack_planes(pt_film *dst, uint32_t rank, uint32_t world, uint32_t planes, const void *d_packed);
+pt_status pt_film_present_planes(pt_film *film, pt_comm *comm, uint32_t root, uint32_t planes,
+                                 pt_film *dst /* root only; ignored elsewhere */, float *device_ms /* may be NULL */);
 
 /* Device memory for the buffers a caller hands to the library (pt_film_create_external, pt_film_present), for hosts
  * that do not link HIP themselves (host/pt_main.cpp is plain g++): hipMalloc / hipFree / blocking copies either way,

@@ -174,6 +174,8 @@ FUSED_BLOCKS = ["ITER", "SHADE", "HIT", "MISS", "SURFACE", "ADD", "BOUNCE", "NEX
 AOV_ALBEDO, AOV_NORMAL, AOV_EMISSION, AOV_DEPTH, AOV_ALPHA, AOV_ID, AOV_COUNT = 0, 1, 2, 3, 4, 5, 6
 AOV_SHAPES = {AOV_ALBEDO: ((3,), np.float32), AOV_NORMAL: ((3,), np.float32), AOV_EMISSION: ((3,), np.float32),
               AOV_DEPTH: ((), np.float32), AOV_ALPHA: ((), np.float32), AOV_ID: ((2,), np.uint32)}
+# include/pt_api.h PT_PLANES_*: the plane sets of film_pack_planes / film_unpack_planes / Comm.present_planes
+PLANES_FILM, PLANES_GUIDES, PLANES_MOMENTS, PLANES_HISTORY, PLANES_COUNTS, PLANES_MOTION, PLANES_ALL = 1, 2, 4, 8, 16, 32, 63
 HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("inst", "<u4")])
 
 # every symbol include/pt_api.h and include/pt_host.h declare
@@ -188,6 +190,7 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_get_stats", "pt_reset_stats", "pt_get_block_counts",
                "pt_comm_unique_id", "pt_comm_create", "pt_comm_ranks", "pt_comm_destroy", "pt_film_present",
                "pt_film_tile_count", "pt_film_pack_tiles", "pt_film_unpack_tiles",
+               "pt_film_planes_words", "pt_film_pack_planes", "pt_film_unpack_planes", "pt_film_present_planes",
                "pt_device_alloc", "pt_device_free", "pt_device_read", "pt_device_write", "pt_ctx_get_tuning", "pt_ctx_set_tuning",
                "pt_scene_snapshot_previous", "pt_film_enable_motion", "pt_film_read_motion", "pt_motion_params_default", "pt_film_motion",
                "pt_film_reproject_motion", "pt_denoise_history_params_default", "pt_film_denoise_history",
@@ -313,6 +316,11 @@ def lib_amd():
         L.pt_film_tile_count.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_film_pack_tiles.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
         L.pt_film_unpack_tiles.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
+        if hasattr(L, "pt_film_present_planes"):   # (the gather of film planes; dev A/B runs load older builds through PT_LIB_AMD)
+            L.pt_film_planes_words.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+            L.pt_film_pack_planes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+            L.pt_film_unpack_planes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+            L.pt_film_present_planes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_float)]
         _amd = L
     return _amd
 
@@ -896,6 +904,13 @@ class Comm:
     def present(self, film, device_image_ptr, root=0):
         self.ctx._check(lib_amd().pt_film_present(film.h, self.h, root, C.c_void_p(device_image_ptr)))
 
+    def present_planes(self, film, dst, planes, root=0):
+        """The named planes (PLANES_*) of every rank's film gathered into the film `dst` on the root (include/pt_api.h
+        pt_film_present_planes) -> this rank's device ms.  dst: a Film on the root, None elsewhere."""
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_film_present_planes(film.h, self.h, root, planes, dst.h if dst is not None else None, C.byref(ms)))
+        return ms.value
+
     def close(self):
         if self.h:
             lib_amd().pt_comm_destroy(self.h)
@@ -946,6 +961,24 @@ def film_pack_tiles(film, rank, world, device_ptr):
 
 def film_unpack_tiles(film, rank, world, device_packed_ptr, device_image_ptr):
     film.ctx._check(lib_amd().pt_film_unpack_tiles(film.h, rank, world, C.c_void_p(device_packed_ptr), C.c_void_p(device_image_ptr)))
+
+
+def film_planes_words(film, planes):
+    """-> S: the 32-bit words per pixel of the plane set `planes` (PLANES_*); a packed tile is one record of 64 * S words."""
+    n = C.c_uint32()
+    film.ctx._check(lib_amd().pt_film_planes_words(film.h, planes, C.byref(n)))
+    return n.value
+
+
+def film_pack_planes(film, rank, world, planes, device_ptr):
+    """The named planes of the film's tiles of (rank, world) into device memory of film_tile_count * 64 * S words (include/pt_api.h
+    pt_film_pack_planes has the layout; distributed.pack_planes_host is its numpy mirror)."""
+    film.ctx._check(lib_amd().pt_film_pack_planes(film.h, rank, world, planes, C.c_void_p(device_ptr)))
+
+
+def film_unpack_planes(dst, rank, world, planes, device_packed_ptr):
+    """Such a buffer into the planes of the film `dst`: exactly the pixels of that rank's tiles, and their bgra8 when PLANES_FILM is named."""
+    dst.ctx._check(lib_amd().pt_film_unpack_planes(dst.h, rank, world, planes, C.c_void_p(device_packed_ptr)))
 
 
 def render(scene, film, params):

@@ -13,6 +13,10 @@ and unpacks them into a separate image; a rank's accumulation film is never writ
 collective, so progressive rendering can continue and present again.  `Presenter` below is the glue
 under `torch.distributed`: the launcher's process group only carries the 128-byte RCCL unique id
 to the ranks (and, in the CPU emulation of the tests, the packed tiles over gloo).
+
+Film passes on a sharded render: `pt_film_present_planes` gathers any set of the film's planes -- the radiance, the
+guides, M, L, K, Q -- into a FILM on the root with the same one collective; `pack_planes_host`, `unpack_planes_host`
+and `gather_planes_host` below mirror its packed layout, `Presenter.present_planes` is the glue.
 """
 import os
 
@@ -83,6 +87,111 @@ def gather_present_host(film, rank, world, dst=0, group=None):
     if counts[rank]:
         dist.send(mine, dst=dst, group=group)
     return None
+
+
+# ---- the gather of film planes (include/pt_api.h pt_film_present_planes): numpy mirrors of the packed layout ----
+# the planes in the record's order: (key of the `planes` dict, channels, PLANES_* bit that names it)
+PLANE_ORDER = [("film", 3, 1), ("albedo", 3, 2), ("normal", 3, 2), ("emission", 3, 2), ("depth", 1, 2), ("alpha", 1, 2), ("id", 2, 2),
+               ("moments", 3, 4), ("history", 1, 8), ("counts", 1, 16), ("motion", 4, 32)]
+
+
+def planes_named(which):
+    """-> [(key, channels)] of the plane set `which` (PLANES_* bits) in the record's order."""
+    if which == 0 or which & ~63:
+        raise ValueError("planes must name at least one of PLANES_* and nothing else")
+    return [(k, c) for k, c, bit in PLANE_ORDER if which & bit]
+
+
+def planes_words(which):
+    """-> S, the 32-bit words per pixel of the set (pt_film_planes_words)."""
+    return sum(c for _, c in planes_named(which))
+
+
+def _words(a, c):
+    """a plane [H, W] or [H, W, c] of a 32-bit dtype as its words [H, W, c] (a view: writes go through)"""
+    a = np.asarray(a)
+    assert a.dtype.itemsize == 4 and a.flags.c_contiguous, "planes are C-contiguous arrays of a 32-bit type"
+    return a.view(np.uint32).reshape(a.shape[0], a.shape[1], c)
+
+
+def bgra8_host(film):
+    """k_resolve's clamp and quantise of a float film [H, W, 3] with A = 255 -> uint8 [H, W, 4] {b, g, r, a}: what the unpack kernel writes."""
+    c = np.asarray(film, np.float32)
+    with np.errstate(invalid="ignore"):
+        q = np.where(c > 0, np.minimum(c, np.float32(1)) * np.float32(255) + np.float32(0.5), np.float32(0)).astype(np.float32)
+    out = np.empty(c.shape[:2] + (4,), np.uint8)
+    out[..., :3] = q.astype(np.uint8)[..., ::-1]
+    out[..., 3] = 255
+    return out
+
+
+def pack_planes_host(planes, rank, world, which):
+    """numpy mirror of k_pack_planes: `planes` maps the keys of PLANE_ORDER to arrays [H, W(, channels)] of a 32-bit dtype (the named ones
+    have to be there) -> uint32 [n_tiles, 64 * S]: per tile one record, inside it the named planes in the fixed order, each a block
+    [64 pixels][channels]; pixels beyond the image edge are zero words."""
+    named = planes_named(which)
+    h, w = np.asarray(planes[named[0][0]]).shape[:2]
+    tl = tile_list(w, h, rank, world)
+    out = np.zeros((len(tl), TILE * TILE * planes_words(which)), np.uint32)
+    off = 0
+    for key, c in named:
+        src = _words(planes[key], c)
+        blk = np.zeros((len(tl), TILE, TILE, c), np.uint32)
+        for k, (tx, ty) in enumerate(tl):
+            part = src[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE]
+            blk[k, :part.shape[0], :part.shape[1]] = part
+        out[:, off:off + TILE * TILE * c] = blk.reshape(len(tl), TILE * TILE * c)
+        off += TILE * TILE * c
+    return out
+
+
+def unpack_planes_host(packed, planes, rank, world, which):
+    """numpy mirror of k_unpack_planes: scatter a rank's records into the named arrays of `planes`, in place: exactly the pixels of that
+    rank's tiles.  With the film in the set and a "bgra8" array [H, W, 4] uint8 in `planes`, those pixels' bgra8 too."""
+    named = planes_named(which)
+    h, w = np.asarray(planes[named[0][0]]).shape[:2]
+    tl = tile_list(w, h, rank, world)
+    packed = np.asarray(packed, np.uint32).reshape(len(tl), TILE * TILE * planes_words(which))
+    off = 0
+    for key, c in named:
+        dst = _words(planes[key], c)
+        blk = packed[:, off:off + TILE * TILE * c].reshape(len(tl), TILE, TILE, c)
+        for k, (tx, ty) in enumerate(tl):
+            y1, x1 = min((ty + 1) * TILE, h), min((tx + 1) * TILE, w)
+            dst[ty * TILE:y1, tx * TILE:x1] = blk[k, :y1 - ty * TILE, :x1 - tx * TILE]
+            if key == "film" and "bgra8" in planes:
+                planes["bgra8"][ty * TILE:y1, tx * TILE:x1] = bgra8_host(dst[ty * TILE:y1, tx * TILE:x1].view(np.float32))
+        off += TILE * TILE * c
+    return planes
+
+
+def gather_planes_host(planes, rank, world, which, dst=0, group=None):
+    """pt_film_present_planes on host arrays over any torch.distributed backend, in the shape of gather_present_host: every rank packs the
+    named planes of its tiles, the root gathers the records and unpacks them.  -> on `dst` a dict of new arrays, the named planes of the whole
+    image (and "bgra8" with the film in the set), None elsewhere; `planes` is not modified."""
+    import torch
+    import torch.distributed as dist
+    named = planes_named(which)
+    h, w = np.asarray(planes[named[0][0]]).shape[:2]
+    rec = TILE * TILE * planes_words(which)
+    mine = torch.from_numpy(pack_planes_host(planes, rank, world, which).view(np.int32))   # (gloo has no uint32)
+    alone = not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1)
+    if not alone and rank != dst:
+        if mine.shape[0]:
+            dist.send(mine, dst=dst, group=group)
+        return None
+    out = {k: np.zeros_like(np.asarray(planes[k])) for k, _ in named}
+    if which & 1:
+        out["bgra8"] = np.zeros((h, w, 4), np.uint8)
+    if alone:
+        return unpack_planes_host(mine.numpy().view(np.uint32), out, rank, world, which)
+    counts = [len(tile_list(w, h, r, world)) for r in range(world)]
+    bufs = [mine if r == dst else torch.zeros((counts[r], rec), dtype=torch.int32) for r in range(world)]
+    for q in [dist.irecv(bufs[r], src=r, group=group) for r in range(world) if r != dst and counts[r]]:
+        q.wait()
+    for r in range(world):
+        unpack_planes_host(bufs[r].numpy().view(np.uint32), out, r, world, which)
+    return out
 
 
 def selftest_film(width, height, rank, world):
@@ -204,6 +313,50 @@ class Presenter:
                 d = buf.to(self.image.device)
                 pt.film_unpack_tiles(self.film, r, self.world, d.data_ptr(), self.image.data_ptr())
             return self.image
+        if self.counts[self.rank]:
+            dist.send(host, dst=0)
+        return None
+
+    def present_planes(self, dst_film, planes):
+        """present() for a set of film planes (pt.PLANES_*), into a FILM: this rank's film -> the named planes (and the bgra8) of `dst_film`
+        on rank 0, over the transport the Presenter was built with.  dst_film: a Film of the same size that has the named planes on rank 0,
+        None elsewhere; every film pass runs on it afterwards.  -> dst_film on rank 0, None elsewhere.  The ranks agree beforehand that
+        their films have the planes (pt_film_present_planes in include/pt_api.h)."""
+        pt, torch, dist = self.pt, self.torch, self.dist
+        if self.comm:
+            self.comm.present_planes(self.film, dst_film if self.rank == 0 else None, planes, root=0)
+            return dst_film if self.rank == 0 else None
+        rec = 64 * pt.film_planes_words(self.film, planes)
+        dev = self.packed.device
+        mine = torch.empty((max(self.counts[self.rank], 1), rec), dtype=torch.int32, device=dev)   # (no fill queued on torch's stream: the pack writes every word)
+        pt.film_pack_planes(self.film, self.rank, self.world, planes, mine.data_ptr())
+        if not self.emulate:   # fallback: the same kernels, device buffers through the process group (RCCL)
+            torch.cuda.synchronize()
+            if self.rank == 0:
+                bufs = [mine] + [torch.zeros((max(self.counts[r], 1), rec), dtype=torch.int32, device=dev) for r in range(1, self.world)]
+                ops = [dist.P2POp(dist.irecv, bufs[r], r) for r in range(1, self.world) if self.counts[r]]
+                for w in (dist.batch_isend_irecv(ops) if ops else []):
+                    w.wait()
+                torch.cuda.synchronize()
+                for r in range(self.world):
+                    pt.film_unpack_planes(dst_film, r, self.world, planes, bufs[r].data_ptr())
+                return dst_film
+            if self.counts[self.rank]:
+                for w in dist.batch_isend_irecv([dist.P2POp(dist.isend, mine, 0)]):
+                    w.wait()
+            return None
+        host = mine.cpu()   # emulation: all ranks on one device, the records carried by gloo
+        if self.rank == 0:
+            for r in range(self.world):
+                buf = host
+                if r != 0:
+                    buf = torch.zeros((max(self.counts[r], 1), rec), dtype=torch.int32)
+                    if self.counts[r]:
+                        dist.recv(buf, src=r)
+                d = buf.to(dev)
+                torch.cuda.synchronize()   # (the copy is torch's stream's, the unpack the context's)
+                pt.film_unpack_planes(dst_film, r, self.world, planes, d.data_ptr())
+            return dst_film
         if self.counts[self.rank]:
             dist.send(host, dst=0)
         return None
