@@ -9,6 +9,7 @@
 #include "pt_math.h"
 #include "pair_leaf.h"
 #include "lds_scene.h"  // the LDS image of a scene: node strides, child codes, staging, byte counts
+#include "pop_batch.h"  // the pop over several stack entries at once (host and device)
 
 #include <hip/hip_ext.h>
 
@@ -111,27 +112,51 @@ __device__ __forceinline__ bool entry_within(uint32_t e, uint32_t cut) { return 
 // level * STRIDE + lane.  In front of level 0 lies one level more, "level -1", that no push writes: the pointer of an empty stack rests there,
 // and a read of the top entry (k_fused reads it with every node, ahead of the pop that may want it) needs no compare for the empty case.
 // STRIDE: threads per block.  compact_stack_bytes: what a plan gives the stack of `levels` entries per lane.
-template <int STRIDE>
+// LOW (k_fused, whose pop reads LOW + 1 entries per pass): the pointers are held LOW levels below the addresses they stand for -- an LDS access
+// adds an unsigned offset to its address register, so the entries BELOW the top are reached from the held register only if it points to the
+// lowest of them; every access then carries its distance as the instruction's offset, and no pass of the pop loop forms a second address.
+// A kernel with LOW > 0 has LOW more levels of its own LDS in front of the stack (fused_lds_covers_leaf_read).
+template <int STRIDE, int LOW = 0>
 struct LaneStack {
-    lds_u32 *top;    // the top entry; `under` while the stack is empty
-    lds_u32 *under;  // the lane's level -1
+    static constexpr int UP = LOW * STRIDE;  // from a held pointer to the entry it stands for
+    lds_u32 *top;    // (LOW levels below) the top entry; `under` while the stack is empty
+    lds_u32 *under;  // (LOW levels below) the lane's level -1
     // lane_base: the lane's dword of the stack's first bytes, i.e. of level -1
-    __device__ __forceinline__ explicit LaneStack(lds_u32 *lane_base) : top(lane_base), under(lane_base) {}
+    __device__ __forceinline__ explicit LaneStack(lds_u32 *lane_base) : top(lane_base - UP), under(lane_base - UP) {}
     __device__ __forceinline__ bool empty() const { return top <= under; }
     __device__ __forceinline__ bool has_entries() const { return top > under; }
     __device__ __forceinline__ void clear() { top = under; }
     // (the compiler forms the new pointer beside the old one and stores at an offset of the old: an add and a move.  An add in place -- the stride
     // in a scalar register the compiler cannot see through -- was measured and left out: DESIGN.md section 6, "The cut key")
-    __device__ __forceinline__ void push(uint32_t e) { top += STRIDE; *top = e; }
-    __device__ __forceinline__ uint32_t peek() const { return *top; }
-    __device__ __forceinline__ uint32_t pop() { const uint32_t e = *top; top -= STRIDE; return e; }
+    __device__ __forceinline__ void push(uint32_t e) { top += STRIDE; top[UP] = e; }
+    __device__ __forceinline__ uint32_t peek() const { return top[UP]; }
+    __device__ __forceinline__ uint32_t pop() { const uint32_t e = top[UP]; top -= STRIDE; return e; }
     __device__ __forceinline__ void drop() { top -= STRIDE; }
+    // the top N = LOW + 1 entries in one go, e[0] the top (pop_batch.h): N reads of one address register with one wait; the levels are STRIDE
+    // dwords apart, so two of them are one ds_read2st64_b32.  Over a BOTTOM entry (below) the reads under it land in the kernel's other LDS
+    // and are never taken
+    template <int N>
+    __device__ __forceinline__ void peek_n(uint32_t (&e)[N]) const
+    {
+        static_assert(N == LOW + 1, "the held pointer is the address of the lowest entry read");
+#pragma unroll
+        for (int i = 0; i < N; i++) e[i] = top[(N - 1 - i) * STRIDE];
+    }
+    // (levels: what a select chain of small constants gave.  Multiplied through, the chain selects among N byte counts that no instruction
+    // takes as literals -- N registers held across the whole loop; kept apart from the multiply it selects among inline constants and the
+    // pointer moves by one shift-and-add)
+    __device__ __forceinline__ void drop_n(uint32_t levels)
+    {
+        int32_t down = -(int32_t)levels;
+        asm("" : "+v"(down));
+        top += down * STRIDE;
+    }
     // k_fused keeps a BOTTOM entry under level 0 instead of asking "empty?" at every pop: key +0 (within every cut key) | the DONE code, so the
     // pop that runs out of entries takes it like any other and returns DONE.  It is written once per lane (arm_bottom) at the plan's level -1;
     // `under` of such a kernel is the address one level BELOW that (other LDS of the kernel: never accessed through the stack): a cleared stack
     // rests ON the bottom entry, a stack whose bottom entry was popped at `under`.
     static constexpr uint32_t BOTTOM = 0x00000000u | C14_DONE;
-    __device__ __forceinline__ void arm_bottom() { under[STRIDE] = BOTTOM; }
+    __device__ __forceinline__ void arm_bottom() { under[STRIDE + UP] = BOTTOM; }
     __device__ __forceinline__ void clear_to_bottom() { top = under + STRIDE; }
     // k_fused: a lane that owns no path at all holds a pointer below `under`, where a level number held -1 (one dword below: never read or
     // written through, and not below LDS byte 0 -- the scene's tables lie in front of every stack and are never empty: fused_lds asserts it)
@@ -157,10 +182,10 @@ __host__ __device__ constexpr size_t compact_stack_bytes(size_t threads, size_t 
 // like any other -- the pops leave it out -- but never returned: when it is the nearest child the step's pop runs instead, as pop(top, kcut, true),
 // and `top` is then the entry the step pushed last (k1, if any was pushed: the keys are sorted), not the stale e_top.
 struct NoSkip { __device__ __forceinline__ bool operator()(uint32_t) const { return false; } };
-template <int STRIDE, bool CUT_PER_STEP = false, bool SKIP = false, class Pop, class IsSkip = NoSkip>
+template <int STRIDE, bool CUT_PER_STEP = false, bool SKIP = false, int LOW, class Pop, class IsSkip = NoSkip>
 __device__ __forceinline__ uint32_t compact_node_step(const float4 *wide, uint32_t cur, const ptm::f3 &inv, const ptm::f3 &invf, const ptm::f3 &on,
                                                       const ptm::f3 &of, uint32_t ax, uint32_t ay, uint32_t az, float tmin, float best_t,
-                                                      LaneStack<STRIDE> &stk, Pop &&pop, [[maybe_unused]] IsSkip &&is_skip = IsSkip())
+                                                      LaneStack<STRIDE, LOW> &stk, Pop &&pop, [[maybe_unused]] IsSkip &&is_skip = IsSkip())
 {
     const float INF = __builtin_inff();
     float t0, t1, t2, t3;

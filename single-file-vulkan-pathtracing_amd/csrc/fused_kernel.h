@@ -100,16 +100,24 @@ __host__ __device__ constexpr FusedLds fused_lds(uint32_t n_wide, uint32_t n_tri
     l.extra = l.stack + (uint32_t)compact_stack_bytes(FTB, stack_levels);  // (its extra level is the BOTTOM entry's)
     return l;
 }
+constexpr int PT_FUSED_POP_N_MAX = 4;  // entries a pass of the pop loop may read together (PT_FUSED_POP_N below)
 // pair_leaf_test<LOAD_D_FIRST> reads the record five float4 behind a leaf's first: for a single triangle at the last position of the last copy
 // that is ptl::D_FIRST_OVERREAD_F4 float4 past the triangle copies -- the shade table must start right there and be at least that long
 constexpr bool fused_lds_covers_leaf_read(uint32_t n_wide, uint32_t n_tris)
 {
     const FusedLds l = fused_lds(n_wide, n_tris, 1u);
-    // (... and more than one stack level of other LDS in front of the stack: `under` and a parked pointer, a level and a dword below the BOTTOM
-    // entry, are no wrapped addresses)
+    // (... and PT_FUSED_POP_N_MAX stack levels and a dword of other LDS in front of the stack: the pop's reads of the levels under the BOTTOM
+    // entry, PT_FUSED_POP_N_MAX - 1 at the most, stay inside the block's LDS, and `under` and a parked pointer, a level and a dword below
+    // BOTTOM and held as many levels lower again (LaneStack's LOW), are no wrapped addresses)
     return l.shade == l.tri + lds_tris_bytes(n_tris) && l.frame - l.shade >= sizeof(float4) * ptl::D_FIRST_OVERREAD_F4 && l.wide == 0u &&
-           l.stack >= l.state + sizeof(uint32_t) * FTB + 4u;
+           l.stack >= l.state + sizeof(uint32_t) * FTB * PT_FUSED_POP_N_MAX + 4u;
 }
+// Entries a pass of the pop loop reads together (pop_batch.h).  Every fused instantiation takes it: none pays for the wider read with scratch
+// memory, spilled registers or VGPRs at 2 or 3 ("Pops in batches": N = 2, 3, 4 alternated on the box; 1 is the one-entry loop)
+#ifndef PT_FUSED_POP_N
+#define PT_FUSED_POP_N 3
+#endif
+static_assert(PT_FUSED_POP_N >= 1 && PT_FUSED_POP_N <= PT_FUSED_POP_N_MAX, "pop_first_within: 1 .. 4 entries per pass");
 static_assert(fused_lds_covers_leaf_read(1, 1) && fused_lds_covers_leaf_read(1, 2) && fused_lds_covers_leaf_read(21, 36) && fused_lds_covers_leaf_read(85, 85),
               "k_fused: s_shade directly behind s_tri (pair_leaf.h LOAD_D_FIRST), tables at LDS byte 0");
 
@@ -178,6 +186,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                                            uint2 *log_arg = nullptr)
 {
     constexpr uint32_t LEAF_BIT = C14_LEAF, DONE = C14_DONE;
+    constexpr int POP_N = PT_FUSED_POP_N;  // entries a pass of the pop loop reads together (pop_pending below)
     constexpr bool GROUPED = MODE == 1, HYB = MODE == 2;
     // SKIP: a bounce ray leaves out the leaf of the triangle it starts on when self_leaf.h's rule says that leaf cannot yield a hit: pair-leaf trees
     // (the rule is per triangle or fan pair); the NEE instantiations, whose shadow rays start on a triangle too, stay as they were
@@ -241,7 +250,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
 
     // (the lane's stack as the address of its top entry, over a BOTTOM entry (+0 | DONE) that every pop may take: the node step's read of the top
     // entry and both pop loops need no "empty?" compare -- LaneStack, extend_kernel.h.  Each lane writes and reads its own: no barrier)
-    LaneStack<FTB> stk((lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.stack) - FTB + threadIdx.x);  // (`under`: a level below the BOTTOM entry, in the path state)
+    LaneStack<FTB, POP_N - 1> stk((lds_u32 *)reinterpret_cast<uint32_t *>(smem + lds.stack) - FTB + threadIdx.x);  // (`under`: a level below the BOTTOM entry, in the path state)
     stk.arm_bottom();
     stk.park();  // (no path yet)
     const int lane = threadIdx.x & 63;
@@ -309,26 +318,43 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     // The stack's pop with the cull against best_t: a loop on the WAVE's condition -- the lanes that are served sit out behind one exec mask (see the
     // node loop) -- with selects inside, not branches (two more vector instructions for eight fewer scalar ones per pass).  r: PENDING for the lanes
     // that still look for an entry
-    constexpr uint32_t PENDING = 0xFFFFFFFFu;
+    // A pass reads the top POP_N entries together (pop_batch.h: the one-entry loop's rule as a priority chain; POP_N = 1 IS that loop): it takes
+    // the first of them that is within the cut, unless that one is the lane's own leaf -- then the next pass goes on below it.  One LDS round
+    // trip and one turn of the loop's scalar bookkeeping for up to POP_N of the siblings that a ray pushed before a leaf step found the hit that
+    // ends it: 5.80 -> 2.72 passes per 64 walked rays on the Cornell box ("Pops in batches").  At the stack's end the reads
+    // below the BOTTOM entry land in the path state, which lies in front of the stack (fused_lds_covers_leaf_read); BOTTOM is within every cut
+    // and comes first, so they are never taken.  A parked lane never pops.
+    constexpr uint32_t PENDING = ptpb::PENDING;
     // kcut: the cut key of the moment's best_t (pop_cut or push_cut, extend_kernel.h), compared with the raw entry
     auto pop_pending = [&](uint32_t r, uint32_t kcut) -> uint32_t {
         while (__ballot(r == PENDING)) {
             if (r == PENDING) {
                 PT_FB(FB_POP)
-                const uint32_t e = stk.pop();  // (the BOTTOM entry ends the search: within every cut key, its code is DONE)
-                if constexpr (SKIP) {
-                    const bool within = entry_within(e, kcut), self = is_self(e);
-                    PT_FB_IF(within & self, FB_SKIP)
-                    r = (within & !self) ? (e & 0x3FFFu) : PENDING;
-                } else {
-                    r = entry_within(e, kcut) ? (e & 0x3FFFu) : PENDING;
-                }
+                uint32_t e[POP_N];
+                stk.template peek_n<POP_N>(e);
+                const ptpb::Popped p = ptpb::pop_first_within<POP_N>(e, kcut, SKIP ? self_leaf : ptpb::NO_SELF);
+                if constexpr (SKIP) { PT_FB_IF(p.own, FB_SKIP) }
+                if constexpr (POP_N == 1) stk.drop();
+                else stk.drop_n(p.dropped);
+                r = p.code;
             }
         }
         return r;
     };
     // (after a leaf step: its accept may have changed best_t, so the cut key is formed here)
     auto pop = [&]() -> uint32_t { return pop_pending(PENDING, pop_cut(best_t)); };
+    // The leaf step's pop: its first pass on entries that were read WITH the leaf's vertices -- nothing is pushed during a leaf step, so they are
+    // what the pop will look at, and the pass has no LDS round trip of its own.  (Not for NEE, whose accept of a shadow ray's hit clears the stack.)
+    constexpr bool POP_WITH_LEAF = !NEE;
+    auto pop_read = [&](const uint32_t (&e)[POP_N]) -> uint32_t {
+        const uint32_t kcut = pop_cut(best_t);
+        PT_FB(FB_POP)
+        const ptpb::Popped p = ptpb::pop_first_within<POP_N>(e, kcut, SKIP ? self_leaf : ptpb::NO_SELF);
+        if constexpr (SKIP) { PT_FB_IF(p.own, FB_SKIP) }
+        if constexpr (POP_N == 1) stk.drop();
+        else stk.drop_n(p.dropped);
+        return pop_pending(p.code, kcut);
+    };
 
     for (;;) {
         PT_FB(FB_ITER)
@@ -782,6 +808,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
         {   // (no `if (tracing)` around it: a lane without a ray holds DONE, and one compare says "a leaf that is not DONE")
             if ((uint32_t)(cur - LEAF_BIT) < DONE - LEAF_BIT) {
                 PT_FB(FB_LEAF)
+                [[maybe_unused]] uint32_t e_pop[POP_N];
+                if constexpr (POP_WITH_LEAF) stk.template peek_n<POP_N>(e_pop);
                 if (PAIRS) {
                     const uint32_t first = cur & 0x7FFu;
                     ptl::pair_leaf_test<true, true>(tri4, (size_t)tri_base + 3 * (size_t)first, ((cur >> 11) & 3u) != 0u, first, pre, orgp, tmin, tmax,
@@ -811,7 +839,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         }
                     }
                 }
-                cur = pop();
+                if constexpr (POP_WITH_LEAF) cur = pop_read(e_pop);
+                else cur = pop();
             }
             if (tracing && cur == DONE) {  // the hit (best_pos, best_V, best_W, best_det) waits in registers for the shade block
                 PT_FB(FB_FINISH)
