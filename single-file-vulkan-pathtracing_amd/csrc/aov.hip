@@ -75,7 +75,7 @@ __global__ __launch_bounds__(TB) void k_aov_reduce(AovConst ac, const uint32_t *
                                                    const float4 *__restrict__ inst_frame, const uint32_t *__restrict__ inst_id, uint32_t n_tris,
                                                    AovPlanes planes, unsigned long long *stats, unsigned long long n_valid_rays)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0 && stats) atomicAdd(stats, n_valid_rays);  // the chunk's rays, once per launch
+    if (blockIdx.x == 0 && threadIdx.x == 0 && stats) atomicAdd(stats + PT_STAT_RAYS, n_valid_rays);  // the chunk's rays, once per launch
     const uint32_t pix = blockIdx.x * TB + threadIdx.x;
     if (pix >= n_pix) return;
     uint32_t px, py;
@@ -279,8 +279,8 @@ __global__ __launch_bounds__(TB, PT_AOV_WAVES) void k_aov_fused(AovConst ac_arg,
             }
         }
     }
-    if (lane == 0 && n_rays_wave && stats) atomicAdd(stats, n_rays_wave);
-    if (lane == 0 && n_cull_wave && stats) atomicAdd(stats + 19, n_cull_wave);  // (pt_stats.rays_culled)
+    if (lane == 0 && n_rays_wave && stats) atomicAdd(stats + PT_STAT_RAYS, n_rays_wave);
+    if (lane == 0 && n_cull_wave && stats) atomicAdd(stats + PT_STAT_RAYS_CULLED, n_cull_wave);  // (pt_stats.rays_culled)
 }
 
 // this rank's 8x8 tiles, row by row (pt_render's own list before its hand-out order: pt_rank_tiles)

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(TB) void k_extend_inst(const float4 *__restrict__ t
     const uint32_t n = *count_in;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (count_zero) *count_zero = 0u;
-        if (stats) atomicAdd(stats, (unsigned long long)n);
+        if (stats) atomicAdd(stats + PT_STAT_RAYS, (unsigned long long)n);
     }
     lds_u64 *my_stack = (lds_u64 *)reinterpret_cast<unsigned long long *>(stack) + threadIdx.x;
     unsigned long long *my_spill = reinterpret_cast<unsigned long long *>(spill) + (size_t)blockIdx.x * TB + threadIdx.x;
@@ -253,8 +253,8 @@ __global__ __launch_bounds__(TB) void k_extend_inst(const float4 *__restrict__ t
             c_tris += __shfl_xor(c_tris, o, 64);
         }
         if (lane == 0 && stats) {
-            atomicAdd(stats + 2, c_nodes);
-            atomicAdd(stats + 3, c_tris);
+            atomicAdd(stats + PT_STAT_NODES, c_nodes);
+            atomicAdd(stats + PT_STAT_TRIS, c_tris);
         }
     }
 }

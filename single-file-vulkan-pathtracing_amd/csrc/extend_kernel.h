@@ -341,7 +341,7 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
     const uint32_t n = *count_in;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (count_zero) *count_zero = 0u;  // the queue the coming shade pass appends to
-        if (stats) atomicAdd(stats, (unsigned long long)n);  // exact ray count
+        if (stats) atomicAdd(stats + PT_STAT_RAYS, (unsigned long long)n);  // exact ray count
     }
     lds_u64 *my_stack = (lds_u64 *)reinterpret_cast<unsigned long long *>(stack) + threadIdx.x;
     LaneStack<TB> stk((lds_u32 *)reinterpret_cast<uint32_t *>(stack) + threadIdx.x);  // (COMPACT)
@@ -632,18 +632,18 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
             c_hit_lanes += __shfl_xor(c_hit_lanes, o, 64);
         }
         if (lane == 0 && stats) {
-            atomicAdd(stats + 2, c_nodes);
-            atomicAdd(stats + 3, c_tris);
-            atomicAdd(stats + 4, c_node_steps);
-            atomicAdd(stats + 5, c_tri_steps);
-            atomicAdd(stats + 8, c_refills);
-            atomicAdd(stats + 9, c_pops);
-            atomicAdd(stats + 10, c_hit_blocks);
-            atomicAdd(stats + 11, c_finishes);
-            atomicAdd(stats + 12, c_iters);
-            atomicAdd(stats + 13, c_leaf_lanes);
-            atomicAdd(stats + 14, c_pop_lanes);
-            atomicAdd(stats + 15, c_hit_lanes);
+            atomicAdd(stats + PT_STAT_NODES, c_nodes);
+            atomicAdd(stats + PT_STAT_TRIS, c_tris);
+            atomicAdd(stats + PT_STAT_NODE_STEPS, c_node_steps);
+            atomicAdd(stats + PT_STAT_TRI_STEPS, c_tri_steps);
+            atomicAdd(stats + PT_STAT_WAVE_REFILLS, c_refills);
+            atomicAdd(stats + PT_STAT_WAVE_POPS, c_pops);
+            atomicAdd(stats + PT_STAT_WAVE_HIT_BLOCKS, c_hit_blocks);
+            atomicAdd(stats + PT_STAT_WAVE_FINISHES, c_finishes);
+            atomicAdd(stats + PT_STAT_WAVE_ITERS, c_iters);
+            atomicAdd(stats + PT_STAT_LEAF_LANES, c_leaf_lanes);
+            atomicAdd(stats + PT_STAT_POP_LANES, c_pop_lanes);
+            atomicAdd(stats + PT_STAT_HIT_LANES, c_hit_lanes);
         }
     }
 }

@@ -104,6 +104,12 @@ pt_status plan_fused_inst(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPl
     fp.grid = ctx->num_cus * per_cu;
     fp.block = FITB;
     fp.refill = pt_tuned(ctx->tune.refill, 48, 1, 64);
+    // the waiting rules of k_extend_inst16 (extend_launch.hip has the measurements), re-swept for this kernel in round 6 on the tree with the
+    // least-area cut (leaves are reached a node earlier): a leaf step waits for 14 lanes (8 / 10 / 12 / 14 / 20 / 24: 16.42 / 16.60 / 16.72 / 16.76 /
+    // 16.52 / 16.32 Grays/s on the 10 000-instance grid at 16 frames), an instance entry for 12 (profiles/r06m_c4_fused_knobs.log)
+    fp.enter_min = pt_tuned(ctx->tune.enter_min, 12, 1, 64);
+    fp.leaf_min = pt_tuned(ctx->tune.leaf_min, 14, 1, 64);
+    fp.node_yield = pt_tuned(ctx->tune.node_yield, 6, 0, 64);
     // stack entries beyond the LDS ones: one dword each, [level][thread], in the context's spill area (sized by ptw_plan_extend for
     // the wavefront kernels' grids; grown here if this grid asks for more)
     const pt_status rcs = ptw_reserve_spill(ctx, (size_t)std::max(pl.spill_levels, 1u) * (size_t)fp.grid * FITB * sizeof(uint32_t));
@@ -166,25 +172,17 @@ pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPla
     return PT_OK;
 }
 
-void ptw_launch_fused(const FusedPlan &fp, bool grouped, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad,
+void ptw_launch_fused(const FusedPlan &fp, int mode, const ptw::FastDiv &div_frames, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad,
                       const pt_scene *s, uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax,
                       hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
-    if (fp.inst) {
-        // the waiting rules of k_extend_inst16 (extend_launch.hip has the measurements), re-swept for this kernel in round 6 on the tree with the
-        // least-area cut (leaves are reached a node earlier): a leaf step waits for 14 lanes (8 / 10 / 12 / 14 / 20 / 24: 16.42 / 16.60 / 16.72 / 16.76 /
-        // 16.52 / 16.32 Grays/s on the 10 000-instance grid at 16 frames), an instance entry for 12 (profiles/r06m_c4_fused_knobs.log)
-        const int enter_min = pt_tuned(s->ctx->tune.enter_min, 12, 1, 64), leaf_min = pt_tuned(s->ctx->tune.leaf_min, 14, 1, 64);
-        const int node_yield = pt_tuned(s->ctx->tune.node_yield, 6, 0, 64);
-        hipExtLaunchKernelGGL(pick_fused_inst(grouped, s->pair_leaves), dim3(fp.grid), dim3(FITB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_tlas16,
+    if (fp.inst) {  // (never head + tail: mode 0 or 1)
+        hipExtLaunchKernelGGL(pick_fused_inst(mode == 1, s->pair_leaves), dim3(fp.grid), dim3(FITB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_tlas16,
                               norm_box_tlas(s), reinterpret_cast<const uint4 *>(s->d_wide16), norm_box_blas(s), s->d_tri4, s->d_shade4, s->n_wide, s->n_tris, s->d_inst6,
                               s->d_tlas_prim_of, fp.inst_frame, 0u, n_slots, next_slot, stats, fp.spill, (uint32_t)fp.grid * FITB, fp.refill,
-                              tmin, tmax, fp.lds_stack, enter_min, leaf_min, node_yield, fp.n_tlas_lds);
+                              tmin, tmax, fp.lds_stack, fp.enter_min, fp.leaf_min, fp.node_yield, fp.n_tlas_lds);
         return;
     }
-    FastDiv div_frames;  // one group: the hand-out order is tile-major (fused_kernel.h), chunk -> (tile, frame) by this
-    div_frames.init(std::max(rc.lanes_active, 1u));
-    const int mode = rc.tail ? 2 : (grouped ? 1 : 0);
     if (fp.nee) {  // (one sample group, no head + tail: render.hip never plans another shape for it)
         if (mode != 0) return;
         hipExtLaunchKernelGGL(pick_fused_nee(fp.pairs), dim3(fp.grid), dim3(FTB), (uint32_t)fp.smem, st, ev0, ev1, 0u, rc, tiles, rad, s->d_wide, s->d_tri4, s->d_shade4,

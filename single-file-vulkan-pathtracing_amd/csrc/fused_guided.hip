@@ -34,23 +34,18 @@ FusedInstLogFn pick_fused_inst_log(bool grouped, bool pairs)
 }
 }  // namespace
 
-pt_status ptw_launch_fused_log(const FusedPlan &fp, bool grouped, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, const pt_scene *s,
+pt_status ptw_launch_fused_log(const FusedPlan &fp, int mode, const ptw::FastDiv &div_frames, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, const pt_scene *s,
                                uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax, uint2 *log, hipStream_t st)
 {
     pt_ctx *ctx = s->ctx;
-    if (fp.inst) {  // (the waiting rules: fused.hip ptw_launch_fused)
-        const int enter_min = pt_tuned(ctx->tune.enter_min, 12, 1, 64), leaf_min = pt_tuned(ctx->tune.leaf_min, 14, 1, 64);
-        const int node_yield = pt_tuned(ctx->tune.node_yield, 6, 0, 64);
-        const FusedInstLogFn fn = pick_fused_inst_log(grouped, s->pair_leaves);
+    if (fp.inst) {
+        const FusedInstLogFn fn = pick_fused_inst_log(mode == 1, s->pair_leaves);
         PT_TRY(ptw_prepare_kernel(ctx, reinterpret_cast<const void *>(fn), FITB, fp.smem));
         hipLaunchKernelGGL(fn, dim3(fp.grid), dim3(FITB), (uint32_t)fp.smem, st, rc, tiles, rad, s->d_tlas16, norm_box_tlas(s), reinterpret_cast<const uint4 *>(s->d_wide16),
                            norm_box_blas(s), s->d_tri4, s->d_shade4, s->n_wide, s->n_tris, s->d_inst6, s->d_tlas_prim_of, fp.inst_frame, 0u, n_slots, next_slot, stats,
-                           fp.spill, (uint32_t)fp.grid * FITB, fp.refill, tmin, tmax, fp.lds_stack, enter_min, leaf_min, node_yield, fp.n_tlas_lds, log);
+                           fp.spill, (uint32_t)fp.grid * FITB, fp.refill, tmin, tmax, fp.lds_stack, fp.enter_min, fp.leaf_min, fp.node_yield, fp.n_tlas_lds, log);
         return PT_OK;
     }
-    FastDiv div_frames;  // (one group: the tile-major hand-out order, fused_kernel.h)
-    div_frames.init(std::max(rc.lanes_active, 1u));
-    const int mode = rc.tail ? 2 : (grouped ? 1 : 0);
     if (fp.nee) {
         if (mode != 0) { ctx->err = "PT_FLAG_NEE on the fused pipeline: one sample group only"; return PT_ERR_UNSUPPORTED; }
         const FusedNeeLogFn fn = pick_fused_nee_log(fp.pairs);

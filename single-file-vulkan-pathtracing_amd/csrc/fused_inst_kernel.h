@@ -509,8 +509,8 @@ __global__ __launch_bounds__(FITB, PT_FUSEDI_WAVES) void PT_FUSEDI_KERNEL(
             // (cur == I16_DONE: the hit (best_pos, best_V, best_W, best_det, best_ipos) waits in registers for the shade block
         }
     }
-    if (lane == 0 && n_rays_wave) atomicAdd(stats, (unsigned long long)n_rays_wave);
-    if (lane == 0 && n_cull_wave) atomicAdd(stats + 19, (unsigned long long)n_cull_wave);  // (pt_stats.rays_culled)
+    if (lane == 0 && n_rays_wave) atomicAdd(stats + PT_STAT_RAYS, (unsigned long long)n_rays_wave);
+    if (lane == 0 && n_cull_wave) atomicAdd(stats + PT_STAT_RAYS_CULLED, (unsigned long long)n_cull_wave);  // (pt_stats.rays_culled)
 }
 #undef PT_FUSEDI_KERNEL
 #undef PT_FUSEDI_LOG_ARG

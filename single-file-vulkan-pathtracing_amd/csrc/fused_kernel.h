@@ -847,8 +847,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
             }
         }
     }
-    if (lane == 0 && n_rays_wave) atomicAdd(stats, (unsigned long long)n_rays_wave);
-    if (lane == 0 && n_cull_wave) atomicAdd(stats + 19, (unsigned long long)n_cull_wave);  // (pt_stats.rays_culled)
+    if (lane == 0 && n_rays_wave) atomicAdd(stats + PT_STAT_RAYS, (unsigned long long)n_rays_wave);
+    if (lane == 0 && n_cull_wave) atomicAdd(stats + PT_STAT_RAYS_CULLED, (unsigned long long)n_cull_wave);  // (pt_stats.rays_culled)
     dev.kernel_end(lane, n_rays_wave, FTB);
     if constexpr (COUNT) {  // (pt_get_block_counts: stats[PT_N_STATS + 2 * block] wave executions, [+ 1] lanes inside them)
         if (lane < 2 * FB_N) atomicAdd(stats + PT_N_STATS + lane, (unsigned long long)fb_of_wave()[lane]);

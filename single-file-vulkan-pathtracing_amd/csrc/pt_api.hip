@@ -29,6 +29,16 @@ static pt_status guarded(pt_ctx *ctx, F &&body)
     }
 }
 
+// what the render entries begin with (args: the other pointers are there): the handles belong together, the device is current, the body runs guarded
+template <class Body>
+static pt_status render_entry(pt_scene *s, pt_film *f, bool args, Body &&body)
+{
+    if (!s || !f || !args) return PT_ERR_INVALID_ARG;
+    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, body);
+}
+
 // ---- tuning (include/pt_api.h pt_tuning): the names PT_TUNE and the Python mirror use, in field order
 static const char *const k_tune_names[] = { "refill", "lds_stack", "extend_blocks", "pipes", "stagger", "sort_bits", "pair_leaves",
                                             "pair_kernel", "topdown4", "rec64", "inst16", "inst16_blocks", "enter_min", "node_yield",
@@ -387,21 +397,8 @@ void pt_params_default(pt_params *p)
     p->sample_groups = 0;
 }
 
-pt_status pt_render(pt_scene *s, pt_film *f, const pt_params *p)
-{
-    if (!s || !f || !p) return PT_ERR_INVALID_ARG;
-    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
-    return guarded(s->ctx, [&] { return ptw_render(s, f, p); });
-}
-
-pt_status pt_render_prepare(pt_scene *s, pt_film *f, const pt_params *p)
-{
-    if (!s || !f || !p) return PT_ERR_INVALID_ARG;
-    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
-    return guarded(s->ctx, [&] { return ptw_prepare(s, f, p); });
-}
+pt_status pt_render(pt_scene *s, pt_film *f, const pt_params *p) { return render_entry(s, f, p, [&] { return ptw_render(s, f, p); }); }
+pt_status pt_render_prepare(pt_scene *s, pt_film *f, const pt_params *p) { return render_entry(s, f, p, [&] { return ptw_prepare(s, f, p); }); }
 
 pt_status pt_film_enable_aov(pt_film *f, void *const *device_planes)
 {
@@ -640,10 +637,7 @@ void pt_adaptive_params_default(pt_adaptive_params *p)
 
 pt_status pt_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p, const pt_adaptive_params *ap, pt_adaptive_result *result)
 {
-    if (!s || !f || !p || !ap) return PT_ERR_INVALID_ARG;
-    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
-    return guarded(s->ctx, [&] { return ptw_render_adaptive(s, f, p, ap, result); });
+    return render_entry(s, f, p && ap, [&] { return ptw_render_adaptive(s, f, p, ap, result); });
 }
 
 void pt_guided_params_default(pt_guided_params *p)
@@ -655,10 +649,7 @@ void pt_guided_params_default(pt_guided_params *p)
 
 pt_status pt_render_guided(pt_scene *s, pt_film *f, const pt_params *p, const pt_guided_params *gp, pt_guided_result *result)
 {
-    if (!s || !f || !p || !gp) return PT_ERR_INVALID_ARG;
-    if (s->ctx != f->ctx) { s->ctx->err = "scene and film belong to different contexts"; return PT_ERR_INVALID_ARG; }
-    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
-    return guarded(s->ctx, [&] { return ptw_render_guided(s, f, p, gp, result); });
+    return render_entry(s, f, p && gp, [&] { return ptw_render_guided(s, f, p, gp, result); });
 }
 
 pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits)
@@ -719,17 +710,16 @@ pt_status pt_get_stats(pt_ctx *ctx, pt_stats *out)
     unsigned long long h[PT_N_STATS];
     PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     PT_HIP(ctx, hipMemcpy(h, ctx->d_stats, sizeof(h), hipMemcpyDeviceToHost));
-    ctx->stats.rays = h[0];
-    ctx->stats.nodes_visited = h[2];
-    ctx->stats.tris_tested = h[3];
-    ctx->stats.node_steps = h[4];
-    ctx->stats.tri_steps = h[5];
-    ctx->stats.wave_refills = h[8]; ctx->stats.wave_pops = h[9]; ctx->stats.wave_hit_blocks = h[10];
-    ctx->stats.wave_finishes = h[11]; ctx->stats.wave_iterations = h[12];
-    ctx->stats.leaf_lanes = h[13]; ctx->stats.pop_lanes = h[14]; ctx->stats.hit_lanes = h[15];
-    ctx->stats.enter_steps = h[16]; ctx->stats.enter_lanes = h[17];
-    ctx->stats.rays_culled = h[19];  // (h[18], h[20]: the ray counters before a launch whose term logs may overflow, render.hip)
-    *out = ctx->stats;
+    ctx->stats.rays = h[PT_STAT_RAYS];
+    ctx->stats.nodes_visited = h[PT_STAT_NODES];
+    ctx->stats.tris_tested = h[PT_STAT_TRIS];
+    ctx->stats.node_steps = h[PT_STAT_NODE_STEPS];
+    ctx->stats.tri_steps = h[PT_STAT_TRI_STEPS];
+    ctx->stats.wave_refills = h[PT_STAT_WAVE_REFILLS]; ctx->stats.wave_pops = h[PT_STAT_WAVE_POPS]; ctx->stats.wave_hit_blocks = h[PT_STAT_WAVE_HIT_BLOCKS];
+    ctx->stats.wave_finishes = h[PT_STAT_WAVE_FINISHES]; ctx->stats.wave_iterations = h[PT_STAT_WAVE_ITERS];
+    ctx->stats.leaf_lanes = h[PT_STAT_LEAF_LANES]; ctx->stats.pop_lanes = h[PT_STAT_POP_LANES]; ctx->stats.hit_lanes = h[PT_STAT_HIT_LANES];
+    ctx->stats.enter_steps = h[PT_STAT_ENTER_STEPS]; ctx->stats.enter_lanes = h[PT_STAT_ENTER_LANES];
+    ctx->stats.rays_culled = h[PT_STAT_RAYS_CULLED];    *out = ctx->stats;
     return PT_OK;
 }
 

@@ -24,6 +24,17 @@
 constexpr int PT_N_STATS = 24;  // u64 slots of pt_ctx::d_stats that pt_get_stats reads ...
 constexpr int PT_N_BLOCKS = 32;  // ... followed by {wave executions, lanes} of up to this many kernel blocks (pt_get_block_counts; fused_kernel.h FusedBlock)
 constexpr int PT_N_STATS_ALL = PT_N_STATS + 2 * PT_N_BLOCKS;
+// The u64 words of pt_ctx::d_stats below PT_N_STATS (1 and 21 .. 23 are unused): the kernels add to them, pt_get_stats reads them
+enum pt_stat_word : int {
+    PT_STAT_RAYS = 0, PT_STAT_RAYS_CULLED = 19,        // the exact ray count; of it, camera rays of slots finished without a walk (pt_stats.rays_culled)
+    PT_STAT_NODES = 2, PT_STAT_TRIS = 3,               // PT_FLAG_COUNT_VISITS: BVH nodes visited, triangles tested ...
+    PT_STAT_NODE_STEPS = 4, PT_STAT_TRI_STEPS = 5,     // ... wave steps of the node code, of the triangle code
+    PT_STAT_OVERFLOW = 6, PT_STAT_SPILL_FILL = 7,      // a slot filled its term log (the launch is redone: render.hip); entries taken from the term spill pool
+    PT_STAT_WAVE_REFILLS = 8, PT_STAT_WAVE_POPS = 9, PT_STAT_WAVE_HIT_BLOCKS = 10, PT_STAT_WAVE_FINISHES = 11, PT_STAT_WAVE_ITERS = 12,  // wave executions
+    PT_STAT_LEAF_LANES = 13, PT_STAT_POP_LANES = 14, PT_STAT_HIT_LANES = 15,  // lanes in leaf steps, pop iterations, divide blocks
+    PT_STAT_ENTER_STEPS = 16, PT_STAT_ENTER_LANES = 17,                       // wave executions of the instance entry, lanes in them
+    PT_STAT_RAYS_SAVED = 18, PT_STAT_RAYS_CULLED_SAVED = 20  // the two ray counters as they were before a launch whose term logs may overflow
+};
 constexpr int PT_MAX_PIPES = 4;  // concurrent wavefront pipelines (streams) per pt_render
 namespace {
 constexpr int TB = 256;                     // threads per block of every kernel of the library
@@ -36,8 +47,7 @@ struct pt_ctx {
     bool own_stream = false;
     int num_cus = 256;
     std::string err;
-    // statistics block in device memory (u64 x 8): [0] rays, [1] unused, [2] BVH4 nodes visited, [3] triangles tested, [4] wave steps of the node code, [5] of the triangle code, [6] term-log overflow flag, [7] term pool fill, [8..12] wave executions of refill / pop iteration / hit block / finish / outer iteration, [13] lanes in leaf steps, [14] lanes in pop iterations, [15] lanes in divide blocks, [16] wave executions of the instance entry, [17] lanes in them
-    unsigned long long *d_stats = nullptr;
+    unsigned long long *d_stats = nullptr;  // the counters in device memory: PT_N_STATS_ALL u64 words, named by pt_stat_word above
     void *d_rad = nullptr;                 // ptw::Radiance of the fused launch in device memory (wavefront_types.h: Radiance::dev) ...
     unsigned char h_rad[128] = {};         // ... and what it holds (uploaded when it changes: the film's buffers only move when they grow)
     pt_stats stats{};
@@ -58,8 +68,8 @@ struct pt_ctx {
     size_t mem_budget = 0;
     pt_tuning tune;            // include/pt_api.h: defaults (-1) + PT_TUNE, filled once by pt_ctx_create
     // fused.hip: the launch attributes / occupancy of the fused kernels for the last LDS size planned ([0] single-level, [1] two-level,
-    // [2] single-level with NEE): a blocking call per frame plans twice (PT_PIPELINE_AUTO's look, then the render) and should not pay
-    // five runtime calls each time
+    // [2] single-level with NEE).  A call plans its fused launch once (render.hip CallPlan); this is for the calls that follow it: a blocking
+    // call per frame should not pay seven runtime calls for the same plan every time
     size_t fused_smem[3] = { 0, 0, 0 };  // key: LDS bytes << 1 | pair-leaf kernel
     int fused_per_cu[3] = { 0, 0, 0 };
 };

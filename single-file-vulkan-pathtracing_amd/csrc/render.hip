@@ -85,31 +85,67 @@ struct Pipe {
     int polls;        // live-count polls queued on this pipeline's stream in the current batch
 };
 
-// What one pt_render call (wavefront pipelines) decides once and every batch uses.
+// What one render (a call of either pipeline, or the redo of one of its batches) decides once and every batch or launch uses.
 struct Job {
     pt_scene *s; pt_film *f; const pt_params *p; pt_ctx *ctx;
-    const TileView *sel = nullptr;  // pt_render_adaptive: the selected tiles (null: the film's own list)
+    const TileView *sel = nullptr;  // pt_render_adaptive: the selected tiles (null: the film's own list) ...
+    TileView picked;                // ... the selection itself (render_call)
+    AdaptCall *ad = nullptr;        // pt_render_adaptive's call
     ExtendPlan pl;
     RenderShape sh;
     RenderConst rc;
     Radiance rad;
-    bool nested = false, profile = false, count_visits = false, async = false, nee = false;
+    bool fused = false, profile = false, count_visits = false, async = false, nee = false;
     bool shade_lds = false, sort_rays = false, stagger = false;
     int n_pipes = 1, sort_bits = 4, shade_grid = 0;
     size_t shade_smem = 0;
-    uint32_t spill_cap = 0;
     const float4 *inst_frame = nullptr, *nee_lights = nullptr;
     uint32_t nee_n_lights = 0;
     float nee_light_area = 0.f;
-    unsigned long long *d_overflow = nullptr, *d_spill_count = nullptr;
-    std::vector<hipEvent_t> ev_extend, ev_shade;  // (start, stop) pairs filled in by the launches (PT_FLAG_PROFILE)
+    FusedPlan fp;                   // PT_PIPELINE_FUSED: the launch plan ...
+    pt_params q;                    // ... the params with the shape the pipeline picked (p points here)
+    int32_t rect[4] = { 0, 0, -1, -1 };  // subject_rect
+    // pt_render_guided: every fused launch also writes the film's first-hit log, sized by the caller, and the reduce behind it folds it into the guides
+    GuidedCall *gd = nullptr;
+    std::vector<hipEvent_t> ev_extend, ev_shade, ev_reduce;  // pooled (start, stop) pairs: the launches' own (PT_FLAG_PROFILE), the guided reduces'
     size_t ev_used = 0;
 };
 
-Radiance job_radiance(const Job &j)
+// The next (start, stop) pair of the pool, remembered in `pairs` for add_event_pairs
+pt_status take_event_pair(Job &j, std::vector<hipEvent_t> &pairs, hipEvent_t &e0, hipEvent_t &e1)
 {
+    PT_TRY(grow_event_pool(j.ctx, j.ev_used + 2));
+    e0 = j.ctx->ev_pool[j.ev_used++]; e1 = j.ctx->ev_pool[j.ev_used++];
+    pairs.push_back(e0); pairs.push_back(e1);
+    return PT_OK;
+}
+void add_event_pairs(const std::vector<hipEvent_t> &pairs, float &ms)
+{
+    for (size_t i = 0; i + 1 < pairs.size(); i += 2) {
+        float a = 0.f;
+        if (hipEventElapsedTime(&a, pairs[i], pairs[i + 1]) == hipSuccess) ms += a;
+    }
+}
+
+// The radiance record of the job's shape over the film's buffers as they stand, with the spill pool's share: worst-case logs never reach the pool.
+// The fused kernels also read it from device memory, for the ends of the log they rarely take (Radiance::dev): uploaded when it changes.
+pt_status set_radiance(Job &j)
+{
+    pt_ctx *ctx = j.ctx;
     const pt_film::Work &w = j.f->work;
-    return { w.d_color, w.d_terms, w.d_terms_over, w.d_nterm, w.d_spill, w.d_spill_head, j.d_spill_count, j.spill_cap, j.d_overflow, nullptr };
+    uint32_t spill_cap = j.sh.bounded ? SPILL_POOL_ENTRIES : 0u;
+    if (ctx->tune.term_spill >= 0) spill_cap = std::min<uint32_t>(spill_cap, (uint32_t)ctx->tune.term_spill);  // tests
+    static_assert(sizeof(Radiance) <= sizeof(pt_ctx::h_rad), "pt_ctx::h_rad holds a Radiance");
+    j.rad = { w.d_color, w.d_terms, w.d_terms_over, w.d_nterm, w.d_spill, w.d_spill_head, ctx->d_stats + PT_STAT_SPILL_FILL, spill_cap,
+              ctx->d_stats + PT_STAT_OVERFLOW, j.fused ? static_cast<const Radiance *>(ctx->d_rad) : nullptr };
+    if (!j.fused || std::memcmp(ctx->h_rad, &j.rad, sizeof(j.rad)) == 0) return PT_OK;
+    // On the stream, ahead of the launch that reads it, from the context's own (pageable) copy.  No kernel can be reading d_rad meanwhile: only the
+    // fused kernels do, every fused call ends with a stream sync, and the redo syncs before it comes here.  A failed copy leaves h_rad equal to no record.
+    std::memcpy(ctx->h_rad, &j.rad, sizeof(j.rad));
+    const hipError_t e = hipMemcpyAsync(ctx->d_rad, ctx->h_rad, sizeof(j.rad), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) std::memset(ctx->h_rad, 0, sizeof(ctx->h_rad));
+    PT_HIP(ctx, e);
+    return PT_OK;
 }
 
 // The pixel rectangle the scene's box projects to (film_work.hip ptw_tiles_subject_first: its tiles are handed out first).  The camera of
@@ -162,27 +198,23 @@ void apply_cull(const pt_ctx *ctx, const pt_params *p, const int32_t rect[4], Re
     }
 }
 
+// ---- once per render, both pipelines: the radiance record, the render constants with the cull ---------------------------------------------
+pt_status job_begin(Job &j)
+{
+    PT_TRY(set_radiance(j));
+    j.rc = ptw_render_const(j.p, ptw_tile_view(j.f, j.sel).n_tiles, j.sh);
+    subject_rect(j.s, j.p, j.rect);
+    apply_cull(j.ctx, j.p, j.rect, j.rc);
+    j.profile = (j.p->flags & PT_FLAG_PROFILE) != 0;  // (never a redo's: redo_batch)
+    return PT_OK;
+}
 // ---- once per call: kernel plan, shape + workspace, number of pipelines, ray-sort scratch, shadow queue -----------------
 pt_status job_setup(Job &j)
 {
     pt_scene *s = j.s; pt_film *f = j.f; const pt_params *p = j.p; pt_ctx *ctx = j.ctx;
     pt_film::Work &w = f->work;
     const uint32_t lanes = j.sh.lanes, groups = j.sh.groups;
-    if (!j.nested) {
-        ctx->stats.frames_in_flight = lanes;
-        ctx->stats.sample_groups = groups;
-    }
-    j.d_overflow = ctx->d_stats + 6; j.d_spill_count = ctx->d_stats + 7;
-    j.spill_cap = j.sh.bounded ? SPILL_POOL_ENTRIES : 0u;  // worst-case logs never reach the pool
-    if (ctx->tune.term_spill >= 0) j.spill_cap = std::min<uint32_t>(j.spill_cap, (uint32_t)ctx->tune.term_spill);  // tests
-    j.rad = job_radiance(j);
-    j.rc = ptw_render_const(p, ptw_tile_view(f, j.sel).n_tiles, j.sh);
-    {
-        int32_t rect[4];
-        subject_rect(s, p, rect);
-        apply_cull(ctx, p, rect, j.rc);
-    }
-    j.profile = !j.nested && (p->flags & PT_FLAG_PROFILE) != 0;  // (a redo would re-record the pooled events of its caller)
+    PT_TRY(job_begin(j));
     j.count_visits = (p->flags & PT_FLAG_COUNT_VISITS) != 0;
     j.async = (p->flags & PT_FLAG_ASYNC) != 0;
     if (j.async && j.profile) { ctx->err = "PT_FLAG_ASYNC and PT_FLAG_PROFILE exclude each other"; return PT_ERR_INVALID_ARG; }
@@ -262,22 +294,44 @@ pt_status job_setup(Job &j)
     return PT_OK;
 }
 
+// ---- the overflow redo, the same for both pipelines -----------------------------------------------------------------------------
+// A batch (wavefront) or launch (fused) whose term logs are bounded can overflow them (scenes where most surfaces emit): the kernels raise
+// PT_STAT_OVERFLOW and nothing of the batch reaches the film -- the wavefront looks before its resolve, the fused pipeline's resolve skips on the flag.
+// The host then puts the ray counters back, renders the same frames with one slot per (frame, pixel) -- the plain accumulator needs no log -- and
+// returns to the call's workspace shape (redo_batch).
+// arm: the two ray counters as they are before the batch, in spare device words: nothing waits for the device.  ON the stream, ahead of the launches
+// that add to them: a plain device-to-device copy runs on the null stream, which the library's non-blocking streams are not ordered against.
+pt_status redo_arm(Job &j)
+{
+    if (!j.sh.bounded) return PT_OK;
+    pt_ctx *ctx = j.ctx;
+    unsigned long long *const w = ctx->d_stats;
+    PT_HIP(ctx, hipMemcpyAsync(w + PT_STAT_RAYS_SAVED, w + PT_STAT_RAYS, sizeof(*w), hipMemcpyDeviceToDevice, ctx->stream));
+    PT_HIP(ctx, hipMemcpyAsync(w + PT_STAT_RAYS_CULLED_SAVED, w + PT_STAT_RAYS_CULLED, sizeof(*w), hipMemcpyDeviceToDevice, ctx->stream));
+    PT_HIP(ctx, hipMemsetAsync(j.rad.spill_count, 0, sizeof(*w), ctx->stream));
+    return PT_OK;
+}
+// check: did a slot fill its term log?  Drains the stream (after the last launch of a blocking call that is the wait the call ends with).
+pt_status redo_check(Job &j, bool &redo)
+{
+    redo = false;
+    if (!j.sh.bounded) return PT_OK;
+    unsigned long long flag = 0;
+    PT_HIP(j.ctx, hipStreamSynchronize(j.ctx->stream));
+    PT_HIP(j.ctx, hipMemcpy(&flag, j.rad.overflow, sizeof(flag), hipMemcpyDeviceToHost));
+    redo = flag != 0ull;
+    return PT_OK;
+}
+pt_status redo_batch(Job &j);  // (the redo itself stands behind the two pipelines it re-enters)
+
 // ---- per batch: the slot lanes split over the pipelines, queue 0 of each filled ---------------------------------------------
-pt_status batch_begin(Job &j, Pipe *pipe, int &pipes_now, unsigned long long &rays_before)
+pt_status batch_begin(Job &j, Pipe *pipe, int &pipes_now)
 {
     pt_ctx *ctx = j.ctx;
     pt_film::Work &w = j.f->work;
     hipStream_t st = ctx->stream;
-    rays_before = 0;
-    if (j.sh.bounded) {  // the exact ray counter as it is before this batch, should the batch have to be redone
-        PT_HIP(ctx, hipStreamSynchronize(st));
-        PT_HIP(ctx, hipMemcpy(&rays_before, ctx->d_stats, sizeof(rays_before), hipMemcpyDeviceToHost));
-        // (rays_culled before the batch: ON the stream, ahead of the k_generate launches that add to word 19 -- a plain device-to-device copy runs
-        // on the null stream, which the library's non-blocking streams are not ordered against)
-        PT_HIP(ctx, hipMemcpyAsync(ctx->d_stats + 20, ctx->d_stats + 19, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-    }
+    PT_TRY(redo_arm(j));
     PT_HIP(ctx, hipMemsetAsync(w.d_count, 0, sizeof(uint32_t) * 2 * PT_MAX_PIPES, st));
-    if (j.sh.bounded) PT_HIP(ctx, hipMemsetAsync(j.d_spill_count, 0, sizeof(unsigned long long), st));
     const uint32_t slot_lanes = j.rc.lanes_active * j.sh.groups;
     pipes_now = std::min<int>(j.n_pipes, (int)slot_lanes);
     for (int k = 0; k < pipes_now; k++) {
@@ -317,9 +371,8 @@ pt_status pipe_round(Job &j, Pipe *pipe, int k, int pipes_now, uint32_t round, b
     const int cur = pp.cur;
     hipEvent_t x0 = nullptr, x1 = nullptr, h0 = nullptr, h1 = nullptr;
     if (j.profile) {  // from the context's pool: creating ~2000 events per call showed in the wall time
-        const pt_status rce = grow_event_pool(ctx, j.ev_used + 4);
-        if (rce != PT_OK) return rce;
-        x0 = ctx->ev_pool[j.ev_used++]; x1 = ctx->ev_pool[j.ev_used++]; h0 = ctx->ev_pool[j.ev_used++]; h1 = ctx->ev_pool[j.ev_used++];
+        PT_TRY(take_event_pair(j, j.ev_extend, x0, x1));
+        PT_TRY(take_event_pair(j, j.ev_shade, h0, h1));
     }
     const uint32_t *perm = nullptr;
     if (j.sort_rays && round > 0) {  // (round 0 is the primary rays: one origin, generated tile by tile)
@@ -369,10 +422,6 @@ pt_status pipe_round(Job &j, Pipe *pipe, int k, int pipes_now, uint32_t round, b
     }
     PT_HIP(ctx, hipGetLastError());  // a launch the runtime refused (LDS size, grid) must not pass for a rendered round
     if (shade_rule) { PT_HIP(ctx, hipEventRecord(ctx->ev_shade[k], pp.st)); shade_recorded[k] = true; }
-    if (j.profile) {
-        j.ev_extend.push_back(x0); j.ev_extend.push_back(x1);
-        j.ev_shade.push_back(h0); j.ev_shade.push_back(h1);
-    }
     ctx->stats.launches_extend++;
     ctx->stats.launches_shade++;
     pp.cur ^= 1;
@@ -438,8 +487,6 @@ void drain_side_streams(pt_ctx *ctx, int pipes_now)
     (void)hipGetLastError();
 }
 
-pt_status render_wavefront(pt_scene *s, pt_film *f, const pt_params *p, const ExtendPlan &pl, bool nested, const TileView *sel = nullptr,
-                           AdaptCall *ad = nullptr);
 // the blend of a batch's frames into the film: k_resolve over the film's own list, k_resolve_adapt over a selection
 void launch_resolve(pt_film *f, const RenderConst &rc, const TileView &tv, const Radiance &rad, hipStream_t st, const unsigned long long *skip_if_set)
 {
@@ -448,103 +495,52 @@ void launch_resolve(pt_film *f, const RenderConst &rc, const TileView &tv, const
 }
 
 // ---- per batch: join, term-log overflow check, resolve (or the same frames once more with one sample group) -----------------
-pt_status batch_finish(Job &j, int pipes_now, unsigned long long rays_before)
+pt_status batch_finish(Job &j, int pipes_now)
 {
-    pt_ctx *ctx = j.ctx; pt_film *f = j.f; const pt_params *p = j.p;
+    pt_ctx *ctx = j.ctx;
     hipStream_t st = ctx->stream;
     for (int k = 1; k < pipes_now; k++) {  // join before the resolve reads every pipeline's slots
         PT_HIP(ctx, hipEventRecord(ctx->ev_join[k], ctx->pipe_stream[k]));
         PT_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join[k], 0));
     }
     bool redo = false;
-    if (j.sh.bounded) {  // did a slot fill its term log?
-        unsigned long long flag = 0;
-        PT_HIP(ctx, hipStreamSynchronize(st));
-        PT_HIP(ctx, hipMemcpy(&flag, j.d_overflow, sizeof(flag), hipMemcpyDeviceToHost));
-        redo = flag != 0ull;
-    }
-    if (!redo) {
-        launch_resolve(f, j.rc, ptw_tile_view(f, j.sel), j.rad, st, nullptr);
-        ctx->stats.launches_other++;
-        return PT_OK;
-    }
-    // Rare (scenes where most surfaces emit): nothing of this batch has touched the film yet.  Put the ray counter back, clear
-    // the flag and render the same frames with one slot per (frame, pixel) -- the plain accumulator needs no log -- then return
-    // to this call's workspace shape.
-    PT_HIP(ctx, hipMemcpy(ctx->d_stats, &rays_before, sizeof(rays_before), hipMemcpyHostToDevice));
-    PT_HIP(ctx, hipMemcpy(ctx->d_stats + 19, ctx->d_stats + 20, sizeof(unsigned long long), hipMemcpyDeviceToDevice));
-    PT_HIP(ctx, hipMemset(j.d_overflow, 0, sizeof(unsigned long long)));
-    ctx->stats.redone_batches++;
-    pt_params q = *p;
-    q.frame = j.rc.frame_base;
-    q.frame_count = j.rc.lanes_active;
-    q.frames_in_flight = j.rc.lanes_active;
-    q.sample_groups = 1;
-    pt_status rc = render_wavefront(j.s, f, &q, j.pl, true, j.sel);
-    if (rc != PT_OK) return rc;
-    rc = ptw_ensure_work(f, p->rank, p->world, j.sh.lanes, j.sh.groups, j.sh.term_cap, j.sh.term_pcap);
-    if (rc != PT_OK) return rc;
-    j.rad = job_radiance(j);
+    PT_TRY(redo_check(j, redo));
+    if (redo) return redo_batch(j);
+    launch_resolve(j.f, j.rc, ptw_tile_view(j.f, j.sel), j.rad, st, nullptr);
+    ctx->stats.launches_other++;
     return PT_OK;
 }
 
-// ---- the wavefront pipelines (PT_PIPELINE_WAVEFRONT, _NEE) ---------------------------------------------------------------
-pt_status render_wavefront(pt_scene *s, pt_film *f, const pt_params *p, const ExtendPlan &pl, bool nested, const TileView *sel, AdaptCall *ad)
+pt_status wavefront_batch(Job &j)
 {
-    pt_ctx *ctx = s->ctx;
-    hipStream_t st = ctx->stream;
-    Job j{};
-    j.s = s; j.f = f; j.p = p; j.ctx = ctx; j.pl = pl; j.nested = nested; j.sel = sel;
-    pt_status rc = ptw_shape_and_work(f, p, j.sh, launch_class(s, pl));
-    if (rc != PT_OK) return rc;
-    TileView picked;
-    if (ad) {  // pt_render_adaptive: the work is planned for the full list; the selection over it, then nothing but the selection
-        rc = ptad_select(f, ad->ap, ptw_tile_view(f, nullptr), &picked, &ad->res);
-        if (rc != PT_OK) return rc;
-        ctx->stats.frames_in_flight = j.sh.lanes;
-        ctx->stats.sample_groups = j.sh.groups;
-        ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
-        if (ad->dry || picked.n_tiles == 0) return PT_OK;
-        j.sel = &picked;
-    }
-    rc = job_setup(j);
-    if (rc != PT_OK) return rc;
-    if (!nested) PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    for (uint32_t done = 0; j.rc.n_slots > 0 && done < p->frame_count; done += j.sh.lanes) {
-        j.rc.frame_base = p->frame + (int32_t)done;
-        j.rc.lanes_active = std::min(j.sh.lanes, p->frame_count - done);
-        Pipe pipe[PT_MAX_PIPES];
-        int pipes_now = 0;
-        unsigned long long rays_before = 0;
-        rc = batch_begin(j, pipe, pipes_now, rays_before);
-        if (rc == PT_OK) rc = run_rounds(j, pipe, pipes_now);
-        if (rc == PT_OK) rc = batch_finish(j, pipes_now, rays_before);
-        if (rc != PT_OK) {
-            drain_side_streams(ctx, std::max(pipes_now, j.n_pipes));
-            return rc;
-        }
-    }
-    if (!nested) PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    Pipe pipe[PT_MAX_PIPES];
+    int pipes_now = 0;
+    pt_status rc = batch_begin(j, pipe, pipes_now);
+    if (rc == PT_OK) rc = run_rounds(j, pipe, pipes_now);
+    if (rc == PT_OK) rc = batch_finish(j, pipes_now);
+    if (rc != PT_OK) drain_side_streams(j.ctx, std::max(pipes_now, j.n_pipes));
+    return rc;
+}
+
+// ---- the end of a call of either pipeline (it began with ev_a): the wait a blocking call ends with, the device times, the workspace, the samples started
+pt_status call_tail(Job &j)
+{
+    pt_ctx *ctx = j.ctx; const pt_params *p = j.p;
+    PT_HIP(ctx, hipEventRecord(ctx->ev_b, ctx->stream));
     if (!j.async) {
-        PT_HIP(ctx, hipStreamSynchronize(st));
+        float ms = 0.f;
+        PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         PT_HIP(ctx, hipGetLastError());
-        if (!nested) {
-            float ms = 0.f;
-            PT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
-            ctx->stats.ms_total += ms;
-        }
+        PT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
+        ctx->stats.ms_total += ms;
     }
-    if (!nested) {
-        ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
-        ctx->stats.paths += (j.sel ? j.sel->pixels : ptw_valid_local_pixels(f, p)) * p->spp_per_frame * p->frame_count;  // samples started
-    }
+    ctx->stats.workspace_bytes = ptw_workspace_bytes(j.f);
+    ctx->stats.paths += (j.sel ? j.sel->pixels : ptw_valid_local_pixels(j.f, p)) * p->spp_per_frame * p->frame_count;  // samples started
     if (j.profile) {
-        for (size_t i = 0; i + 1 < j.ev_extend.size(); i += 2) {
-            float a = 0.f, b = 0.f;
-            if (hipEventElapsedTime(&a, j.ev_extend[i], j.ev_extend[i + 1]) == hipSuccess) ctx->stats.ms_extend += a;
-            if (hipEventElapsedTime(&b, j.ev_shade[i], j.ev_shade[i + 1]) == hipSuccess) ctx->stats.ms_shade += b;
-        }
+        add_event_pairs(j.ev_extend, ctx->stats.ms_extend);
+        add_event_pairs(j.ev_shade, ctx->stats.ms_shade);
     }
+    if (j.gd) add_event_pairs(j.ev_reduce, j.gd->guide_ms);
     return PT_OK;
 }
 
@@ -632,217 +628,237 @@ uint32_t fused_tail_samples(const pt_ctx *ctx, const pt_film *f, const pt_params
     return (uint32_t)std::max(0, std::min<int>(t, (int)spp - 1));
 }
 
-// gd (pt_render_guided): every launch also writes the film's first-hit log (fused_guided.hip), and the reduce behind it folds the log into the
-// guide planes (guided.hip).  The caller has sized the log for the frames in flight it passes.
-pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const ExtendPlan &pl, bool nested, bool prepare_only, const TileView *sel = nullptr,
-                       AdaptCall *ad = nullptr, GuidedCall *gd = nullptr)
+// What every render entry decides first (plan_call): the params with the pipeline resolved, the closest-hit plan, and the fused launch plan --
+// resolve_pipeline's when PT_PIPELINE_AUTO had it look, else made where the fused pipeline first needs it; a call plans the launch once.
+struct CallPlan {
+    pt_params p;
+    ExtendPlan pl;
+    FusedPlan fp;  // planned if fp_valid, and then for this value of PT_FLAG_NEE
+    bool fp_valid = false, fp_nee = false;
+};
+pt_status call_fused_plan(pt_scene *s, CallPlan &cp)
 {
-    pt_ctx *ctx = s->ctx;
-    hipStream_t st = ctx->stream;
+    const bool nee = (cp.p.flags & PT_FLAG_NEE) != 0;
+    if (cp.fp_valid && cp.fp_nee == nee) return PT_OK;
+    cp.fp = FusedPlan{};
+    cp.fp_nee = nee;
+    const pt_status rc = ptw_plan_fused(s, cp.pl, cp.p.tmin, cp.fp, nee);
+    cp.fp_valid = rc == PT_OK;
+    return rc;
+}
+
+// HEAD + TAIL slots (fused_kernel.h MODE 2): where the library picks the groups itself and the launch holds few frames, a pixel's frame is one
+// head slot of spp - S samples and S one-sample tail slots -- the launch ends with short work and only the tail's radiance terms go through
+// the log (see fused_tail_samples for S).  PT_ERR_OOM: no room for the logs.
+pt_status fused_tail_shape(Job &j, uint32_t tail)
+{
+    pt_film *f = j.f;
+    const pt_params *p = &j.q;
+    RenderShape &sh = j.sh;
+    j.q.sample_groups = 1;
+    sh = RenderShape{};
+    sh.lanes = p->frames_in_flight; sh.groups = 1; sh.group_size = p->spp_per_frame; sh.tail = tail;
+    const uint32_t worst = p->max_depth;                       // a tail slot is one sample: at most one term per ray
+    sh.term_pcap = std::min(worst, 3u);
+    const uint64_t n_tail = (uint64_t)sh.lanes * tail * (uint64_t)((f->w + 7) / 8) * ((f->h + 7) / 8) * 64ull / std::max(p->world, 1u) + 64;
+    uint64_t ocap = std::min<uint64_t>(worst - sh.term_pcap, (1ull << 30) / std::max<uint64_t>(n_tail * sizeof(float4), 1));
+    if (j.ctx->tune.term_ocap >= 0) ocap = std::min<uint64_t>(ocap, (uint64_t)j.ctx->tune.term_ocap);
+    sh.term_cap = sh.term_pcap + (uint32_t)ocap;
+    sh.bounded = sh.term_cap < worst;
+    return ptw_ensure_work(f, p->rank, p->world, sh.lanes, 1, sh.term_cap, sh.term_pcap, false, tail);
+}
+
+// ---- step 1, shape and workspace: what pt_render_prepare stops after and pt_render_guided sizes its log by ----------------------------------
+pt_status fused_shape(Job &j, CallPlan &cp)
+{
+    pt_scene *s = j.s; pt_film *f = j.f; pt_ctx *ctx = j.ctx;
+    const pt_params *p_in = &cp.p;
     if (p_in->width > 0xFFFFu || p_in->height > 0xFFFFu) {  // (the kernel keeps a path's pixel as two 16-bit halves of one LDS word)
         ctx->err = "PT_PIPELINE_FUSED renders images up to 65535 x 65535";
         return PT_ERR_UNSUPPORTED;
     }
-    FusedPlan fp;
-    const bool nee = (p_in->flags & PT_FLAG_NEE) != 0;
-    pt_status rc_ = ptw_plan_fused(s, pl, p_in->tmin, fp, nee);
-    if (rc_ != PT_OK) return rc_;
-    if (nee && (p_in->flags & PT_FLAG_COUNT_VISITS)) {
+    PT_TRY(call_fused_plan(s, cp));
+    j.fp = cp.fp;
+    if ((p_in->flags & PT_FLAG_NEE) && (p_in->flags & PT_FLAG_COUNT_VISITS)) {
         ctx->err = "PT_FLAG_COUNT_VISITS on the fused pipeline: not with PT_FLAG_NEE (the NEE kernel has no instrumented form)";
         return PT_ERR_UNSUPPORTED;
     }
     if (p_in->flags & PT_FLAG_COUNT_VISITS) {  // the instrumented twin of the single-level kernel (wave-level block counts: pt_get_block_counts)
-        if (fp.inst || !fp.pairs) {
+        if (j.fp.inst || !j.fp.pairs) {
             ctx->err = "PT_FLAG_COUNT_VISITS on the fused pipeline: single-level scenes with pair leaves only (the two-level kernel has no instrumented form)";
             return PT_ERR_UNSUPPORTED;
         }
-        fp.count = true;
+        j.fp.count = true;
     }
-    int32_t rect[4];
-    subject_rect(s, p_in, rect);
-    pt_params q;
-    fused_shape_defaults(f, p_in, fp, rect, q);
-    const pt_params *p = &q;
-    RenderShape sh;
-    // HEAD + TAIL slots (fused_kernel.h MODE 2): where the library picks the groups itself and the launch holds few frames, a pixel's frame is one
-    // head slot of spp - S samples and S one-sample tail slots -- the launch ends with short work and only the tail's radiance terms go through
-    // the log (see fused_tail_samples for S).
-    const uint32_t tail = (!fp.inst && !fp.nee && !nested && p_in->sample_groups == 0) ? fused_tail_samples(ctx, f, p_in, q.frames_in_flight, rect) : 0u;
+    subject_rect(s, p_in, j.rect);
+    fused_shape_defaults(f, p_in, j.fp, j.rect, j.q);
+    j.p = &j.q;
+    RenderShape &sh = j.sh;
+    pt_status rc = PT_OK;
+    const uint32_t tail = (!j.fp.inst && !j.fp.nee && p_in->sample_groups == 0) ? fused_tail_samples(ctx, f, p_in, j.q.frames_in_flight, j.rect) : 0u;
     if (tail) {
-        q.sample_groups = 1;
-        sh = RenderShape{};
-        sh.lanes = q.frames_in_flight; sh.groups = 1; sh.group_size = p->spp_per_frame; sh.tail = tail;
-        const uint32_t worst = p->max_depth;                       // a tail slot is one sample: at most one term per ray
-        sh.term_pcap = std::min(worst, 3u);
-        const uint64_t n_tail = (uint64_t)sh.lanes * tail * (uint64_t)((f->w + 7) / 8) * ((f->h + 7) / 8) * 64ull / std::max(p->world, 1u) + 64;
-        uint64_t ocap = std::min<uint64_t>(worst - sh.term_pcap, (1ull << 30) / std::max<uint64_t>(n_tail * sizeof(float4), 1));
-        if (ctx->tune.term_ocap >= 0) ocap = std::min<uint64_t>(ocap, (uint64_t)ctx->tune.term_ocap);
-        sh.term_cap = sh.term_pcap + (uint32_t)ocap;
-        sh.bounded = sh.term_cap < worst;
-        rc_ = ptw_ensure_work(f, p->rank, p->world, sh.lanes, 1, sh.term_cap, sh.term_pcap, false, tail);
-        if (rc_ == PT_ERR_OOM) {  // (no room for the logs: the plain shape)
-            fused_shape_defaults(f, p_in, fp, rect, q);
+        rc = fused_tail_shape(j, tail);
+        if (rc == PT_ERR_OOM) {  // (no room for the logs: the plain shape)
+            fused_shape_defaults(f, p_in, j.fp, j.rect, j.q);
             sh = RenderShape{};
         }
     }
     for (; !sh.tail;) {
-        rc_ = ptw_shape_and_work(f, p, sh, 3, false);
-        if (rc_ != PT_ERR_OOM) break;
+        rc = ptw_shape_and_work(f, j.p, sh, 3, false);
+        if (rc != PT_ERR_OOM) break;
         // a shape this function chose (the caller passed 0) and that does not fit is planned again smaller, like the wavefront's AUTO
         // shapes: first fewer sample groups (the next smaller divisor of spp), then fewer frames in flight
-        if (p_in->sample_groups == 0 && q.sample_groups > 1) {
-            uint32_t g = q.sample_groups - 1;
+        if (p_in->sample_groups == 0 && j.q.sample_groups > 1) {
+            uint32_t g = j.q.sample_groups - 1;
             while (g > 1 && p_in->spp_per_frame % g) g--;
-            q.sample_groups = g;
-        } else if (p_in->frames_in_flight == 0 && q.frames_in_flight > 1) {
-            q.frames_in_flight = (q.frames_in_flight + 1) / 2;
+            j.q.sample_groups = g;
+        } else if (p_in->frames_in_flight == 0 && j.q.frames_in_flight > 1) {
+            j.q.frames_in_flight = (j.q.frames_in_flight + 1) / 2;
         } else {
             break;
         }
     }
-    if (!nested) {
-        ctx->stats.frames_in_flight = sh.lanes;
-        ctx->stats.sample_groups = sh.groups;
-        ctx->stats.tail_samples = sh.tail;
-    }
-    if (rc_ != PT_OK) return rc_;
-    if (fp.nee && (sh.groups != 1 || sh.tail || sh.bounded)) {  // (fused_shape_defaults plans nothing else for it: k_fused_nee is MODE 0 only)
+    ctx->stats.frames_in_flight = sh.lanes;
+    ctx->stats.sample_groups = sh.groups;
+    ctx->stats.tail_samples = sh.tail;
+    if (rc != PT_OK) return rc;
+    if (j.fp.nee && (sh.groups != 1 || sh.tail || sh.bounded)) {  // (fused_shape_defaults plans nothing else for it: k_fused_nee is MODE 0 only)
         ctx->err = "PT_FLAG_NEE on the fused pipeline: one sample group only";
         return PT_ERR_UNSUPPORTED;
     }
     ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
-    if (prepare_only) return PT_OK;
-    if (!sel) {  // (a selection inherits the order of the list it was made from)
-        const int32_t none[4] = { 0, 0, -1, -1 };
-        rc_ = ptw_tiles_subject_first(f, ctx->tune.fused_subject == 0 ? none : rect, st);
-        if (rc_ != PT_OK) return rc_;
-    }
-    TileView picked;
-    if (ad) {  // pt_render_adaptive: the work is planned for the full list; the selection over it, then nothing but the selection
-        rc_ = ptad_select(f, ad->ap, ptw_tile_view(f, nullptr), &picked, &ad->res);
-        if (rc_ != PT_OK) return rc_;
-        if (ad->dry || picked.n_tiles == 0) return PT_OK;
-        sel = &picked;
-    }
-    pt_film::Work &w = f->work;
-    unsigned long long *const d_overflow = ctx->d_stats + 6, *const d_spill_count = ctx->d_stats + 7;
-    uint32_t spill_cap = sh.bounded ? SPILL_POOL_ENTRIES : 0u;
-    if (ctx->tune.term_spill >= 0) spill_cap = std::min<uint32_t>(spill_cap, (uint32_t)ctx->tune.term_spill);
-    static_assert(sizeof(Radiance) <= sizeof(pt_ctx::h_rad), "pt_ctx::h_rad holds a Radiance");
-    // (the record the kernel gets by value, and the same in device memory for the ends of the log it rarely takes: Radiance::dev)
-    Radiance rad{};
-    auto set_rad = [&]() -> pt_status {
-        rad = { w.d_color, w.d_terms, w.d_terms_over, w.d_nterm, w.d_spill, w.d_spill_head, d_spill_count, spill_cap, d_overflow, static_cast<const Radiance *>(ctx->d_rad) };
-        if (std::memcmp(ctx->h_rad, &rad, sizeof(rad)) != 0) {
-            std::memcpy(ctx->h_rad, &rad, sizeof(rad));
-            PT_HIP(ctx, hipMemcpyAsync(ctx->d_rad, ctx->h_rad, sizeof(rad), hipMemcpyHostToDevice, st));
-        }
-        return PT_OK;
-    };
-    rc_ = set_rad();
-    if (rc_ != PT_OK) return rc_;
-    RenderConst rc = ptw_render_const(p, ptw_tile_view(f, sel).n_tiles, sh);
-    apply_cull(ctx, p, rect, rc);
-    const bool profile = !nested && (p->flags & PT_FLAG_PROFILE) != 0;
-    ctx->stats.extend_variant = pl.variant;
+    return PT_OK;
+}
+
+// ---- per render (a call, or the redo of one of its launches): tile order, radiance record, render constants --------------------------------------
+pt_status fused_begin(Job &j)
+{
+    pt_ctx *ctx = j.ctx;
+    PT_TRY(job_begin(j));
+    ctx->stats.extend_variant = j.pl.variant;
     ctx->stats.pipelines = 1;
-    if (!nested) PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    std::vector<hipEvent_t> evs;
-    size_t ev_used = 0;
-    if (gd && (size_t)sh.lanes * rc.slots_per_lane * rc.spp > f->gd.cap) {  // (never: ptw_render_guided sized the log for this shape)
+    if (j.gd && (size_t)j.sh.lanes * j.rc.slots_per_lane * j.rc.spp > j.f->gd.cap) {  // (never: ptw_render_guided sized the log for this shape)
         ctx->err = "pt_render_guided: the first-hit log is smaller than the launch";
         return PT_ERR_OOM;
     }
-    for (uint32_t done = 0; rc.n_slots > 0 && done < p->frame_count; done += sh.lanes) {
-        const TileView tv = ptw_tile_view(f, sel);
-        rc.frame_base = p->frame + (int32_t)done;
-        rc.lanes_active = std::min(sh.lanes, p->frame_count - done);
-        // A launch whose term logs are bounded can overflow them (scenes where most surfaces emit): k_fused raises d_overflow, k_resolve then
-        // leaves the film alone, and the host -- which looks at the flag once the stream is idle anyway: after the call's last launch, or
-        // before the next launch of a longer call, whose blend must follow this one's -- renders the same frames again with one group.
-        // Nothing here waits for the device before the launch: the ray counter to restore is kept in a spare device word.
-        unsigned long long *const d_rays_before = ctx->d_stats + 18;
-        if (sh.bounded) {
-            PT_HIP(ctx, hipMemcpyAsync(d_rays_before, ctx->d_stats, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-            PT_HIP(ctx, hipMemcpyAsync(ctx->d_stats + 20, ctx->d_stats + 19, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));  // (rays_culled)
-            PT_HIP(ctx, hipMemsetAsync(d_spill_count, 0, sizeof(unsigned long long), st));
-        }
-        PT_HIP(ctx, hipMemsetAsync(w.d_count, 0, sizeof(uint32_t) * PTW_COUNT_WORDS, st));  // the slot counters (fused_kernel.h: eight, 128 B apart)
-        const uint32_t n_slots = rc.lanes_active * sh.groups * rc.slots_per_lane;  // (head + tail: the launch's head slots; its tail slots follow from rc)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (profile) {
-            rc_ = grow_event_pool(ctx, ev_used + 2);
-            if (rc_ != PT_OK) return rc_;
-            e0 = ctx->ev_pool[ev_used++]; e1 = ctx->ev_pool[ev_used++];
-            evs.push_back(e0); evs.push_back(e1);
-        }
-        if (gd) {
-            rc_ = ptw_launch_fused_log(fp, sh.groups > 1, rc, tv.d_tiles, rad, s, n_slots, w.d_count, ctx->d_stats, p->tmin, p->tmax, f->gd.d_log, st);
-            if (rc_ != PT_OK) return rc_;
-            gd->launches++;
-        } else {
-            ptw_launch_fused(fp, sh.groups > 1, rc, tv.d_tiles, rad, s, n_slots, w.d_count, ctx->d_stats, p->tmin, p->tmax, st, e0, e1);  // (rc.tail != 0: the head + tail kernel)
-        }
-        PT_HIP(ctx, hipGetLastError());
-        ctx->stats.launches_extend++;
-        ctx->stats.rounds++;
-        launch_resolve(f, rc, tv, rad, st, sh.bounded ? d_overflow : nullptr);
-        ctx->stats.launches_other++;
-        if (gd) {
-            // The launch's frames into the guide planes, timed by a pair of pooled events (the call is not profiled).  Queued here, before the overflow
-            // flag is looked at: a launch whose term log overflows still walks every path to its end, so its log is complete, and the redo below --
-            // which numbers its slots by the one-group tile order, another list than a grouped launch's (film_work.hip) -- neither writes nor needs it.
-            rc_ = grow_event_pool(ctx, ev_used + 2);
-            if (rc_ != PT_OK) return rc_;
-            hipEvent_t g0 = ctx->ev_pool[ev_used++], g1 = ctx->ev_pool[ev_used++];
-            evs.push_back(g0); evs.push_back(g1);
-            PT_HIP(ctx, hipEventRecord(g0, st));
-            const uint32_t last = p->frame_count - 1u - done;  // the call's last frame, counted from this launch's first
-            ptg_launch_reduce(s, f, rc, tv.d_tiles, last, fp.inst_frame, st);
-            PT_HIP(ctx, hipGetLastError());
-            PT_HIP(ctx, hipEventRecord(g1, st));
-            ctx->stats.launches_other++;
-        }
-        bool redo = false;
-        if (sh.bounded) {
-            unsigned long long flag = 0;
-            PT_HIP(ctx, hipStreamSynchronize(st));  // (the last launch of a blocking call: the wait the call ends with)
-            PT_HIP(ctx, hipMemcpy(&flag, d_overflow, sizeof(flag), hipMemcpyDeviceToHost));
-            redo = flag != 0ull;
-        }
-        if (redo) {  // a slot filled its term log: the same frames once more with one group
-            PT_HIP(ctx, hipMemcpy(ctx->d_stats, d_rays_before, sizeof(unsigned long long), hipMemcpyDeviceToDevice));
-            PT_HIP(ctx, hipMemcpy(ctx->d_stats + 19, ctx->d_stats + 20, sizeof(unsigned long long), hipMemcpyDeviceToDevice));
-            PT_HIP(ctx, hipMemset(d_overflow, 0, sizeof(unsigned long long)));
-            ctx->stats.redone_batches++;
-            pt_params r = *p;
-            r.frame = rc.frame_base; r.frame_count = rc.lanes_active; r.frames_in_flight = rc.lanes_active; r.sample_groups = 1;
-            rc_ = render_fused(s, f, &r, pl, true, false, sel);
-            if (rc_ != PT_OK) return rc_;
-            if (gd) gd->launches++;
-            rc_ = ptw_ensure_work(f, p->rank, p->world, sh.lanes, sh.groups, sh.term_cap, sh.term_pcap, false, sh.tail);
-            if (rc_ != PT_OK) return rc_;
-            rc_ = set_rad();
-            if (rc_ != PT_OK) return rc_;
-        }
+    return PT_OK;
+}
+// the fused pipeline's hand-out order: the tiles that can see the scene first (a selection inherits the order of the list it was made from)
+pt_status fused_order_tiles(Job &j)
+{
+    const int32_t none[4] = { 0, 0, -1, -1 };
+    return j.sel || !j.fused ? PT_OK : ptw_tiles_subject_first(j.f, j.ctx->tune.fused_subject == 0 ? none : j.rect, j.ctx->stream);
+}
+
+// ---- step 2, one launch: its frames through the fused kernel and k_resolve (pt_render_guided: the log and its reduce), then a look at the overflow flag,
+// which the host takes once the stream is idle anyway: after the call's last launch, or before the next of a longer call, whose blend must follow this one's
+pt_status fused_launch(Job &j, uint32_t done)
+{
+    pt_ctx *ctx = j.ctx; pt_scene *s = j.s; pt_film *f = j.f; const pt_params *p = j.p;
+    hipStream_t st = ctx->stream;
+    RenderConst &rc = j.rc;
+    const TileView tv = ptw_tile_view(f, j.sel);
+    PT_TRY(redo_arm(j));
+    PT_HIP(ctx, hipMemsetAsync(f->work.d_count, 0, sizeof(uint32_t) * PTW_COUNT_WORDS, st));  // the slot counters (fused_kernel.h: eight, 128 B apart)
+    const uint32_t n_slots = rc.lanes_active * j.sh.groups * rc.slots_per_lane;  // (head + tail: the launch's head slots; its tail slots follow from rc)
+    const int mode = rc.tail ? 2 : (j.sh.groups > 1 ? 1 : 0);
+    FastDiv div_frames;
+    div_frames.init(std::max(rc.lanes_active, 1u));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (j.profile) PT_TRY(take_event_pair(j, j.ev_extend, e0, e1));
+    if (j.gd) {
+        PT_TRY(ptw_launch_fused_log(j.fp, mode, div_frames, rc, tv.d_tiles, j.rad, s, n_slots, f->work.d_count, ctx->d_stats, p->tmin, p->tmax, f->gd.d_log, st));
+        j.gd->launches++;
+    } else {
+        ptw_launch_fused(j.fp, mode, div_frames, rc, tv.d_tiles, j.rad, s, n_slots, f->work.d_count, ctx->d_stats, p->tmin, p->tmax, st, e0, e1);
     }
-    if (!nested) PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-    PT_HIP(ctx, hipStreamSynchronize(st));
     PT_HIP(ctx, hipGetLastError());
-    if (!nested) {
-        float ms = 0.f;
-        PT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
-        ctx->stats.ms_total += ms;
-        ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
-        ctx->stats.paths += (sel ? sel->pixels : ptw_valid_local_pixels(f, p)) * p->spp_per_frame * p->frame_count;
+    ctx->stats.launches_extend++;
+    ctx->stats.rounds++;
+    launch_resolve(f, rc, tv, j.rad, st, j.sh.bounded ? j.rad.overflow : nullptr);  // (leaves the film alone when the flag is up)
+    ctx->stats.launches_other++;
+    if (j.gd) {
+        // The launch's frames into the guide planes, timed by a pair of pooled events (the call is not profiled).  Queued here, before the overflow
+        // flag is looked at: a launch whose term log overflows still walks every path to its end, so its log is complete, and the redo --
+        // which numbers its slots by the one-group tile order, another list than a grouped launch's (film_work.hip) -- neither writes nor needs it.
+        hipEvent_t g0 = nullptr, g1 = nullptr;
+        PT_TRY(take_event_pair(j, j.ev_reduce, g0, g1));
+        PT_HIP(ctx, hipEventRecord(g0, st));
+        const uint32_t last = p->frame_count - 1u - done;  // the call's last frame, counted from this launch's first
+        ptg_launch_reduce(s, f, rc, tv.d_tiles, last, j.fp.inst_frame, st);
+        PT_HIP(ctx, hipGetLastError());
+        PT_HIP(ctx, hipEventRecord(g1, st));
+        ctx->stats.launches_other++;
     }
-    for (size_t i = 0; i + 1 < evs.size(); i += 2) {
-        float a = 0.f;
-        if (hipEventElapsedTime(&a, evs[i], evs[i + 1]) != hipSuccess) continue;
-        if (gd) gd->guide_ms += a;  // (a guided call is not profiled: the pairs are its reduce launches')
-        else ctx->stats.ms_extend += a;
+    bool redo = false;
+    PT_TRY(redo_check(j, redo));
+    return redo ? redo_batch(j) : PT_OK;
+}
+
+// ---- both pipelines: the frames of a render, batch by batch or launch by launch -----------------------------------------------------------------
+pt_status render_frames(Job &j)
+{
+    for (uint32_t done = 0; j.rc.n_slots > 0 && done < j.p->frame_count; done += j.sh.lanes) {
+        j.rc.frame_base = j.p->frame + (int32_t)done;
+        j.rc.lanes_active = std::min(j.sh.lanes, j.p->frame_count - done);
+        PT_TRY(j.fused ? fused_launch(j, done) : wavefront_batch(j));
     }
     return PT_OK;
+}
+// step 1 of a call, and all of pt_render_prepare's: shape and workspace (pt_stats: frames_in_flight, sample_groups, tail_samples, workspace_bytes)
+pt_status call_shape(Job &j, CallPlan &cp)
+{
+    if (j.fused) return fused_shape(j, cp);
+    const pt_status rc = ptw_shape_and_work(j.f, j.p, j.sh, launch_class(j.s, j.pl));
+    j.ctx->stats.frames_in_flight = j.sh.lanes;
+    j.ctx->stats.sample_groups = j.sh.groups;
+    if (rc == PT_OK) j.ctx->stats.workspace_bytes = ptw_workspace_bytes(j.f);
+    return rc;
+}
+// a call: shape and workspace, [the adaptive selection,] the render's set-up, its frames between ev_a and ev_b, the timed tail
+pt_status render_call(Job &j, CallPlan &cp)
+{
+    pt_ctx *ctx = j.ctx;
+    PT_TRY(call_shape(j, cp));
+    PT_TRY(fused_order_tiles(j));
+    if (j.ad) {  // pt_render_adaptive: the work is planned for the full list; the selection over it, then nothing but the selection
+        PT_TRY(ptad_select(j.f, j.ad->ap, ptw_tile_view(j.f, nullptr), &j.picked, &j.ad->res));
+        if (j.ad->dry || j.picked.n_tiles == 0) return PT_OK;
+        j.sel = &j.picked;
+    }
+    PT_TRY(j.fused ? fused_begin(j) : job_setup(j));
+    PT_HIP(ctx, hipEventRecord(ctx->ev_a, ctx->stream));
+    PT_TRY(render_frames(j));
+    return call_tail(j);
+}
+// The redo of one batch or launch of j (redo_arm): its frames as a render of their own with one sample group -- below the call's timing and stats, and
+// without PT_FLAG_PROFILE, which would re-record the caller's pooled events -- then back to the call's shape.
+pt_status redo_batch(Job &j)
+{
+    pt_ctx *ctx = j.ctx;
+    unsigned long long *const w = ctx->d_stats;
+    PT_HIP(ctx, hipMemcpy(w + PT_STAT_RAYS, w + PT_STAT_RAYS_SAVED, sizeof(*w), hipMemcpyDeviceToDevice));  // (the stream is idle: redo_check)
+    PT_HIP(ctx, hipMemcpy(w + PT_STAT_RAYS_CULLED, w + PT_STAT_RAYS_CULLED_SAVED, sizeof(*w), hipMemcpyDeviceToDevice));
+    PT_HIP(ctx, hipMemset(j.rad.overflow, 0, sizeof(*w)));
+    ctx->stats.redone_batches++;
+    Job r{};
+    r.s = j.s; r.f = j.f; r.ctx = ctx; r.sel = j.sel; r.pl = j.pl; r.fused = j.fused; r.fp = j.fp;
+    std::copy(j.rect, j.rect + 4, r.rect);
+    r.q = *j.p;
+    r.q.frame = j.rc.frame_base; r.q.frame_count = r.q.frames_in_flight = j.rc.lanes_active; r.q.sample_groups = 1;
+    r.q.flags &= ~(uint32_t)PT_FLAG_PROFILE;
+    r.p = &r.q;
+    PT_TRY(ptw_shape_and_work(r.f, r.p, r.sh, r.fused ? 3 : launch_class(r.s, r.pl), !r.fused));
+    PT_TRY(fused_order_tiles(r));
+    PT_TRY(r.fused ? fused_begin(r) : job_setup(r));
+    PT_TRY(render_frames(r));
+    if (j.gd) j.gd->launches++;
+    if (!r.async) {
+        PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        PT_HIP(ctx, hipGetLastError());
+    }
+    PT_TRY(ptw_ensure_work(j.f, j.p->rank, j.p->world, j.sh.lanes, j.sh.groups, j.sh.term_cap, j.sh.term_pcap, !j.fused, j.sh.tail));
+    return set_radiance(j);  // (the workspace only grows, but its buffers may have moved)
 }
 
 // PT_PIPELINE_AUTO (what pt_params_default returns): the reference's raygen shader is one invocation per pixel that owns its path
@@ -859,17 +875,17 @@ pt_status render_fused(pt_scene *s, pt_film *f, const pt_params *p_in, const Ext
 // Measured on one MI355X, Cornell box, spp 32, depth 8, three alternations, ms per frame wavefront NEE / fused NEE (Grays/s with the shadow rays):
 // 1080p 16 frames per call 14.90 / 10.40 (24.4 / 35.0); 1080p one blocking frame per call 26.06 / 12.94 (14.0 / 28.1); the reference's 1024 x 1024
 // launch, one blocking frame 18.0 / 8.33 (10.2 / 22.1) -- same frame-0 film.  Fused NEE is ahead at every shape: no shape rule.
-uint32_t resolve_pipeline(pt_scene *s, const pt_params *p, const ExtendPlan &pl)
+uint32_t resolve_pipeline(pt_scene *s, CallPlan &cp)
 {
+    const pt_params *p = &cp.p;
     const bool nee = (p->flags & PT_FLAG_NEE) != 0;
     if (nee && p->pipeline == PT_PIPELINE_WAVEFRONT) return PT_PIPELINE_WAVEFRONT_NEE;
     if (p->pipeline != PT_PIPELINE_AUTO) return p->pipeline;
     const uint32_t wavefront = nee ? PT_PIPELINE_WAVEFRONT_NEE : PT_PIPELINE_WAVEFRONT;
     if ((p->flags & (PT_FLAG_ASYNC | PT_FLAG_COUNT_VISITS)) || p->extend != PT_EXTEND_AUTO || p->width > 0xFFFFu || p->height > 0xFFFFu)
         return wavefront;
-    FusedPlan fp;
     const std::string keep = s->ctx->err;
-    const pt_status rc = ptw_plan_fused(s, pl, p->tmin, fp, nee);  // (NEE: refuses instanced scenes)
+    const pt_status rc = call_fused_plan(s, cp);  // (NEE: refuses instanced scenes; the plan stays with the call: fused_shape)
     if (rc != PT_OK) s->ctx->err = keep;  // (not an error of this call: the scene is simply not the fused kernel's)
     if (rc != PT_OK) return wavefront;
     if (nee) return PT_PIPELINE_FUSED;
@@ -880,12 +896,39 @@ uint32_t resolve_pipeline(pt_scene *s, const pt_params *p, const ExtendPlan &pl)
     // pt_internal.h) its shapes shrink until the fused kernel is ahead at every frame count (8 frames: 15.0 against 15.5 Grays/s,
     // profiles/r06e_mem_budget.log).  So the queues only where they are >= 15 % ahead AND the caller has raised the budget to what they
     // take: one frame per launch with >= 16 GB.
-    if (fp.inst) {
+    if (cp.fp.inst) {
         const uint32_t per_launch = p->frames_in_flight ? std::min(p->frames_in_flight, p->frame_count) : std::min(p->frame_count, 32u);
         const size_t budget = s->ctx->mem_budget;
         if (per_launch == 1u && (budget == 0 || budget >= ((size_t)16 << 30))) return PT_PIPELINE_WAVEFRONT;
     }
     return PT_PIPELINE_FUSED;
+}
+
+// What every entry begins with: the scene repaired, the params checked, the closest-hit kernel planned, the pipeline resolved (pt_stats.pipeline).
+// pt_render and pt_render_prepare repair first -- a repair may bring back the instance set a failed pt_scene_update parked.  pt_render_adaptive and
+// pt_render_guided, their own parameter struct validated, pass their rule about pt_params (-> why not, or null): tested behind check_params and
+// ahead of the repair, as they always tested it.
+using EntryRule = const char *(*)(const pt_params *);
+pt_status plan_call(pt_scene *s, pt_film *f, const pt_params *p_in, CallPlan &cp, EntryRule rule = nullptr)
+{
+    pt_ctx *ctx = s->ctx;
+    if (!rule && s->broken) PT_TRY(ptb_repair(s));
+    PT_TRY(check_params(s, f, p_in));
+    if (const char *why = rule ? rule(p_in) : nullptr) { ctx->err = why; return PT_ERR_UNSUPPORTED; }
+    if (rule && s->broken) PT_TRY(ptb_repair(s));
+    PT_TRY(ptw_plan_extend(s, p_in->extend, cp.pl));
+    cp.p = *p_in;
+    cp.p.pipeline = resolve_pipeline(s, cp);
+    ctx->stats.pipeline = cp.p.pipeline;
+    return PT_OK;
+}
+// the job of a planned call (the fused pipeline points p at its own shaped copy: fused_shape)
+Job make_job(pt_scene *s, pt_film *f, const CallPlan &cp)
+{
+    Job j{};
+    j.s = s; j.f = f; j.p = &cp.p; j.ctx = s->ctx; j.pl = cp.pl;
+    j.fused = cp.p.pipeline == PT_PIPELINE_FUSED;
+    return j;
 }
 
 }  // namespace
@@ -894,49 +937,28 @@ uint32_t resolve_pipeline(pt_scene *s, const pt_params *p, const ExtendPlan &pl)
 pt_status ptw_prepare(pt_scene *s, pt_film *f, const pt_params *p_in)
 {
     pt_ctx *ctx = s->ctx;
-    pt_status rc_ = s->broken ? ptb_repair(s) : PT_OK;  // first: a repair may bring back the instance set a failed pt_scene_update parked
-    if (rc_ != PT_OK) return rc_;
-    rc_ = check_params(s, f, p_in);
-    if (rc_ != PT_OK) return rc_;
-    ExtendPlan pl;
-    rc_ = ptw_plan_extend(s, p_in->extend, pl);
-    if (rc_ != PT_OK) return rc_;
-    pt_params p_res = *p_in;
-    p_res.pipeline = resolve_pipeline(s, p_in, pl);
-    const pt_params *p = &p_res;
-    ctx->stats.pipeline = p->pipeline;
-    if (p->pipeline == PT_PIPELINE_FUSED) return render_fused(s, f, p, pl, false, true);
-    RenderShape sh;
-    rc_ = ptw_shape_and_work(f, p, sh, launch_class(s, pl));
-    ctx->stats.frames_in_flight = sh.lanes;
-    ctx->stats.sample_groups = sh.groups;
-    if (rc_ != PT_OK) return rc_;
-    ctx->stats.workspace_bytes = ptw_workspace_bytes(f);
-    rc_ = ensure_schedule_objects(ctx, 3);
-    if (rc_ != PT_OK) return rc_;
+    CallPlan cp;
+    PT_TRY(plan_call(s, f, p_in, cp));
+    Job j = make_job(s, f, cp);
+    PT_TRY(call_shape(j, cp));
+    if (j.fused) return PT_OK;
+    const pt_params *p = &cp.p;
+    const RenderShape &sh = j.sh;
+    PT_TRY(ensure_schedule_objects(ctx, 3));
     if (p->flags & PT_FLAG_PROFILE) {  // the pooled (start, stop) events of every extend / shade launch of one batch (4 per round and pipeline)
         const size_t batches = ((size_t)p->frame_count + sh.lanes - 1) / sh.lanes;
-        rc_ = grow_event_pool(ctx, std::min<size_t>(4ull * sh.group_size * p->max_depth * 3ull * batches, 1u << 16));
-        if (rc_ != PT_OK) return rc_;
+        PT_TRY(grow_event_pool(ctx, std::min<size_t>(4ull * sh.group_size * p->max_depth * 3ull * batches, 1u << 16)));
     }
     return PT_OK;
 }
 
 pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p_in)
 {
-    pt_status rc_ = s->broken ? ptb_repair(s) : PT_OK;  // first: a repair may bring back the instance set a failed pt_scene_update parked
-    if (rc_ != PT_OK) return rc_;
-    rc_ = check_params(s, f, p_in);
-    if (rc_ != PT_OK) return rc_;
-    ExtendPlan pl;
-    rc_ = ptw_plan_extend(s, p_in->extend, pl);
-    if (rc_ != PT_OK) return rc_;
-    pt_params p_res = *p_in;
-    p_res.pipeline = resolve_pipeline(s, p_in, pl);
-    const pt_params *p = &p_res;
-    s->ctx->stats.pipeline = p->pipeline;
-    rc_ = p->pipeline == PT_PIPELINE_FUSED ? render_fused(s, f, p, pl, false, false) : render_wavefront(s, f, p, pl, false);
-    if (rc_ == PT_OK) f->m2.frames = (uint32_t)p->frame + p->frame_count;  // what the film and its second-moment plane now average
+    CallPlan cp;
+    PT_TRY(plan_call(s, f, p_in, cp));
+    Job j = make_job(s, f, cp);
+    const pt_status rc_ = render_call(j, cp);
+    if (rc_ == PT_OK) f->m2.frames = (uint32_t)p_in->frame + p_in->frame_count;  // what the film and its second-moment plane now average
     return rc_;
 }
 
@@ -957,20 +979,14 @@ pt_status ptw_render_adaptive(pt_scene *s, pt_film *f, const pt_params *p_in, co
     ad.ap = ap;
     ad.dry = p_in->frame_count == 0;
     if (ad.dry) p_res.frame_count = 1;  // (a dry run plans one frame's work: it needs the rank's tile list and nothing else)
-    pt_status rc_ = check_params(s, f, &p_res);
-    if (rc_ != PT_OK) return rc_;
-    if (p_in->flags & (PT_FLAG_ASYNC | PT_FLAG_PROFILE | PT_FLAG_COUNT_VISITS)) {
-        ctx->err = "pt_render_adaptive: not with PT_FLAG_ASYNC, PT_FLAG_PROFILE or PT_FLAG_COUNT_VISITS (the call reads the selection's count back)";
-        return PT_ERR_UNSUPPORTED;
-    }
-    rc_ = s->broken ? ptb_repair(s) : PT_OK;
-    if (rc_ != PT_OK) return rc_;
-    ExtendPlan pl;
-    rc_ = ptw_plan_extend(s, p_in->extend, pl);
-    if (rc_ != PT_OK) return rc_;
-    p_res.pipeline = resolve_pipeline(s, &p_res, pl);
-    ctx->stats.pipeline = p_res.pipeline;
-    rc_ = p_res.pipeline == PT_PIPELINE_FUSED ? render_fused(s, f, &p_res, pl, false, false, nullptr, &ad) : render_wavefront(s, f, &p_res, pl, false, nullptr, &ad);
+    CallPlan cp;
+    PT_TRY(plan_call(s, f, &p_res, cp, [](const pt_params *p) -> const char * {
+        const bool bad = (p->flags & (PT_FLAG_ASYNC | PT_FLAG_PROFILE | PT_FLAG_COUNT_VISITS)) != 0;
+        return bad ? "pt_render_adaptive: not with PT_FLAG_ASYNC, PT_FLAG_PROFILE or PT_FLAG_COUNT_VISITS (the call reads the selection's count back)" : nullptr;
+    }));
+    Job j = make_job(s, f, cp);
+    j.ad = &ad;
+    const pt_status rc_ = render_call(j, cp);
     if (rc_ == PT_OK && result) *result = ad.res;
     return rc_;
 }
@@ -984,38 +1000,26 @@ pt_status ptw_render_guided(pt_scene *s, pt_film *f, const pt_params *p_in, cons
     if (!f->aov.enabled) return pt_bad(ctx, "the film has no guide buffers: pt_film_enable_aov first");
     if (gp->mode > PT_GUIDED_TWO_CALLS) return pt_bad(ctx, "pt_guided_params.mode is none of PT_GUIDED_AUTO, _SINGLE_PASS, _TWO_CALLS");
     PT_TRY(pt_check_reserved(ctx, "pt_guided_params", gp->reserved));
-    pt_status rc_ = check_params(s, f, p_in);
-    if (rc_ != PT_OK) return rc_;
-    if (p_in->flags & ~(uint32_t)PT_FLAG_NEE) {
-        ctx->err = "pt_render_guided takes no flag but PT_FLAG_NEE: blocking, not instrumented (pt_render_aov's rule)";
-        return PT_ERR_UNSUPPORTED;
-    }
-    if (p_in->pipeline == PT_PIPELINE_WAVEFRONT_NEE) {
-        ctx->err = "pt_render_guided: PT_FLAG_NEE names the estimator (pt_render_aov takes PT_PIPELINE_WAVEFRONT, _FUSED or _AUTO)";
-        return PT_ERR_UNSUPPORTED;
-    }
-    rc_ = s->broken ? ptb_repair(s) : PT_OK;
-    if (rc_ != PT_OK) return rc_;
-    ExtendPlan pl;
-    rc_ = ptw_plan_extend(s, p_in->extend, pl);
-    if (rc_ != PT_OK) return rc_;
-    pt_params p_res = *p_in;
-    p_res.pipeline = resolve_pipeline(s, p_in, pl);
+    CallPlan cp;
+    PT_TRY(plan_call(s, f, p_in, cp, [](const pt_params *p) -> const char * {
+        if (p->flags & ~(uint32_t)PT_FLAG_NEE) return "pt_render_guided takes no flag but PT_FLAG_NEE: blocking, not instrumented (pt_render_aov's rule)";
+        const bool nee_by_pipeline = p->pipeline == PT_PIPELINE_WAVEFRONT_NEE;
+        return nee_by_pipeline ? "pt_render_guided: PT_FLAG_NEE names the estimator (pt_render_aov takes PT_PIPELINE_WAVEFRONT, _FUSED or _AUTO)" : nullptr;
+    }));
     // the single pass: where a fused kernel renders these params and pt_render_aov's fused or queue form would serve them too
-    bool single = gp->mode != PT_GUIDED_TWO_CALLS && p_res.pipeline == PT_PIPELINE_FUSED && p_in->extend == PT_EXTEND_AUTO && p_in->width <= 0xFFFFu &&
+    bool single = gp->mode != PT_GUIDED_TWO_CALLS && cp.p.pipeline == PT_PIPELINE_FUSED && p_in->extend == PT_EXTEND_AUTO && p_in->width <= 0xFFFFu &&
                   p_in->height <= 0xFFFFu;
     const char *why = "pt_render would not run a fused kernel for these params (PT_GUIDED_AUTO takes the two calls)";
     if (single) {  // (PT_PIPELINE_FUSED by name: the scene has to be of the fused kernels' class)
-        FusedPlan fp;
         const std::string keep = ctx->err;
-        single = ptw_plan_fused(s, pl, p_in->tmin, fp, (p_in->flags & PT_FLAG_NEE) != 0) == PT_OK;
+        single = call_fused_plan(s, cp) == PT_OK;
         ctx->err = keep;
     }
     // the log: the frames per launch pt_render would take, or as many as fit beside its workspace (planned again for fewer: at most twice)
     bool have_log = false;
     for (int pass = 0; single && !have_log && pass < 4; pass++) {
-        rc_ = render_fused(s, f, &p_res, pl, false, true);
-        if (rc_ != PT_OK) return rc_;
+        Job shape = make_job(s, f, cp);
+        PT_TRY(fused_shape(shape, cp));
         const uint32_t lanes = std::max(ctx->stats.frames_in_flight, 1u);
         const size_t per_frame = (size_t)f->work.n_tiles * 64 * p_in->spp_per_frame;  // records
         if (per_frame == 0) { have_log = true; break; }  // (a rank without tiles: nothing is launched)
@@ -1024,7 +1028,7 @@ pt_status ptw_render_guided(pt_scene *s, pt_film *f, const pt_params *p_in, cons
         if (fit == 0) { single = false; why = "pt_render_guided: not one frame of the first-hit log fits the memory budget"; break; }
         if (fit < lanes) {  // (equal launches, as pt_render batches its frames: 16 frames where 15 fit are 8 + 8)
             const size_t batches = (p_in->frame_count + fit - 1) / fit;
-            p_res.frames_in_flight = (uint32_t)std::min<size_t>(fit, (p_in->frame_count + batches - 1) / batches);
+            cp.p.frames_in_flight = (uint32_t)std::min<size_t>(fit, (p_in->frame_count + batches - 1) / batches);
             continue;
         }
         const std::string keep = ctx->err;
@@ -1038,19 +1042,18 @@ pt_status ptw_render_guided(pt_scene *s, pt_film *f, const pt_params *p_in, cons
     if (single && !have_log) { single = false; why = "pt_render_guided: the first-hit log does not fit beside the render workspace"; }
     if (!single && gp->mode == PT_GUIDED_SINGLE_PASS) { ctx->err = why; return PT_ERR_UNSUPPORTED; }
     if (single) {
-        ctx->stats.pipeline = PT_PIPELINE_FUSED;
         GuidedCall gd;
-        rc_ = render_fused(s, f, &p_res, pl, false, false, nullptr, nullptr, &gd);
-        if (rc_ != PT_OK) return rc_;
+        Job j = make_job(s, f, cp);
+        j.gd = &gd;
+        PT_TRY(render_call(j, cp));
         f->m2.frames = (uint32_t)p_in->frame + p_in->frame_count;
         if (result) { result->single_pass = 1; result->launches = gd.launches; result->guide_ms = gd.guide_ms; }
         return PT_OK;
     }
-    rc_ = ptw_render(s, f, p_in);
-    if (rc_ != PT_OK) return rc_;
+    PT_TRY(ptw_render(s, f, p_in));
     const uint32_t rendered_by = ctx->stats.pipeline;
     const float ms_before = ctx->stats.ms_total;
-    rc_ = pta_render(s, f, p_in);
+    const pt_status rc_ = pta_render(s, f, p_in);
     ctx->stats.pipeline = rendered_by;
     if (rc_ == PT_OK && result) result->guide_ms = ctx->stats.ms_total - ms_before;
     return rc_;

@@ -78,8 +78,8 @@ __global__ __launch_bounds__(TB) void k_generate(RenderConst rc, const uint32_t 
     if (rc.cull_on) {  // (uniform: every thread of the block is here)
         for (int o = 32; o > 0; o >>= 1) n_culled += (uint32_t)__shfl_xor((int)n_culled, o, 64);
         if ((threadIdx.x & 63u) == 0u && n_culled) {
-            atomicAdd(stats, (unsigned long long)n_culled);        // pt_stats.rays
-            atomicAdd(stats + 19, (unsigned long long)n_culled);   // pt_stats.rays_culled
+            atomicAdd(stats + PT_STAT_RAYS, (unsigned long long)n_culled);        // pt_stats.rays
+            atomicAdd(stats + PT_STAT_RAYS_CULLED, (unsigned long long)n_culled);   // pt_stats.rays_culled
         }
     }
 }

@@ -7,7 +7,8 @@
 //   aov.hip             pt_render_aov: the guide buffers' kernels, plan and launch
 //   adaptive.hip        pt_render_adaptive: the selection of the tiles a render runs over, and the resolve that blends by a pixel's own count
 //   film_work.hip       the film's workspace: how many slots a render gets (RenderShape) and the buffers behind them
-//   render.hip          pt_render / pt_render_prepare / pt_trace: batches, pipelines on streams, rounds, polls, redo
+//   render.hip          pt_render / _prepare / _adaptive / _guided / pt_trace: one CallPlan (pipeline resolved, kernels planned once) and one Job per call;
+//                       wavefront: batches, pipelines on streams, rounds, polls; fused: shape, launches; shared: redo, selection, radiance record, timed tail
 //
 // Kernels are launched from the translation unit that defines them, so each unit exports small launchers; what crosses
 // the units is plain data (wavefront_types.h) and the structs below.  Inside a unit every kernel family has ONE picker
@@ -155,18 +156,20 @@ struct FusedPlan {
     uint32_t n_tlas_lds = 0;             // ... its TLAS nodes staged in LDS
     uint32_t *spill = nullptr;           // ... its stack entries beyond lds_stack: [levels][grid * block] dwords of the context's spill area
     const float4 *inst_frame = nullptr;  // ... the (instance, triangle) normal + tangent table, or null
+    int enter_min = 12, leaf_min = 14, node_yield = 6;  // ... the waiting rules of its walk (fused.hip plan_fused_inst)
 };
 pt_status ptw_plan_fused(pt_scene *s, const ExtendPlan &pl, float tmin, FusedPlan &fp, bool nee = false);
-void ptw_launch_fused(const FusedPlan &fp, bool grouped, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad,
+// mode: 0 one sample group, 1 several, 2 head + tail slots; div_frames: by rc.lanes_active, chunk -> (tile, frame) of one group's hand-out order (fused_kernel.h)
+void ptw_launch_fused(const FusedPlan &fp, int mode, const ptw::FastDiv &div_frames, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad,
                       const pt_scene *s, uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax,
                       hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 // fused_guided.hip: the same launch by the kernels that also write the first-hit log (pt_render_guided; guided_kernel.h has the log's layout)
-pt_status ptw_launch_fused_log(const FusedPlan &fp, bool grouped, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, const pt_scene *s,
+pt_status ptw_launch_fused_log(const FusedPlan &fp, int mode, const ptw::FastDiv &div_frames, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, const pt_scene *s,
                                uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax, uint2 *log, hipStream_t st);
 // guided.hip: the records of the launch's frames folded into the film's guide planes (id_frame: the frame of the launch that is the call's last, or
 // >= rc.lanes_active); inst_frame: FusedPlan::inst_frame
 void ptg_launch_reduce(const pt_scene *s, pt_film *f, const ptw::RenderConst &rc, const uint32_t *tiles, uint32_t id_frame, const float4 *inst_frame, hipStream_t st);
-// What pt_render_guided hands down to render_fused (render.hip): every launch writes the film's log and is followed by the reduce.
+// What pt_render_guided hands down to the fused pipeline (render.hip Job::gd): every launch writes the film's log and is followed by the reduce.
 struct GuidedCall {
     uint32_t launches = 0;              // fused launches of the call
     float guide_ms = 0.f;               // device time of the reduce launches
