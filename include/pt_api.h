@@ -763,6 +763,76 @@ typedef struct pt_hit {
 pt_status pt_trace(pt_scene *scene, const float *rays6, uint32_t n, float tmin, float tmax,
                    uint32_t extend /* PT_EXTEND_* */, pt_hit *hits);
 
+/* ---- ray queries on device buffers: closest hit, any hit, the surface at the hit ------------------------------------------------------
+ * pt_trace_device(scene, desc, n, device_ms) answers n rays that already lie in DEVICE memory (a torch tensor's data_ptr()) into DEVICE memory:
+ * no host loop, no copy, no allocation after the first call.  The rays are repacked by a kernel into the queue layout of the extend kernels the
+ * renderer uses, walked in chunks of desc.chunk_rays by the kernel pt_trace would take for desc.extend (every scene class: LDS, HBM, the 8-wide
+ * tree, both two-level kernels), and the hit records are turned into the caller's arrays by kernels again.  pt_trace is untouched.
+ *
+ *   PT_TRACE_CLOSEST  d_hits[i] is byte for byte what pt_trace returns for ray i with the same tmin, tmax and extend (instanced scenes too: inst,
+ *                     ties to the lowest (instance, primitive)).  d_hits may be NULL when only the surface record is wanted.  d_tmax must be
+ *                     NULL: PT_ERR_UNSUPPORTED otherwise -- the kernels' per-ray bound belongs to their any-hit instantiations, which end a walk
+ *                     at the FIRST hit below the bound, and no closest-hit instantiation reads a per-ray bound.
+ *   PT_TRACE_ANY      d_occluded[i] = 1 exactly when the closest-hit query of ray i with the ray's bound as tmax finds a triangle (tmin < t < bound,
+ *                     opaque, no culling), else 0.  The bound is d_tmax[i], or desc.tmax for every ray when d_tmax is NULL (the call then fills its
+ *                     bound plane with it).  Runs the any-hit instantiations (the NEE pipeline's shadow-ray kernels), which stop at the first hit.
+ *                     d_hits and the four surface pointers must be NULL.
+ *
+ * The surface record (PT_TRACE_CLOSEST; each of the four planes n x 3 floats, dense, any may be NULL) is what closesthit.rchit:50-65 computes at
+ * the hit, in binary32 with every operation rounded on its own (no contraction, denormals kept), A B C the hit triangle's vertices, (u, v) the
+ * hit's attributes:
+ *   d_position  b0 = (1 - u) - v, then per component P = (A * b0 + B * u) + C * v.  Instanced scenes: per row (m0 m1 m2 m3) of the instance's
+ *               3x4 object->world matrix the component becomes ((m0 * P.x + m1 * P.y) + m2 * P.z) + m3.
+ *   d_normal    the triangle's shading normal -normalize(cross(B - A, C - A)), never flipped towards the ray: the per-sample value PT_AOV_NORMAL
+ *               averages.  Instanced scenes: in world space -- the inverse transpose of the instance's matrix applied as
+ *               (i0 * n.x + i1 * n.y) + i2 * n.z per component and renormalised by a correctly rounded square root and divide, or the same
+ *               value read from the per-(instance, triangle) table where the context keeps one (pt_tuning.inst_frames).
+ *   d_albedo    the face's Kd (not Kd / pi: PT_AOV_ALBEDO's convention).
+ *   d_emission  the face's Ke.
+ * A ray that misses gets +0.0 in all three components of every plane.  All five CLOSEST outputs NULL is PT_ERR_INVALID_ARG.
+ *
+ * Execution.  Everything runs on the context's stream, behind the work already queued there (pt_scene_update's rule: a query queued before an
+ * update sees the old geometry).  The call blocks unless PT_TRACE_ASYNC is set; with the flag it only queues, pt_sync waits, the inputs have to
+ * stay valid and the outputs are defined only after that wait.  *device_ms (nullable): first kernel to last kernel; 0, and no event is touched,
+ * under PT_TRACE_ASYNC.  pt_stats: launches_extend grows by the number of chunks, ms_extend by the extend kernels' own time (blocking calls only),
+ * launches_other by the pack and unpack launches; rays and paths stay (they count a render's rays and samples).  A scene that lost its trees is
+ * repaired first, as pt_trace does.  NaN rays behave as in pt_trace; a NaN bound is outside the contract.  n == 0 is PT_OK and launches nothing.  n is 64-bit: a tensor of
+ * rays can exceed 2^32 bytes; chunk_rays bounds the workspace, not n.
+ *
+ * Workspace: a chunk's rays, hit records and bound plane, 48 B per ray of min(chunk_rays, n rounded up to 64), belong to the CONTEXT: made by the
+ * first call, only growing (a second call with the same or a smaller chunk allocates nothing), counted against pt_tuning.mem_budget_mb
+ * (PT_ERR_OOM when a chunk does not fit: nothing is launched, the context stays usable and a smaller chunk_rays works), freed by pt_ctx_destroy.
+ * pt_trace_workspace_bytes reports the bytes held.  PT_TRACE_DEFAULT_CHUNK_RAYS is 2^22 rays (192 MiB, and only for queries that large): of the
+ * chunks 2^16 .. 2^22 swept on the MI355X over 2^24 rays (scripts/probe_trace_device.py, profiles/trace_device_probe.json) the largest was the
+ * fastest on both scenes and no smaller one lay within its spread -- Cornell box 0.68 ms at 2^20, 0.52 at 2^21, 0.45 at 2^22; 1 M-triangle soup
+ * 7.7 / 5.4 / 4.4 ms: every chunk ends in a tail in which the extend kernel's persistent waves run out of rays.  Nothing beyond 2^22 was swept
+ * (DESIGN.md section 22).
+ *
+ * Refusals, with nothing launched and nothing written -- PT_ERR_INVALID_ARG: NULL scene or desc; NULL d_rays6 with n > 0; an unknown mode or
+ * flag; a nonzero reserved word; tmin or tmax not finite, or tmax <= tmin; PT_TRACE_CLOSEST with all of d_hits and the surface pointers NULL or
+ * with d_occluded set; PT_TRACE_ANY with d_occluded NULL or with d_hits or a surface pointer set; an unknown extend value.  PT_ERR_UNSUPPORTED:
+ * d_tmax with PT_TRACE_CLOSEST; PT_EXTEND_FLAT and the variants the scene has no tree for (pt_trace's rules).                                */
+enum { PT_TRACE_CLOSEST = 0, PT_TRACE_ANY = 1 };
+enum { PT_TRACE_ASYNC = 1u };
+#define PT_TRACE_DEFAULT_CHUNK_RAYS (1u << 22)
+typedef struct pt_trace_desc {
+    const void *d_rays6;     /* DEVICE, n x {origin.xyz, direction.xyz} f32, dense, 4-byte aligned */
+    const void *d_tmax;      /* DEVICE n f32 per-ray upper bound (PT_TRACE_ANY), or NULL: `tmax` for every ray */
+    void *d_hits;            /* CLOSEST: DEVICE n x pt_hit (20 B), may be NULL */
+    void *d_occluded;        /* ANY: DEVICE n x uint8, 1 = some triangle with tmin < t < bound */
+    void *d_position, *d_normal, *d_albedo, *d_emission;  /* CLOSEST: DEVICE n x 3 f32 each, any may be NULL */
+    float tmin, tmax;
+    uint32_t mode;           /* PT_TRACE_* */
+    uint32_t extend;         /* PT_EXTEND_*, pt_trace's rules */
+    uint32_t flags;          /* PT_TRACE_ASYNC or 0 */
+    uint32_t chunk_rays;     /* rays per launch; 0 = PT_TRACE_DEFAULT_CHUNK_RAYS; rounded up to a multiple of 64 */
+    uint32_t reserved[4];    /* must be 0 */
+} pt_trace_desc;             /* 104 bytes */
+void pt_trace_desc_default(pt_trace_desc *d);   /* pointers NULL, tmin 0.001, tmax 10000, CLOSEST, AUTO */
+pt_status pt_trace_device(pt_scene *scene, const pt_trace_desc *desc, uint64_t n, float *device_ms /* may be NULL */);
+/* the device bytes the context holds for pt_trace_device (0 before the first call) */
+pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes);
+
 /* ---- multi-GPU: assembling the presented image of a tile-sharded render ---------- */
 /* The reference renders on physical device 0 (main.cpp:105) and copies its storage image to the swapchain
  * (main.cpp:661-667).  Here N ranks -- processes or host threads, one context and one GPU each -- render the

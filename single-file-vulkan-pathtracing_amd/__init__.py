@@ -132,6 +132,18 @@ class AdaptiveResult(C.Structure):
                 ("select_ms", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+TRACE_CLOSEST, TRACE_ANY = 0, 1   # include/pt_api.h PT_TRACE_*: the query pt_trace_device answers
+TRACE_ASYNC = 1                   # ... PT_TRACE_ASYNC: queue only, Context.sync() waits
+
+
+class TraceDesc(C.Structure):
+    """include/pt_api.h pt_trace_desc: a ray query on device buffers (pt_trace_device)."""
+    _fields_ = [("d_rays6", C.c_void_p), ("d_tmax", C.c_void_p), ("d_hits", C.c_void_p), ("d_occluded", C.c_void_p),
+                ("d_position", C.c_void_p), ("d_normal", C.c_void_p), ("d_albedo", C.c_void_p), ("d_emission", C.c_void_p),
+                ("tmin", C.c_float), ("tmax", C.c_float), ("mode", C.c_uint32), ("extend", C.c_uint32), ("flags", C.c_uint32),
+                ("chunk_rays", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
 GUIDED_AUTO = 0          # include/pt_api.h PT_GUIDED_*: which form pt_render_guided takes
 GUIDED_SINGLE_PASS = 1
 GUIDED_TWO_CALLS = 2
@@ -196,7 +208,8 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_film_reproject_motion", "pt_denoise_history_params_default", "pt_film_denoise_history",
                "pt_upsample_params_default", "pt_film_upsample", "pt_film_read_upsampled",
                "pt_film_enable_counts", "pt_film_read_counts", "pt_adaptive_params_default", "pt_render_adaptive",
-               "pt_guided_params_default", "pt_render_guided"]
+               "pt_guided_params_default", "pt_render_guided",
+               "pt_trace_desc_default", "pt_trace_device", "pt_trace_workspace_bytes"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium", "pth_self_leaf_rule", "pth_self_leaf_c1", "pth_self_leaf_skip"]
 
@@ -299,6 +312,11 @@ def lib_amd():
             L.pt_guided_params_default.restype = None
             L.pt_render_guided.argtypes = [vp, vp, C.POINTER(Params), C.POINTER(GuidedParams), C.POINTER(GuidedResult)]
         L.pt_trace.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, vp]
+        if hasattr(L, "pt_trace_device"):   # (ray queries on device buffers; dev A/B runs load older builds through PT_LIB_AMD)
+            L.pt_trace_desc_default.argtypes = [C.POINTER(TraceDesc)]
+            L.pt_trace_desc_default.restype = None
+            L.pt_trace_device.argtypes = [vp, C.POINTER(TraceDesc), C.c_uint64, C.POINTER(C.c_float)]
+            L.pt_trace_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
         if hasattr(L, "pt_get_block_counts"):   # (API version 6; dev A/B runs load older builds through PT_LIB_AMD)
@@ -506,6 +524,10 @@ def reproject_default_params():
     return _default_params(ReprojectParams, "pt_reproject_params_default")
 
 
+def trace_default_desc():
+    return _default_params(TraceDesc, "pt_trace_desc_default")
+
+
 def motion_default_params():
     return _default_params(MotionParams, "pt_motion_params_default")
 
@@ -551,6 +573,12 @@ class Context:
 
     def reset_stats(self):
         self._check(lib_amd().pt_reset_stats(self.h))
+
+    def trace_workspace_bytes(self):
+        """Device bytes the context holds for Scene.trace_device / trace_tensors (pt_trace_workspace_bytes): 0 before the first call."""
+        n = C.c_uint64(0)
+        self._check(lib_amd().pt_trace_workspace_bytes(self.h, C.byref(n)))
+        return n.value
 
     def block_counts(self):
         """{block: (wave executions, lanes inside)} of the instrumented fused kernel since reset_stats (pt_get_block_counts; render with
@@ -646,6 +674,54 @@ class Scene:
         hits = np.zeros(r.shape[0], dtype=HIT_DTYPE)
         self.ctx._check(lib_amd().pt_trace(self.h, r.ctypes.data, r.shape[0], tmin, tmax, extend, hits.ctypes.data))
         return hits
+
+    def trace_device(self, n, rays_ptr, tmax_ptr=None, hits_ptr=None, occluded_ptr=None, position_ptr=None, normal_ptr=None, albedo_ptr=None,
+                     emission_ptr=None, mode=TRACE_CLOSEST, tmin=0.001, tmax=10000.0, extend=EXTEND_AUTO, flags=0, chunk_rays=0):
+        """pt_trace_device over raw DEVICE pointers (include/pt_api.h has the layouts): n rays at rays_ptr, the outputs the mode allows.
+        -> device_ms (0 under TRACE_ASYNC: the call only queues, Context.sync() waits)."""
+        d = trace_default_desc()
+        d.d_rays6, d.d_tmax, d.d_hits, d.d_occluded = rays_ptr, tmax_ptr, hits_ptr, occluded_ptr
+        d.d_position, d.d_normal, d.d_albedo, d.d_emission = position_ptr, normal_ptr, albedo_ptr, emission_ptr
+        d.tmin, d.tmax, d.mode, d.extend, d.flags, d.chunk_rays = tmin, tmax, mode, extend, flags, chunk_rays
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_trace_device(self.h, C.byref(d), n, C.byref(ms)))
+        return ms.value
+
+    def trace_tensors(self, rays, tmax_per_ray=None, mode=TRACE_CLOSEST, surface=False, tmin=0.001, tmax=10000.0, extend=EXTEND_AUTO, chunk_rays=0):
+        """Ray queries on torch tensors, nothing through the host.  rays: float32 CUDA tensor [n, 6] {origin, direction} (made contiguous if it
+        is not).  TRACE_CLOSEST -> dict of tensors: prim (int32, -1 = miss), t, u, v (float32), inst (int32) -- views of one [n, 5] buffer in
+        pt_hit's layout, no copy -- and, with surface, position / normal / albedo / emission [n, 3].  TRACE_ANY -> bool tensor [n], True = some
+        triangle with tmin < t < bound; the bound is tmax_per_ray[i] (float32 CUDA tensor [n]) or tmax."""
+        import torch
+        if rays.dtype != torch.float32 or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be a float32 CUDA tensor of shape [n, 6]")
+        rays = rays.contiguous()
+        n, dev = rays.shape[0], rays.device
+        bound = None
+        if tmax_per_ray is not None:
+            if tmax_per_ray.dtype != torch.float32 or tmax_per_ray.device != dev or tmax_per_ray.numel() != n:
+                raise ValueError("tmax_per_ray must be a float32 tensor of n elements on the rays' device")
+            bound = tmax_per_ray.contiguous()
+        kw = dict(tmax_ptr=bound.data_ptr() if bound is not None else None, mode=mode, tmin=tmin, tmax=tmax, extend=extend, chunk_rays=chunk_rays)
+        # The rays (and the outputs' allocations) were produced on torch's current stream; the query runs on the context's.  So torch's stream is
+        # drained first.  The call itself is blocking -- it returns after the context's stream has finished -- which orders the outputs before
+        # whatever torch queues next.  (No TRACE_ASYNC here: torch would have no event to wait on.)
+        if mode == TRACE_ANY:
+            occ = torch.empty(n, dtype=torch.uint8, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self.trace_device(n, rays.data_ptr(), occluded_ptr=occ.data_ptr(), **kw)
+            return occ.view(torch.bool)
+        hits = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        hits_f = hits.view(torch.float32)   # the same memory: pt_hit is {u32, f32, f32, f32, u32}
+        out = {"prim": hits[:, 0], "t": hits_f[:, 1], "u": hits_f[:, 2], "v": hits_f[:, 3], "inst": hits[:, 4]}
+        planes = {}
+        if surface:
+            for name in ("position", "normal", "albedo", "emission"):
+                out[name] = torch.empty((n, 3), dtype=torch.float32, device=dev)
+                planes[name + "_ptr"] = out[name].data_ptr()
+        torch.cuda.current_stream(dev).synchronize()
+        self.trace_device(n, rays.data_ptr(), hits_ptr=hits.data_ptr(), **planes, **kw)
+        return out
 
     def close(self):
         if self.h:

@@ -159,6 +159,7 @@ void pt_ctx_destroy(pt_ctx *ctx)
     if (ctx->d_rad) (void)hipFree(ctx->d_rad);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->d_spill) (void)hipFree(ctx->d_spill);
+    ptt_free(ctx);
     if (ctx->ev_a) (void)hipEventDestroy(ctx->ev_a);
     if (ctx->ev_b) (void)hipEventDestroy(ctx->ev_b);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -658,6 +659,31 @@ pt_status pt_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, floa
     if (n && (!rays6 || !hits)) { s->ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
     PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
     return guarded(s->ctx, [&] { return ptw_trace(s, rays6, n, tmin, tmax, extend, hits); });
+}
+
+void pt_trace_desc_default(pt_trace_desc *d)
+{
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    d->tmin = 0.001f;
+    d->tmax = 10000.0f;
+    d->mode = PT_TRACE_CLOSEST;
+    d->extend = PT_EXTEND_AUTO;
+}
+
+pt_status pt_trace_device(pt_scene *s, const pt_trace_desc *d, uint64_t n, float *device_ms)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    if (!d) return pt_bad(s->ctx, "null argument");
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return ptt_trace_device(s, d, n, device_ms); });
+}
+
+pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes)
+{
+    if (!ctx || !bytes) return PT_ERR_INVALID_ARG;
+    *bytes = ctx->tr.bytes;
+    return PT_OK;
 }
 
 pt_status pt_device_alloc(pt_ctx *ctx, size_t bytes, void **out)

@@ -72,6 +72,16 @@ struct pt_ctx {
     // call per frame should not pay seven runtime calls for the same plan every time
     size_t fused_smem[3] = { 0, 0, 0 };  // key: LDS bytes << 1 | pair-leaf kernel
     int fused_per_cu[3] = { 0, 0, 0 };
+    // pt_trace_device (trace_device.hip): one chunk of rays in the extend kernels' queue layout, their hit records and the any-hit kernels' bound
+    // plane.  The context's scratch, made by the first call; it only grows, counts against mem_budget and is freed by pt_ctx_destroy.
+    struct Trace {
+        float4 *d_rayA = nullptr; float2 *d_rayB = nullptr;        // {origin.xyz, direction.x} {direction.y, direction.z}
+        float4 *d_hit = nullptr; uint32_t *d_hit_inst = nullptr;   // {bits(pos), t, u, v}; the instance's TLAS leaf position
+        float *d_bound = nullptr;                                  // PT_TRACE_ANY: ray_tmax
+        uint32_t *d_count = nullptr;                               // [2]: the chunk's ray count (what the extend kernels read), a spare word
+        size_t cap = 0;                                            // rays the per-ray arrays hold
+        size_t bytes = 0;                                          // device bytes of all of the above
+    } tr;
 };
 // The workspace budget a context plans within when the caller names none: 8 GB.  Round 6, one MI355X, Grays/s at 2 / 4 / 8 / 16 / 32 GB / no
 // bound: the 10 000-instance grid through the queues 13.6 / 15.0 / 15.0 / 15.1 / 15.4 / 15.3 (the fused kernel 15.5 in 0.6 GB at every budget);
@@ -407,6 +417,9 @@ pt_status ptw_render(pt_scene *s, pt_film *f, const pt_params *p);
 pt_status ptw_prepare(pt_scene *s, pt_film *f, const pt_params *p);
 pt_status ptw_trace(pt_scene *s, const float *rays6, uint32_t n, float tmin, float tmax, uint32_t extend, pt_hit *hits);
 void ptw_free_work(pt_film *f);
+// trace_device.hip: pt_trace_device (validates everything but the null scene / desc) and the context's workspace behind it
+pt_status ptt_trace_device(pt_scene *s, const pt_trace_desc *d, uint64_t n, float *device_ms);
+void ptt_free(pt_ctx *ctx);
 // aov.hip: guide buffers of the first hit
 pt_status pta_enable(pt_film *f, void *const *device_planes);
 pt_status pta_render(pt_scene *s, pt_film *f, const pt_params *p);

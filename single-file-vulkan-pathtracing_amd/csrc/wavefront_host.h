@@ -6,6 +6,7 @@
 //   fused.hip           PT_PIPELINE_FUSED: k_fused (fused_kernel.h), its plan and its launcher
 //   aov.hip             pt_render_aov: the guide buffers' kernels, plan and launch
 //   adaptive.hip        pt_render_adaptive: the selection of the tiles a render runs over, and the resolve that blends by a pixel's own count
+//   trace_device.hip    pt_trace_device: rays in device memory packed into the queues, the extend launch per chunk, hit records into the caller's arrays
 //   film_work.hip       the film's workspace: how many slots a render gets (RenderShape) and the buffers behind them
 //   render.hip          pt_render / _prepare / _adaptive / _guided / pt_trace: one CallPlan (pipeline resolved, kernels planned once) and one Job per call;
 //                       wavefront: batches, pipelines on streams, rounds, polls; fused: shape, launches; shared: redo, selection, radiance record, timed tail
