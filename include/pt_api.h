@@ -46,8 +46,9 @@ typedef struct pt_film pt_film;   /* replaces the storage Image (main.cpp:481-48
  *         keeps ownership of a stream it passes in.                                        */
 pt_status pt_ctx_create(int device, void *stream, pt_ctx **out);
 void pt_ctx_destroy(pt_ctx *ctx);
-/* Tuning knobs of a context: launch shapes and kernel choices that change SPEED, never results (every combination is
- * covered by the bit-exact parity tests).  -1 = the built-in choice, which is what was measured best on MI355X
+/* Tuning knobs of a context: launch shapes and kernel choices that change SPEED, never results (every knob is set off
+ * its default by a bit-exact parity test, and tests/test_tuning_knobs.py fails when a new one is not; of the COMBINATIONS
+ * only those the tests name are covered).  -1 = the built-in choice, which is what was measured best on MI355X
  * (DESIGN.md section 6 has the numbers).  pt_ctx_create fills the defaults and then applies the environment variable
  * PT_TUNE once ("name=value,name=value", names as below) -- the library reads no other tuning from the environment,
  * and nothing at all inside pt_render.  Set before pt_scene_create (pair_leaves is read when a scene's BVH4 is built). */

@@ -258,7 +258,8 @@ def test_refit_that_breaks_a_pair_leaf(pt, orc, gpu_ctx, cornell_arrays):
 
 @pytest.mark.gpu
 def test_refit_of_a_big_scene(pt, orc, gpu_ctx):
-    """> 2048 triangles: the PLOC tree's collapse, its 64-B top-down copy and the 8-wide nodes refitted in place."""
+    """> 2048 triangles: the LBVH's collapse (this uniform soup's PLOC rebuild is not adopted, area ratio 0.988; tests/test_ploc_trees.py
+    refits adopted trees), its 64-B top-down copy and the 8-wide nodes refitted in place."""
     from test_gpu_parity import _check_bvh8
     v, i, f = _soup(3000, 21, spread=0.05)
     v = (v.reshape(-1, 3) * np.float32([0.9, 0.9, 0.9]) + np.float32([0, -1, 0])).reshape(-1).astype(np.float32)
