@@ -834,6 +834,73 @@ pt_status pt_trace_device(pt_scene *scene, const pt_trace_desc *desc, uint64_t n
 /* the device bytes the context holds for pt_trace_device (0 before the first call) */
 pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes);
 
+/* ---- path-traced radiance for caller-supplied rays ------------------------------------------------------------------------------------
+ * pt_radiance_device(scene, desc, n, device_ms) answers "what radiance arrives along these rays?" for n rays that lie in DEVICE memory, into
+ * DEVICE memory: the estimator of pt_render started from the caller's rays instead of the camera of raygen.rgen:51-57 -- a perspective,
+ * fisheye or thin-lens camera, a light probe, a bake, a batch of training rays.  The rays are put into the path queues of the wavefront
+ * pipeline by a kernel; the extend, shade and shadow kernels pt_render runs (every scene class: LDS, HBM, the 8-wide tree, both two-level
+ * kernels) carry the paths, one slot per (ray, sample); a kernel reduces the samples into the caller's arrays.  pt_render is untouched.
+ *
+ * Arithmetic: binary32, every operation rounded on its own, no contraction, denormals kept.  For ray i and sample s = 0 .. spp-1:
+ *   Seed    with d_seeds: d_seeds[i*spp + s], verbatim.  Otherwise a + b (mod 2^32) with (a, b) = pcg2d((uint32)(i + index_base), m)
+ *           (common.glsl:21-31) and m = s + (uint32)((int32)spp * frame) + 1, make_seed's m.  i is the ray's position in the whole call,
+ *           never its position in a chunk.
+ *   Path    sample s owns an accumulator c_s that starts at +0; weight = 1; the ray is ray i, taken as given (not normalised, as pt_trace
+ *           takes it) and the same for every sample: the caller supplies jitter by supplying more rays.  From there the loop is
+ *           raygen.rgen:62-83 exactly as pt_render runs it from a camera ray: a miss adds weight * env and ends the path; a hit adds
+ *           weight * Ke (with PT_RADIANCE_NEE at depth 0 only); with PT_RADIANCE_NEE the hit then takes the light sample and shadow ray of
+ *           PT_PIPELINE_WAVEFRONT_NEE (three random numbers, drawn before the bounce's two; none at the path's last hit); the bounce follows.
+ *   Reduce  C = +0; for s ascending C = C + c_s; mean = C / (float)spp.  d_moment2 the same over c_s * c_s per channel.  This is NOT
+ *           pt_render's single accumulator across the samples of a pixel (which adds every term of every sample to one sum); the two are
+ *           the same at spp = 1.
+ *   Store   without PT_RADIANCE_ACCUMULATE d_radiance[i] = mean.  With it (mean + old * (float)frame) / (float)(frame + 1), the film's
+ *           blend; the old value is not read when frame == 0 (+0 stands for it).  d_moment2 follows the same rule.
+ *
+ * Execution.  Blocking.  Everything runs on the context's stream, behind the work already queued there.  Per chunk of desc.chunk_rays rays:
+ * one generate launch, max_depth rounds of (extend, shade [, shadow extend, shadow add]) through one pipeline, one resolve launch; nothing is
+ * polled, so a chunk whose paths have all ended still launches its remaining (empty) rounds.  *device_ms (nullable): first kernel to last.
+ * pt_stats: rays grows by the closest-hit and shadow queries traced, exactly as pt_render counts them for the same estimator; paths by
+ * n * spp; rounds, launches_extend, launches_shade, launches_other by what ran; extend_variant is the kernel that ran.  A scene that lost its
+ * trees is repaired first, as pt_trace does.  n == 0 is PT_OK and launches nothing.
+ *
+ * Workspace: a chunk's slots (rays x spp) at 132 B each -- two path queues, hit records, instance words, accumulators -- plus 64 B per slot
+ * for the shadow queue from the first PT_RADIANCE_NEE call on, belong to the CONTEXT: made by the first call, only growing, counted against
+ * pt_tuning.mem_budget_mb (PT_ERR_OOM when a chunk does not fit: nothing is launched, the context stays usable and a smaller chunk_rays
+ * works), freed by pt_ctx_destroy; pt_radiance_workspace_bytes reports the bytes held.  chunk_rays = 0 takes
+ * max(64, PT_RADIANCE_DEFAULT_CHUNK_SLOTS / spp) rays, rounded up to a multiple of 64 and capped by n; a chunk never exceeds 2^30 slots.
+ * PT_RADIANCE_DEFAULT_CHUNK_SLOTS is 2^24 slots (2.1 GiB, 3.1 GiB with the shadow queue, and only for calls that large): of the chunks
+ * 2^18 .. 2^24 slots swept on the MI355X over the 1920 x 1080 camera rays at 8 samples, depth 8 (scripts/probe_radiance_device.py,
+ * profiles/radiance_device_probe.json) the largest was the fastest on both scenes and no smaller one lay within its spread -- Cornell box
+ * 4.72 ms at 2^20, 3.23 at 2^22, 2.95 at 2^23, 2.76 at 2^24; 1 M-triangle soup 52.0 / 27.0 / 21.0 / 18.3 ms: every chunk pays its rounds'
+ * launches and ends each round in a tail in which the extend kernel's persistent waves run out of rays.  Nothing beyond 2^24 was swept; a
+ * caller short of memory names a smaller chunk_rays.
+ *
+ * Refusals, with nothing launched and nothing written -- PT_ERR_INVALID_ARG: NULL scene or desc; NULL d_rays6 or d_radiance with n > 0; spp
+ * or max_depth outside 1..65535; unknown flag bits; a nonzero reserved word; tmin, tmax or an env component not finite, or tmax <= tmin;
+ * PT_RADIANCE_ACCUMULATE with frame < 0; an unknown extend value.  PT_ERR_UNSUPPORTED: PT_EXTEND_FLAT and the variants the scene has no
+ * tree for (pt_trace's rules).  PT_ERR_OOM: above.                                                                                       */
+enum { PT_RADIANCE_NEE = 1u, PT_RADIANCE_ACCUMULATE = 2u };
+#define PT_RADIANCE_DEFAULT_CHUNK_SLOTS (1u << 24)
+typedef struct pt_radiance_desc {
+    const void *d_rays6;     /* DEVICE n x {origin.xyz, direction.xyz} f32, dense, 4-byte aligned; taken as given (not normalised), as pt_trace takes them */
+    const void *d_seeds;     /* DEVICE n x spp u32: the RNG state sample s of ray i starts with, [i*spp + s]; NULL = the rule above */
+    void *d_radiance;        /* DEVICE n x 3 f32, required */
+    void *d_moment2;         /* DEVICE n x 3 f32, may be NULL */
+    float tmin, tmax;        /* defaults 0.001, 10000 */
+    float env[3];            /* default (0.7, 0.6, 0.5) */
+    uint32_t spp, max_depth; /* defaults 32, 8; 1..65535 each (pt_render's limits) */
+    int32_t  frame;          /* default 0 */
+    uint32_t index_base;     /* default 0: ray i hashes as i + index_base */
+    uint32_t flags;          /* PT_RADIANCE_* */
+    uint32_t extend;         /* PT_EXTEND_*, pt_trace's rules */
+    uint32_t chunk_rays;     /* rays per pass; 0 = automatic; rounded up to a multiple of 64 */
+    uint32_t reserved[4];    /* must be 0 */
+} pt_radiance_desc;          /* 96 bytes */
+void pt_radiance_desc_default(pt_radiance_desc *d);   /* pointers NULL, the defaults above, no flags, AUTO */
+pt_status pt_radiance_device(pt_scene *scene, const pt_radiance_desc *desc, uint64_t n, float *device_ms /* may be NULL */);
+/* the device bytes the context holds for pt_radiance_device (0 before the first call) */
+pt_status pt_radiance_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes);
+
 /* ---- multi-GPU: assembling the presented image of a tile-sharded render ---------- */
 /* The reference renders on physical device 0 (main.cpp:105) and copies its storage image to the swapchain
  * (main.cpp:661-667).  Here N ranks -- processes or host threads, one context and one GPU each -- render the

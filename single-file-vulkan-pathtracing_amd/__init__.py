@@ -144,6 +144,17 @@ class TraceDesc(C.Structure):
                 ("chunk_rays", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
+RADIANCE_NEE, RADIANCE_ACCUMULATE = 1, 2   # include/pt_api.h PT_RADIANCE_*: the estimator and the store of pt_radiance_device
+
+
+class RadianceDesc(C.Structure):
+    """include/pt_api.h pt_radiance_desc: path-traced radiance for rays on device buffers (pt_radiance_device)."""
+    _fields_ = [("d_rays6", C.c_void_p), ("d_seeds", C.c_void_p), ("d_radiance", C.c_void_p), ("d_moment2", C.c_void_p),
+                ("tmin", C.c_float), ("tmax", C.c_float), ("env", C.c_float * 3), ("spp", C.c_uint32), ("max_depth", C.c_uint32),
+                ("frame", C.c_int32), ("index_base", C.c_uint32), ("flags", C.c_uint32), ("extend", C.c_uint32), ("chunk_rays", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 GUIDED_AUTO = 0          # include/pt_api.h PT_GUIDED_*: which form pt_render_guided takes
 GUIDED_SINGLE_PASS = 1
 GUIDED_TWO_CALLS = 2
@@ -209,7 +220,8 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_upsample_params_default", "pt_film_upsample", "pt_film_read_upsampled",
                "pt_film_enable_counts", "pt_film_read_counts", "pt_adaptive_params_default", "pt_render_adaptive",
                "pt_guided_params_default", "pt_render_guided",
-               "pt_trace_desc_default", "pt_trace_device", "pt_trace_workspace_bytes"]
+               "pt_trace_desc_default", "pt_trace_device", "pt_trace_workspace_bytes",
+               "pt_radiance_desc_default", "pt_radiance_device", "pt_radiance_workspace_bytes"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium", "pth_self_leaf_rule", "pth_self_leaf_c1", "pth_self_leaf_skip"]
 
@@ -317,6 +329,11 @@ def lib_amd():
             L.pt_trace_desc_default.restype = None
             L.pt_trace_device.argtypes = [vp, C.POINTER(TraceDesc), C.c_uint64, C.POINTER(C.c_float)]
             L.pt_trace_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+        if hasattr(L, "pt_radiance_device"):   # (radiance for caller-supplied rays; as above)
+            L.pt_radiance_desc_default.argtypes = [C.POINTER(RadianceDesc)]
+            L.pt_radiance_desc_default.restype = None
+            L.pt_radiance_device.argtypes = [vp, C.POINTER(RadianceDesc), C.c_uint64, C.POINTER(C.c_float)]
+            L.pt_radiance_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
         if hasattr(L, "pt_get_block_counts"):   # (API version 6; dev A/B runs load older builds through PT_LIB_AMD)
@@ -528,6 +545,10 @@ def trace_default_desc():
     return _default_params(TraceDesc, "pt_trace_desc_default")
 
 
+def radiance_default_desc():
+    return _default_params(RadianceDesc, "pt_radiance_desc_default")
+
+
 def motion_default_params():
     return _default_params(MotionParams, "pt_motion_params_default")
 
@@ -578,6 +599,12 @@ class Context:
         """Device bytes the context holds for Scene.trace_device / trace_tensors (pt_trace_workspace_bytes): 0 before the first call."""
         n = C.c_uint64(0)
         self._check(lib_amd().pt_trace_workspace_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def radiance_workspace_bytes(self):
+        """Device bytes the context holds for Scene.radiance_device / radiance_tensors (pt_radiance_workspace_bytes): 0 before the first call."""
+        n = C.c_uint64(0)
+        self._check(lib_amd().pt_radiance_workspace_bytes(self.h, C.byref(n)))
         return n.value
 
     def block_counts(self):
@@ -722,6 +749,52 @@ class Scene:
         torch.cuda.current_stream(dev).synchronize()
         self.trace_device(n, rays.data_ptr(), hits_ptr=hits.data_ptr(), **planes, **kw)
         return out
+
+    def radiance_device(self, n, rays_ptr, radiance_ptr, seeds_ptr=None, moment2_ptr=None, spp=32, max_depth=8, tmin=0.001, tmax=10000.0, env=None,
+                        frame=0, index_base=0, flags=0, extend=EXTEND_AUTO, chunk_rays=0):
+        """pt_radiance_device over raw DEVICE pointers (include/pt_api.h has the layouts and the arithmetic): n rays at rays_ptr, their mean
+        radiance to radiance_ptr (and the mean of the samples' squares to moment2_ptr).  Blocking -> device_ms."""
+        d = radiance_default_desc()
+        d.d_rays6, d.d_seeds, d.d_radiance, d.d_moment2 = rays_ptr, seeds_ptr, radiance_ptr, moment2_ptr
+        d.tmin, d.tmax, d.spp, d.max_depth, d.frame, d.index_base = tmin, tmax, spp, max_depth, frame, index_base
+        d.flags, d.extend, d.chunk_rays = flags, extend, chunk_rays
+        if env is not None:
+            d.env = (C.c_float * 3)(*env)
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_radiance_device(self.h, C.byref(d), n, C.byref(ms)))
+        return ms.value
+
+    def radiance_tensors(self, rays, spp=32, max_depth=8, seeds=None, nee=False, out=None, moment2=False, frame=0, accumulate=False, tmin=0.001,
+                         tmax=10000.0, env=None, index_base=0, extend=EXTEND_AUTO, chunk_rays=0):
+        """Path-traced radiance along torch rays, nothing through the host.  rays: float32 CUDA tensor [n, 6] {origin, direction} (made contiguous
+        if it is not); seeds: optional int32 / uint32 tensor of n * spp RNG states; out: a contiguous float32 [n, 3] tensor to store into (or, with
+        accumulate, to blend into by `frame`), made here when None; moment2: True for a new second-moment tensor, or a tensor like `out`.
+        -> the [n, 3] radiance tensor, or (radiance, moment2)."""
+        import torch
+        if rays.dtype != torch.float32 or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be a float32 CUDA tensor of shape [n, 6]")
+        rays = rays.contiguous()
+        n, dev = rays.shape[0], rays.device
+
+        def plane(t, what):
+            if t is None or t is True:
+                return torch.zeros((n, 3), dtype=torch.float32, device=dev) if accumulate and frame else torch.empty((n, 3), dtype=torch.float32, device=dev)
+            if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (n, 3) or not t.is_contiguous():
+                raise ValueError(what + " must be a contiguous float32 tensor [n, 3] on the rays' device")
+            return t
+        out = plane(out, "out")
+        m2 = plane(moment2, "moment2") if moment2 is not False and moment2 is not None else None
+        if seeds is not None:
+            if seeds.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or seeds.device != dev or seeds.numel() != n * spp:
+                raise ValueError("seeds must be an int32 / uint32 tensor of n * spp elements on the rays' device")
+            seeds = seeds.contiguous()
+        flags = (RADIANCE_NEE if nee else 0) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        # (torch's stream is drained first and the call blocks: Scene.trace_tensors has the reasons)
+        torch.cuda.current_stream(dev).synchronize()
+        self.radiance_device(n, rays.data_ptr(), out.data_ptr(), seeds_ptr=seeds.data_ptr() if seeds is not None else None,
+                             moment2_ptr=m2.data_ptr() if m2 is not None else None, spp=spp, max_depth=max_depth, tmin=tmin, tmax=tmax, env=env,
+                             frame=frame, index_base=index_base, flags=flags, extend=extend, chunk_rays=chunk_rays)
+        return (out, m2) if m2 is not None else out
 
     def close(self):
         if self.h:

@@ -160,6 +160,7 @@ void pt_ctx_destroy(pt_ctx *ctx)
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->d_spill) (void)hipFree(ctx->d_spill);
     ptt_free(ctx);
+    ptr_free(ctx);
     if (ctx->ev_a) (void)hipEventDestroy(ctx->ev_a);
     if (ctx->ev_b) (void)hipEventDestroy(ctx->ev_b);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -683,6 +684,33 @@ pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes)
 {
     if (!ctx || !bytes) return PT_ERR_INVALID_ARG;
     *bytes = ctx->tr.bytes;
+    return PT_OK;
+}
+
+void pt_radiance_desc_default(pt_radiance_desc *d)
+{
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    d->tmin = 0.001f;
+    d->tmax = 10000.0f;
+    d->env[0] = 0.7f; d->env[1] = 0.6f; d->env[2] = 0.5f;  // miss.rmiss:10
+    d->spp = 32;
+    d->max_depth = 8;
+    d->extend = PT_EXTEND_AUTO;
+}
+
+pt_status pt_radiance_device(pt_scene *s, const pt_radiance_desc *d, uint64_t n, float *device_ms)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    if (!d) return pt_bad(s->ctx, "null argument");
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return ptr_radiance_device(s, d, n, device_ms); });
+}
+
+pt_status pt_radiance_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes)
+{
+    if (!ctx || !bytes) return PT_ERR_INVALID_ARG;
+    *bytes = (uint64_t)ctx->rd.bytes + (uint64_t)ctx->rd.sq_bytes;
     return PT_OK;
 }
 

@@ -82,6 +82,21 @@ struct pt_ctx {
         size_t cap = 0;                                            // rays the per-ray arrays hold
         size_t bytes = 0;                                          // device bytes of all of the above
     } tr;
+    // pt_radiance_device (radiance_device.hip): one chunk of path slots -- the two path queues of the wavefront kernels, the hit records, one
+    // accumulator per slot -- and, from the first PT_RADIANCE_NEE call on, the shadow queue.  The context's scratch like `tr`: made by the first
+    // call, only growing, counted against mem_budget, freed by pt_ctx_destroy.
+    struct Radiance {
+        uint2 *d_qid[2] = { nullptr, nullptr }; float4 *d_qstate[2] = { nullptr, nullptr };   // {slot, sample | depth << 16} {seed, weight}
+        float4 *d_qrayA[2] = { nullptr, nullptr }; float2 *d_qrayB[2] = { nullptr, nullptr };
+        float4 *d_hit = nullptr; uint32_t *d_hit_inst = nullptr;
+        float4 *d_color = nullptr;                                 // a slot's accumulator (ptw::Radiance::color)
+        uint32_t *d_count = nullptr;                               // [4]: the two queues' sizes, the shadow queue's, a spare word
+        uint32_t *d_tiles = nullptr;                               // [1]: the zeroed tile word k_shade's slot_pixel reads
+        float4 *d_sq_rayA = nullptr; float2 *d_sq_rayB = nullptr; float4 *d_sq_contrib = nullptr; float4 *d_sq_hit = nullptr;
+        float *d_sq_tmax = nullptr; uint32_t *d_sq_slot = nullptr;
+        size_t cap = 0, cap_sq = 0;                                // slots the per-slot arrays / the shadow queue hold
+        size_t bytes = 0, sq_bytes = 0;                            // device bytes of the two sets
+    } rd;
 };
 // The workspace budget a context plans within when the caller names none: 8 GB.  Round 6, one MI355X, Grays/s at 2 / 4 / 8 / 16 / 32 GB / no
 // bound: the 10 000-instance grid through the queues 13.6 / 15.0 / 15.0 / 15.1 / 15.4 / 15.3 (the fused kernel 15.5 in 0.6 GB at every budget);
@@ -420,6 +435,9 @@ void ptw_free_work(pt_film *f);
 // trace_device.hip: pt_trace_device (validates everything but the null scene / desc) and the context's workspace behind it
 pt_status ptt_trace_device(pt_scene *s, const pt_trace_desc *d, uint64_t n, float *device_ms);
 void ptt_free(pt_ctx *ctx);
+// radiance_device.hip: pt_radiance_device (validates everything but the null scene / desc) and the context's workspace behind it
+pt_status ptr_radiance_device(pt_scene *s, const pt_radiance_desc *d, uint64_t n, float *device_ms);
+void ptr_free(pt_ctx *ctx);
 // aov.hip: guide buffers of the first hit
 pt_status pta_enable(pt_film *f, void *const *device_planes);
 pt_status pta_render(pt_scene *s, pt_film *f, const pt_params *p);

@@ -219,17 +219,9 @@ pt_status job_setup(Job &j)
     j.async = (p->flags & PT_FLAG_ASYNC) != 0;
     if (j.async && j.profile) { ctx->err = "PT_FLAG_ASYNC and PT_FLAG_PROFILE exclude each other"; return PT_ERR_INVALID_ARG; }
 
-    // k_shade: 2 paths per thread (one queue-tail atomic per 512 paths), 8 blocks per CU (flat between 4 and 16)
-    j.shade_grid = ctx->num_cus * 8;
-    j.shade_smem = sizeof(float4) * 8 * (size_t)s->n_tris;  // tri4 + shade4 + the tangent frames
-    j.shade_lds = j.shade_smem <= 16 * 1024 && !j.pl.bvh8;  // per-triangle tables of small scenes are staged in LDS (in the BVH4's order)
-    // instanced scenes: world-space normal + tangent per (instance, triangle), built once (lbvh_build.hip); pt_tuning.inst_frames = 0
-    // keeps the per-hit transform
-    if (s->n_inst && !j.pl.bvh8 && ctx->tune.inst_frames != 0) {
-        const pt_status rcf = ptb_ensure_inst_frames(s);
-        if (rcf != PT_OK) return rcf;
-        j.inst_frame = s->d_inst_frame;
-    }
+    // k_shade's launch shape and, for instanced scenes, its (instance, triangle) frame table (wavefront_host.h)
+    ptw_shade_shape(ctx, s, j.pl, j.shade_grid, j.shade_smem, j.shade_lds);
+    PT_TRY(ptw_shade_inst_frames(s, j.pl, j.inst_frame));
     // Pipelines: the slot lanes of a batch are split into parts that run their rounds independently on separate streams, so
     // the VALU-bound traversal of one overlaps the memory-bound shading of another.  Two for most shapes (a third: C4 -1 ... -3 %,
     // C5 -3 ... -6 %; a fourth loses everywhere).  THREE where both kernels keep their tables in LDS, the scene has one level and
@@ -269,14 +261,8 @@ pt_status job_setup(Job &j)
         }
     }
     j.nee = p->pipeline == PT_PIPELINE_WAVEFRONT_NEE;
-    // the emitters the NEE pipeline samples: the scene's, or -- instanced -- every instance's copy of them in world space
-    if (j.nee && s->n_inst) {
-        const pt_status rcl = ptb_ensure_inst_lights(s);
-        if (rcl != PT_OK) return rcl;
-    }
-    j.nee_lights = s->n_inst ? s->d_lights_inst : s->d_lights;
-    j.nee_n_lights = s->n_inst ? s->n_lights_inst : s->n_lights;
-    j.nee_light_area = s->n_inst ? s->light_area_inst : s->light_area;
+    // the emitters the NEE pipeline samples (wavefront_host.h)
+    PT_TRY(ptw_nee_lights(s, j.nee, j.nee_lights, j.nee_n_lights, j.nee_light_area));
     if (j.nee && (size_t)w.n_slots > w.cap_sq) {  // the shadow queue: at most one entry per live path and round
         const size_t ns = w.n_slots;
         w.cap_sq = 0;

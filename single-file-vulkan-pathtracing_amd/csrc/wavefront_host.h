@@ -102,6 +102,34 @@ struct ShadeLaunch {
     uint32_t *sq_count = nullptr;
 };
 void ptw_launch_shade(const ShadeLaunch &a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+// What every caller of k_shade decides the same way (render.hip job_setup, radiance_device.hip), once each:
+// the launch shape -- 2 paths per thread (one queue-tail atomic per 512 paths), 8 blocks per CU (flat between 4 and 16); the per-triangle tables of
+// small scenes are staged in LDS (tri4 + shade4 + the tangent frames, in the BVH4's order)
+inline void ptw_shade_shape(const pt_ctx *ctx, const pt_scene *s, const ExtendPlan &pl, int &grid, size_t &smem, bool &lds_tables)
+{
+    grid = ctx->num_cus * 8;
+    smem = sizeof(float4) * 8 * (size_t)s->n_tris;
+    lds_tables = smem <= 16 * 1024 && !pl.bvh8;
+}
+// ... instanced scenes: world-space normal + tangent per (instance, triangle), built once (lbvh_build.hip); pt_tuning.inst_frames = 0 keeps the
+// per-hit transform (-> null)
+inline pt_status ptw_shade_inst_frames(pt_scene *s, const ExtendPlan &pl, const float4 *&inst_frame)
+{
+    inst_frame = nullptr;
+    if (!(s->n_inst && !pl.bvh8 && s->ctx->tune.inst_frames != 0)) return PT_OK;
+    PT_TRY(ptb_ensure_inst_frames(s));
+    inst_frame = s->d_inst_frame;
+    return PT_OK;
+}
+// ... the emitters the NEE estimator samples: the scene's, or -- instanced -- every instance's copy of them in world space (built on first NEE use)
+inline pt_status ptw_nee_lights(pt_scene *s, bool nee, const float4 *&lights, uint32_t &n_lights, float &light_area)
+{
+    if (nee && s->n_inst) PT_TRY(ptb_ensure_inst_lights(s));
+    lights = s->n_inst ? s->d_lights_inst : s->d_lights;
+    n_lights = s->n_inst ? s->n_lights_inst : s->n_lights;
+    light_area = s->n_inst ? s->light_area_inst : s->light_area;
+    return PT_OK;
+}
 // (stats: the context's counters -- k_generate counts the camera rays of the slots it finishes without a walk, RenderConst::cull)
 void ptw_launch_generate(const ptw::RenderConst &rc, const uint32_t *tiles, uint32_t slot_base, uint32_t n_slots, const ptw::Radiance &rad,
                          const ptw::QueueView &out, uint32_t *count_out, unsigned long long *stats, int num_cus, hipStream_t st);
