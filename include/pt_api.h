@@ -875,11 +875,33 @@ pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes);
  * launches and ends each round in a tail in which the extend kernel's persistent waves run out of rays.  Nothing beyond 2^24 was swept; a
  * caller short of memory names a smaller chunk_rays.
  *
+ * The single-kernel form.  PT_RADIANCE_FUSED runs the paths of a chunk through ONE persistent kernel, PT_PIPELINE_FUSED's, started from the
+ * caller's rays: a lane keeps its path in registers and LDS from the given ray to the path's end and HBM sees one 16-B accumulator per slot.
+ * Seed / Path / Reduce / Store above hold word for word: d_radiance and d_moment2 have the same bits in both forms, for both estimators, with
+ * and without d_seeds, with PT_RADIANCE_ACCUMULATE; pt_stats.rays and .paths grow by the same amounts.  It applies to the single-level class
+ * of PT_PIPELINE_FUSED (the same rule decides): a scene without instances whose BVH4, triangles and shading tables live in LDS
+ * (PT_EXTEND_LDS plan, no stack spill, tables <= 16 KB), tmin > 0, desc.extend == PT_EXTEND_AUTO; the plain estimator and PT_RADIANCE_NEE;
+ * pair-leaf trees and leaves of up to four (pt_tuning.pair_leaves = 0).  Everywhere else PT_RADIANCE_FUSED is PT_ERR_UNSUPPORTED with nothing
+ * launched or written (the text names the class).  PT_RADIANCE_AUTO takes the single-kernel form where it applies AND won the measurements
+ * of DESIGN.md section 25 for that estimator -- on the MI355X it won every measured shape, 1.1x to 2.4x, for both estimators, so AUTO takes it
+ * wherever it applies -- the wavefront form everywhere else (also where the single-kernel form's workspace does not fit the budget), and is
+ * never an error the call would not be without the flag.  Both bits together: PT_ERR_INVALID_ARG.  With neither bit the call is what it was: same kernels, same workspace, same pt_stats
+ * fields.  The value 4 is no flag: it stays an unknown bit (PT_ERR_INVALID_ARG).
+ * pt_stats under either bit: pipeline = PT_PIPELINE_FUSED, or PT_PIPELINE_WAVEFRONT / _WAVEFRONT_NEE, for the form that ran (without the
+ * bits the field is not touched).  The single-kernel form adds, per chunk, one to each of rounds, launches_extend (the fused launch) and
+ * launches_other (the resolve), nothing to launches_shade; extend_variant = PT_EXTEND_LDS.
+ * Its workspace is a set of its own that belongs to the context like the other: exactly
+ *     16 * C * spp + 1024 bytes,   C = the chunk's rays = min(up64(chunk_rays or the automatic chunk), up64(n)), up64 = rounded up to 64
+ * (one accumulator per slot and the kernel's eight slot counters, 128 B apart), for the largest C * spp so far; made by the first such call,
+ * only growing, counted against pt_tuning.mem_budget_mb together with the other sets (PT_ERR_OOM: nothing launched, the context stays usable,
+ * a smaller chunk_rays works), freed by pt_ctx_destroy, included in pt_radiance_workspace_bytes.  A context that only ever runs this form
+ * never allocates the 132-B-per-slot set.  chunk_rays = 0 is the rule above.
+ *
  * Refusals, with nothing launched and nothing written -- PT_ERR_INVALID_ARG: NULL scene or desc; NULL d_rays6 or d_radiance with n > 0; spp
- * or max_depth outside 1..65535; unknown flag bits; a nonzero reserved word; tmin, tmax or an env component not finite, or tmax <= tmin;
+ * or max_depth outside 1..65535; unknown flag bits; PT_RADIANCE_FUSED together with PT_RADIANCE_AUTO; a nonzero reserved word; tmin, tmax or an env component not finite, or tmax <= tmin;
  * PT_RADIANCE_ACCUMULATE with frame < 0; an unknown extend value.  PT_ERR_UNSUPPORTED: PT_EXTEND_FLAT and the variants the scene has no
- * tree for (pt_trace's rules).  PT_ERR_OOM: above.                                                                                       */
-enum { PT_RADIANCE_NEE = 1u, PT_RADIANCE_ACCUMULATE = 2u };
+ * tree for (pt_trace's rules); PT_RADIANCE_FUSED outside its class.  PT_ERR_OOM: above.                                                   */
+enum { PT_RADIANCE_NEE = 1u, PT_RADIANCE_ACCUMULATE = 2u, /* (4: no flag) */ PT_RADIANCE_FUSED = 8u, PT_RADIANCE_AUTO = 16u };
 #define PT_RADIANCE_DEFAULT_CHUNK_SLOTS (1u << 24)
 typedef struct pt_radiance_desc {
     const void *d_rays6;     /* DEVICE n x {origin.xyz, direction.xyz} f32, dense, 4-byte aligned; taken as given (not normalised), as pt_trace takes them */

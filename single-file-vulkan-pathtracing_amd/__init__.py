@@ -145,6 +145,7 @@ class TraceDesc(C.Structure):
 
 
 RADIANCE_NEE, RADIANCE_ACCUMULATE = 1, 2   # include/pt_api.h PT_RADIANCE_*: the estimator and the store of pt_radiance_device
+RADIANCE_FUSED, RADIANCE_AUTO = 8, 16      # ... its form: the single-kernel one (or PT_ERR_UNSUPPORTED) | the library's choice; neither: the wavefront form
 
 
 class RadianceDesc(C.Structure):
@@ -765,12 +766,17 @@ class Scene:
         return ms.value
 
     def radiance_tensors(self, rays, spp=32, max_depth=8, seeds=None, nee=False, out=None, moment2=False, frame=0, accumulate=False, tmin=0.001,
-                         tmax=10000.0, env=None, index_base=0, extend=EXTEND_AUTO, chunk_rays=0):
+                         tmax=10000.0, env=None, index_base=0, extend=EXTEND_AUTO, chunk_rays=0, form="wavefront"):
         """Path-traced radiance along torch rays, nothing through the host.  rays: float32 CUDA tensor [n, 6] {origin, direction} (made contiguous
         if it is not); seeds: optional int32 / uint32 tensor of n * spp RNG states; out: a contiguous float32 [n, 3] tensor to store into (or, with
         accumulate, to blend into by `frame`), made here when None; moment2: True for a new second-moment tensor, or a tensor like `out`.
+        form: "wavefront" (the queues), "fused" (PT_RADIANCE_FUSED: the single kernel, an error where it does not apply) or "auto"
+        (PT_RADIANCE_AUTO); the result does not depend on it.
         -> the [n, 3] radiance tensor, or (radiance, moment2)."""
         import torch
+        forms = {"wavefront": 0, "fused": RADIANCE_FUSED, "auto": RADIANCE_AUTO}
+        if form not in forms:
+            raise ValueError('form must be "wavefront", "fused" or "auto"')
         if rays.dtype != torch.float32 or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 6:
             raise ValueError("rays must be a float32 CUDA tensor of shape [n, 6]")
         rays = rays.contiguous()
@@ -788,7 +794,7 @@ class Scene:
             if seeds.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or seeds.device != dev or seeds.numel() != n * spp:
                 raise ValueError("seeds must be an int32 / uint32 tensor of n * spp elements on the rays' device")
             seeds = seeds.contiguous()
-        flags = (RADIANCE_NEE if nee else 0) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        flags = (RADIANCE_NEE if nee else 0) | (RADIANCE_ACCUMULATE if accumulate else 0) | forms[form]
         # (torch's stream is drained first and the call blocks: Scene.trace_tensors has the reasons)
         torch.cuda.current_stream(dev).synchronize()
         self.radiance_device(n, rays.data_ptr(), out.data_ptr(), seeds_ptr=seeds.data_ptr() if seeds is not None else None,

@@ -31,6 +31,7 @@
 // Radiance goes where the wavefront pipeline puts it (struct Radiance): one accumulator per slot written when the slot is
 // complete (one sample group), or the ordered term logs that k_resolve replays (several groups) -- k_resolve is shared.
 #pragma once
+#include "radiance_device_kernel.h"  // (RAYS: the index arithmetic of the hand-out and the seed rule, shared with the host's restatement test)
 
 // Block shape: the scene tables (9.2 KB for the Cornell box) are per block, the stack and the path state (20 dwords) per
 // thread, so bigger blocks leave more of the 160 KB to waves: 256 threads = 5 blocks = 5 waves per SIMD; 512 threads =
@@ -175,7 +176,12 @@ enum FusedBlock : int {
 // LOG (pt_render_guided, fused_guided.hip): the shade block stores the first hit of every camera ray -- {best_pos, bits(best_t)}, a miss as PT_MISS --
 // at gd_log_index (guided_kernel.h): k_aov_reduce's input order per frame of the launch.  No LDS, no accumulator; the instantiations with LOG =
 // false carry none of it.
-template <int MODE, bool PAIRS, bool COUNT, bool NEE = false, bool LOG = false>
+// RAYS (pt_radiance_device with PT_RADIANCE_FUSED, fused_rays.hip): a slot is one sample of one of the CALLER's rays, not a pixel's frame.  The
+// hand-out knows no tiles -- hand-out position -> slot -> (sample, ray) by radiance_device_kernel.h's rdf_* -- and a fresh slot loads its ray and
+// takes or hashes its seed where a pixel's slot builds a camera ray: weight 1, accumulator +0, depth 0, no jitter, no normalisation, no rnd, no
+// leaf left out.  Such a lane goes from step (2) straight to step (4); steps (1) and (3) carry its path as they carry a camera's.  rc.spp is 1 and
+// rc.n_slots the live slots (n_slots_arg: rounded up to 64); div_frames divides by the chunk's rays.  MODE 0 only; FS_PXY and FS_MB are unused.
+template <int MODE, bool PAIRS, bool COUNT, bool NEE = false, bool LOG = false, bool RAYS = false>
 __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *__restrict__ tiles_arg, Radiance rad_arg,
                                            const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
                                            const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
@@ -183,7 +189,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                                            uint32_t *next_slot_arg, unsigned long long *stats_arg, int refill_arg, float tmin_arg,
                                            float tmax_arg, int lds_stack, FastDiv div_frames_arg, float self_c1_arg = 0.f,
                                            const float4 *__restrict__ lights_arg = nullptr, uint32_t n_lights_arg = 0u, float light_area_arg = 0.f,
-                                           uint2 *log_arg = nullptr)
+                                           uint2 *log_arg = nullptr, RdRays rays_arg = RdRays{})
 {
     constexpr uint32_t LEAF_BIT = C14_LEAF, DONE = C14_DONE;
     constexpr int POP_N = PT_FUSED_POP_N;  // entries a pass of the pop loop reads together (pop_pending below)
@@ -196,6 +202,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                   "self_leaf.h names leaves as the staged nodes do; the root's code stands for `none`");
     static_assert(!NEE || (MODE == 0 && !COUNT), "NEE: one sample group, no instrumented twin");
     static_assert(!LOG || !COUNT, "the first-hit log: no instrumented twin");
+    static_assert(!RAYS || (MODE == 0 && !COUNT && !LOG), "caller rays: one sample per slot, no instrumented twin, no first-hit log");
+    static_assert(RDF_PARTS == (uint32_t)PT_FUSED_PARTS, "radiance_device_kernel.h restates the hand-out's parts");
     // (everything the persistent loop reads: a scalar register of its own -- own_sgprs)
     const RenderConst rc = ptm::own_sgprs(rc_arg);
     const Radiance rad = ptm::own_sgprs(rad_arg);
@@ -216,6 +224,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
     }
     uint2 *log = nullptr;  // LOG: the first-hit log of the launch
     if constexpr (LOG) log = ptm::own_sgprs(log_arg);
+    RdRays rays{};  // RAYS: the chunk's rows and seeds
+    if constexpr (RAYS) rays = ptm::own_sgprs(rays_arg);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // ---- LDS: BVH4 nodes | three permuted triangle copies | shade4 | tangent frames | stack | path state (fused_lds)
     const FusedLds lds = fused_lds(n_wide, n_tris, (uint32_t)lds_stack);
@@ -392,7 +402,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 PT_FB(FB_HIT)
                 slot = my_state[FS_SLOT * FTB]; ctr = my_state[FS_CTR * FTB]; seed = my_state[FS_SEED * FTB];
                 wr = __uint_as_float(my_state[FS_WR * FTB]); wg = __uint_as_float(my_state[FS_WG * FTB]); wb = __uint_as_float(my_state[FS_WB * FTB]);
-                pxy = my_state[FS_PXY * FTB];
+                if constexpr (!RAYS) pxy = my_state[FS_PXY * FTB];
                 uint32_t sample = ctr & 0xFFFFu, depth = ctr >> 16;
                 // raygen.rgen:76 `color += weight * emission` (adding +0 changes no bit of a non-negative accumulator, so
                 // non-emitters are skipped -- as k_shade does; NaN compares false and still adds)
@@ -506,7 +516,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     bounce = !terminated;  // (the bounce itself: step (3), beside the camera rays)
                     sample += terminated ? 1u : 0u;
                     depth = terminated ? 0u : depth;
-                    const bool more = HYB ? (!logs && sample < rc.head_samples)  // (a tail slot is one sample)
+                    const bool more = RAYS ? false                                // (a caller's ray: the slot is one sample)
+                                    : HYB ? (!logs && sample < rc.head_samples)  // (a tail slot is one sample)
                                           : sample < rc.spp;                      // (one group: the slot is the pixel's whole frame)
                     need_primary = terminated & more;  // the slot's next sample: raygen.rgen:45-60
                     if (terminated & !more) {  // the slot is complete
@@ -526,7 +537,9 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                     sample++;
                     depth = 0;
                     bool more;
-                    if (!GROUPED) {
+                    if (RAYS) {
+                        more = false;  // (a caller's ray: the slot is one sample)
+                    } else if (!GROUPED) {
                         more = sample < rc.spp;  // (NEE, one group: the slot is the pixel's whole frame)
                     } else {
                         const uint32_t lane_slot = rc.div_spl.div(slot);  // = frame lane * groups + sample group (slot_pixel)
@@ -568,7 +581,8 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         const uint32_t plen = HYB ? ((ns + PT_FUSED_PARTS - 1) / PT_FUSED_PARTS + 63u) & ~63u : part_len;
                         const uint32_t part_begin = grp ? w_part * plen : 0u,
                                        part_end = grp ? min(part_begin + plen, ns)
-                                                      : (((ns >> 6) + (uint32_t)PT_FUSED_PARTS - 1u - w_part) / (uint32_t)PT_FUSED_PARTS) << 6;
+                                                      : RAYS ? rdf_part_end(ns, w_part)
+                                                             : (((ns >> 6) + (uint32_t)PT_FUSED_PARTS - 1u - w_part) / (uint32_t)PT_FUSED_PARTS) << 6;
                         uint32_t rel = 0, size = 0;
                         if (lane == 0) {
                             uint32_t *cnt = next_slot + (w_part + ((HYB && w_tails) ? (uint32_t)PT_FUSED_PARTS : 0u)) * (uint32_t)PT_FUSED_PART_STRIDE;
@@ -596,7 +610,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         }
                     }
                     if (out_of_slots) dev.out_of_slots();
-                    if (!out_of_slots && (uint32_t)lane < (w_end - w_base + 63u) / 64u) {
+                    if (!RAYS && !out_of_slots && (uint32_t)lane < (w_end - w_base + 63u) / 64u) {
                         if (GROUPED || (HYB && w_tails)) {
                             const uint32_t c = slot_base + w_base + 64u * (uint32_t)lane;   // a 64-aligned chunk of slots = one 8x8 tile
                             s_wtile[lane] = tiles[(c - rc.div_spl.div(c) * rc.slots_per_lane) >> 6];
@@ -612,48 +626,68 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 if (wants && rank < take) {
                     PT_FB(FB_TAKE)
                     const uint32_t mine = w_next + rank;
-                    uint32_t f, g, local;
-                    if (HYB && w_tails) {  // tail slot `mine` of the launch: (frame lane, tail j, pixel); sample head_samples + j
-                        const uint32_t lane_slot = rc.div_spl.div(mine);
-                        f = rc.div_tail.div(lane_slot); g = lane_slot - f * rc.tail;
-                        local = mine - lane_slot * rc.slots_per_lane;
-                        slot = rc.n_head + mine;
-                    } else if (GROUPED) {
-                        slot = slot_base + mine;
-                        const uint32_t lane_slot = rc.div_spl.div(slot);
-                        f = rc.div_groups.div(lane_slot); g = lane_slot - f * rc.groups;
-                        local = slot - lane_slot * rc.slots_per_lane;
-                    } else {  // hand-out order -> slot: chunk q of the order is (tile q / frames, frame q % frames)
-                        const uint32_t q = (mine >> 6) * (uint32_t)PT_FUSED_PARTS + w_part;
-                        const uint32_t t = div_frames.div(q);
-                        f = q - t * rc.lanes_active; g = 0u;
-                        local = t * 64u + (mine & 63u);
-                        slot = slot_base + f * rc.slots_per_lane + local;
-                    }
-                    const uint32_t tw = s_wtile[(mine - w_base) >> 6];
-                    const uint32_t px = (tw & 0xFFFFu) * 8u + (local & 7u), py = (tw >> 16) * 8u + ((local >> 3) & 7u);
-                    const uint32_t sample0 = (HYB && w_tails) ? rc.head_samples + g : g * rc.group_size;
-                    const bool in_image = px < rc.width && py < rc.height && f < rc.lanes_active && sample0 < rc.spp;
-                    if (in_image && ptc::pixel_culled(rc, px, py)) {
-                        PT_FB(FB_CULLED)
-                        // every sample of the slot: one camera ray, a miss, color += 1 * env -- without the walk that would find nothing (fused_cull.h)
-                        if (GROUPED) cull_n = ptc::finish_group(rc, rad, slot, g);
-                        else if (!(HYB && w_tails)) cull_n = ptc::finish_plain(rc, rad, slot);
-                        // (head + tail: the head slot stands for ALL spp samples of such a pixel -- the same adds in the same order -- and its
-                        // tail slots are nothing: k_resolve does not replay the logs of a pixel outside the rectangle)
-                    } else if (in_image) {
-                        pxy = px | (py << 16);
-                        ctr = sample0;
-                        my_state[FS_A * FTB] = 0u;  // colour.r = +0.0f | term count = 0
-                        if (!GROUPED) { my_state[FS_B * FTB] = 0u; my_state[FS_C * FTB] = 0u; }
-                        my_state[FS_MB * FTB] = (uint32_t)((int32_t)rc.spp * (rc.frame_base + (int32_t)f)) + 1u;
-                        stk.clear_to_bottom();  // (a path)
-                        need_primary = true;
-                        dev.slot_begin();
-                    } else if (GROUPED) {
-                        rad.nterm[slot] = 0u;  // (a slot outside the image or the batch: k_resolve never reads it, kept defined anyway)
-                    } else if (HYB && w_tails) {
-                        rad.nterm[slot - rc.n_head] = 0u;
+                    if constexpr (RAYS) {
+                        // hand-out position -> slot; a slot of the launch's rounding beyond the chunk's last is nobody's.  A live one: its ray as
+                        // given (rows 24 B apart, 4-byte aligned: six dword loads), its seed, then step (4)
+                        slot = rdf_slot(mine, w_part);
+                        if (rdf_live(slot, rc.n_slots)) {
+                            uint32_t s_i, r_i;
+                            rdf_sample_ray(slot, rays.m, div_frames, s_i, r_i);
+                            const float *row = rays.rays6 + 6 * (size_t)r_i;
+                            org = { row[0], row[1], row[2] };
+                            dir = { row[3], row[4], row[5] };
+                            seed = rdf_seed(rays, r_i, s_i);
+                            wr = wg = wb = 1.0f;
+                            ctr = 0u;  // sample 0, depth 0
+                            my_state[FS_A * FTB] = 0u; my_state[FS_B * FTB] = 0u; my_state[FS_C * FTB] = 0u;  // colour = +0.0f
+                            if constexpr (SKIP) self_leaf = ptsl::CODE_NONE;  // (a caller's ray may start on a triangle: tmin < t decides, as in k_extend)
+                            got_ray = true;
+                            dev.slot_begin();
+                        }
+                    } else {
+                        uint32_t f, g, local;
+                        if (HYB && w_tails) {  // tail slot `mine` of the launch: (frame lane, tail j, pixel); sample head_samples + j
+                            const uint32_t lane_slot = rc.div_spl.div(mine);
+                            f = rc.div_tail.div(lane_slot); g = lane_slot - f * rc.tail;
+                            local = mine - lane_slot * rc.slots_per_lane;
+                            slot = rc.n_head + mine;
+                        } else if (GROUPED) {
+                            slot = slot_base + mine;
+                            const uint32_t lane_slot = rc.div_spl.div(slot);
+                            f = rc.div_groups.div(lane_slot); g = lane_slot - f * rc.groups;
+                            local = slot - lane_slot * rc.slots_per_lane;
+                        } else {  // hand-out order -> slot: chunk q of the order is (tile q / frames, frame q % frames)
+                            const uint32_t q = (mine >> 6) * (uint32_t)PT_FUSED_PARTS + w_part;
+                            const uint32_t t = div_frames.div(q);
+                            f = q - t * rc.lanes_active; g = 0u;
+                            local = t * 64u + (mine & 63u);
+                            slot = slot_base + f * rc.slots_per_lane + local;
+                        }
+                        const uint32_t tw = s_wtile[(mine - w_base) >> 6];
+                        const uint32_t px = (tw & 0xFFFFu) * 8u + (local & 7u), py = (tw >> 16) * 8u + ((local >> 3) & 7u);
+                        const uint32_t sample0 = (HYB && w_tails) ? rc.head_samples + g : g * rc.group_size;
+                        const bool in_image = px < rc.width && py < rc.height && f < rc.lanes_active && sample0 < rc.spp;
+                        if (in_image && ptc::pixel_culled(rc, px, py)) {
+                            PT_FB(FB_CULLED)
+                            // every sample of the slot: one camera ray, a miss, color += 1 * env -- without the walk that would find nothing (fused_cull.h)
+                            if (GROUPED) cull_n = ptc::finish_group(rc, rad, slot, g);
+                            else if (!(HYB && w_tails)) cull_n = ptc::finish_plain(rc, rad, slot);
+                            // (head + tail: the head slot stands for ALL spp samples of such a pixel -- the same adds in the same order -- and its
+                            // tail slots are nothing: k_resolve does not replay the logs of a pixel outside the rectangle)
+                        } else if (in_image) {
+                            pxy = px | (py << 16);
+                            ctr = sample0;
+                            my_state[FS_A * FTB] = 0u;  // colour.r = +0.0f | term count = 0
+                            if (!GROUPED) { my_state[FS_B * FTB] = 0u; my_state[FS_C * FTB] = 0u; }
+                            my_state[FS_MB * FTB] = (uint32_t)((int32_t)rc.spp * (rc.frame_base + (int32_t)f)) + 1u;
+                            stk.clear_to_bottom();  // (a path)
+                            need_primary = true;
+                            dev.slot_begin();
+                        } else if (GROUPED) {
+                            rad.nterm[slot] = 0u;  // (a slot outside the image or the batch: k_resolve never reads it, kept defined anyway)
+                        } else if (HYB && w_tails) {
+                            rad.nterm[slot - rc.n_head] = 0u;
+                        }
                     }
                 }
                 w_next += take;
@@ -731,7 +765,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 PT_FB(FB_SETUP)
                 my_state[FS_SLOT * FTB] = slot; my_state[FS_CTR * FTB] = ctr; my_state[FS_SEED * FTB] = seed;
                 my_state[FS_WR * FTB] = __float_as_uint(wr); my_state[FS_WG * FTB] = __float_as_uint(wg); my_state[FS_WB * FTB] = __float_as_uint(wb);
-                my_state[FS_PXY * FTB] = pxy;
+                if constexpr (!RAYS) my_state[FS_PXY * FTB] = pxy;
                 if constexpr (NEE) {
                     my_nee[FS_NEE_POS * FTB] = shadow ? bpos : PT_MISS;
                     if (shadow) {
@@ -918,4 +952,27 @@ __global__ __launch_bounds__(FTB, PT_FUSED_WAVES_NEE) void k_fused_nee_log(Rende
 {
     fused_body<0, PAIRS, false, true, true>(rc, tiles, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, slot_base, n_slots, next_slot, stats, refill,
                                             tmin, tmax, lds_stack, div_frames, 0.f, lights, n_lights, light_area, log);
+}
+// the kernels of PT_RADIANCE_FUSED (RAYS): k_fused<0, PAIRS> and k_fused_nee<PAIRS> started from the caller's rays.  `tiles` is gone, `rays` is new;
+// div_m divides by the chunk's rays.  Instantiated in fused_rays.hip only.
+template <bool PAIRS>
+__global__ __launch_bounds__(FTB, PT_FUSED_WAVES) void k_fused_rays(RenderConst rc, Radiance rad, const float4 *__restrict__ g_wide, const float4 *__restrict__ g_tri4,
+                                                                   const float4 *__restrict__ g_shade4, const float4 *__restrict__ g_frame4,
+                                                                   uint32_t n_wide, uint32_t n_tris, uint32_t n_slots, uint32_t *next_slot,
+                                                                   unsigned long long *stats, int refill, float tmin, float tmax, int lds_stack,
+                                                                   FastDiv div_m, float self_c1, RdRays rays)
+{
+    fused_body<0, PAIRS, false, false, false, true>(rc, nullptr, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, 0u, n_slots, next_slot, stats, refill, tmin,
+                                                    tmax, lds_stack, div_m, self_c1, nullptr, 0u, 0.f, nullptr, rays);
+}
+template <bool PAIRS>
+__global__ __launch_bounds__(FTB, PT_FUSED_WAVES_NEE) void k_fused_nee_rays(RenderConst rc, Radiance rad, const float4 *__restrict__ g_wide,
+                                                                           const float4 *__restrict__ g_tri4, const float4 *__restrict__ g_shade4,
+                                                                           const float4 *__restrict__ g_frame4, uint32_t n_wide, uint32_t n_tris,
+                                                                           uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, int refill,
+                                                                           float tmin, float tmax, int lds_stack, FastDiv div_m,
+                                                                           const float4 *__restrict__ lights, uint32_t n_lights, float light_area, RdRays rays)
+{
+    fused_body<0, PAIRS, false, true, false, true>(rc, nullptr, rad, g_wide, g_tri4, g_shade4, g_frame4, n_wide, n_tris, 0u, n_slots, next_slot, stats, refill, tmin,
+                                                   tmax, lds_stack, div_m, 0.f, lights, n_lights, light_area, nullptr, rays);
 }

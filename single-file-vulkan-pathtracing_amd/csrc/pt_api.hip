@@ -710,7 +710,7 @@ pt_status pt_radiance_device(pt_scene *s, const pt_radiance_desc *d, uint64_t n,
 pt_status pt_radiance_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes)
 {
     if (!ctx || !bytes) return PT_ERR_INVALID_ARG;
-    *bytes = (uint64_t)ctx->rd.bytes + (uint64_t)ctx->rd.sq_bytes;
+    *bytes = (uint64_t)ctx->rd.bytes + (uint64_t)ctx->rd.sq_bytes + (uint64_t)ctx->rd.f_bytes;
     return PT_OK;
 }
 

@@ -96,6 +96,11 @@ struct pt_ctx {
         float *d_sq_tmax = nullptr; uint32_t *d_sq_slot = nullptr;
         size_t cap = 0, cap_sq = 0;                                // slots the per-slot arrays / the shadow queue hold
         size_t bytes = 0, sq_bytes = 0;                            // device bytes of the two sets
+        // PT_RADIANCE_FUSED: a set of its own -- the accumulators k_radiance_resolve reads and the fused kernel's eight slot counters.  A context
+        // that only ever runs the single-kernel form holds nothing else
+        float4 *d_fcolor = nullptr;
+        uint32_t *d_fcount = nullptr;                              // PTW_FUSED_COUNT_BYTES
+        size_t cap_f = 0, f_bytes = 0;
     } rd;
 };
 // The workspace budget a context plans within when the caller names none: 8 GB.  Round 6, one MI355X, Grays/s at 2 / 4 / 8 / 16 / 32 GB / no

@@ -53,6 +53,42 @@ __device__ __forceinline__ void rd_generate(const float *__restrict__ rays6, con
     rayB[slot] = make_float2(r4, r5);
 }
 
+// ---- the single-kernel form (PT_RADIANCE_FUSED: fused_kernel.h RAYS, fused_rays.hip): the index arithmetic of its slot hand-out ---------------
+// The chunk's m * spp slots keep the layout above (slot = s * m + r), so k_radiance_resolve reads what the fused kernel stored.  The kernel hands
+// slots out as k_fused does with one sample group: the launch's slot count, a multiple of 64, is cut into 64-slot chunks, part p of RDF_PARTS owns
+// every RDF_PARTS-th chunk beginning with chunk p and has a counter of its own; position `mine` of part p is slot ((mine >> 6) * RDF_PARTS + p) * 64
+// + (mine & 63).  m * spp is no multiple of 64 in general and the part arithmetic drops a partial last chunk, so the launch hands out
+// rdf_launch_slots (rounded UP) and the kernel leaves the slots that are not live alone.  tests/radiance_fused_host.cpp runs these statements.
+constexpr uint32_t RDF_PARTS = 8u;
+// what a launch takes beside k_fused's arguments: the chunk's rows and seeds, and the two halves of the hashed seed's inputs that do not change
+// with the slot -- index0 = (uint32)first + index_base (the ray's position in the call is first + r), seed_m0 = spp * (uint32)frame + 1
+struct RdRays {
+    const float *rays6;
+    const uint32_t *seeds;
+    uint32_t m, spp, index0, seed_m0;
+};
+inline RdRays rdf_rays(const float *rays6, const uint32_t *seeds, const RdCall &c, uint64_t first, uint32_t m)
+{
+    return { rays6, seeds, m, c.spp, (uint32_t)first + c.index_base, c.spp * (uint32_t)c.frame + 1u };
+}
+constexpr uint32_t rdf_launch_slots(uint32_t live) { return (live + 63u) & ~63u; }  // (the launcher's, on the host)
+// positions part p hands out of a launch of ns slots (ns a multiple of 64): 64 x the chunks q < ns / 64 with q % RDF_PARTS == p
+__device__ __forceinline__ uint32_t rdf_part_end(uint32_t ns, uint32_t part) { return (((ns >> 6) + RDF_PARTS - 1u - part) / RDF_PARTS) << 6; }
+__device__ __forceinline__ uint32_t rdf_slot(uint32_t mine, uint32_t part) { return (((mine >> 6) * RDF_PARTS + part) << 6) + (mine & 63u); }
+__device__ __forceinline__ bool rdf_live(uint32_t slot, uint32_t live) { return slot < live; }
+// slot -> (sample, ray of the chunk); div_m divides by m (wavefront_types.h FastDiv, or anything with its div)
+template <class Div>
+__device__ __forceinline__ void rdf_sample_ray(uint32_t slot, uint32_t m, const Div &div_m, uint32_t &s, uint32_t &r)
+{
+    s = div_m.div(slot);
+    r = slot - s * m;
+}
+// the seed rd_generate gives sample s of ray r
+__device__ __forceinline__ uint32_t rdf_seed(const RdRays &a, uint32_t r, uint32_t s)
+{
+    return a.seeds ? a.seeds[(size_t)r * a.spp + s] : rd_hashed_seed(r + a.index0, s + a.seed_m0);
+}
+
 // ---- k_radiance_resolve: ray r of the chunk -> the ordered sum of its samples' accumulators, / spp, the store or the film's blend -------------
 // radiance / moment2: the chunk's first row (moment2 nullable).  An old value is read only under accumulate at frame != 0.
 __device__ __forceinline__ void rd_resolve(const float4 *__restrict__ color, const RdCall &c, uint32_t r, uint32_t m, float *__restrict__ radiance,

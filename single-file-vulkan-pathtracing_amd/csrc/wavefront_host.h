@@ -195,6 +195,13 @@ void ptw_launch_fused(const FusedPlan &fp, int mode, const ptw::FastDiv &div_fra
 // fused_guided.hip: the same launch by the kernels that also write the first-hit log (pt_render_guided; guided_kernel.h has the log's layout)
 pt_status ptw_launch_fused_log(const FusedPlan &fp, int mode, const ptw::FastDiv &div_frames, const ptw::RenderConst &rc, const uint32_t *tiles, const ptw::Radiance &rad, const pt_scene *s,
                                uint32_t n_slots, uint32_t *next_slot, unsigned long long *stats, float tmin, float tmax, uint2 *log, hipStream_t st);
+// fused_rays.hip: the single-level kernels started from a caller's rays (pt_radiance_device with PT_RADIANCE_FUSED; fused_kernel.h RAYS).  rc.n_slots: the
+// chunk's live slots, m * spp, sample-major; rays6 / seeds: the chunk's rows; index0, seed_m0: radiance_device_kernel.h RdRays.  next_slot: eight
+// zeroed counters, PT_FUSED_PART_STRIDE dwords apart
+pt_status ptw_launch_fused_rays(const FusedPlan &fp, const ptw::RenderConst &rc, const ptw::Radiance &rad, const pt_scene *s, uint32_t *next_slot, unsigned long long *stats,
+                                float tmin, float tmax, const float *rays6, const uint32_t *seeds, uint32_t m, uint32_t spp, uint32_t index0, uint32_t seed_m0,
+                                hipStream_t st);
+constexpr size_t PTW_FUSED_COUNT_BYTES = 8 * 32 * sizeof(uint32_t);  // ... in bytes (fused_kernel.h PT_FUSED_PARTS x PT_FUSED_PART_STRIDE dwords)
 // guided.hip: the records of the launch's frames folded into the film's guide planes (id_frame: the frame of the launch that is the call's last, or
 // >= rc.lanes_active); inst_frame: FusedPlan::inst_frame
 void ptg_launch_reduce(const pt_scene *s, pt_film *f, const ptw::RenderConst &rc, const uint32_t *tiles, uint32_t id_frame, const float4 *inst_frame, hipStream_t st);
