@@ -809,12 +809,31 @@ pt_status pt_trace(pt_scene *scene, const float *rays6, uint32_t n, float tmin, 
  * 7.7 / 5.4 / 4.4 ms: every chunk ends in a tail in which the extend kernel's persistent waves run out of rays.  Nothing beyond 2^22 was swept
  * (DESIGN.md section 22).
  *
+ * The single-kernel form.  PT_TRACE_FUSED runs the rays of a launch through ONE persistent kernel: a lane reads row i of d_rays6 (and, for
+ * PT_TRACE_ANY, d_tmax[i]), walks the scene in LDS and writes ray i's answer straight into the caller's arrays -- no pack and unpack launches, no
+ * queues, no hit records in memory and NO workspace (pt_trace_workspace_bytes is unchanged by such a call; a context that only ever runs this form
+ * reports 0).  The outputs are byte for byte those of the queue form, for both modes and every subset of the output pointers, and every statement
+ * and refusal above holds (d_tmax with PT_TRACE_CLOSEST stays PT_ERR_UNSUPPORTED).  It applies where the queue form would run the compact LDS
+ * kernel: a single-level scene, desc.extend == PT_EXTEND_AUTO, nodes and triangles within the LDS class (24 KB, 2047 triangles, 16 stack entries)
+ * and tmin > 0; pair-leaf trees and leaves of up to four (pt_tuning.pair_leaves = 0 or pair_kernel = 0).  Everywhere else -- instanced scenes,
+ * scenes beyond the LDS class, a named extend kernel, tmin <= 0 -- PT_TRACE_FUSED is PT_ERR_UNSUPPORTED with nothing launched or written (the text
+ * names the class).  chunk_rays bounds the queue form's workspace and is ignored: one launch per 2^30 rays.  pt_stats: launches_extend grows by one
+ * per launch, ms_extend by the kernel's own time (blocking calls), launches_other and rounds stay, extend_variant = PT_EXTEND_LDS.
+ * PT_TRACE_AUTO takes the single-kernel form where it applies AND won the measurements of DESIGN.md section 26 for the kind of query (PT_TRACE_CLOSEST
+ * into d_hits alone, PT_TRACE_CLOSEST with surface planes, PT_TRACE_ANY), else the queue form; it is never an error the call would not be without
+ * it.  Measured on the MI355X (Cornell box, 2^20 and 2^24 rays, coherent and shuffled, medians of 7 against the queue form of the previous
+ * build, profiles/trace_fused_probe.json): the single-kernel form's slowest pass was faster than the queue form's fastest on every shape of every
+ * kind -- d_hits alone 1.36x .. 2.10x, with the surface planes 1.20x .. 1.98x, PT_TRACE_ANY 1.45x .. 2.29x -- so PT_TRACE_AUTO takes it for all
+ * three kinds wherever it applies.
+ * Under either bit pt_stats.pipeline says which form ran (PT_PIPELINE_FUSED / PT_PIPELINE_WAVEFRONT); without them the field is not touched and the
+ * call is exactly the queue form above.  PT_TRACE_ASYNC combines with both.  The two bits together are PT_ERR_INVALID_ARG.
+ *
  * Refusals, with nothing launched and nothing written -- PT_ERR_INVALID_ARG: NULL scene or desc; NULL d_rays6 with n > 0; an unknown mode or
- * flag; a nonzero reserved word; tmin or tmax not finite, or tmax <= tmin; PT_TRACE_CLOSEST with all of d_hits and the surface pointers NULL or
+ * flag; PT_TRACE_FUSED together with PT_TRACE_AUTO; a nonzero reserved word; tmin or tmax not finite, or tmax <= tmin; PT_TRACE_CLOSEST with all of d_hits and the surface pointers NULL or
  * with d_occluded set; PT_TRACE_ANY with d_occluded NULL or with d_hits or a surface pointer set; an unknown extend value.  PT_ERR_UNSUPPORTED:
- * d_tmax with PT_TRACE_CLOSEST; PT_EXTEND_FLAT and the variants the scene has no tree for (pt_trace's rules).                                */
+ * d_tmax with PT_TRACE_CLOSEST; PT_EXTEND_FLAT and the variants the scene has no tree for (pt_trace's rules); PT_TRACE_FUSED outside its class. */
 enum { PT_TRACE_CLOSEST = 0, PT_TRACE_ANY = 1 };
-enum { PT_TRACE_ASYNC = 1u };
+enum { PT_TRACE_ASYNC = 1u, /* (2: no flag) */ PT_TRACE_FUSED = 4u, PT_TRACE_AUTO = 8u };
 #define PT_TRACE_DEFAULT_CHUNK_RAYS (1u << 22)
 typedef struct pt_trace_desc {
     const void *d_rays6;     /* DEVICE, n x {origin.xyz, direction.xyz} f32, dense, 4-byte aligned */
@@ -825,7 +844,7 @@ typedef struct pt_trace_desc {
     float tmin, tmax;
     uint32_t mode;           /* PT_TRACE_* */
     uint32_t extend;         /* PT_EXTEND_*, pt_trace's rules */
-    uint32_t flags;          /* PT_TRACE_ASYNC or 0 */
+    uint32_t flags;          /* PT_TRACE_ASYNC | one of PT_TRACE_FUSED, PT_TRACE_AUTO, or 0 */
     uint32_t chunk_rays;     /* rays per launch; 0 = PT_TRACE_DEFAULT_CHUNK_RAYS; rounded up to a multiple of 64 */
     uint32_t reserved[4];    /* must be 0 */
 } pt_trace_desc;             /* 104 bytes */

@@ -134,6 +134,7 @@ class AdaptiveResult(C.Structure):
 
 TRACE_CLOSEST, TRACE_ANY = 0, 1   # include/pt_api.h PT_TRACE_*: the query pt_trace_device answers
 TRACE_ASYNC = 1                   # ... PT_TRACE_ASYNC: queue only, Context.sync() waits
+TRACE_FUSED, TRACE_AUTO = 4, 8    # ... its form: the single kernel (or PT_ERR_UNSUPPORTED) | the library's choice; neither: the queues
 
 
 class TraceDesc(C.Structure):
@@ -715,12 +716,18 @@ class Scene:
         self.ctx._check(lib_amd().pt_trace_device(self.h, C.byref(d), n, C.byref(ms)))
         return ms.value
 
-    def trace_tensors(self, rays, tmax_per_ray=None, mode=TRACE_CLOSEST, surface=False, tmin=0.001, tmax=10000.0, extend=EXTEND_AUTO, chunk_rays=0):
+    def trace_tensors(self, rays, tmax_per_ray=None, mode=TRACE_CLOSEST, surface=False, tmin=0.001, tmax=10000.0, extend=EXTEND_AUTO, chunk_rays=0,
+                      form="queues"):
         """Ray queries on torch tensors, nothing through the host.  rays: float32 CUDA tensor [n, 6] {origin, direction} (made contiguous if it
         is not).  TRACE_CLOSEST -> dict of tensors: prim (int32, -1 = miss), t, u, v (float32), inst (int32) -- views of one [n, 5] buffer in
         pt_hit's layout, no copy -- and, with surface, position / normal / albedo / emission [n, 3].  TRACE_ANY -> bool tensor [n], True = some
-        triangle with tmin < t < bound; the bound is tmax_per_ray[i] (float32 CUDA tensor [n]) or tmax."""
+        triangle with tmin < t < bound; the bound is tmax_per_ray[i] (float32 CUDA tensor [n]) or tmax.
+        form: "queues" (pack, extend, unpack), "fused" (PT_TRACE_FUSED: the single kernel, an error where it does not apply) or "auto"
+        (PT_TRACE_AUTO); the result does not depend on it."""
         import torch
+        forms = {"queues": 0, "fused": TRACE_FUSED, "auto": TRACE_AUTO}
+        if form not in forms:
+            raise ValueError('form must be "queues", "fused" or "auto"')
         if rays.dtype != torch.float32 or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 6:
             raise ValueError("rays must be a float32 CUDA tensor of shape [n, 6]")
         rays = rays.contiguous()
@@ -730,7 +737,8 @@ class Scene:
             if tmax_per_ray.dtype != torch.float32 or tmax_per_ray.device != dev or tmax_per_ray.numel() != n:
                 raise ValueError("tmax_per_ray must be a float32 tensor of n elements on the rays' device")
             bound = tmax_per_ray.contiguous()
-        kw = dict(tmax_ptr=bound.data_ptr() if bound is not None else None, mode=mode, tmin=tmin, tmax=tmax, extend=extend, chunk_rays=chunk_rays)
+        kw = dict(tmax_ptr=bound.data_ptr() if bound is not None else None, mode=mode, tmin=tmin, tmax=tmax, extend=extend, chunk_rays=chunk_rays,
+                  flags=forms[form])
         # The rays (and the outputs' allocations) were produced on torch's current stream; the query runs on the context's.  So torch's stream is
         # drained first.  The call itself is blocking -- it returns after the context's stream has finished -- which orders the outputs before
         # whatever torch queues next.  (No TRACE_ASYNC here: torch would have no event to wait on.)

@@ -9,6 +9,8 @@
 //   k_trace_occluded   hit records -> one byte per ray
 // one chunk of desc.chunk_rays after the other on the context's stream, through a workspace that belongs to the context and only grows.
 // The per-lane bodies are trace_device_kernel.h (compiled for the host by tests/trace_device_host.cpp).  No LDS, no scratch.
+// PT_TRACE_FUSED / PT_TRACE_AUTO: where the scene is of the compact LDS kernel's class the rays of a launch go through ONE kernel instead
+// (trace_fused.hip), with no workspace; this unit has the class test, PT_TRACE_AUTO's table and the launch loop (trace_fused below).
 #include "wavefront_host.h"
 
 #include <algorithm>
@@ -69,6 +71,65 @@ pt_status ensure_trace(pt_ctx *ctx, size_t rays)
     return rc;
 }
 
+// What PT_TRACE_AUTO takes where the single-kernel form applies, per kind of query { PT_TF_HITS, PT_TF_SURFACE, PT_TF_ANY }: the single-kernel form
+// only where its max lay below the parent build's min on EVERY measured shape of that kind (profiles/trace_fused_probe.json:
+// 2^20 and 2^24 rays, coherent and shuffled -- it did on all four shapes of all three kinds, by 1.36x .. 2.10x, 1.20x .. 1.98x and 1.45x .. 2.29x)
+constexpr bool TD_AUTO_TAKES_FUSED[3] = { true, true, true };
+
+// Does the single-kernel form apply?  The class is the compact LDS kernel's (k_extend_lds7 / _lds7p) with the variant left to the library.
+// -> null, or what keeps the call out of the class
+const char *trace_fused_refusal(const pt_scene *s, const pt_trace_desc *d, const ExtendPlan &pl)
+{
+    if (s->n_inst) return "the scene is instanced";
+    if (d->extend != PT_EXTEND_AUTO) return "pt_trace_desc.extend names a kernel (it must be PT_EXTEND_AUTO)";
+    if (!(pl.lds_scene && !pl.spill)) return "the scene is beyond the compact LDS kernel (24 KB of nodes and triangles, 2047 triangles, 16 stack entries)";
+    if (!(d->tmin > 0.f)) return "tmin <= 0 (one-dword stack entries order like their distances for positive ones only)";
+    return nullptr;
+}
+
+// the launches of a call through k_trace_fused: one per 2^30 rays, straight from the caller's rows to the caller's records
+pt_status trace_fused(pt_scene *s, const pt_trace_desc *d, uint64_t n, const ExtendPlan &pl, const TraceFusedPlan &tp, float *device_ms)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    if (device_ms) *device_ms = 0.f;
+    const uint64_t n_launches = (n + TD_MAX_CHUNK - 1) / TD_MAX_CHUNK;
+    const bool async = (d->flags & PT_TRACE_ASYNC) != 0;
+    if (!async) {
+        while (ctx->ev_pool.size() < 2 * n_launches) {
+            hipEvent_t e = nullptr;
+            PT_HIP(ctx, hipEventCreate(&e));
+            ctx->ev_pool.push_back(e);
+        }
+        PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    }
+    for (uint64_t c = 0; c < n_launches; c++) {
+        const uint64_t off = c * TD_MAX_CHUNK;
+        const uint32_t m = (uint32_t)std::min<uint64_t>(TD_MAX_CHUNK, n - off);
+        const auto plane = [&](void *p) { return p ? static_cast<float *>(p) + 3 * off : nullptr; };
+        const TraceFusedIO io = { static_cast<const float *>(d->d_rays6) + 6 * off,
+                                  d->d_tmax ? static_cast<const float *>(d->d_tmax) + off : nullptr,
+                                  d->d_hits ? static_cast<pt_hit *>(d->d_hits) + off : nullptr,
+                                  d->d_occluded ? static_cast<uint8_t *>(d->d_occluded) + off : nullptr,
+                                  plane(d->d_position), plane(d->d_normal), plane(d->d_albedo), plane(d->d_emission) };
+        ptw_launch_trace_fused(tp, s, io, m, d->tmin, d->tmax, st, async ? nullptr : ctx->ev_pool[2 * c], async ? nullptr : ctx->ev_pool[2 * c + 1]);
+    }
+    ctx->stats.launches_extend += (uint32_t)n_launches;
+    ctx->stats.extend_variant = pl.variant;
+    ctx->stats.pipeline = PT_PIPELINE_FUSED;
+    PT_HIP(ctx, hipGetLastError());
+    if (async) return PT_OK;
+    PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipGetLastError());
+    if (device_ms) PT_HIP(ctx, hipEventElapsedTime(device_ms, ctx->ev_a, ctx->ev_b));
+    for (uint64_t c = 0; c < n_launches; c++) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->ev_pool[2 * c], ctx->ev_pool[2 * c + 1]) == hipSuccess) ctx->stats.ms_extend += ms;
+    }
+    return PT_OK;
+}
+
 }  // namespace
 
 void ptt_free(pt_ctx *ctx)
@@ -83,7 +144,9 @@ pt_status ptt_trace_device(pt_scene *s, const pt_trace_desc *d, uint64_t n, floa
     hipStream_t st = ctx->stream;
     // ---- refusals: nothing launched, nothing written
     if (d->mode > PT_TRACE_ANY) return pt_bad(ctx, "pt_trace_desc.mode is neither PT_TRACE_CLOSEST nor PT_TRACE_ANY");
-    if (d->flags & ~(uint32_t)PT_TRACE_ASYNC) return pt_bad(ctx, "pt_trace_desc.flags has bits other than PT_TRACE_ASYNC");
+    if (d->flags & ~(uint32_t)(PT_TRACE_ASYNC | PT_TRACE_FUSED | PT_TRACE_AUTO)) return pt_bad(ctx, "pt_trace_desc.flags has bits other than PT_TRACE_ASYNC, _FUSED and _AUTO");
+    const uint32_t form = d->flags & (uint32_t)(PT_TRACE_FUSED | PT_TRACE_AUTO);
+    if (form == (uint32_t)(PT_TRACE_FUSED | PT_TRACE_AUTO)) return pt_bad(ctx, "pt_trace_desc.flags: PT_TRACE_FUSED and PT_TRACE_AUTO exclude each other");
     PT_TRY(pt_check_reserved(ctx, "pt_trace_desc", d->reserved));
     if (!(std::isfinite(d->tmin) && std::isfinite(d->tmax) && d->tmax > d->tmin)) return pt_bad(ctx, "pt_trace_desc: tmin and tmax must be finite, tmin < tmax");
     const bool any = d->mode == PT_TRACE_ANY;
@@ -108,6 +171,20 @@ pt_status ptt_trace_device(pt_scene *s, const pt_trace_desc *d, uint64_t n, floa
     if (n == 0) { if (device_ms) *device_ms = 0.f; return PT_OK; }
     ExtendPlan pl;
     PT_TRY(ptw_plan_extend(s, d->extend, pl));  // (repairs a scene that lost its trees; builds the 8-wide tree on first request)
+    // the form: the single-kernel one where PT_TRACE_FUSED asks for it (or refuses), or where PT_TRACE_AUTO finds it applies and measured faster
+    if (form) {
+        const int kind = any ? PT_TF_ANY : surface ? PT_TF_SURFACE : PT_TF_HITS;
+        const char *why = trace_fused_refusal(s, d, pl);
+        if (why && form == PT_TRACE_FUSED) {
+            ctx->err = std::string("PT_TRACE_FUSED is for single-level scenes that the compact LDS kernel walks (PT_EXTEND_AUTO, tmin > 0): ") + why;
+            return PT_ERR_UNSUPPORTED;
+        }
+        if (!why && (form == PT_TRACE_FUSED || TD_AUTO_TAKES_FUSED[kind])) {
+            TraceFusedPlan tp;
+            PT_TRY(ptw_plan_trace_fused(s, pl, kind, tp));
+            return trace_fused(s, d, n, pl, tp, device_ms);
+        }
+    }
     const float4 *inst_frame = nullptr;
     if (surface && s->n_inst && ctx->tune.inst_frames != 0) {  // the table k_shade<INST> and k_aov_reduce<INST> read, when the context uses it
         PT_TRY(ptb_ensure_inst_frames(s));
@@ -162,6 +239,7 @@ pt_status ptt_trace_device(pt_scene *s, const pt_trace_desc *d, uint64_t n, floa
     }
     ctx->stats.launches_extend += (uint32_t)n_chunks;
     ctx->stats.launches_other += others;
+    if (form) ctx->stats.pipeline = PT_PIPELINE_WAVEFRONT;  // (PT_TRACE_AUTO: the form that ran)
     PT_HIP(ctx, hipGetLastError());
     if (async) return PT_OK;
     PT_HIP(ctx, hipEventRecord(ctx->ev_b, st));

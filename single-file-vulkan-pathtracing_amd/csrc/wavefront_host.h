@@ -7,6 +7,7 @@
 //   aov.hip             pt_render_aov: the guide buffers' kernels, plan and launch
 //   adaptive.hip        pt_render_adaptive: the selection of the tiles a render runs over, and the resolve that blends by a pixel's own count
 //   trace_device.hip    pt_trace_device: rays in device memory packed into the queues, the extend launch per chunk, hit records into the caller's arrays
+//   trace_fused.hip     ... its single-kernel form (PT_TRACE_FUSED): k_trace_fused, its plan and its launch
 //   film_work.hip       the film's workspace: how many slots a render gets (RenderShape) and the buffers behind them
 //   render.hip          pt_render / _prepare / _adaptive / _guided / pt_trace: one CallPlan (pipeline resolved, kernels planned once) and one Job per call;
 //                       wavefront: batches, pipelines on streams, rounds, polls; fused: shape, launches; shared: redo, selection, radiance record, timed tail
@@ -77,6 +78,28 @@ void ptw_launch_extend(const ExtendPlan &pl, pt_scene *s, const float4 *rayA, co
                        const uint32_t *count_in, uint32_t *count_zero, unsigned long long *stats, float tmin, float tmax, bool count,
                        bool raw_hit, hipStream_t st, int pipe = 0, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
                        const uint32_t *perm = nullptr, const float *ray_tmax = nullptr);
+
+// ---- trace_fused.hip (pt_trace_device with PT_TRACE_FUSED: one kernel from the caller's rows to the caller's records) --------------------
+enum { PT_TF_HITS = 0, PT_TF_SURFACE = 1, PT_TF_ANY = 2 };  // the kinds of query: CLOSEST into d_hits alone | with surface planes | ANY
+struct TraceFusedPlan {
+    int kind = PT_TF_HITS;
+    bool pairs = false;  // ExtendPlan::pairs
+    size_t smem = 0;     // ExtendPlan::smem: the compact LDS kernel's image and stack
+    int grid = 0, refill = 16;
+};
+// the caller's arrays of one launch, each at the launch's first ray.  hits: pt_hit rows (PT_TF_HITS: set; PT_TF_SURFACE: nullable, as is each
+// plane); d_tmax (PT_TF_ANY): nullable
+struct TraceFusedIO {
+    const float *rays6, *d_tmax;
+    void *hits;
+    uint8_t *occluded;
+    float *position, *normal, *albedo, *emission;
+};
+// for a plan of the compact LDS class (pl.lds_scene && !pl.spill; the caller has checked tmin > 0): the grid from the kernel's own occupancy
+pt_status ptw_plan_trace_fused(pt_scene *s, const ExtendPlan &pl, int kind, TraceFusedPlan &tp);
+// n <= 2^30 rays (the row index inside a launch is 32 bits); ev0 / ev1 (nullable): the kernel's own start / stop events
+void ptw_launch_trace_fused(const TraceFusedPlan &tp, const pt_scene *s, const TraceFusedIO &io, uint32_t n, float tmin, float tmax, hipStream_t st,
+                            hipEvent_t ev0, hipEvent_t ev1);
 
 // ---- shade_kernels.hip -----------------------------------------------------------------------------------------------
 // everything a k_shade launch takes; `in` / `out` / the counts change from round to round, the rest per batch
