@@ -176,6 +176,29 @@ enum { PT_SCENE_UPDATE_REFIT = 0, PT_SCENE_UPDATE_REBUILD = 1 };
 pt_status pt_scene_update(pt_scene *scene, const float *vertices, uint32_t n_verts,
                           const uint32_t *indices, uint32_t n_tris, uint32_t mode);
 
+/* pt_scene_create and pt_scene_update for geometry that lives in DEVICE memory (a simulation, skinning, an optimiser moving a mesh): the
+ * arrays have the layouts of pt_scene_create -- d_vertices f32 [3 * n_verts], d_indices u32 [3 * n_tris], d_faces f32 [6 * n_tris] -- dense,
+ * 4-byte aligned, on the context's device.  After either call the scene is in the state the host call would have left with host copies of
+ * the same bytes: every read-back, every field of pt_scene_get_info but build_ms, every render, trace and film pass, and whatever a later
+ * pt_scene_set_bvh_quality, pt_scene_set_instances or update in either form builds from the scene's kept state are equal bit for bit.  Host
+ * and device updates of one scene may be mixed freely.
+ * Execution: blocking, and ordered after the work queued on the context's stream (a PT_FLAG_ASYNC render queued before the update sees the
+ * old geometry).  The arrays are read on the context's stream: the caller must have finished writing them.  They are not retained: after
+ * return -- whatever the status -- they may be freed or overwritten; the scene holds copies, as the host calls do.
+ * No vertex, index or face array crosses to the host, in either direction.  What is read back is bounded: one word of the index check; the
+ * emitters' count, their records (80 B each) and, at create, their primitive ids (a scene made from host arrays sends its ids, 4 B each, to
+ * the device once, at its first device update); and, for scenes of at most 2048 triangles only, the triangles' boxes (32 B each, as the host
+ * calls read them) and one byte per triangle of the pair relation: about 100 KB at most.
+ * Refusals are those of the host calls, with nothing changed in the scene and *out = NULL for create: NULL arguments, empty arrays, n_tris
+ * different from the scene's, an unknown mode, n_tris >= 2^28, and an index >= n_verts ("vertex index out of range").  The index check is a
+ * kernel that reads only the 3 * n_tris words of d_indices and runs before any kernel follows an index: an index out of range is never
+ * used as an address.  PT_SCENE_UPDATE_REFIT turns into a rebuild under pt_scene_update's rule, and a failed rebuild leaves the scene broken
+ * as there.  DESIGN.md section 27.                                                                                                          */
+pt_status pt_scene_create_device(pt_ctx *ctx, const void *d_vertices, uint32_t n_verts,
+                                 const void *d_indices, uint32_t n_tris, const void *d_faces, pt_scene **out);
+pt_status pt_scene_update_device(pt_scene *scene, const void *d_vertices, uint32_t n_verts,
+                                 const void *d_indices, uint32_t n_tris, uint32_t mode);
+
 /* Debug/parity read-back of the device-built LBVH.  keys/prim_of_pos: n_tris entries each;
  * nodes16: n_nodes x 16 dwords {lmin[3] lmax[3] rmin[3] rmax[3] left right 0 0}, child bit31 =
  * leaf (sorted position).  Any pointer may be NULL.                                         */

@@ -205,7 +205,7 @@ HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
 
 # every symbol include/pt_api.h and include/pt_host.h declare
 API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "pt_scene_create", "pt_scene_destroy",
-               "pt_scene_set_instances", "pt_scene_set_bvh_quality", "pt_scene_update",
+               "pt_scene_set_instances", "pt_scene_set_bvh_quality", "pt_scene_update", "pt_scene_create_device", "pt_scene_update_device",
                "pt_scene_get_info", "pt_scene_read_bvh", "pt_scene_read_bvh4", "pt_scene_read_bvh8", "pt_film_create", "pt_film_create_external", "pt_film_clear",
                "pt_film_read_f32", "pt_film_read_bgra8", "pt_film_destroy", "pt_params_default", "pt_render",
                "pt_render_prepare", "pt_trace", "pt_film_enable_aov", "pt_render_aov", "pt_film_read_aov",
@@ -262,6 +262,8 @@ def lib_amd():
         L.pt_scene_set_instances.argtypes = [vp, vp, C.c_uint32]
         L.pt_scene_set_bvh_quality.argtypes = [vp, C.c_uint32]
         L.pt_scene_update.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
+        L.pt_scene_create_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(vp)]
+        L.pt_scene_update_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
         L.pt_scene_get_info.argtypes = [vp, C.POINTER(SceneInfo)]
         L.pt_scene_read_bvh.argtypes = [vp, vp, vp, vp]
         L.pt_scene_read_bvh4.argtypes = [vp, vp]
@@ -664,6 +666,54 @@ class Scene:
         if v.size % 3 or i.size % 3:
             raise ValueError("vertices must be 3*nv, indices 3*nt")
         self.ctx._check(lib_amd().pt_scene_update(self.h, v.ctypes.data, v.size // 3, i.ctypes.data, i.size // 3, mode))
+
+    @staticmethod
+    def _geometry_tensors(vertices, indices, faces=None):
+        """The tensor rules of from_tensors / update_tensors -> contiguous (vertices, indices[, faces]); ValueError before a device is touched."""
+        import torch
+        index_types = (torch.int32, getattr(torch, "uint32", torch.int32))   # (int32 reinterpreted as u32: a negative index is out of range)
+        for name, t, kinds, per in (("vertices", vertices, (torch.float32,), 3), ("indices", indices, index_types, 3), ("faces", faces, (torch.float32,), 6)):
+            if t is None and name == "faces":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype not in kinds:
+                raise ValueError(f"{name} must be a {'int32 / uint32' if name == 'indices' else 'float32'} CUDA tensor")
+            if t.numel() % per or (name == "faces" and t.numel() != 2 * indices.numel()):
+                raise ValueError("vertices must be 3*nv, indices 3*nt, faces 6*nt")
+        for name, t in (("vertices", vertices), ("indices", indices), ("faces", faces)):
+            if t is not None and not t.is_cuda:
+                raise ValueError(f"{name} must be a CUDA tensor")
+            if t is not None and t.device != vertices.device:
+                raise ValueError("vertices, indices and faces must be on one device")
+        out = [vertices.contiguous(), indices.contiguous()] + ([faces.contiguous()] if faces is not None else [])
+        return out
+
+    @classmethod
+    def from_tensors(cls, ctx, vertices, indices, faces):
+        """A scene from torch tensors on the GPU, nothing through the host (pt_scene_create_device): vertices and faces float32 CUDA tensors of
+        3*nv and 6*nt elements, indices an int32 (or uint32) tensor of 3*nt; made contiguous if they are not.  Equal to Scene(ctx, ...) of
+        their host copies, bit for bit."""
+        import torch
+        v, i, f = cls._geometry_tensors(vertices, indices, faces)
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        torch.cuda.current_stream(v.device).synchronize()   # (Scene.trace_tensors has the reasons)
+        ctx._check(lib_amd().pt_scene_create_device(ctx.h, v.data_ptr(), v.numel() // 3, i.data_ptr(), i.numel() // 3, f.data_ptr(), C.byref(self.h)))
+        return self
+
+    def update_device(self, n_verts, vertices_ptr, n_tris, indices_ptr, mode=SCENE_UPDATE_REFIT):
+        """pt_scene_update_device over raw DEVICE pointers: f32 [3 * n_verts] and u32 [3 * n_tris], dense (include/pt_api.h).  Blocking."""
+        self.ctx._check(lib_amd().pt_scene_update_device(self.h, vertices_ptr, n_verts, indices_ptr, n_tris, mode))
+
+    def update_tensors(self, vertices, indices, mode=SCENE_UPDATE_REFIT):
+        """Scene.update for torch tensors on the GPU, nothing through the host: a float32 CUDA tensor of 3*nv elements and an int32 (or uint32)
+        tensor of 3*nt on the same device, made contiguous if they are not.  The result equals update() of their host copies."""
+        import torch
+        v, i = self._geometry_tensors(vertices, indices)
+        # The tensors were written on torch's current stream and the update reads them on the context's: torch's stream is drained first.  The
+        # call is blocking, which orders the read before whatever torch queues next (Scene.trace_tensors).
+        torch.cuda.current_stream(v.device).synchronize()
+        self.update_device(v.numel() // 3, v.data_ptr(), i.numel() // 3, i.data_ptr(), mode=mode)
 
     def snapshot_previous(self):
         """Remembers the scene as it stands now -- vertex positions and instance matrices -- as "the previous geometry" of Film.motion

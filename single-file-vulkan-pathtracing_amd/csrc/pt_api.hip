@@ -202,8 +202,30 @@ pt_status pt_scene_create(pt_ctx *ctx, const float *vertices, uint32_t n_verts, 
     pt_scene *s = new (std::nothrow) pt_scene();
     if (!s) return PT_ERR_OOM;
     s->ctx = ctx;
-    pt_status rc = guarded(ctx, [&] { return ptb_build_scene(s, vertices, n_verts, indices, n_tris, faces); });
+    pt_status rc = guarded(ctx, [&] { return ptb_build_scene(s, { vertices, n_verts, indices, faces, false }, n_tris); });
     if (rc != PT_OK) { pt_scene_destroy(s); return rc; }
+    *out = s;
+    return PT_OK;
+}
+
+// The arrays in device memory: the refusals of pt_scene_create, the index check as a kernel (scene_device.hip) before any kernel follows an index.
+// A failure waits for the stream before it returns: the caller's arrays are not read after the call, whatever it answers.
+pt_status pt_scene_create_device(pt_ctx *ctx, const void *d_vertices, uint32_t n_verts, const void *d_indices, uint32_t n_tris, const void *d_faces,
+                                 pt_scene **out)
+{
+    if (!ctx) return PT_ERR_INVALID_ARG;
+    if (!out || !d_vertices || !d_indices || !d_faces) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    *out = nullptr;
+    if (n_tris == 0 || n_verts == 0) { ctx->err = "empty scene"; return PT_ERR_INVALID_ARG; }
+    if (n_tris >= (1u << 28)) { ctx->err = "too many triangles (the BVH4 leaf encoding holds 2^28 - 1)"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    PT_TRY(guarded(ctx, [&] { return ptsd_check_indices(ctx, static_cast<const uint32_t *>(d_indices), n_tris, n_verts); }));
+    pt_scene *s = new (std::nothrow) pt_scene();
+    if (!s) return PT_ERR_OOM;
+    s->ctx = ctx;
+    const pt_geometry g = { static_cast<const float *>(d_vertices), n_verts, static_cast<const uint32_t *>(d_indices), static_cast<const float *>(d_faces), true };
+    pt_status rc = guarded(ctx, [&] { return ptb_build_scene(s, g, n_tris); });
+    if (rc != PT_OK) { (void)hipStreamSynchronize(ctx->stream); pt_scene_destroy(s); return rc; }
     *out = s;
     return PT_OK;
 }
@@ -244,7 +266,24 @@ pt_status pt_scene_update(pt_scene *s, const float *vertices, uint32_t n_verts, 
     for (size_t i = 0; i < 3 * (size_t)n_tris; i++)
         if (indices[i] >= n_verts) { ctx->err = "vertex index out of range"; return PT_ERR_INVALID_ARG; }
     PT_HIP(ctx, hipSetDevice(ctx->device));
-    return guarded(ctx, [&] { return ptb_update_scene(s, vertices, n_verts, indices, mode); });
+    return guarded(ctx, [&] { return ptb_update_scene(s, { vertices, n_verts, indices, nullptr, false }, mode); });
+}
+
+pt_status pt_scene_update_device(pt_scene *s, const void *d_vertices, uint32_t n_verts, const void *d_indices, uint32_t n_tris, uint32_t mode)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = s->ctx;
+    if (!d_vertices || !d_indices) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    if (mode > PT_SCENE_UPDATE_REBUILD) { ctx->err = "unknown update mode"; return PT_ERR_INVALID_ARG; }
+    if (n_tris == 0 || n_verts == 0) { ctx->err = "empty scene"; return PT_ERR_INVALID_ARG; }
+    if (n_tris != s->n_tris) { ctx->err = "an update keeps the scene's triangles (and their materials): n_tris must equal the scene's"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    // on the context's stream, so behind whatever is queued there; nothing of the scene has changed when it refuses
+    PT_TRY(guarded(ctx, [&] { return ptsd_check_indices(ctx, static_cast<const uint32_t *>(d_indices), n_tris, n_verts); }));
+    const pt_geometry g = { static_cast<const float *>(d_vertices), n_verts, static_cast<const uint32_t *>(d_indices), nullptr, true };
+    const pt_status rc = guarded(ctx, [&] { return ptb_update_scene(s, g, mode); });
+    if (rc != PT_OK) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
 }
 
 pt_status pt_scene_get_info(const pt_scene *s, pt_scene_info *info)

@@ -170,6 +170,7 @@ struct pt_scene {
     float light_area = 0.f;
     std::vector<float4> h_lights;   // host copy of d_lights: instancing makes its world-space copies from it
     std::vector<uint32_t> h_light_prim;  // the primitive of each emitter (pt_scene_update recomputes the records from new vertices)
+    uint32_t *d_light_prim = nullptr;    // ... on the device, for pt_scene_update_device (scene_device.hip; null until a device call needs it)
     // instanced scenes: every instance's emitters in world space, gl_InstanceID-major, same 5-float4 layout and running cdf
     std::vector<float> h_xforms;    // the instance set's object->world matrices as given (gl_InstanceID order): ptb_ensure_inst_lights
     float4 *d_lights_inst = nullptr;  // built on the first NEE render of the instance set
@@ -382,9 +383,11 @@ struct DevBuf {
 };
 
 #define PT_BROKEN_SCENE_MSG "the scene lost its acceleration structure in a failed rebuild (out of memory?): call pt_scene_set_bvh_quality again, or recreate it"
-// lbvh_build.hip
-pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices,
-                          uint32_t n_tris, const float *h_faces);
+// The scene arrays as a caller hands them over (include/pt_api.h has the layouts): in host memory (pt_scene_create, pt_scene_update) or in device
+// memory (pt_scene_create_device, pt_scene_update_device).  faces: pt_scene_create* only.
+struct pt_geometry { const float *vertices; uint32_t n_verts; const uint32_t *indices; const float *faces; bool on_device; };
+// scene_build.hip
+pt_status ptb_build_scene(pt_scene *s, const pt_geometry &g, uint32_t n_tris);
 pt_status ptb_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n);
 pt_status ptb_set_bvh_quality(pt_scene *s, uint32_t quality);
 void ptb_free_scene_buffers(pt_scene *s);
@@ -394,7 +397,15 @@ pt_status ptb_ensure_inst_frames(pt_scene *s);  // the table k_shade reads inste
 pt_status ptb_repair(pt_scene *s);        // no-op unless a rebuild of the tree products failed earlier: then one more try
 pt_status ptb_ensure_wide8(pt_scene *s);  // builds the 8-wide nodes of a scene that was created without them
 // pt_scene_update: new positions for the scene's triangles (mode PT_SCENE_UPDATE_REFIT / _REBUILD; arguments checked by the caller)
-pt_status ptb_update_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices, uint32_t mode);
+pt_status ptb_update_scene(pt_scene *s, const pt_geometry &g, uint32_t mode);
+// scene_device.hip: what the host paths of the two do on the host, as kernels over arrays in device memory.  check_indices: PT_ERR_INVALID_ARG
+// ("vertex index out of range") when one of the 3 * n_tris indices is >= n_verts; it reads d_indices only and waits for the answer.
+// find_emitters (create): n_lights, h_light_prim / d_light_prim and an unfilled d_lights from d_faces.  host_products: d_lights, h_lights and
+// light_area from d_tri_orig, d_faces and the emitters' ids, and (pair != nullptr: small scenes) find_fan_pairs' relation from d_tri_orig, behind
+// one wait for the stream.
+pt_status ptsd_check_indices(pt_ctx *ctx, const uint32_t *d_indices, uint32_t n_tris, uint32_t n_verts);
+pt_status ptsd_find_emitters(pt_scene *s);
+pt_status ptsd_host_products(pt_scene *s, std::vector<uint8_t> *pair);
 constexpr uint32_t PT_SAH_MAX_TRIS = 2048;
 // bvh4_sah_device.hip: surface-area sweep on the device (one workgroup) -> BVH4 rows (32 dwords each) + leaf order
 // pair_with_next (nullable): [n] flags, triangle i and i+1 are the two halves (v0,v1,v2),(v0,v2,v3) of a quad and form ONE primitive

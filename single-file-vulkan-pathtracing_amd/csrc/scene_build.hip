@@ -170,7 +170,7 @@ std::vector<pt_buf> ptb_scene_buffers(pt_scene *s, pt_scene_life life)
     switch (life) {
     case PT_LIFE_SOURCE:  // live as long as the scene: the kept triangles and materials, the per-triangle tables, the emitters
         return { pt_buf_of(s->d_tri_orig), pt_buf_of(s->d_faces), pt_buf_of(s->d_tri4), pt_buf_of(s->d_shade4), pt_buf_of(s->d_shade64),
-                 pt_buf_of(s->d_ke4), pt_buf_of(s->d_frame4), pt_buf_of(s->d_lights) };
+                 pt_buf_of(s->d_ke4), pt_buf_of(s->d_frame4), pt_buf_of(s->d_lights), pt_buf_of(s->d_light_prim) };
     case PT_LIFE_TREE:  // everything that hangs off the binary tree: dropped and made again by a rebuild
         return { pt_buf_of(s->d_nodes), pt_buf_of(s->d_keys), pt_buf_of(s->d_prim_of), pt_buf_of(s->d_prim_of_sah), pt_buf_of(s->d_wide_lbvh),
                  pt_buf_of(s->d_wide_sah), pt_buf_of(s->d_wide16), pt_buf_of(s->d_wide16t), pt_buf_of(s->d_wide8), pt_buf_of(s->d_prim_of8),
@@ -410,26 +410,34 @@ static void find_fan_pairs(const float *h_vertices, const uint32_t *h_indices, u
     }
 }
 
-// The caller's vertices and indices on the device and, after gather(), the de-indexed triangles in d_tri_orig with their boxes here.
+// The caller's vertices and indices on the device -- copies of host arrays, or the caller's own device arrays, read where they lie -- and, after
+// gather(), the de-indexed triangles in d_tri_orig with their boxes here.
 struct GeometryUpload {
     DevBuf<float> d_vert;
     DevBuf<uint32_t> d_idx;
     DevBuf<float4> d_tlo, d_thi;
-    pt_status upload(pt_ctx *ctx, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices, uint32_t n)
+    const float *vert = nullptr;    // what gather() reads
+    const uint32_t *idx = nullptr;
+    pt_status upload(pt_ctx *ctx, const pt_geometry &g, uint32_t n)
     {
         hipStream_t st = ctx->stream;
-        PT_HIP(ctx, d_vert.alloc(3 * (size_t)n_verts));
-        PT_HIP(ctx, d_idx.alloc(3 * (size_t)n));
+        if (!g.on_device) {
+            PT_HIP(ctx, d_vert.alloc(3 * (size_t)g.n_verts));
+            PT_HIP(ctx, d_idx.alloc(3 * (size_t)n));
+        }
         PT_HIP(ctx, d_tlo.alloc(n));
         PT_HIP(ctx, d_thi.alloc(n));
-        PT_HIP(ctx, hipMemcpyAsync(d_vert.p, h_vertices, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, st));
-        PT_HIP(ctx, hipMemcpyAsync(d_idx.p, h_indices, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+        vert = g.vertices; idx = g.indices;
+        if (g.on_device) return PT_OK;
+        PT_HIP(ctx, hipMemcpyAsync(d_vert.p, g.vertices, sizeof(float) * 3 * (size_t)g.n_verts, hipMemcpyHostToDevice, st));
+        PT_HIP(ctx, hipMemcpyAsync(d_idx.p, g.indices, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
         PT_HIP(ctx, hipStreamSynchronize(st));  // pageable host sources are done with
+        vert = d_vert.p; idx = d_idx.p;
         return PT_OK;
     }
     void gather(pt_scene *s)
     {
-        k_gather<<<(s->n_tris + TB - 1) / TB, TB, 0, s->ctx->stream>>>(d_vert.p, d_idx.p, s->n_tris, s->d_tri_orig, d_tlo.p, d_thi.p);
+        k_gather<<<(s->n_tris + TB - 1) / TB, TB, 0, s->ctx->stream>>>(vert, idx, s->n_tris, s->d_tri_orig, d_tlo.p, d_thi.p);
     }
 };
 
@@ -472,12 +480,13 @@ static pt_status build_at_quality(pt_scene *s, uint32_t quality, bool want8)
     return PT_OK;
 }
 
-pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices,
-                          uint32_t n_tris, const float *h_faces)
+pt_status ptb_build_scene(pt_scene *s, const pt_geometry &g, uint32_t n_tris)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     const uint32_t n = n_tris;
+    const float *h_vertices = g.vertices, *h_faces = g.faces;  // (host pointers on the host path only)
+    const uint32_t *h_indices = g.indices;
     s->n_tris = n;
     // the de-indexed triangles and the per-face materials stay resident (72 B per triangle): a change of the BVH quality,
     // or the first request for the 8-wide nodes, re-packs the tables from them in another leaf order
@@ -486,11 +495,14 @@ pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts
                              pt_buf_of(s->d_tri4, sizeof(float4) * 3 * (size_t)n), pt_buf_of(s->d_shade4, sizeof(float4) * 3 * (size_t)n),
                              pt_buf_of(s->d_shade64, sizeof(float4) * 4 * (size_t)n), pt_buf_of(s->d_ke4, sizeof(float4) * (size_t)n),
                              pt_buf_of(s->d_frame4, sizeof(float4) * 2 * (size_t)n) }));
-    PT_HIP(ctx, hipMemcpyAsync(s->d_faces, h_faces, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, st));
+    PT_HIP(ctx, hipMemcpyAsync(s->d_faces, g.faces, sizeof(float) * 6 * (size_t)n, g.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     GeometryUpload up;
-    PT_TRY(up.upload(ctx, h_vertices, n_verts, h_indices, n));
+    PT_TRY(up.upload(ctx, g, n));
     up.gather(s);
-    {   // emitters for the NEE pipeline (push_emitter), and which primitives they are (pt_scene_update recomputes them)
+    if (g.on_device) {  // the emitters by kernels, from d_faces and the gathered triangles (scene_device.hip): the bits of the loop below
+        PT_TRY(ptsd_find_emitters(s));
+        PT_TRY(ptsd_host_products(s, n <= PT_SAH_MAX_TRIS ? &s->h_pair : nullptr));
+    } else {   // emitters for the NEE pipeline (push_emitter), and which primitives they are (pt_scene_update recomputes them)
         std::vector<float4> lights;
         float run = 0.f;
         s->h_light_prim.clear();
@@ -509,7 +521,7 @@ pt_status ptb_build_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts
     }
     if (n <= PT_SAH_MAX_TRIS) {  // small scene: keep what a build of the surface-area BVH4 reads
         PT_TRY(keep_host_boxes(s, up.d_tlo.p, up.d_thi.p));
-        find_fan_pairs(h_vertices, h_indices, n, s->h_pair);
+        if (!g.on_device) find_fan_pairs(h_vertices, h_indices, n, s->h_pair);
     }
     // the tree of the default quality (ePreferFastTrace, main.cpp:419): PLOC for big scenes; small scenes get the LBVH and the exact
     // surface-area BVH4 on top.  The 8-wide nodes only when the context asks AUTO to use them.
@@ -820,12 +832,12 @@ static pt_status refit_tree_products(pt_scene *s, const float4 *d_tlo, const flo
     return PT_OK;
 }
 
-static pt_status update_tree_products(pt_scene *s, const float4 *d_tlo, const float4 *d_thi, bool refit)
+static pt_status update_tree_products(pt_scene *s, const float4 *d_tlo, const float4 *d_thi, bool refit, bool upload_lights)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     const bool small = s->n_tris <= PT_SAH_MAX_TRIS;
-    if (s->n_lights) PT_HIP(ctx, hipMemcpyAsync(s->d_lights, s->h_lights.data(), sizeof(float4) * s->h_lights.size(), hipMemcpyHostToDevice, st));
+    if (s->n_lights && upload_lights) PT_HIP(ctx, hipMemcpyAsync(s->d_lights, s->h_lights.data(), sizeof(float4) * s->h_lights.size(), hipMemcpyHostToDevice, st));
     if (small) PT_TRY(keep_host_boxes(s, d_tlo, d_thi));
     if (refit) {
         const pt_status rc = refit_tree_products(s, d_tlo, d_thi);
@@ -839,29 +851,28 @@ static pt_status update_tree_products(pt_scene *s, const float4 *d_tlo, const fl
     return build_at_quality(s, s->quality, small || s->d_wide8 != nullptr || ctx->tune.hbm8 == 1);
 }
 
-pt_status ptb_update_scene(pt_scene *s, const float *h_vertices, uint32_t n_verts, const uint32_t *h_indices, uint32_t mode)
+pt_status ptb_update_scene(pt_scene *s, const pt_geometry &g, uint32_t mode)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     const uint32_t n = s->n_tris;
     const bool small = n <= PT_SAH_MAX_TRIS;
+    const float *h_vertices = g.vertices;  // (host pointers on the host path only)
+    const uint32_t *h_indices = g.indices;
     PT_HIP(ctx, hipStreamSynchronize(st));  // after whatever is queued on the scene (a PT_FLAG_ASYNC render included)
     // host-side products first: until the triangles are overwritten below, a failure leaves the scene as it was
+    // (arrays in device memory: the same products by kernels from the gathered triangles, below)
     std::vector<float4> lights;
     float run = 0.f;
-    for (size_t k = 0; k < s->h_light_prim.size(); k++) {
+    for (size_t k = 0; k < s->h_light_prim.size() && !g.on_device; k++) {
         const uint32_t t = s->h_light_prim[k];
         push_emitter(h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 0], h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 1],
                      h_vertices + 3 * (size_t)h_indices[3 * (size_t)t + 2], s->h_lights[5 * k + 4], run, lights);
     }
     std::vector<uint8_t> pair;
-    if (small) find_fan_pairs(h_vertices, h_indices, n, pair);
-    bool pairs_hold = true;  // every pair leaf of the held trees is still a pair (a pair that newly forms changes no bits)
-    for (uint32_t i = 0; i < s->h_pair.size() && i < pair.size(); i++)
-        if (s->h_pair[i] && !pair[i]) pairs_hold = false;
-    const bool refit = mode == PT_SCENE_UPDATE_REFIT && !s->broken && (pairs_hold || !s->d_wide_sah || !s->sah_pair_leaves);
+    if (small && !g.on_device) find_fan_pairs(h_vertices, h_indices, n, pair);
     GeometryUpload up;
-    PT_TRY(up.upload(ctx, h_vertices, n_verts, h_indices, n));
+    PT_TRY(up.upload(ctx, g, n));
     PT_HIP(ctx, hipEventRecord(ctx->ev_a, st));
     // from here on the scene holds the new triangles: a failure marks it broken (the repair builds from them, never from a mix)
     const uint32_t quality = s->quality;
@@ -869,11 +880,21 @@ pt_status ptb_update_scene(pt_scene *s, const float *h_vertices, uint32_t n_vert
     const uint32_t n_inst = (uint32_t)(xforms.size() / 12);
     if (n_inst) ptb_free_instances(s);  // the TLAS, the instances' frames and emitters are made again from the new BLAS below
     up.gather(s);
+    pt_status rc = PT_OK;
+    if (g.on_device) {  // scene_device.hip: d_lights, h_lights and light_area; the pair relation (none where it could not be read: always a valid one)
+        rc = ptsd_host_products(s, small ? &pair : nullptr);
+        if (small && rc != PT_OK) pair.assign(n, 0);
+    } else {
+        s->h_lights = lights;
+        s->light_area = run;
+    }
+    bool pairs_hold = true;  // every pair leaf of the held trees is still a pair (a pair that newly forms changes no bits)
+    for (uint32_t i = 0; i < s->h_pair.size() && i < pair.size(); i++)
+        if (s->h_pair[i] && !pair[i]) pairs_hold = false;
+    const bool refit = mode == PT_SCENE_UPDATE_REFIT && !s->broken && (pairs_hold || !s->d_wide_sah || !s->sah_pair_leaves);
     // the fan-pair relation a later surface-area build reads: the new arrays' (a pair-leaf tree the refit keeps has only pairs that still hold)
     if (small) s->h_pair = pair;
-    s->h_lights = lights;
-    s->light_area = run;
-    const pt_status rc = update_tree_products(s, up.d_tlo.p, up.d_thi.p, refit);
+    if (rc == PT_OK) rc = update_tree_products(s, up.d_tlo.p, up.d_thi.p, refit, !g.on_device);
     if (rc != PT_OK) mark_broken(s, quality);
     if (n_inst) s->h_xforms = xforms;  // parked: set again below, or by the next successful build of the broken scene
     if (rc != PT_OK) return rc;
