@@ -199,6 +199,24 @@ pt_status pt_scene_create_device(pt_ctx *ctx, const void *d_vertices, uint32_t n
 pt_status pt_scene_update_device(pt_scene *scene, const void *d_vertices, uint32_t n_verts,
                                  const void *d_indices, uint32_t n_tris, uint32_t mode);
 
+/* pt_scene_set_instances for matrices that live in DEVICE memory (a rigid-body simulation, a pose optimiser): d_xforms3x4 holds n object->world
+ * 3x4 row-major f32 matrices in pt_scene_set_instances' layout, dense, 4-byte aligned, on the context's device.  n = 0 restores the
+ * single-level scene (the pointer may then be NULL); NULL with n > 0 is PT_ERR_INVALID_ARG.  After the call -- whatever its status -- the scene
+ * is in the state pt_scene_set_instances leaves with a host copy of the same bytes: every field of pt_scene_get_info but build_ms, every
+ * render on every pipeline (the NEE ones included), pt_trace, pt_trace_device, pt_radiance_device, pt_render_aov, pt_render_guided,
+ * pt_scene_snapshot_previous + pt_film_motion + pt_film_reproject_motion, and whatever a later update, quality change, instance set or repair
+ * builds from the scene's kept state are equal bit for bit.  Host and device sets of one scene may be mixed freely.
+ * Refusals are the host call's and leave what it leaves (the old set is dropped before the matrices are looked at: a refused call leaves the
+ * scene single-level): "instance matrix has a NaN/Inf" and "instance matrix is singular", decided for the lowest failing instance, its input
+ * check before its inverse check; a broken scene is PT_ERR_UNSUPPORTED (PT_BROKEN_SCENE_MSG).
+ * Execution: blocking, and ordered after the work queued on the context's stream (a PT_FLAG_ASYNC render queued before sees the old set).
+ * The array is read on the context's stream; it is not retained and may be freed after return.  The scene keeps a copy in device memory
+ * (48 B per instance).  One verdict word crosses to the host; no matrix and no inverse does, in either direction, neither in the call nor in
+ * what follows it: the first render of any pipeline (the NEE pipelines' emitter copies are made by a kernel, and one float -- their total
+ * area -- is read back), pt_scene_snapshot_previous and pt_film_motion (device-to-device copies), the re-set of the instances behind a
+ * pt_scene_update[_device], the restoring of a parked set after a repair.  DESIGN.md section 28.                                        */
+pt_status pt_scene_set_instances_device(pt_scene *scene, const void *d_xforms3x4, uint32_t n);
+
 /* Debug/parity read-back of the device-built LBVH.  keys/prim_of_pos: n_tris entries each;
  * nodes16: n_nodes x 16 dwords {lmin[3] lmax[3] rmin[3] rmax[3] left right 0 0}, child bit31 =
  * leaf (sorted position).  Any pointer may be NULL.                                         */

@@ -206,6 +206,7 @@ HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
 # every symbol include/pt_api.h and include/pt_host.h declare
 API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "pt_scene_create", "pt_scene_destroy",
                "pt_scene_set_instances", "pt_scene_set_bvh_quality", "pt_scene_update", "pt_scene_create_device", "pt_scene_update_device",
+               "pt_scene_set_instances_device",
                "pt_scene_get_info", "pt_scene_read_bvh", "pt_scene_read_bvh4", "pt_scene_read_bvh8", "pt_film_create", "pt_film_create_external", "pt_film_clear",
                "pt_film_read_f32", "pt_film_read_bgra8", "pt_film_destroy", "pt_params_default", "pt_render",
                "pt_render_prepare", "pt_trace", "pt_film_enable_aov", "pt_render_aov", "pt_film_read_aov",
@@ -264,6 +265,7 @@ def lib_amd():
         L.pt_scene_update.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
         L.pt_scene_create_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(vp)]
         L.pt_scene_update_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
+        L.pt_scene_set_instances_device.argtypes = [vp, vp, C.c_uint32]
         L.pt_scene_get_info.argtypes = [vp, C.POINTER(SceneInfo)]
         L.pt_scene_read_bvh.argtypes = [vp, vp, vp, vp]
         L.pt_scene_read_bvh4.argtypes = [vp, vp]
@@ -714,6 +716,33 @@ class Scene:
         # call is blocking, which orders the read before whatever torch queues next (Scene.trace_tensors).
         torch.cuda.current_stream(v.device).synchronize()
         self.update_device(v.numel() // 3, v.data_ptr(), i.numel() // 3, i.data_ptr(), mode=mode)
+
+    def set_instances_device(self, xforms_ptr, n):
+        """pt_scene_set_instances_device over a raw DEVICE pointer: n object->world 3x4 row-major f32 matrices, dense (include/pt_api.h).
+        n = 0 restores the single-level scene (the pointer may then be None).  Blocking."""
+        self.ctx._check(lib_amd().pt_scene_set_instances_device(self.h, xforms_ptr if n else None, n))
+
+    @staticmethod
+    def _instance_tensor(xforms):
+        """The tensor rule of set_instances_tensor -> the contiguous tensor; ValueError before a device is touched."""
+        import torch
+        if not isinstance(xforms, torch.Tensor) or xforms.dtype != torch.float32:
+            raise ValueError("xforms must be a float32 CUDA tensor")
+        if xforms.numel() % 12:
+            raise ValueError("xforms must hold 12*n elements (n 3x4 matrices)")
+        if not xforms.is_cuda:
+            raise ValueError("xforms must be a CUDA tensor")
+        return xforms.contiguous()
+
+    def set_instances_tensor(self, xforms):
+        """Scene.set_instances for a torch tensor on the GPU, nothing through the host: a float32 CUDA tensor of 12*n elements (n 3x4
+        matrices), made contiguous if it is not; an empty tensor restores the single-level scene.  The result equals set_instances() of
+        its host copy, bit for bit."""
+        import torch
+        x = self._instance_tensor(xforms)
+        torch.cuda.current_stream(x.device).synchronize()   # (update_tensors has the reasons)
+        n = x.numel() // 12
+        self.set_instances_device(x.data_ptr() if n else None, n)
 
     def snapshot_previous(self):
         """Remembers the scene as it stands now -- vertex positions and instance matrices -- as "the previous geometry" of Film.motion

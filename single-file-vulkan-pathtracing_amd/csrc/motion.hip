@@ -49,7 +49,7 @@ pt_status ptm_snapshot(pt_scene *s)
     const pt_status rb = s->broken ? ptb_repair(s) : PT_OK;  // (as pt_render: a repair may bring back a parked instance set)
     if (rb != PT_OK) return rb;
     const uint32_t n_inst = s->n_inst;
-    if (s->h_xforms.size() != 12 * (size_t)n_inst) { ctx->err = "pt_scene_snapshot_previous: the scene's instance set is incomplete"; return PT_ERR_UNSUPPORTED; }
+    if (pt_given_instances(s) != (size_t)n_inst) { ctx->err = "pt_scene_snapshot_previous: the scene's instance set is incomplete"; return PT_ERR_UNSUPPORTED; }
     const size_t tri_bytes = sizeof(float4) * 3 * (size_t)s->n_tris, xf_bytes = sizeof(float4) * 3 * (size_t)n_inst;
     // both new copies are made first and swapped in at the end, the old ones freed after them: a call that fails at any point leaves the
     // previous snapshot -- triangles and matrices -- as it was
@@ -60,7 +60,9 @@ pt_status ptm_snapshot(pt_scene *s)
     PT_TRY(ptb_scene_alloc(s, "the previous geometry", fresh));
     // ordered after the work queued on the stream (an update's gather, a render that still reads the triangles)
     hipError_t e = hipMemcpyAsync(d_tri, s->d_tri_orig, tri_bytes, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && n_inst) e = hipMemcpyAsync(d_xf, s->h_xforms.data(), xf_bytes, hipMemcpyHostToDevice, st);
+    // (the matrices as given: from the host copy, or device to device after pt_scene_set_instances_device)
+    if (e == hipSuccess && n_inst && s->d_xforms) e = hipMemcpyAsync(d_xf, s->d_xforms, xf_bytes, hipMemcpyDeviceToDevice, st);
+    else if (e == hipSuccess && n_inst) e = hipMemcpyAsync(d_xf, s->h_xforms.data(), xf_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -92,7 +94,7 @@ pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *
     if (rb != PT_OK) return rb;
     const uint32_t n_inst = s->n_inst;
     if (n_inst != s->prev.n_inst) return pt_bad(ctx, "the scene's instance count differs from the snapshot's");
-    if (s->h_xforms.size() != 12 * (size_t)n_inst) { ctx->err = "pt_film_motion: the scene's instance set is incomplete"; return PT_ERR_UNSUPPORTED; }
+    if (pt_given_instances(s) != (size_t)n_inst) { ctx->err = "pt_film_motion: the scene's instance set is incomplete"; return PT_ERR_UNSUPPORTED; }
     MoConst mc{};
     mc.w = f->w; mc.h = f->h;
     const uint32_t n_blocks = fp_grid(f->w, f->h, &mc.n_bx);
@@ -108,8 +110,18 @@ pt_status ptm_motion(pt_scene *s, pt_film *f, const pt_motion_params *p, float *
     hipStream_t st = ctx->stream;
     // the scene's matrices as they are now, in gl_InstanceID order, into the second half of the snapshot's array
     // (once per pt_scene_set_instances, not once per call; compared as bytes: -0 is not +0 here)
-    if (n_inst && (s->prev.h_now.size() != s->h_xforms.size() || std::memcmp(s->prev.h_now.data(), s->h_xforms.data(), sizeof(float) * s->h_xforms.size()) != 0)) {
+    // (after pt_scene_set_instances_device: device to device, once per set -- the scene's set counter decides, nothing is compared)
+    if (n_inst && s->d_xforms) {
+        if (s->prev.now_set != s->xf_set) {
+            s->prev.h_now.clear();
+            s->prev.now_set = 0;
+            PT_HIP(ctx, hipMemcpyAsync(s->prev.d_xf + xf_rows, s->d_xforms, sizeof(float4) * xf_rows, hipMemcpyDeviceToDevice, st));
+            PT_HIP(ctx, hipStreamSynchronize(st));
+            s->prev.now_set = s->xf_set;
+        }
+    } else if (n_inst && (s->prev.h_now.size() != s->h_xforms.size() || std::memcmp(s->prev.h_now.data(), s->h_xforms.data(), sizeof(float) * s->h_xforms.size()) != 0)) {
         s->prev.h_now.clear();
+        s->prev.now_set = 0;
         PT_HIP(ctx, hipMemcpyAsync(s->prev.d_xf + xf_rows, s->h_xforms.data(), sizeof(float4) * xf_rows, hipMemcpyHostToDevice, st));
         PT_HIP(ctx, hipStreamSynchronize(st));
         s->prev.h_now = s->h_xforms;

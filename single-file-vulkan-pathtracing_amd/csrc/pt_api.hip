@@ -239,6 +239,19 @@ pt_status pt_scene_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n
     return guarded(s->ctx, [&] { return ptb_set_instances(s, xforms3x4, n); });
 }
 
+// The matrices in device memory: the refusals of pt_scene_set_instances, its loop as a kernel (scene_instances.hip).  A failure waits for the
+// stream before it returns: the caller's array is not read after the call, whatever it answers.
+pt_status pt_scene_set_instances_device(pt_scene *s, const void *d_xforms3x4, uint32_t n)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    if (n && !d_xforms3x4) { s->ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    if (n >= (1u << 28)) { s->ctx->err = "too many instances"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    const pt_status rc = guarded(s->ctx, [&] { return ptb_set_instances_device(s, static_cast<const float *>(d_xforms3x4), n); });
+    if (rc != PT_OK) (void)hipStreamSynchronize(s->ctx->stream);
+    return rc;
+}
+
 void pt_scene_destroy(pt_scene *s)
 {
     if (!s) return;

@@ -173,6 +173,11 @@ struct pt_scene {
     uint32_t *d_light_prim = nullptr;    // ... on the device, for pt_scene_update_device (scene_device.hip; null until a device call needs it)
     // instanced scenes: every instance's emitters in world space, gl_InstanceID-major, same 5-float4 layout and running cdf
     std::vector<float> h_xforms;    // the instance set's object->world matrices as given (gl_InstanceID order): ptb_ensure_inst_lights
+    // ... or, after pt_scene_set_instances_device, in device memory: 3 float4 per instance, gl_InstanceID order.  Exactly one of the two holds
+    // the set (pt_given_instances); both survive parking (scene_build.hip restore_parked_instances).  xf_set counts the sets that succeeded.
+    float4 *d_xforms = nullptr;
+    uint32_t n_xforms_dev = 0;
+    uint64_t xf_set = 0;
     float4 *d_lights_inst = nullptr;  // built on the first NEE render of the instance set
     uint32_t n_lights_inst = 0;
     float light_area_inst = 0.f;
@@ -197,9 +202,12 @@ struct pt_scene {
         float4 *d_xf = nullptr;
         uint32_t n_inst = 0;       // 0: single-level
         std::vector<float> h_now;  // what the second half of d_xf holds (empty: nothing yet): pt_film_motion uploads only when h_xforms differs
+        uint64_t now_set = 0;      // ... after a device set: the pt_scene::xf_set it was copied at (0: not from a device set)
         uint64_t bytes = 0;        // device bytes of both: added to pt_scene_info.device_bytes
     } prev;
 };
+// the number of matrices the scene keeps as given -- on the host or on the device -- whether they are set (n_inst) or parked
+inline size_t pt_given_instances(const pt_scene *s) { return s->d_xforms ? (size_t)s->n_xforms_dev : s->h_xforms.size() / 12; }
 
 // An optional plane of a film (M, L, Q below): absent until its pt_film_enable_* call, then the film's own allocation or the caller's memory.
 // pt_plane_enable / pt_plane_read / pt_planes_clear / pt_planes_free (film_work.hip) are all that allocate, zero, read back and free one.
@@ -406,6 +414,14 @@ pt_status ptb_update_scene(pt_scene *s, const pt_geometry &g, uint32_t mode);
 pt_status ptsd_check_indices(pt_ctx *ctx, const uint32_t *d_indices, uint32_t n_tris, uint32_t n_verts);
 pt_status ptsd_find_emitters(pt_scene *s);
 pt_status ptsd_host_products(pt_scene *s, std::vector<uint8_t> *pair);
+// ... and its fold alone: the cdf words of the n records of d_lights from their terms d_half[0..n), the total to *d_total (queued on st)
+void ptsd_launch_fold(const float *d_half, uint32_t n, float4 *d_lights, float *d_total, hipStream_t st);
+// scene_instances.hip: what pt_scene_set_instances does on the host with the matrices, as kernels.  check_invert: the
+// n records {m, inv} into d_rec, the matrices as given into d_kept (3 float4 each), and the host loop's first error as one word (SI_OK: none;
+// else (instance << 1) | kind), behind one wait for the stream.  inst_lights: ptb_ensure_inst_lights' table from s->d_xforms and d_lights.
+pt_status ptsi_check_invert(pt_ctx *ctx, const float *d_xforms3x4, uint32_t n, float4 *d_rec, float4 *d_kept, uint32_t *d_verdict, uint32_t *verdict);
+pt_status ptsi_inst_lights(pt_scene *s);
+pt_status ptb_set_instances_device(pt_scene *s, const float *d_xforms3x4, uint32_t n);
 constexpr uint32_t PT_SAH_MAX_TRIS = 2048;
 // bvh4_sah_device.hip: surface-area sweep on the device (one workgroup) -> BVH4 rows (32 dwords each) + leaf order
 // pair_with_next (nullable): [n] flags, triangle i and i+1 are the two halves (v0,v1,v2),(v0,v2,v3) of a quad and form ONE primitive
@@ -419,7 +435,8 @@ void ptb_free_instances(pt_scene *s);
 struct pt_buf { void **p; size_t bytes; };  // one buffer of a set: where its pointer lives, the bytes it is to have (not read when it is freed)
 template <class T> inline pt_buf pt_buf_of(T *&p, size_t bytes = 0) { return { reinterpret_cast<void **>(&p), bytes }; }
 // scene_build.hip: every device pointer of a scene, named once, by lifetime -- what frees a lifetime is pt_scratch_free over its list
-enum pt_scene_life { PT_LIFE_SOURCE, PT_LIFE_TREE, PT_LIFE_INSTANCES, PT_LIFE_PREVIOUS };
+// (PT_LIFE_GIVEN: the instance set as given, in device memory -- freed with the instances, but carried across an update's parking)
+enum pt_scene_life { PT_LIFE_SOURCE, PT_LIFE_TREE, PT_LIFE_INSTANCES, PT_LIFE_PREVIOUS, PT_LIFE_GIVEN };
 std::vector<pt_buf> ptb_scene_buffers(pt_scene *s, pt_scene_life life);
 // pt_scratch_alloc for a set of scene buffers (all of them or none; PT_ERR_OOM / PT_ERR_HIP with HIP's sticky error cleared), behind the
 // tests' failure injection (pt_tuning.fail_rebuild)

@@ -5,6 +5,7 @@
 // per-hit operations), and for instanced scenes the TLAS, the per-instance matrices and the world-space emitter / frame tables.
 #include "bvh_build.h"
 #include "self_leaf.h"
+#include "scene_instances_kernel.h"  // si_invert_3x4, SI_OK: one set of statements for the host call and the device call
 
 #include <hip/hip_fp16.h>
 
@@ -178,6 +179,8 @@ std::vector<pt_buf> ptb_scene_buffers(pt_scene *s, pt_scene_life life)
     case PT_LIFE_INSTANCES:
         return { pt_buf_of(s->d_inst6), pt_buf_of(s->d_tlas_wide), pt_buf_of(s->d_tlas_prim_of), pt_buf_of(s->d_tlas16), pt_buf_of(s->d_inst_frame),
                  pt_buf_of(s->d_lights_inst) };
+    case PT_LIFE_GIVEN:
+        return { pt_buf_of(s->d_xforms) };
     default:  // PT_LIFE_PREVIOUS
         return { pt_buf_of(s->prev.d_tri), pt_buf_of(s->prev.d_xf) };
     }
@@ -290,12 +293,26 @@ static void mark_broken(pt_scene *s, uint32_t quality)
     s->broken = true;
 }
 
-// An instanced scene whose BLAS could not be built (pt_scene_update) keeps its instance set parked in h_xforms while n_inst = 0 and the
-// scene is broken.  Every successful build of the tree products ends here and sets the instances again; if that fails, the scene is
+// An instanced scene whose BLAS could not be built (pt_scene_update) keeps its instance set parked in h_xforms (or, given in device memory,
+// in d_xforms) while n_inst = 0 and the scene is broken.  Every successful build of the tree products ends here and sets the instances again; if that fails, the scene is
 // broken again with the set still parked, so no way out of the broken state drops the instances.
 static pt_status restore_parked_instances(pt_scene *s, uint32_t quality)
 {
-    if (s->n_inst || s->h_xforms.empty()) return PT_OK;
+    if (s->n_inst || !pt_given_instances(s)) return PT_OK;
+    if (s->d_xforms) {  // the set lives on the device: set again from there (the call makes its own kept copy; this one is freed behind it)
+        float4 *d_xf = s->d_xforms;
+        const uint32_t n = s->n_xforms_dev;
+        s->d_xforms = nullptr; s->n_xforms_dev = 0;
+        const pt_status rc = ptb_set_instances_device(s, reinterpret_cast<const float *>(d_xf), n);
+        if (rc != PT_OK) {
+            const std::string err = s->ctx->err;
+            mark_broken(s, quality);
+            s->d_xforms = d_xf; s->n_xforms_dev = n;
+            s->ctx->err = err;
+        } else
+            (void)hipFree(d_xf);
+        return rc;
+    }
     const std::vector<float> xf = s->h_xforms;
     const pt_status rc = ptb_set_instances(s, xf.data(), (uint32_t)(xf.size() / 12));
     if (rc != PT_OK) {
@@ -635,20 +652,7 @@ __global__ __launch_bounds__(TB) void k_inst_sort(const float4 *__restrict__ ins
     for (int k = 0; k < 6; k++) sorted6[6 * (size_t)pos + k] = inst6[6 * (size_t)id + k];
 }
 
-// world -> object matrix: adjugate / determinant in binary64, rounded once to float
-static void invert_3x4(const float m[12], float inv[12])
-{
-    const double a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[4], a11 = m[5], a12 = m[6], a20 = m[8], a21 = m[9], a22 = m[10];
-    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-    const double det = (a00 * c00 + a01 * c01) + a02 * c02;
-    const double i00 = c00 / det, i01 = (a02 * a21 - a01 * a22) / det, i02 = (a01 * a12 - a02 * a11) / det;
-    const double i10 = c01 / det, i11 = (a00 * a22 - a02 * a20) / det, i12 = (a02 * a10 - a00 * a12) / det;
-    const double i20 = c02 / det, i21 = (a01 * a20 - a00 * a21) / det, i22 = (a00 * a11 - a01 * a10) / det;
-    const double tx = m[3], ty = m[7], tz = m[11];
-    inv[0] = (float)i00; inv[1] = (float)i01; inv[2] = (float)i02;  inv[3] = (float)(-((i00 * tx + i01 * ty) + i02 * tz));
-    inv[4] = (float)i10; inv[5] = (float)i11; inv[6] = (float)i12;  inv[7] = (float)(-((i10 * tx + i11 * ty) + i12 * tz));
-    inv[8] = (float)i20; inv[9] = (float)i21; inv[10] = (float)i22; inv[11] = (float)(-((i20 * tx + i21 * ty) + i22 * tz));
-}
+// (world -> object matrix: si_invert_3x4, scene_instances_kernel.h -- adjugate / determinant in binary64, rounded once to float)
 
 // World-space normal and tangent of every (instance, triangle): what k_shade's instanced branch used to evaluate per hit -- the
 // normal by the inverse transpose, renormalised (a square root and three true divides), and createCoordinateSystem on it (another
@@ -697,10 +701,11 @@ pt_status ptb_ensure_inst_lights(pt_scene *s)
     pt_ctx *ctx = s->ctx;
     if (!s->n_inst || !s->n_lights || s->d_lights_inst) return PT_OK;
     const uint64_t copies = (uint64_t)s->n_inst * s->n_lights;
-    if (copies > (1ull << 24) || s->h_xforms.size() != 12 * (size_t)s->n_inst) {
+    if (copies > (1ull << 24) || pt_given_instances(s) != (size_t)s->n_inst) {
         ctx->err = "the NEE pipeline would need " + std::to_string(copies) + " world-space emitter copies (instances x emitters); the limit is 16 777 216";
         return PT_ERR_UNSUPPORTED;
     }
+    if (s->d_xforms) return ptsi_inst_lights(s);  // the set lives on the device: the same loop as a kernel (scene_instances.hip)
     const uint32_t n = s->n_inst;
     const float *xforms3x4 = s->h_xforms.data();
     std::vector<float4> wl;
@@ -728,16 +733,19 @@ void ptb_free_instances(pt_scene *s)
     s->h_xforms.clear();
     s->h_xforms.shrink_to_fit();
     pt_scratch_free(ptb_scene_buffers(s, PT_LIFE_INSTANCES), nullptr, 0);
+    pt_scratch_free(ptb_scene_buffers(s, PT_LIFE_GIVEN), nullptr, 0);
+    s->n_xforms_dev = 0;
     s->n_lights_inst = 0; s->light_area_inst = 0.f;
     s->n_tlas16 = 0;
     s->n_inst = 0; s->n_tlas_wide = 0; s->tlas_height = 0;
 }
 
+static pt_status set_instances_from_records(pt_scene *s, DevBuf<float4> &d_in, uint32_t n, const float *h_given, DevBuf<float4> &d_given);
+
 pt_status ptb_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n)
 {
     pt_ctx *ctx = s->ctx;
-    hipStream_t st = ctx->stream;
-    PT_HIP(ctx, hipStreamSynchronize(st));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ptb_free_instances(s);
     if (n == 0) return PT_OK;
     if (s->broken) { ctx->err = PT_BROKEN_SCENE_MSG; return PT_ERR_UNSUPPORTED; }
@@ -748,19 +756,52 @@ pt_status ptb_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n)
             if (!(m[k] == m[k]) || __builtin_isinf(m[k])) { ctx->err = "instance matrix has a NaN/Inf"; return PT_ERR_INVALID_ARG; }
             rec[24 * (size_t)i + k] = m[k];
         }
-        invert_3x4(m, &rec[24 * (size_t)i + 12]);
+        si_invert_3x4(m, &rec[24 * (size_t)i + 12]);
         for (int k = 12; k < 24; k++)
             if (!(rec[24 * (size_t)i + k] == rec[24 * (size_t)i + k]) || __builtin_isinf(rec[24 * (size_t)i + k])) {
                 ctx->err = "instance matrix is singular";
                 return PT_ERR_INVALID_ARG;
             }
     }
-    // nothing hangs on the scene before the whole set -- the TLAS and the sorted matrices -- exists: a failure leaves it single-level
-    DevBuf<float4> d_in, d_tlo, d_thi, d_inst6;
+    DevBuf<float4> d_in;
     PT_HIP(ctx, d_in.alloc(6 * (size_t)n));
+    PT_HIP(ctx, hipMemcpy(d_in.p, rec.data(), sizeof(float) * 24 * (size_t)n, hipMemcpyHostToDevice));
+    DevBuf<float4> none;
+    return set_instances_from_records(s, d_in, n, xforms3x4, none);
+}
+
+// The matrices in device memory: the same refusals decided by a kernel (scene_instances.hip), one verdict word back; the records never leave
+// the device and the set as given is kept there (d_xforms) for what the host call keeps h_xforms for.
+pt_status ptb_set_instances_device(pt_scene *s, const float *d_xforms3x4, uint32_t n)
+{
+    pt_ctx *ctx = s->ctx;
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ptb_free_instances(s);
+    if (n == 0) return PT_OK;
+    if (s->broken) { ctx->err = PT_BROKEN_SCENE_MSG; return PT_ERR_UNSUPPORTED; }
+    DevBuf<float4> d_in, d_kept;
+    DevBuf<uint32_t> d_verdict;
+    PT_HIP(ctx, d_in.alloc(6 * (size_t)n));
+    PT_HIP(ctx, d_kept.alloc(3 * (size_t)n));
+    PT_HIP(ctx, d_verdict.alloc(1));
+    uint32_t verdict = SI_OK;
+    PT_TRY(ptsi_check_invert(ctx, d_xforms3x4, n, d_in.p, d_kept.p, d_verdict.p, &verdict));
+    if (verdict != SI_OK) {
+        ctx->err = (verdict & 1u) ? "instance matrix is singular" : "instance matrix has a NaN/Inf";
+        return PT_ERR_INVALID_ARG;
+    }
+    return set_instances_from_records(s, d_in, n, nullptr, d_kept);
+}
+
+// d_in: the n records {m, inv} in gl_InstanceID order.  On success the scene keeps the set as given: h_given's copy, or d_given itself.
+static pt_status set_instances_from_records(pt_scene *s, DevBuf<float4> &d_in, uint32_t n, const float *h_given, DevBuf<float4> &d_given)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    // nothing hangs on the scene before the whole set -- the TLAS and the sorted matrices -- exists: a failure leaves it single-level
+    DevBuf<float4> d_tlo, d_thi, d_inst6;
     PT_HIP(ctx, d_tlo.alloc(n));
     PT_HIP(ctx, d_thi.alloc(n));
-    PT_HIP(ctx, hipMemcpy(d_in.p, rec.data(), sizeof(float) * 24 * (size_t)n, hipMemcpyHostToDevice));
     const uint32_t g = (n + TB - 1) / TB;
     k_inst_boxes<<<g, TB, 0, st>>>(s->d_wide, d_in.p, n, d_tlo.p, d_thi.p);
     BvhOut o;
@@ -785,7 +826,9 @@ pt_status ptb_set_instances(pt_scene *s, const float *xforms3x4, uint32_t n)
     for (int k = 0; k < 3; k++) { s->tlas_norm_c[k] = o.norm_c[k]; s->tlas_norm_s[k] = o.norm_s[k]; s->tlas_norm_rs[k] = o.norm_rs[k]; }
     for (int k = 0; k < 3; k++) { s->tlas_bmin[k] = o.bmin[k]; s->tlas_bmax[k] = o.bmax[k]; }
     // (the emitters' world-space copies for the NEE pipeline are made on that pipeline's first render: ptb_ensure_inst_lights)
-    s->h_xforms.assign(xforms3x4, xforms3x4 + 12 * (size_t)n);
+    if (h_given) s->h_xforms.assign(h_given, h_given + 12 * (size_t)n);
+    else { s->d_xforms = d_given.release(); s->n_xforms_dev = n; }
+    s->xf_set++;
     s->n_inst = n;
     s->n_tlas_wide = o.n_wide;
     s->tlas_height = std::max(o.height, o.height_tree);  // (of the tree the TLAS was collapsed from: the stack bound)
@@ -877,7 +920,10 @@ pt_status ptb_update_scene(pt_scene *s, const pt_geometry &g, uint32_t mode)
     // from here on the scene holds the new triangles: a failure marks it broken (the repair builds from them, never from a mix)
     const uint32_t quality = s->quality;
     const std::vector<float> xforms = s->h_xforms;  // the instance set -- or the one an earlier failed update parked (restore_parked_instances)
-    const uint32_t n_inst = (uint32_t)(xforms.size() / 12);
+    float4 *const d_xforms = s->d_xforms;           // ... given in device memory: the buffer itself is carried across
+    const uint32_t n_xforms_dev = s->n_xforms_dev;
+    const uint32_t n_inst = (uint32_t)pt_given_instances(s);
+    s->d_xforms = nullptr;
     if (n_inst) ptb_free_instances(s);  // the TLAS, the instances' frames and emitters are made again from the new BLAS below
     up.gather(s);
     pt_status rc = PT_OK;
@@ -896,7 +942,7 @@ pt_status ptb_update_scene(pt_scene *s, const pt_geometry &g, uint32_t mode)
     if (small) s->h_pair = pair;
     if (rc == PT_OK) rc = update_tree_products(s, up.d_tlo.p, up.d_thi.p, refit, !g.on_device);
     if (rc != PT_OK) mark_broken(s, quality);
-    if (n_inst) s->h_xforms = xforms;  // parked: set again below, or by the next successful build of the broken scene
+    if (n_inst) { s->h_xforms = xforms; s->d_xforms = d_xforms; s->n_xforms_dev = n_xforms_dev; }  // parked: set again below, or by the next successful build of the broken scene
     if (rc != PT_OK) return rc;
     return restore_parked_instances(s, quality);
 }

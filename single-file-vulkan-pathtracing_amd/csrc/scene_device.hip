@@ -74,6 +74,11 @@ __global__ __launch_bounds__(TB) void k_sd_fan_flags(const float4 *__restrict__ 
 
 }  // namespace
 
+void ptsd_launch_fold(const float *d_half, uint32_t n, float4 *d_lights, float *d_total, hipStream_t st)
+{
+    k_sd_emitter_fold<<<1, SD_FOLD, 0, st>>>(d_half, n, d_lights, d_total);
+}
+
 pt_status ptsd_check_indices(pt_ctx *ctx, const uint32_t *d_indices, uint32_t n_tris, uint32_t n_verts)
 {
     hipStream_t st = ctx->stream;
