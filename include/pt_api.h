@@ -259,7 +259,9 @@ enum {
      * SHADOW ray queued -- a third queue, compacted like the others and traced by the same extend kernels as an
      * any-hit query; the emission of a surface the path runs into counts for camera rays only.  Same random stream
      * otherwise (three more numbers per hit).  Fully specified arithmetic like the reference path's (the tests' CPU checker restates it bit for bit).  Instanced scenes sample every instance's copy of the emitters (world space, one cdf).
-     * One sample group per pixel.  The same estimator is PT_FLAG_NEE on any pipeline value: WAVEFRONT | PT_FLAG_NEE is this pipeline. */
+     * One sample group per pixel.  The same estimator is PT_FLAG_NEE on any pipeline value: WAVEFRONT | PT_FLAG_NEE is this pipeline.
+     * The shadow ray's range is (tmin, 0.999 dist), dist the distance to the sampled point, whatever tmax is: tmax bounds the path's rays only
+     * (PT_FLAG_NEE and PT_RADIANCE_NEE alike). */
     PT_PIPELINE_WAVEFRONT_NEE = 1,
     /* The reference's estimator, bit for bit, as ONE persistent kernel -- the shape of the reference's own raygen shader
      * (raygen.rgen:41-91: one invocation owns its path): traversal and shading in the same lane, path state in LDS, no
@@ -817,8 +819,10 @@ pt_status pt_trace(pt_scene *scene, const float *rays6, uint32_t n, float tmin, 
  *                     at the FIRST hit below the bound, and no closest-hit instantiation reads a per-ray bound.
  *   PT_TRACE_ANY      d_occluded[i] = 1 exactly when the closest-hit query of ray i with the ray's bound as tmax finds a triangle (tmin < t < bound,
  *                     opaque, no culling), else 0.  The bound is d_tmax[i], or desc.tmax for every ray when d_tmax is NULL (the call then fills its
- *                     bound plane with it).  Runs the any-hit instantiations (the NEE pipeline's shadow-ray kernels), which stop at the first hit.
- *                     d_hits and the four surface pointers must be NULL.
+ *                     bound plane with it).  Both ends are strict: a triangle at exactly t == bound does not occlude.  Where d_tmax is given,
+ *                     desc.tmax plays no part in the answer (it must still be finite and above tmin): a bound beyond it, +inf included, is
+ *                     honoured as it stands, and a bound at or below tmin occludes nothing.  Runs the any-hit instantiations (the
+ *                     NEE pipeline's shadow-ray kernels), which stop at the first hit.  d_hits and the four surface pointers must be NULL.
  *
  * The surface record (PT_TRACE_CLOSEST; each of the four planes n x 3 floats, dense, any may be NULL) is what closesthit.rchit:50-65 computes at
  * the hit, in binary32 with every operation rounded on its own (no contraction, denormals kept), A B C the hit triangle's vertices, (u, v) the

@@ -234,7 +234,8 @@ __device__ __forceinline__ void extend8_body(const uint4 *__restrict__ nodes8, N
             const float4 a = rec64[4 * (size_t)pos + 0], b = rec64[4 * (size_t)pos + 1], c = rec64[4 * (size_t)pos + 2];
             float t, V, W, det;
             bool divided = false;
-            if (ptm::tri_test(pre, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det, COUNT ? &divided : nullptr)) {
+            // (shadow rays: tmin < t < the ray's own bound, strictly -- best_t until the first hit, which ends the walk; tmax plays no part)
+            if (ptm::tri_test(pre, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, ptl::leaf_upper(ray_tmax != nullptr, best_t, tmax), t, V, W, det, COUNT ? &divided : nullptr)) {
                 // closest t; equal t -> lowest gl_PrimitiveID
                 bool closer = t < best_t;
                 if (!closer && t == best_t)

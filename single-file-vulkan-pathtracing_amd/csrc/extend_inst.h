@@ -190,9 +190,10 @@ __global__ __launch_bounds__(TB) void k_extend_inst(const float4 *__restrict__ t
                         const size_t ti = LDS_BLAS ? (size_t)tri_base + 3 * (size_t)pos : 3 * (size_t)pos;
                         const float4 a = tri4[ti + 0], b = tri4[ti + 1], c = tri4[ti + 2];
                         float t, V, W, det;
+                        const float upper = ptl::leaf_upper(SHADOW, best_t, tmax);  // (shadow rays: tmin < t < the ray's own bound, strictly; tmax plays no part)
                         const bool th = LDS_BLAS
-                            ? ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det)
-                            : ptm::tri_test(pre, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det);
+                            ? ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, upper, t, V, W, det)
+                            : ptm::tri_test(pre, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, upper, t, V, W, det);
                         if (th) {
                             const uint32_t prim = __float_as_uint(a.w);
                             // closest t; equal t -> lowest (gl_InstanceID, gl_PrimitiveID)

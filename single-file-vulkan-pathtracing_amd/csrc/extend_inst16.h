@@ -237,8 +237,9 @@ __global__ __launch_bounds__(TB) void k_extend_inst16(const uint4 *__restrict__ 
                     if (ptl::closer_instanced(t, V, W, det, pos, prim, cur_ipos, cur_iid, best_t, best_V, best_W, best_det, best_pos, best_prim, best_ipos, best_iid) && SHADOW)
                         sp = 0;  // any hit will do: nothing pending any more (the pop below finds the stack empty)
                 };
+                // (shadow rays: tmin < t < the ray's own bound, strictly -- best_t until the first hit, which ends the walk; tmax plays no part)
                 if (PAIRS) {
-                    ptl::pair_leaf_test(s_tri, (size_t)tri_base + 3 * (size_t)first, cnt == 2u, first, pre, orgp, tmin, tmax, accept,
+                    ptl::pair_leaf_test(s_tri, (size_t)tri_base + 3 * (size_t)first, cnt == 2u, first, pre, orgp, tmin, ptl::leaf_upper(SHADOW, best_t, tmax), accept,
                                         [&] {
                                             PT_COUNT_WAVE(c_hit_blocks);
                                             if (COUNT) c_hit_lanes++;
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(TB) void k_extend_inst16(const uint4 *__restrict__ 
                         const float4 a = s_tri[ti + 0], b = s_tri[ti + 1], c = s_tri[ti + 2];
                         float t, V, W, det;
                         bool divided = false;
-                        if (ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det, COUNT ? &divided : nullptr))
+                        if (ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, ptl::leaf_upper(SHADOW, best_t, tmax), t, V, W, det, COUNT ? &divided : nullptr))
                             accept(t, V, W, det, pos, __float_as_uint(a.w));
                         if (COUNT && divided) { PT_COUNT_WAVE(c_hit_blocks); c_hit_lanes++; }
                     }

@@ -552,7 +552,8 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                     const bool two = ((cur >> 11) & 3u) != 0u;  // count - 1: a fan pair at positions first, first + 1
                     if (COUNT) { c_tris += two ? 2u : 1u; c_leaf_lanes++; }
                     PT_COUNT_WAVE(c_tri_steps);
-                    ptl::pair_leaf_test(tri4, (size_t)tri_base + 3 * (size_t)first, two, first, pre, orgp, tmin, tmax,
+                    // (any-hit walks: the range ends at the ray's own bound -- best_t until the first hit, which ends the walk -- and tmax plays no part)
+                    ptl::pair_leaf_test(tri4, (size_t)tri_base + 3 * (size_t)first, two, first, pre, orgp, tmin, ptl::leaf_upper(ray_tmax != nullptr, best_t, tmax),
                                         [&](float t, float V, float W, float det, uint32_t pos, uint32_t) {
                                             if (ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos) && ray_tmax)
                                                 clear_stack();  // any hit will do: nothing pending any more
@@ -577,9 +578,10 @@ __device__ __forceinline__ void extend_body(const float4 *__restrict__ g_wide, c
                     const float4 a = tp[ti + 0], b = tp[ti + 1], c = tp[ti + 2];
                     float t, V, W, det;
                     bool divided = false;
+                    const float upper = ptl::leaf_upper(ray_tmax != nullptr, best_t, tmax);  // (any-hit walks: tmin < t < the ray's own bound, strictly; tmax plays no part)
                     const bool th = LDS_SCENE
-                        ? ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det, COUNT ? &divided : nullptr)
-                        : ptm::tri_test(pre, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det, COUNT ? &divided : nullptr);
+                        ? ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, upper, t, V, W, det, COUNT ? &divided : nullptr)
+                        : ptm::tri_test(pre, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, upper, t, V, W, det, COUNT ? &divided : nullptr);
                     if (COUNT && divided) { PT_COUNT_WAVE(c_hit_blocks); c_hit_lanes++; }
                     if (th) {
                         // closest t; equal t -> lowest gl_PrimitiveID (the OBJ has coincident quads)

@@ -844,9 +844,13 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                 PT_FB(FB_LEAF)
                 [[maybe_unused]] uint32_t e_pop[POP_N];
                 if constexpr (POP_WITH_LEAF) stk.template peek_n<POP_N>(e_pop);
+                // NEE: a shadow ray's range is tmin < t < its own bound, strictly -- best_t until the first hit, which ends the walk -- and tmax plays no
+                // part in it (the oracle's orc_trace(..., tmin, 0.999 dist)); a path ray's ends at tmax, and a hit AT best_t goes on to the tie rule
+                [[maybe_unused]] bool shadow_walk = false;
+                if constexpr (NEE) shadow_walk = my_nee[FS_NEE_POS * FTB] != PT_MISS;
                 if (PAIRS) {
                     const uint32_t first = cur & 0x7FFu;
-                    ptl::pair_leaf_test<true, true>(tri4, (size_t)tri_base + 3 * (size_t)first, ((cur >> 11) & 3u) != 0u, first, pre, orgp, tmin, tmax,
+                    ptl::pair_leaf_test<true, true>(tri4, (size_t)tri_base + 3 * (size_t)first, ((cur >> 11) & 3u) != 0u, first, pre, orgp, tmin, ptl::leaf_upper(NEE && shadow_walk, best_t, tmax),
                                         [&](float t, float V, float W, float det, uint32_t pos, uint32_t) {
                                             [[maybe_unused]] const bool closer =
                                                 ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos);
@@ -862,7 +866,7 @@ __device__ __forceinline__ void fused_body(RenderConst rc_arg, const uint32_t *_
                         const size_t ti = (size_t)tri_base + 3 * (size_t)pos;
                         const float4 a = tri4[ti + 0], b = tri4[ti + 1], c = tri4[ti + 2];
                         float t, V, W, det;
-                        if (ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det, nullptr)) {
+                        if (ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, ptl::leaf_upper(NEE && shadow_walk, best_t, tmax), t, V, W, det, nullptr)) {
                             bool closer = t < best_t;  // closest t; equal t -> lowest gl_PrimitiveID (the first vertex of a record carries it)
                             if (!closer && t == best_t)
                                 closer = best_pos == PT_MISS || __float_as_uint(a.w) < __float_as_uint(tri4[(size_t)tri_base + 3 * (size_t)best_pos].w);

@@ -1,12 +1,14 @@
 // pair_leaf.h -- ONE source of the fan-pair leaf step of the scenes that live in LDS: the watertight test (Woop, Benthin, Wald, JCGT 2013)
 // of a leaf that is one triangle (v0, v1, v2) or a fan pair (v0, v1, v2) + (v0, v2, v3), with the sheared vertices and the products of the
-// shared edge v0-v2 computed once, the true divide, the range check tmin < t < tmax -- and the two closest-hit rules that go with it.
+// shared edge v0-v2 computed once, the true divide, the range check tmin < t < tmax (the caller's upper end: ptl::leaf_upper) -- the range check
+// itself and the two closest-hit rules that go with it are hit_rule.h, which also compiles for the host.
 // Stands in for what the driver does behind traceRayEXT (raygen.rgen:63-75) for opaque, un-culled triangles (main.cpp:508, 525, 536).
 //
 // Four kernels instantiate it: k_extend (PAIRS: k_extend_lds7p) and k_fused for single-level scenes, k_extend_inst16 and k_fused_inst for
 // two-level ones.  Until round 5 each of them carried its own copy of these lines, kept equal by the parity tests only.
 #pragma once
 #include "pt_math.h"
+#include "hit_rule.h"
 
 namespace ptl {
 
@@ -52,7 +54,7 @@ __device__ __forceinline__ void pair_leaf_test(const float4 *tri4, size_t ti, bo
         const float T = (U * (pre.Sz * z0) + V * (pre.Sz * z1)) + W * (pre.Sz * z2);
         const float t = ptm::fdiv(T, det);
         // outside the range: a NaN goes on, which is neither closer than nor equal to anything (one select instead of two branches)
-        accept(((t > tmin) & (t < tmax)) ? t : __builtin_nanf(""), V, W, det, pos, prim);
+        accept(in_range(t, tmin, tmax) ? t : __builtin_nanf(""), V, W, det, pos, prim);
     };
     const float UA = Cx * By - Cy * Bx, VA = pAC - qAC, WA = Bx * Ay - By * Ax;
     const bool inA = inside(UA, VA, WA);
@@ -79,35 +81,6 @@ __device__ __forceinline__ void pair_leaf_test(const float4 *tri4, size_t ti, bo
     if (inA && inB) finish(UB, VB, WB, Az_, Cz_, Dz_, first + 1u, primB);
 }
 
-// Single-level rule: closest t; equal t -> lowest gl_PrimitiveID (the OBJ has coincident quads).  The ids of the two rivals are read when it
-// happens (the third vertex of every record carries its triangle's id, k_pack), not kept.  -> true: the hit replaced the best one.
-__device__ __forceinline__ bool closer_single_level(const float4 *tri4, uint32_t tri_base, float t, float V, float W, float det, uint32_t pos,
-                                                    float &best_t, float &best_V, float &best_W, float &best_det, uint32_t &best_pos)
-{
-    bool closer = t < best_t;
-    if (closer) {
-        best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos;
-    } else if (t == best_t) {  // (rare, and apart from the common path: merged into `closer` it cost every divide block seven scalar instructions)
-        if (best_pos == PT_MISS || __float_as_uint(tri4[(size_t)tri_base + 3 * (size_t)pos + 2].w) <
-                                       __float_as_uint(tri4[(size_t)tri_base + 3 * (size_t)best_pos + 2].w)) {
-            best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos;
-            closer = true;
-        }
-    }
-    return closer;
-}
-
-// Two-level rule: closest t; equal t -> lowest (gl_InstanceID, gl_PrimitiveID).
-__device__ __forceinline__ bool closer_instanced(float t, float V, float W, float det, uint32_t pos, uint32_t prim, uint32_t cur_ipos, uint32_t cur_iid,
-                                                 float &best_t, float &best_V, float &best_W, float &best_det, uint32_t &best_pos, uint32_t &best_prim,
-                                                 uint32_t &best_ipos, uint32_t &best_iid)
-{
-    if (t < best_t || (t == best_t && (cur_iid < best_iid || (cur_iid == best_iid && prim < best_prim)))) {
-        best_t = t; best_V = V; best_W = W; best_det = det; best_pos = pos; best_prim = prim;
-        best_ipos = cur_ipos; best_iid = cur_iid;
-        return true;
-    }
-    return false;
-}
+// (the two closest-hit rules that go with it, closer_single_level and closer_instanced: hit_rule.h)
 
 }  // namespace ptl

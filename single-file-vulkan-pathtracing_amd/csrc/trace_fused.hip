@@ -145,7 +145,8 @@ __global__ __launch_bounds__(TB, PT_EXTEND_WAVES) void k_trace_fused(const float
                 if (cur != DONE && (cur & LEAF_BIT)) {
                     const uint32_t first = cur & 0x7FFu;
                     const bool two = ((cur >> 11) & 3u) != 0u;  // count - 1: a fan pair at positions first, first + 1
-                    ptl::pair_leaf_test(tri4, (size_t)tri_base + 3 * (size_t)first, two, first, pre, orgp, tmin, tmax,
+                    // (ANY: tmin < t < the ray's own bound, strictly -- best_t until the first hit, which ends the walk; tmax plays no part)
+                    ptl::pair_leaf_test(tri4, (size_t)tri_base + 3 * (size_t)first, two, first, pre, orgp, tmin, ptl::leaf_upper(ANY, best_t, tmax),
                                         [&](float t, float V, float W, float det, uint32_t pos, uint32_t) {
                                             if (ptl::closer_single_level(tri4, tri_base, t, V, W, det, pos, best_t, best_V, best_W, best_det, best_pos) && ANY)
                                                 stk.clear();  // any hit will do: nothing pending any more
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(TB, PT_EXTEND_WAVES) void k_trace_fused(const float
                     const size_t ti = (size_t)tri_base + 3 * (size_t)pos;
                     const float4 a = tri4[ti + 0], b = tri4[ti + 1], c = tri4[ti + 2];
                     float t, V, W, det;
-                    if (ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, tmax, t, V, W, det)) {
+                    if (ptm::tri_test_perm(pre, orgp, { a.x, a.y, a.z }, { b.x, b.y, b.z }, { c.x, c.y, c.z }, tmin, ptl::leaf_upper(ANY, best_t, tmax), t, V, W, det)) {
                         // closest t; equal t -> lowest gl_PrimitiveID (the OBJ has coincident quads)
                         const uint32_t prim = __float_as_uint(a.w);
                         if (t < best_t || (t == best_t && prim < best_prim)) {
