@@ -156,7 +156,7 @@ pt_status pt_scene_set_bvh_quality(pt_scene *scene, uint32_t quality);
 
 /* Moves the scene's geometry: the counterpart of eAllowUpdate + BuildAccelerationStructureModeKHR::eUpdate.  vertices /
  * indices as for pt_scene_create, n_tris equal to the scene's (PT_ERR_INVALID_ARG otherwise, and on any argument error the
- * scene is left as it was); the per-face materials stay.  Blocking, and ordered after the work already queued on the context's
+ * scene is left as it was); the per-face materials stay (pt_scene_set_faces changes those).  Blocking, and ordered after the work already queued on the context's
  * stream (a PT_FLAG_ASYNC render of the scene sees the old geometry); films are not touched.  Afterwards every render, trace and
  * read-back sees the new geometry, and images, ray counts and hit records equal those of a scene freshly created from the same
  * arrays, in either mode:
@@ -216,6 +216,35 @@ pt_status pt_scene_update_device(pt_scene *scene, const void *d_vertices, uint32
  * area -- is read back), pt_scene_snapshot_previous and pt_film_motion (device-to-device copies), the re-set of the instances behind a
  * pt_scene_update[_device], the restoring of a parked set after a repair.  DESIGN.md section 28.                                        */
 pt_status pt_scene_set_instances_device(pt_scene *scene, const void *d_xforms3x4, uint32_t n);
+
+/* New per-face materials for the scene's triangles, without a rebuild: faces has pt_scene_create's layout (Kd.rgb, Ke.rgb: 6 floats per
+ * triangle, n_tris rows) in host memory (pt_scene_set_faces) or, dense and 4-byte aligned, in DEVICE memory on the context's device
+ * (pt_scene_set_faces_device).  After either call the scene is, bit for bit, in the state of a scene that had been created with the new
+ * faces and had then taken the same later calls (quality changes, instance sets, updates, snapshots, the first request for the 8-wide tree):
+ * every render on every pipeline (the NEE ones and instanced scenes included), pt_trace, pt_trace_device with its albedo and emission planes
+ * and pt_radiance_device in both forms, pt_render_aov, pt_render_guided, every film pass fed by them and every field of pt_scene_get_info.
+ * The trees are not touched: pt_scene_read_bvh, _bvh4 and _bvh8 return the bytes they returned before the call, and build_ms keeps its value.
+ * What the call rewrites is the kept copy of the materials, a few words per triangle of the shading tables, the emitter set of the NEE
+ * pipelines (its size may grow, shrink, reach 0 or leave 0) and, for instanced scenes, its world-space copies (made again by the next NEE
+ * render, whose limit of 2^24 copies then applies to the new count).
+ * Values are taken as pt_scene_create takes them, with no range check: -0.0, denormals, negative, overflowing, infinite, NaN (a triangle
+ * emits where a Ke component is != 0: -0.0 emits nothing, a NaN does).  Host and device forms may be mixed freely, with each other and with
+ * both forms of update and instance set.
+ * Execution: blocking, and ordered after the work queued on the context's stream (a PT_FLAG_ASYNC render queued before the call sees the old
+ * materials).  The array is read during the call and not retained: after return -- whatever the status -- it may be freed or overwritten.
+ * The host form uploads the array and then takes the device form's path: one path, one set of bits.  In the device form no face array crosses
+ * to the host; what is read back is what pt_scene_create_device reads back for emitters: their count, their ids (4 B each) and their records
+ * (80 B each).
+ * Refusals, each leaving the scene exactly as it was -- PT_ERR_INVALID_ARG: NULL scene or array; n_tris different from the scene's.
+ * PT_ERR_UNSUPPORTED: a broken scene (PT_BROKEN_SCENE_MSG; pt_scene_set_instances' rule).  PT_ERR_OOM: the new emitter set, or the staged
+ * copy of the materials (24 B per triangle, held during the call), cannot be allocated.  Every allocation and every read-back happens before
+ * the first write to anything the scene owns: the call works on a staged copy of the faces and a staged emitter set, then swaps, so a failed
+ * call renders the old materials on, never a mix.
+ * pt_scene_read_faces: the scene's kept copy of the materials, f32 [6 * n_tris] (what it was created with, or the last set); NULL is
+ * PT_ERR_INVALID_ARG.  It answers for a broken scene too.  DESIGN.md section 30.                                                          */
+pt_status pt_scene_set_faces(pt_scene *scene, const float *faces, uint32_t n_tris);
+pt_status pt_scene_set_faces_device(pt_scene *scene, const void *d_faces, uint32_t n_tris);
+pt_status pt_scene_read_faces(const pt_scene *scene, float *faces);
 
 /* Debug/parity read-back of the device-built LBVH.  keys/prim_of_pos: n_tris entries each;
  * nodes16: n_nodes x 16 dwords {lmin[3] lmax[3] rmin[3] rmax[3] left right 0 0}, child bit31 =

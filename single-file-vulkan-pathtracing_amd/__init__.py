@@ -206,7 +206,7 @@ HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
 # every symbol include/pt_api.h and include/pt_host.h declare
 API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "pt_scene_create", "pt_scene_destroy",
                "pt_scene_set_instances", "pt_scene_set_bvh_quality", "pt_scene_update", "pt_scene_create_device", "pt_scene_update_device",
-               "pt_scene_set_instances_device",
+               "pt_scene_set_instances_device", "pt_scene_set_faces", "pt_scene_set_faces_device", "pt_scene_read_faces",
                "pt_scene_get_info", "pt_scene_read_bvh", "pt_scene_read_bvh4", "pt_scene_read_bvh8", "pt_film_create", "pt_film_create_external", "pt_film_clear",
                "pt_film_read_f32", "pt_film_read_bgra8", "pt_film_destroy", "pt_params_default", "pt_render",
                "pt_render_prepare", "pt_trace", "pt_film_enable_aov", "pt_render_aov", "pt_film_read_aov",
@@ -266,6 +266,10 @@ def lib_amd():
         L.pt_scene_create_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(vp)]
         L.pt_scene_update_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
         L.pt_scene_set_instances_device.argtypes = [vp, vp, C.c_uint32]
+        if hasattr(L, "pt_scene_set_faces"):   # (materials without a rebuild; dev A/B runs load older builds through PT_LIB_AMD)
+            L.pt_scene_set_faces.argtypes = [vp, vp, C.c_uint32]
+            L.pt_scene_set_faces_device.argtypes = [vp, vp, C.c_uint32]
+            L.pt_scene_read_faces.argtypes = [vp, vp]
         L.pt_scene_get_info.argtypes = [vp, C.POINTER(SceneInfo)]
         L.pt_scene_read_bvh.argtypes = [vp, vp, vp, vp]
         L.pt_scene_read_bvh4.argtypes = [vp, vp]
@@ -743,6 +747,52 @@ class Scene:
         torch.cuda.current_stream(x.device).synchronize()   # (update_tensors has the reasons)
         n = x.numel() // 12
         self.set_instances_device(x.data_ptr() if n else None, n)
+
+    def set_faces(self, faces):
+        """New per-face materials (Kd.rgb, Ke.rgb: 6 floats per triangle) for the scene's triangles, without a rebuild (pt_scene_set_faces):
+        afterwards the scene is what Scene(ctx, vertices, indices, faces) followed by the same later calls would be, bit for bit."""
+        f = np.ascontiguousarray(faces, dtype=np.float32).reshape(-1)
+        if f.size % 6:
+            raise ValueError("faces must be 6*nt")
+        self.ctx._check(lib_amd().pt_scene_set_faces(self.h, f.ctypes.data, f.size // 6))
+
+    def set_faces_device(self, faces_ptr, n_tris):
+        """pt_scene_set_faces_device over a raw DEVICE pointer: f32 [6 * n_tris], dense (include/pt_api.h).  Blocking."""
+        self.ctx._check(lib_amd().pt_scene_set_faces_device(self.h, faces_ptr, n_tris))
+
+    def _n_tris(self):
+        """the scene's triangle count (it never changes): asked once, from the scene's record -- no device call"""
+        if getattr(self, "_nt", None) is None:
+            self._nt = int(self.info().n_tris)
+        return self._nt
+
+    def _faces_tensor(self, faces):
+        """The tensor rule of set_faces_tensor, in _geometry_tensors' order (type, sizes, device) -> the tensor; ValueError before a device is
+        touched.  Unlike the geometry wrappers it copies nothing: a tensor that is not contiguous is refused."""
+        import torch
+        if not isinstance(faces, torch.Tensor) or faces.dtype != torch.float32:
+            raise ValueError("faces must be a float32 CUDA tensor")
+        if not faces.is_contiguous():
+            raise ValueError("faces must be contiguous")
+        if faces.numel() != 6 * self._n_tris():
+            raise ValueError("faces must hold 6*nt elements, nt the scene's triangle count")
+        if not faces.is_cuda:
+            raise ValueError("faces must be a CUDA tensor")
+        return faces
+
+    def set_faces_tensor(self, faces):
+        """Scene.set_faces for a torch tensor on the GPU, nothing through the host: a contiguous float32 CUDA tensor of 6*nt elements, nt the
+        scene's triangle count.  The result equals set_faces() of its host copy, bit for bit."""
+        import torch
+        f = self._faces_tensor(faces)
+        torch.cuda.current_stream(f.device).synchronize()   # (update_tensors has the reasons)
+        self.set_faces_device(f.data_ptr(), f.numel() // 6)
+
+    def read_faces(self):
+        """-> the scene's kept copy of the materials, float32 [6 * n_tris] (pt_scene_read_faces)"""
+        f = np.zeros(6 * self.info().n_tris, dtype=np.float32)
+        self.ctx._check(lib_amd().pt_scene_read_faces(self.h, f.ctypes.data))
+        return f
 
     def snapshot_previous(self):
         """Remembers the scene as it stands now -- vertex positions and instance matrices -- as "the previous geometry" of Film.motion

@@ -299,6 +299,40 @@ pt_status pt_scene_update_device(pt_scene *s, const void *d_vertices, uint32_t n
     return rc;
 }
 
+// New per-face materials for the scene's triangles (scene_build.hip ptb_set_faces).  The host form uploads into the staged copy the device form
+// fills by a device-to-device copy: one path from there, one set of bits.  A failure waits for the stream before it returns: the caller's array
+// is not read after the call, whatever it answers.
+static pt_status set_faces(pt_scene *s, const float *faces, uint32_t n_tris, bool on_device)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = s->ctx;
+    if (!faces) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    if (n_tris != s->n_tris) { ctx->err = "new materials keep the scene's triangles: n_tris must equal the scene's"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    const pt_status rc = guarded(ctx, [&] { return ptb_set_faces(s, faces, on_device); });
+    if (rc != PT_OK) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+pt_status pt_scene_set_faces(pt_scene *s, const float *faces, uint32_t n_tris) { return set_faces(s, faces, n_tris, false); }
+
+pt_status pt_scene_set_faces_device(pt_scene *s, const void *d_faces, uint32_t n_tris)
+{
+    return set_faces(s, static_cast<const float *>(d_faces), n_tris, true);
+}
+
+// The kept copy of the materials: of source lifetime, so a broken scene answers too.
+pt_status pt_scene_read_faces(const pt_scene *s, float *faces)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    pt_ctx *ctx = s->ctx;
+    if (!faces) { ctx->err = "null argument"; return PT_ERR_INVALID_ARG; }
+    PT_HIP(ctx, hipSetDevice(ctx->device));
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PT_HIP(ctx, hipMemcpy(faces, s->d_faces, sizeof(float) * 6 * (size_t)s->n_tris, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 pt_status pt_scene_get_info(const pt_scene *s, pt_scene_info *info)
 {
     if (!s || !info) return PT_ERR_INVALID_ARG;

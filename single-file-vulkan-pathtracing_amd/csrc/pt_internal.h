@@ -414,6 +414,29 @@ pt_status ptb_update_scene(pt_scene *s, const pt_geometry &g, uint32_t mode);
 pt_status ptsd_check_indices(pt_ctx *ctx, const uint32_t *d_indices, uint32_t n_tris, uint32_t n_verts);
 pt_status ptsd_find_emitters(pt_scene *s);
 pt_status ptsd_host_products(pt_scene *s, std::vector<uint8_t> *pair);
+// An emitter set by reference: the scene's own (what the two calls above fill), or a staged one that pt_scene_set_faces fills from the new
+// materials while the scene renders the old ones on, and swaps in when it is whole.
+struct pt_emitters {
+    float4 *&d_lights; uint32_t *&d_light_prim; uint32_t &n_lights; float &light_area;
+    std::vector<float4> &h_lights; std::vector<uint32_t> &h_light_prim;
+};
+inline pt_emitters pt_scene_emitters(pt_scene *s) { return { s->d_lights, s->d_light_prim, s->n_lights, s->light_area, s->h_lights, s->h_light_prim }; }
+struct pt_staged_emitters {
+    float4 *d_lights = nullptr; uint32_t *d_light_prim = nullptr; uint32_t n_lights = 0; float light_area = 0.f;
+    std::vector<float4> h_lights; std::vector<uint32_t> h_light_prim;
+    pt_staged_emitters() = default;
+    pt_staged_emitters(const pt_staged_emitters &) = delete;
+    pt_staged_emitters &operator=(const pt_staged_emitters &) = delete;
+    ~pt_staged_emitters() { if (d_lights) (void)hipFree(d_lights); if (d_light_prim) (void)hipFree(d_light_prim); }  // (what was not swapped in)
+    pt_emitters set() { return { d_lights, d_light_prim, n_lights, light_area, h_lights, h_light_prim }; }
+};
+// ... the same two for any set: the emitters of the materials d_faces (f32 [6 * n_tris], device) over the scene's d_tri_orig, into `e`
+pt_status ptsd_find_emitters(pt_scene *s, const float *d_faces, pt_emitters e);
+pt_status ptsd_host_products(pt_scene *s, const float *d_faces, pt_emitters e, std::vector<uint8_t> *pair);
+// scene_build.hip: pt_scene_set_faces[_device] behind the argument checks -- faces: f32 [6 * n_tris] in host or device memory.  scene_faces.hip:
+// its kernel, the material words of the per-triangle tables in leaf order `order` from d_faces (queued on st).
+pt_status ptb_set_faces(pt_scene *s, const float *faces, bool on_device);
+void ptsf_launch_set_faces(pt_scene *s, const float *d_faces, const uint32_t *order, hipStream_t st);
 // ... and its fold alone: the cdf words of the n records of d_lights from their terms d_half[0..n), the total to *d_total (queued on st)
 void ptsd_launch_fold(const float *d_half, uint32_t n, float4 *d_lights, float *d_total, hipStream_t st);
 // scene_instances.hip: what pt_scene_set_instances does on the host with the matrices, as kernels.  check_invert: the

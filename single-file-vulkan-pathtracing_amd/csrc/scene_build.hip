@@ -220,6 +220,11 @@ static pt_status alloc_filled(pt_scene *s, const char *what, const std::vector<p
     return PT_OK;
 }
 
+// The leaf order the traversed tree's per-triangle tables are packed in -- the prim_of the last k_pack of d_tri4 / d_shade4 / d_shade64 / d_ke4 was
+// given: the surface-area BVH4's (builder 1) or the PLOC tree's (builder 2), else the LBVH's.  What a refit re-packs in, and what
+// pt_scene_set_faces rewrites the material words in.
+static const uint32_t *traversed_order(const pt_scene *s) { return s->bvh4_builder != 0u ? s->d_prim_of_sah : s->d_prim_of; }
+
 // leaf_pad() of the device build, same float operations
 static float leaf_pad_of(const float *bmin, const float *bmax)
 {
@@ -863,7 +868,7 @@ static pt_status refit_tree_products(pt_scene *s, const float4 *d_tlo, const flo
     if (rc == PT_OK && s->d_wide8)
         rc = ptb_refit_wide(ctx, 2, s->d_wide8, s->n_wide8, d_tlo, d_thi, s->d_prim_of8, n, pad, s->norm_c, s->norm_rs);
     if (rc != PT_OK) return rc;
-    const uint32_t *order = s->bvh4_builder != 0u ? s->d_prim_of_sah : s->d_prim_of;  // the traversed leaf order
+    const uint32_t *order = traversed_order(s);
     if (s->d_wide8)  // (d_shade4 is scratch here: the k_pack below writes it)
         k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, s->d_prim_of8, n, s->d_tri4_8, s->d_shade4, s->d_shade64_8, s->d_ke4_8);
     k_pack<<<gt, TB, 0, st>>>(s->d_tri_orig, s->d_faces, order, n, s->d_tri4, s->d_shade4, s->d_shade64, s->d_ke4, s->d_frame4);
@@ -945,4 +950,54 @@ pt_status ptb_update_scene(pt_scene *s, const pt_geometry &g, uint32_t mode)
     if (n_inst) { s->h_xforms = xforms; s->d_xforms = d_xforms; s->n_xforms_dev = n_xforms_dev; }  // parked: set again below, or by the next successful build of the broken scene
     if (rc != PT_OK) return rc;
     return restore_parked_instances(s, quality);
+}
+
+// ---- pt_scene_set_faces / pt_scene_set_faces_device: new per-face materials for the same triangles -------
+// No tree, node or geometry table depends on a material.  What does: the kept copy d_faces (a rebuild, a quality change and the first 8-wide
+// request re-pack from it), the material words of the per-triangle tables (scene_faces.hip), the emitter set of the NEE pipelines (scene_device.hip's
+// kernels, the host loop's bits) and, instanced, its world-space copies (dropped: the next NEE render makes them again).  Everything the call
+// allocates or reads back happens on a STAGED copy of the faces and a STAGED emitter set, before the first write to anything the scene owns: a
+// call that fails leaves the scene rendering the old materials, never a mix.
+static pt_status set_faces_staged(pt_scene *s, const float *faces, bool on_device, DevBuf<float> &d_new, pt_staged_emitters &em)
+{
+    pt_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t bytes = sizeof(float) * 6 * (size_t)s->n_tris;
+    PT_TRY(pt_scratch_alloc(ctx, "the staged materials", { pt_buf_of(d_new.p, bytes) }, nullptr, 0));
+    PT_HIP(ctx, hipMemcpyAsync(d_new.p, faces, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    PT_TRY(ptsd_find_emitters(s, d_new.p, em.set()));             // the count and the ids come back ...
+    PT_TRY(ptsd_host_products(s, d_new.p, em.set(), nullptr));    // ... then the records and their total area
+    // nothing below allocates or reads back: the material words in place, then the swap
+    ptsf_launch_set_faces(s, d_new.p, traversed_order(s), st);
+    PT_HIP(ctx, hipGetLastError());
+    PT_HIP(ctx, hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+pt_status ptb_set_faces(pt_scene *s, const float *faces, bool on_device)
+{
+    pt_ctx *ctx = s->ctx;
+    PT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // after whatever is queued on the scene (a PT_FLAG_ASYNC render included)
+    if (s->broken) { ctx->err = PT_BROKEN_SCENE_MSG; return PT_ERR_UNSUPPORTED; }
+    DevBuf<float> d_new;
+    pt_staged_emitters em;
+    const pt_status rc = set_faces_staged(s, faces, on_device, d_new, em);
+    if (rc != PT_OK) {  // (nothing queued may outlive the staged set it writes to)
+        const std::string err = ctx->err;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipGetLastError();
+        ctx->err = err;
+        return rc;
+    }
+    std::swap(s->d_faces, d_new.p);  // (the old copy goes with d_new)
+    std::swap(s->d_lights, em.d_lights);
+    std::swap(s->d_light_prim, em.d_light_prim);  // never the ids of another emitter set: refreshed with the set, or gone with it
+    s->n_lights = em.n_lights;
+    s->light_area = em.light_area;
+    s->h_lights.swap(em.h_lights);
+    s->h_light_prim.swap(em.h_light_prim);
+    // the instances' world-space emitter copies were the old set's: ptb_ensure_inst_lights / ptsi_inst_lights make them again on the next NEE render
+    pt_scratch_free({ pt_buf_of(s->d_lights_inst) }, nullptr, 0);
+    s->n_lights_inst = 0; s->light_area_inst = 0.f;
+    return PT_OK;
 }

@@ -95,7 +95,9 @@ pt_status ptsd_check_indices(pt_ctx *ctx, const uint32_t *d_indices, uint32_t n_
     return bad ? pt_bad(ctx, "vertex index out of range") : PT_OK;
 }
 
-pt_status ptsd_find_emitters(pt_scene *s)
+pt_status ptsd_find_emitters(pt_scene *s) { return ptsd_find_emitters(s, s->d_faces, pt_scene_emitters(s)); }
+
+pt_status ptsd_find_emitters(pt_scene *s, const float *d_faces, pt_emitters e)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
@@ -103,45 +105,47 @@ pt_status ptsd_find_emitters(pt_scene *s)
     DevBuf<uint32_t> d_place, d_sums;
     PT_HIP(ctx, d_place.alloc((size_t)n + 1));
     PT_HIP(ctx, d_sums.alloc(((size_t)n + 1 + SC_TILE - 1) / SC_TILE));
-    k_sd_emitter_flags<<<g, TB, 0, st>>>(s->d_faces, n, d_place.p);
+    k_sd_emitter_flags<<<g, TB, 0, st>>>(d_faces, n, d_place.p);
     exclusive_scan(d_place.p, n + 1, d_sums.p, st);
     uint32_t count = 0;
     PT_HIP(ctx, hipMemcpyAsync(&count, d_place.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PT_HIP(ctx, hipStreamSynchronize(st));
     PT_HIP(ctx, hipGetLastError());
-    s->n_lights = count;
-    s->h_light_prim.assign(count, 0u);
+    e.n_lights = count;
+    e.h_light_prim.assign(count, 0u);
     if (!count) return PT_OK;
-    PT_TRY(ptb_scene_alloc(s, "the emitter table", { pt_buf_of(s->d_lights, sizeof(float4) * 5 * (size_t)count), pt_buf_of(s->d_light_prim, sizeof(uint32_t) * count) }));
-    k_sd_emitter_compact<<<g, TB, 0, st>>>(d_place.p, n, s->d_light_prim);
+    PT_TRY(ptb_scene_alloc(s, "the emitter table", { pt_buf_of(e.d_lights, sizeof(float4) * 5 * (size_t)count), pt_buf_of(e.d_light_prim, sizeof(uint32_t) * count) }));
+    k_sd_emitter_compact<<<g, TB, 0, st>>>(d_place.p, n, e.d_light_prim);
     PT_HIP(ctx, hipGetLastError());
-    PT_HIP(ctx, hipMemcpyAsync(s->h_light_prim.data(), s->d_light_prim, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, st));
+    PT_HIP(ctx, hipMemcpyAsync(e.h_light_prim.data(), e.d_light_prim, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, st));
     PT_HIP(ctx, hipStreamSynchronize(st));
     return PT_OK;
 }
 
 // One scratch allocation, one wait: the records and their fold, the pair flags of a small scene (pair != nullptr), then everything the host keeps.
-pt_status ptsd_host_products(pt_scene *s, std::vector<uint8_t> *pair)
+pt_status ptsd_host_products(pt_scene *s, std::vector<uint8_t> *pair) { return ptsd_host_products(s, s->d_faces, pt_scene_emitters(s), pair); }
+
+pt_status ptsd_host_products(pt_scene *s, const float *d_faces, pt_emitters e, std::vector<uint8_t> *pair)
 {
     pt_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
-    const uint32_t n = s->n_lights, nt = s->n_tris;
-    s->h_lights.assign(5 * (size_t)n, make_float4(0.f, 0.f, 0.f, 0.f));
-    s->light_area = 0.f;
+    const uint32_t n = e.n_lights, nt = s->n_tris;
+    e.h_lights.assign(5 * (size_t)n, make_float4(0.f, 0.f, 0.f, 0.f));
+    e.light_area = 0.f;
     if (!n && !pair) return PT_OK;
-    if (n && !s->d_light_prim) {  // a scene made from host arrays: the emitters' ids go to the device once and stay
-        PT_HIP(ctx, hipMalloc((void **)&s->d_light_prim, sizeof(uint32_t) * n));
-        PT_HIP(ctx, hipMemcpyAsync(s->d_light_prim, s->h_light_prim.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
+    if (n && !e.d_light_prim) {  // a scene made from host arrays: the emitters' ids go to the device once and stay
+        PT_HIP(ctx, hipMalloc((void **)&e.d_light_prim, sizeof(uint32_t) * n));
+        PT_HIP(ctx, hipMemcpyAsync(e.d_light_prim, e.h_light_prim.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
     }
     DevBuf<float> d_scratch;  // [n] the terms of the fold, [1] its total, then nt bytes of pair flags
     PT_HIP(ctx, d_scratch.alloc((size_t)n + 1 + (pair ? (nt + 3) / 4 : 0)));
     uint8_t *d_same = reinterpret_cast<uint8_t *>(d_scratch.p + n + 1);
     std::vector<uint8_t> same(pair ? nt : 0);
     if (n) {
-        k_sd_emitter_records<<<(n + TB - 1) / TB, TB, 0, st>>>(s->d_tri_orig, s->d_faces, s->d_light_prim, n, s->d_lights, d_scratch.p);
-        k_sd_emitter_fold<<<1, SD_FOLD, 0, st>>>(d_scratch.p, n, s->d_lights, d_scratch.p + n);
-        PT_HIP(ctx, hipMemcpyAsync(s->h_lights.data(), s->d_lights, sizeof(float4) * 5 * (size_t)n, hipMemcpyDeviceToHost, st));
-        PT_HIP(ctx, hipMemcpyAsync(&s->light_area, d_scratch.p + n, sizeof(float), hipMemcpyDeviceToHost, st));
+        k_sd_emitter_records<<<(n + TB - 1) / TB, TB, 0, st>>>(s->d_tri_orig, d_faces, e.d_light_prim, n, e.d_lights, d_scratch.p);
+        k_sd_emitter_fold<<<1, SD_FOLD, 0, st>>>(d_scratch.p, n, e.d_lights, d_scratch.p + n);
+        PT_HIP(ctx, hipMemcpyAsync(e.h_lights.data(), e.d_lights, sizeof(float4) * 5 * (size_t)n, hipMemcpyDeviceToHost, st));
+        PT_HIP(ctx, hipMemcpyAsync(&e.light_area, d_scratch.p + n, sizeof(float), hipMemcpyDeviceToHost, st));
     }
     if (pair) {
         k_sd_fan_flags<<<(nt + TB - 1) / TB, TB, 0, st>>>(s->d_tri_orig, nt, d_same);
