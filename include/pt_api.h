@@ -927,6 +927,69 @@ pt_status pt_trace_device(pt_scene *scene, const pt_trace_desc *desc, uint64_t n
 /* the device bytes the context holds for pt_trace_device (0 before the first call) */
 pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes);
 
+/* ---- closest point on the mesh for points in device memory ------------------------------------------------------------------------------
+ * pt_nearest_device(scene, desc, n, device_ms) answers, for n points that lie in DEVICE memory, "which point of the mesh is closest to P, on
+ * which triangle, and how far away?" into DEVICE memory: penetration depth, contact candidates, a point-to-mesh or Chamfer loss, an unsigned
+ * distance field.  One persistent kernel per launch reads row i of d_points, walks the scene's BVH4 (the tree pt_scene_read_bvh4 returns, kept
+ * current by pt_scene_update[_device]) by box distance and writes query i's answer straight into the caller's arrays.
+ *
+ * Definition.  The result is bit-exact by construction: all arithmetic is binary32, every operation rounded on its own, no contraction, denormals
+ * kept; dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; min, max and clamp are selects (a NaN stays a NaN).  For a query P and a triangle with
+ * vertices A, B, C (as pt_scene_create got them), the region algorithm of Ericson, Real-Time Collision Detection 5.1.5, in this order:
+ *   ab = B - A, ac = C - A, ap = P - A;  d1 = dot(ab, ap), d2 = dot(ac, ap);           d1 <= 0 && d2 <= 0             -> (u, v) = (0, 0)
+ *   bp = P - B;  d3 = dot(ab, bp), d4 = dot(ac, bp);                                     d3 >= 0 && d4 <= d3            -> (1, 0)
+ *   vc = d1 * d4 - d3 * d2;                                                              vc <= 0 && d1 >= 0 && d3 <= 0  -> (d1 / (d1 - d3), 0)
+ *   cp = P - C;  d5 = dot(ab, cp), d6 = dot(ac, cp);                                     d6 >= 0 && d5 <= d6            -> (0, 1)
+ *   vb = d5 * d2 - d1 * d6;                                                              vb <= 0 && d2 >= 0 && d6 <= 0  -> (0, d2 / (d2 - d6))
+ *   va = d3 * d6 - d5 * d4, e = d4 - d3, f = d5 - d6;                                    va <= 0 && e >= 0 && f >= 0    -> w = e / (e + f), (1 - w, w)
+ *   otherwise  s = (va + vb) + vc                                                                                       -> (vb / s, vc / s)
+ * with the true IEEE divide; u and v are the weights of B and C (pt_hit's convention).  Then per component Q = (A + ab * u) + ac * v, CLAMPED to
+ * [min(A, B, C), max(A, B, C)]; D = P - Q; dist2 = (D.x * D.x + D.y * D.y) + D.z * D.z.  (The clamp does nothing in exact arithmetic.  It is
+ * what makes the tree walk exact: with it dist2 is never below the same expression's distance to any fp32 box that contains the triangle's
+ * vertices -- csrc/nearest_kernel.h has the lemma -- so skipping a box that lies strictly beyond the best dist2 found loses nothing.)
+ * Search radius: m = d_max_dist[i], or desc.max_dist for every query; r2 = m * m if m >= 0; a negative or NaN m finds nothing.
+ * Winner: over ALL triangles with dist2 <= r2 the least dist2, then the lowest primitive id.  A NaN dist2 (the interior branch of a degenerate
+ * triangle, a NaN query) never wins.  d_nearest[i] = {prim, dist2, u, v} of the winner, d_point[i] = its Q.
+ * Miss: a query that finds nothing gets prim = 0xFFFFFFFF, dist2 = u = v = +0.0, and d_point = +0.0 three times.
+ * The answer is a property of the triangles alone: it does not depend on the tree, the builder (pt_scene_set_bvh_quality), the form, the launch
+ * shape or any pt_tuning knob, and equals the loop over all triangles bit for bit.
+ *
+ * Execution.  Blocking, on the context's stream, behind the work already queued there.  A scene that lost its trees is repaired first, as
+ * pt_trace_device does.  n == 0 is PT_OK and launches nothing.  n is 64-bit: one launch per 2^30 queries.  No workspace: stack entries beyond
+ * the per-lane LDS share (pt_tuning.lds_stack) go to the context's stack-spill area, which the ray kernels use too; pt_trace_workspace_bytes is
+ * unchanged.  pt_stats: launches_other grows by the number of launches; rays, paths, launches_extend, pipeline and extend_variant are not
+ * touched.  *device_ms (nullable): first kernel to last kernel.  pt_tuning.refill, lds_stack and extend_blocks shape the launch as they shape the
+ * ray kernels'.
+ * Forms.  PT_NEAREST_LDS stages the nodes (144 B each) and one copy of the triangles (48 B each) in LDS; it applies while that image and the
+ * stack (lds_stack x 2 KB per block) fit 96 KB.  PT_NEAREST_GLOBAL reads both through the caches and always applies.  PT_NEAREST_AUTO is
+ * PT_NEAREST_GLOBAL for every scene: it would take the LDS form for scenes of the ray kernels' LDS class (24 KB) only if that form's slowest
+ * measured pass beat the GLOBAL form's fastest on every shape (pt_trace_device's rule for PT_TRACE_AUTO).  Measured on the MI355X (Cornell box,
+ * 2^20 and 2^24 queries on a lattice and near the surface, in order and shuffled, medians of 7, profiles/nearest_probe.json): the LDS form's
+ * medians are 1.04 .. 1.21x faster on all eight shapes -- 2^24 lattice queries 0.66 against 0.73 ms (25 against 23 G queries/s), 2^20 shuffled
+ * 0.076 against 0.082 ms -- but on one shape its slowest pass (0.0645 ms) does not beat the GLOBAL form's fastest (0.0634 ms), so the rule keeps
+ * AUTO on GLOBAL; a caller who knows the scene fits names PT_NEAREST_LDS.  The 1 M-triangle soup answers 2^20 queries in 0.71 .. 0.89 ms.
+ *
+ * Refusals, with nothing launched and nothing written -- PT_ERR_INVALID_ARG: NULL scene or desc; NULL d_points with n > 0; d_nearest and d_point
+ * both NULL; an unknown form; flags != 0; a nonzero reserved word; max_dist NaN or negative when d_max_dist is NULL.  PT_ERR_UNSUPPORTED: an
+ * instanced scene -- distance under an instance's general 3x4 matrix is not object-space distance (pt_scene_set_instances with n = 0 restores
+ * the mesh); PT_NEAREST_LDS for a scene whose image does not fit.
+ * Out of scope: instanced scenes; signed distance (the caller has prim, and the face normal by pt_trace_device's conventions); k nearest; an
+ * asynchronous flag. */
+typedef struct pt_nearest { uint32_t prim; float dist2, u, v; } pt_nearest;   /* 16 bytes */
+enum { PT_NEAREST_AUTO = 0, PT_NEAREST_LDS = 1, PT_NEAREST_GLOBAL = 2 };
+typedef struct pt_nearest_desc {
+    const void *d_points;    /* DEVICE n x 3 f32, dense, 4-byte aligned */
+    const void *d_max_dist;  /* DEVICE n f32 per-query search radius, or NULL: `max_dist` for every query */
+    void *d_nearest;         /* DEVICE n x pt_nearest, may be NULL */
+    void *d_point;           /* DEVICE n x 3 f32: the closest point itself, may be NULL */
+    float max_dist;          /* default +inf */
+    uint32_t form;           /* PT_NEAREST_* */
+    uint32_t flags;          /* must be 0 */
+    uint32_t reserved[5];    /* must be 0 */
+} pt_nearest_desc;           /* 64 bytes */
+void pt_nearest_desc_default(pt_nearest_desc *d);   /* pointers NULL, max_dist +inf, AUTO */
+pt_status pt_nearest_device(pt_scene *scene, const pt_nearest_desc *desc, uint64_t n, float *device_ms /* may be NULL */);
+
 /* ---- path-traced radiance for caller-supplied rays ------------------------------------------------------------------------------------
  * pt_radiance_device(scene, desc, n, device_ms) answers "what radiance arrives along these rays?" for n rays that lie in DEVICE memory, into
  * DEVICE memory: the estimator of pt_render started from the caller's rays instead of the camera of raygen.rgen:51-57 -- a perspective,

@@ -145,6 +145,16 @@ class TraceDesc(C.Structure):
                 ("chunk_rays", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
+NEAREST_AUTO, NEAREST_LDS, NEAREST_GLOBAL = 0, 1, 2   # include/pt_api.h PT_NEAREST_*: the form pt_nearest_device takes
+NEAREST_DTYPE = np.dtype([("prim", "<u4"), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4")])   # pt_nearest
+
+
+class NearestDesc(C.Structure):
+    """include/pt_api.h pt_nearest_desc: closest-point queries on device buffers (pt_nearest_device)."""
+    _fields_ = [("d_points", C.c_void_p), ("d_max_dist", C.c_void_p), ("d_nearest", C.c_void_p), ("d_point", C.c_void_p),
+                ("max_dist", C.c_float), ("form", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
 RADIANCE_NEE, RADIANCE_ACCUMULATE = 1, 2   # include/pt_api.h PT_RADIANCE_*: the estimator and the store of pt_radiance_device
 RADIANCE_FUSED, RADIANCE_AUTO = 8, 16      # ... its form: the single-kernel one (or PT_ERR_UNSUPPORTED) | the library's choice; neither: the wavefront form
 
@@ -224,7 +234,8 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_film_enable_counts", "pt_film_read_counts", "pt_adaptive_params_default", "pt_render_adaptive",
                "pt_guided_params_default", "pt_render_guided",
                "pt_trace_desc_default", "pt_trace_device", "pt_trace_workspace_bytes",
-               "pt_radiance_desc_default", "pt_radiance_device", "pt_radiance_workspace_bytes"]
+               "pt_radiance_desc_default", "pt_radiance_device", "pt_radiance_workspace_bytes",
+               "pt_nearest_desc_default", "pt_nearest_device"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium", "pth_self_leaf_rule", "pth_self_leaf_c1", "pth_self_leaf_skip"]
 
@@ -344,6 +355,10 @@ def lib_amd():
             L.pt_radiance_desc_default.restype = None
             L.pt_radiance_device.argtypes = [vp, C.POINTER(RadianceDesc), C.c_uint64, C.POINTER(C.c_float)]
             L.pt_radiance_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+        if hasattr(L, "pt_nearest_device"):   # (closest point on the mesh; as above)
+            L.pt_nearest_desc_default.argtypes = [C.POINTER(NearestDesc)]
+            L.pt_nearest_desc_default.restype = None
+            L.pt_nearest_device.argtypes = [vp, C.POINTER(NearestDesc), C.c_uint64, C.POINTER(C.c_float)]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
         if hasattr(L, "pt_get_block_counts"):   # (API version 6; dev A/B runs load older builds through PT_LIB_AMD)
@@ -557,6 +572,10 @@ def trace_default_desc():
 
 def radiance_default_desc():
     return _default_params(RadianceDesc, "pt_radiance_desc_default")
+
+
+def nearest_default_desc():
+    return _default_params(NearestDesc, "pt_nearest_desc_default")
 
 
 def motion_default_params():
@@ -886,6 +905,48 @@ class Scene:
                 planes[name + "_ptr"] = out[name].data_ptr()
         torch.cuda.current_stream(dev).synchronize()
         self.trace_device(n, rays.data_ptr(), hits_ptr=hits.data_ptr(), **planes, **kw)
+        return out
+
+    def nearest_device(self, n, points_ptr, max_dist_ptr=None, nearest_ptr=None, point_ptr=None, max_dist=float("inf"), form=NEAREST_AUTO):
+        """pt_nearest_device over raw DEVICE pointers (include/pt_api.h has the layouts and the arithmetic): n points at points_ptr, their
+        closest triangle {prim, dist2, u, v} to nearest_ptr and / or the closest point itself to point_ptr.  Blocking -> device_ms."""
+        d = nearest_default_desc()
+        d.d_points, d.d_max_dist, d.d_nearest, d.d_point = points_ptr, max_dist_ptr, nearest_ptr, point_ptr
+        d.max_dist, d.form = max_dist, form
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_nearest_device(self.h, C.byref(d), n, C.byref(ms)))
+        return ms.value
+
+    def nearest_tensors(self, points, max_dist=None, max_dist_per_query=None, point=False, form="auto"):
+        """Closest point on the mesh for torch points, nothing through the host.  points: float32 CUDA tensor [n, 3] (made contiguous if it is
+        not); max_dist: one search radius (None: unbounded) or max_dist_per_query: float32 CUDA tensor [n].  -> dict of tensors: prim (int32,
+        -1 = nothing within the radius), dist2, u, v (float32) -- views of one [n, 4] buffer in pt_nearest's layout, no copy -- and, with
+        point, point [n, 3].  form: "auto", "lds" (PT_NEAREST_LDS: an error where the scene does not fit) or "global"; the result does not
+        depend on it."""
+        forms = {"auto": NEAREST_AUTO, "lds": NEAREST_LDS, "global": NEAREST_GLOBAL}
+        if form not in forms:
+            raise ValueError('form must be "auto", "lds" or "global"')
+        import torch
+        if points.dtype != torch.float32 or not points.is_cuda or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a float32 CUDA tensor of shape [n, 3]")
+        points = points.contiguous()
+        n, dev = points.shape[0], points.device
+        radii = None
+        if max_dist_per_query is not None:
+            if max_dist_per_query.dtype != torch.float32 or max_dist_per_query.device != dev or max_dist_per_query.numel() != n:
+                raise ValueError("max_dist_per_query must be a float32 tensor of n elements on the points' device")
+            radii = max_dist_per_query.contiguous()
+        rec = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        rec_f = rec.view(torch.float32)   # the same memory: pt_nearest is {u32, f32, f32, f32}
+        out = {"prim": rec[:, 0], "dist2": rec_f[:, 1], "u": rec_f[:, 2], "v": rec_f[:, 3]}
+        if point:
+            out["point"] = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        # the points were produced on torch's current stream, the query runs on the context's: torch's is drained first, and the call is blocking
+        # (trace_tensors' rule)
+        torch.cuda.current_stream(dev).synchronize()
+        self.nearest_device(n, points.data_ptr(), max_dist_ptr=radii.data_ptr() if radii is not None else None, nearest_ptr=rec.data_ptr(),
+                            point_ptr=out["point"].data_ptr() if point else None, max_dist=float("inf") if max_dist is None else max_dist,
+                            form=forms[form])
         return out
 
     def radiance_device(self, n, rays_ptr, radiance_ptr, seeds_ptr=None, moment2_ptr=None, spp=32, max_depth=8, tmin=0.001, tmax=10000.0, env=None,
