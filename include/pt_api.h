@@ -973,8 +973,9 @@ pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes);
  * both NULL; an unknown form; flags != 0; a nonzero reserved word; max_dist NaN or negative when d_max_dist is NULL.  PT_ERR_UNSUPPORTED: an
  * instanced scene -- distance under an instance's general 3x4 matrix is not object-space distance (pt_scene_set_instances with n = 0 restores
  * the mesh); PT_NEAREST_LDS for a scene whose image does not fit.
- * Out of scope: instanced scenes; signed distance (the caller has prim, and the face normal by pt_trace_device's conventions); k nearest; an
- * asynchronous flag. */
+ * Out of scope: instanced scenes; k nearest; an asynchronous flag.  (Signed distance: the sign is pt_crossings_device's business, below -- the
+ * face normal of `prim` is the wrong answer wherever Q lies on an edge or a vertex; the Python binding's Scene.signed_distance_tensors puts the
+ * two calls together.) */
 typedef struct pt_nearest { uint32_t prim; float dist2, u, v; } pt_nearest;   /* 16 bytes */
 enum { PT_NEAREST_AUTO = 0, PT_NEAREST_LDS = 1, PT_NEAREST_GLOBAL = 2 };
 typedef struct pt_nearest_desc {
@@ -989,6 +990,87 @@ typedef struct pt_nearest_desc {
 } pt_nearest_desc;           /* 64 bytes */
 void pt_nearest_desc_default(pt_nearest_desc *d);   /* pointers NULL, max_dist +inf, AUTO */
 pt_status pt_nearest_device(pt_scene *scene, const pt_nearest_desc *desc, uint64_t n, float *device_ms /* may be NULL */);
+
+/* ---- crossing counts and winding for rays in device memory ------------------------------------------------------------------------------
+ * pt_crossings_device(scene, desc, n, device_ms) answers, for n rays that lie in DEVICE memory, "how many triangles does this ray cross inside
+ * its range, and what is the signed sum of the crossings?" into DEVICE memory: the parity of the count says on which side of a closed surface
+ * the origin lies (inside / outside, the sign of a signed distance), the count itself gives thickness and occupancy.  No other walk of the
+ * library can say it: closest-hit walks shrink their range and any-hit walks stop.  One persistent kernel per launch reads row i, walks the
+ * scene's BVH4 (the tree pt_scene_read_bvh4 returns) with the ray's whole range and writes ray i's two words straight into the caller's arrays.
+ *
+ * Definition.  Bit-exact by construction: all arithmetic is binary32, every operation rounded on its own, no contraction, denormals kept; min
+ * and max are selects.  Ray i: origin O and direction D = row i of d_rays6, or O = row i of d_points and D = desc.direction; range (tmin, b)
+ * with b = d_tmax[i], or desc.tmax for every ray.  A triangle (A, B, C) COUNTS when both hold:
+ *   Triangle test.  pt_trace's canonical test accepts it with tmin < t < b (both ends exclusive): dominant axis kz = the first largest |D|
+ *     component, kx = kz + 1, ky = kz + 2 (mod 3); Sx = D.kx / D.kz, Sy = D.ky / D.kz, Sz = 1 / D.kz by true divides; per vertex P' = P - O,
+ *     x = P'.kx - Sx * P'.kz, y = P'.ky - Sy * P'.kz; U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax; rejected when some
+ *     of U, V, W is < 0 and some is > 0 (a zero edge function counts as inside); det = (U + V) + W, rejected when det == 0;
+ *     t = ((U * (Sz * A'.kz) + V * (Sz * B'.kz)) + W * (Sz * C'.kz)) / det; a NaN anywhere rejects.  No tie rule is involved: every accepted
+ *     triangle counts, duplicates included.
+ *   Own-box test.  pad = the largest absolute ordinate of the scene's box (pt_scene_info.bbox_min / bbox_max) times 2^-18 -- what every builder
+ *     and the refit put around every leaf.  lo = min(A, B, C) - pad, hi = max(A, B, C) + pad per component.  inv = 1 / copysign(max(|d|, 1e-20), d)
+ *     per component d of D, the correctly rounded reciprocal.  Per axis x0 = (lo - O) * inv, x1 = (hi - O) * inv;
+ *     tn = max(max(min x, min y), max(min z, tmin));  tf = min(min(max x, max y), min(max z, b));  the test passes iff tn <= tf * 1.0000004f.
+ * count[i] (u32) = the number of triangles that count.  winding[i] (i32) = the sum over them of +1 where det > 0 and -1 where det < 0.
+ * What the sign means: det has the sign of -(cross(B - A, C - A) . D) * D.kz (the triangle test does not swap kx and ky for a negative
+ * dominant component).  So for a ray whose dominant direction component is POSITIVE, det > 0 (+1) is a triangle whose geometric normal
+ * cross(B - A, C - A) points against the ray -- the ray enters through its front -- and det < 0 (-1) one it leaves through the front of; for a
+ * NEGATIVE dominant component the two swap.  winding * sign(D.kz) is therefore (entered - left) by cross(B - A, C - A): 0 outside a closed,
+ * consistently oriented mesh whichever way it is oriented, +-1 inside, the sign telling the orientation.  (pth_load_obj negates Y, which
+ * reverses the orientation of a loaded OBJ: a caller who needs the sign's meaning pins it on one triangle of the arrays given to
+ * pt_scene_create.)
+ * Rays that answer count = winding = 0 without a walk: a non-finite component of O or D; a NaN b; b <= tmin.  (A zero direction needs no rule:
+ * its shears are 0 / 0 = NaN and the triangle test rejects every triangle.)
+ * Why the own-box test is part of the definition.  A loop over all triangles meets triangles far away in units of their own size, whose
+ * sheared coordinates are quantised so coarsely that two edge functions cancel to exactly 0: a "hit" at a vertex of a triangle the ray never
+ * comes near.  A closest-hit walk is rarely hurt by them, a count over all triangles is exposed on every triangle; the own box drops them.  And
+ * it makes the tree walk exact by a lemma (csrc/crossings_kernel.h): for a finite ray the slab test has no NaN and is monotone in the box, so a
+ * ray that passes a triangle's own padded box passes every fp32 box that contains it -- every box on the path to the triangle, through
+ * pt_scene_update refits too.  The result is a property of the triangles and the scene's box alone: it does not depend on the tree, the builder
+ * (pt_scene_set_bvh_quality), the form, the launch shape or any pt_tuning knob, and equals the loop over all triangles bit for bit.
+ * Caveats that follow from the acceptance rule: a ray through a shared edge counts both triangles, a ray through a vertex the whole fan, a
+ * duplicated face twice.  Parity means inside / outside for closed meshes only, and off those measure-zero sets; callers vote over a few
+ * directions (the Python binding's Scene.inside_tensors).
+ *
+ * Execution.  Blocking, on the context's stream, behind the work already queued there.  A scene that lost its trees is repaired first.
+ * n == 0 is PT_OK and launches nothing.  n is 64-bit: one launch per 2^30 rays.  No workspace: stack entries (4 bytes) beyond the per-lane LDS
+ * share (pt_tuning.lds_stack) go to the context's stack-spill area.  pt_stats: launches_other grows by the number of launches; rays, paths,
+ * launches_extend, pipeline and extend_variant are not touched.  *device_ms (nullable): first kernel to last kernel.  pt_tuning.refill,
+ * lds_stack and extend_blocks shape the launch as they shape pt_nearest_device's.
+ * Forms.  PT_CROSSINGS_LDS stages the nodes (144 B each) and one copy of the triangles (48 B each) in LDS; it applies while that image and the
+ * stack (lds_stack x 1 KB per block) fit 96 KB.  PT_CROSSINGS_GLOBAL reads both through the caches and always applies.  PT_CROSSINGS_AUTO takes
+ * the LDS form for scenes of the ray kernels' LDS class (24 KB) and the GLOBAL form for every other scene.  The rule is pt_nearest_device's: the
+ * LDS form only if its slowest measured pass beat the GLOBAL form's fastest on every shape measured.  Measured on the MI355X (Cornell box, 2^20
+ * and 2^24 rays from a lattice, in order and shuffled, range (0.001, +inf), the forms alternated in one loop, medians of 7 with min .. max,
+ * scripts/probe_crossings.py -> profiles/crossings_probe.json): 2^20 in order 0.0994 (0.0980 .. 0.1022) against 0.1084 (0.1059 .. 0.1104) ms
+ * -- the narrowest of the four, 0.1022 below 0.1059 --, 2^20 shuffled 0.0996 against 0.1258, 2^24 in order 1.161 against 1.381, 2^24
+ * shuffled 0.947 against 1.455 (17.7 against 11.5 G rays/s): the LDS form's slowest pass beat the GLOBAL form's fastest on all four, by
+ * 1.09 .. 1.54x in the medians, outputs byte-equal.  The walk never prunes, so a big scene is slow: the 1 M-triangle soup (6.9 crossings per
+ * ray on average) takes 8.8 .. 9.4 ms for 2^20 rays and 118 .. 144 ms for 2^24, 10 .. 17x pt_trace_device's any-hit on the same rays
+ * (DESIGN.md section 32).
+ *
+ * Refusals, with nothing launched and nothing written -- PT_ERR_INVALID_ARG: NULL scene or desc; d_rays6 and d_points both set or both NULL
+ * with n > 0; d_count and d_winding both NULL; an unknown form; flags != 0; a nonzero reserved word; tmin not finite; tmax NaN or <= tmin while
+ * d_tmax is NULL; a non-finite direction while d_points is set.  PT_ERR_UNSUPPORTED: PT_CROSSINGS_LDS for a scene whose image does not fit;
+ * an instanced scene -- counting under instances is well defined for rays (unlike distance) and is simply not built: it needs a two-level
+ * walk and a pad per instance (pt_scene_set_instances with n = 0 restores the mesh).
+ * Out of scope: instanced scenes; a fill rule that counts a shared edge once; the list of the hits; an asynchronous flag; the generalized
+ * winding number. */
+enum { PT_CROSSINGS_AUTO = 0, PT_CROSSINGS_LDS = 1, PT_CROSSINGS_GLOBAL = 2 };
+typedef struct pt_crossings_desc {
+    const void *d_rays6;     /* DEVICE n x {origin.xyz, direction.xyz} f32, dense, 4-byte aligned, or NULL */
+    const void *d_points;    /* DEVICE n x 3 f32 origins sharing `direction`, or NULL; exactly one of the two */
+    const void *d_tmax;      /* DEVICE n f32 per-ray upper end, or NULL: `tmax` for every ray */
+    void *d_count;           /* DEVICE n x u32, may be NULL */
+    void *d_winding;         /* DEVICE n x i32, may be NULL (not both) */
+    float direction[3];      /* the direction of every d_points ray */
+    float tmin, tmax;        /* defaults 0 and +inf; range tmin < t < bound, both ends exclusive */
+    uint32_t form;           /* PT_CROSSINGS_* */
+    uint32_t flags;          /* must be 0 */
+    uint32_t reserved[3];    /* must be 0 */
+} pt_crossings_desc;         /* 80 bytes */
+void pt_crossings_desc_default(pt_crossings_desc *d);   /* pointers NULL, direction 0, tmin 0, tmax +inf, AUTO */
+pt_status pt_crossings_device(pt_scene *scene, const pt_crossings_desc *desc, uint64_t n, float *device_ms /* may be NULL */);
 
 /* ---- path-traced radiance for caller-supplied rays ------------------------------------------------------------------------------------
  * pt_radiance_device(scene, desc, n, device_ms) answers "what radiance arrives along these rays?" for n rays that lie in DEVICE memory, into

@@ -155,6 +155,23 @@ class NearestDesc(C.Structure):
                 ("max_dist", C.c_float), ("form", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+CROSSINGS_AUTO, CROSSINGS_LDS, CROSSINGS_GLOBAL = 0, 1, 2   # include/pt_api.h PT_CROSSINGS_*: the form pt_crossings_device takes
+
+
+class CrossingsDesc(C.Structure):
+    """include/pt_api.h pt_crossings_desc: crossing counts and winding for rays on device buffers (pt_crossings_device)."""
+    _fields_ = [("d_rays6", C.c_void_p), ("d_points", C.c_void_p), ("d_tmax", C.c_void_p), ("d_count", C.c_void_p), ("d_winding", C.c_void_p),
+                ("direction", C.c_float * 3), ("tmin", C.c_float), ("tmax", C.c_float), ("form", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+# Scene.inside_tensors' directions, in this order: unit vectors (to rounding), none along an axis, none in a coordinate plane, no two with the
+# same dominant axis among the first three.  A ray from a point is wrong about "inside" only where it passes through an edge or a vertex (the
+# acceptance rule counts both triangles / the whole fan) or grazes the surface; different directions do so at different points.
+INSIDE_DIRECTIONS = tuple(tuple(float(c) / float(np.sqrt(float(x * x + y * y + z * z))) for c in (x, y, z))
+                          for x, y, z in ((3, 2, 1), (-2, 6, -3), (2, -3, 6), (-6, -2, 3), (1, -4, -8)))
+
+
 RADIANCE_NEE, RADIANCE_ACCUMULATE = 1, 2   # include/pt_api.h PT_RADIANCE_*: the estimator and the store of pt_radiance_device
 RADIANCE_FUSED, RADIANCE_AUTO = 8, 16      # ... its form: the single-kernel one (or PT_ERR_UNSUPPORTED) | the library's choice; neither: the wavefront form
 
@@ -235,7 +252,8 @@ API_SYMBOLS = ["pt_ctx_create", "pt_ctx_destroy", "pt_last_error", "pt_sync", "p
                "pt_guided_params_default", "pt_render_guided",
                "pt_trace_desc_default", "pt_trace_device", "pt_trace_workspace_bytes",
                "pt_radiance_desc_default", "pt_radiance_device", "pt_radiance_workspace_bytes",
-               "pt_nearest_desc_default", "pt_nearest_device"]
+               "pt_nearest_desc_default", "pt_nearest_device",
+               "pt_crossings_desc_default", "pt_crossings_device"]
 HOST_SYMBOLS = ["pth_load_obj", "pth_load_obj_ex", "pth_free_scene", "pth_write_ppm_bgra8", "pth_write_pfm", "pth_write_soup_obj", "pth_make_soup",
                 "pth_make_stadium", "pth_self_leaf_rule", "pth_self_leaf_c1", "pth_self_leaf_skip"]
 
@@ -359,6 +377,10 @@ def lib_amd():
             L.pt_nearest_desc_default.argtypes = [C.POINTER(NearestDesc)]
             L.pt_nearest_desc_default.restype = None
             L.pt_nearest_device.argtypes = [vp, C.POINTER(NearestDesc), C.c_uint64, C.POINTER(C.c_float)]
+        if hasattr(L, "pt_crossings_device"):   # (crossing counts and winding; as above)
+            L.pt_crossings_desc_default.argtypes = [C.POINTER(CrossingsDesc)]
+            L.pt_crossings_desc_default.restype = None
+            L.pt_crossings_device.argtypes = [vp, C.POINTER(CrossingsDesc), C.c_uint64, C.POINTER(C.c_float)]
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
         if hasattr(L, "pt_get_block_counts"):   # (API version 6; dev A/B runs load older builds through PT_LIB_AMD)
@@ -576,6 +598,10 @@ def radiance_default_desc():
 
 def nearest_default_desc():
     return _default_params(NearestDesc, "pt_nearest_desc_default")
+
+
+def crossings_default_desc():
+    return _default_params(CrossingsDesc, "pt_crossings_desc_default")
 
 
 def motion_default_params():
@@ -948,6 +974,83 @@ class Scene:
                             point_ptr=out["point"].data_ptr() if point else None, max_dist=float("inf") if max_dist is None else max_dist,
                             form=forms[form])
         return out
+
+    def crossings_device(self, n, rays_ptr=None, points_ptr=None, direction=None, tmax_ptr=None, count_ptr=None, winding_ptr=None, tmin=0.0,
+                         tmax=float("inf"), form=CROSSINGS_AUTO):
+        """pt_crossings_device over raw DEVICE pointers (include/pt_api.h has the layouts and the arithmetic): n rays at rays_ptr, or n origins at
+        points_ptr sharing `direction`; how many triangles each crosses in (tmin, bound) to count_ptr and / or the signed sum to winding_ptr.
+        Blocking -> device_ms."""
+        d = crossings_default_desc()
+        d.d_rays6, d.d_points, d.d_tmax, d.d_count, d.d_winding = rays_ptr, points_ptr, tmax_ptr, count_ptr, winding_ptr
+        if direction is not None:
+            d.direction = (C.c_float * 3)(*direction)
+        d.tmin, d.tmax, d.form = tmin, tmax, form
+        ms = C.c_float(0.0)
+        self.ctx._check(lib_amd().pt_crossings_device(self.h, C.byref(d), n, C.byref(ms)))
+        return ms.value
+
+    def crossings_tensors(self, rays=None, points=None, direction=None, tmin=0.0, tmax=None, tmax_per_ray=None, winding=False, form="auto"):
+        """How many triangles torch rays cross, nothing through the host.  rays: float32 CUDA tensor [n, 6] {origin, direction}, or points: float32
+        CUDA tensor [n, 3] with one `direction` (three floats) for all of them -- exactly one of the two; made contiguous if they are not.  The
+        range is tmin < t < tmax (None: unbounded) or tmax_per_ray (float32 CUDA tensor [n]).  -> count, an int32 tensor [n] (the library's u32
+        words viewed as int32), or with winding=True (count, winding).  form: "auto", "lds" (PT_CROSSINGS_LDS: an error where the scene does not
+        fit) or "global"; the result does not depend on it."""
+        forms = {"auto": CROSSINGS_AUTO, "lds": CROSSINGS_LDS, "global": CROSSINGS_GLOBAL}
+        if form not in forms:
+            raise ValueError('form must be "auto", "lds" or "global"')
+        if (rays is None) == (points is None):
+            raise ValueError("exactly one of rays and points")
+        import torch
+        src, width = (rays, 6) if rays is not None else (points, 3)
+        if src.dtype != torch.float32 or not src.is_cuda or src.dim() != 2 or src.shape[1] != width:
+            raise ValueError(f"{'rays' if rays is not None else 'points'} must be a float32 CUDA tensor of shape [n, {width}]")
+        if points is not None and (direction is None or len(direction) != 3):
+            raise ValueError("points need a direction of three floats")
+        src = src.contiguous()
+        n, dev = src.shape[0], src.device
+        bound = None
+        if tmax_per_ray is not None:
+            if tmax_per_ray.dtype != torch.float32 or tmax_per_ray.device != dev or tmax_per_ray.numel() != n:
+                raise ValueError("tmax_per_ray must be a float32 tensor of n elements on the rays' device")
+            bound = tmax_per_ray.contiguous()
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        wind = torch.empty(n, dtype=torch.int32, device=dev) if winding else None
+        if n == 0:   # (an empty tensor's data_ptr() is NULL, which the library would read as "no output named")
+            return (count, wind) if winding else count
+        # the rays were produced on torch's current stream, the query runs on the context's: torch's is drained first, and the call is blocking
+        # (trace_tensors' rule)
+        torch.cuda.current_stream(dev).synchronize()
+        self.crossings_device(n, rays_ptr=src.data_ptr() if rays is not None else None, points_ptr=src.data_ptr() if points is not None else None,
+                              direction=[float(c) for c in direction] if points is not None else None,
+                              tmax_ptr=bound.data_ptr() if bound is not None else None, count_ptr=count.data_ptr(),
+                              winding_ptr=wind.data_ptr() if winding else None, tmin=tmin, tmax=float("inf") if tmax is None else tmax,
+                              form=forms[form])
+        return (count, wind) if winding else count
+
+    def inside_tensors(self, points, votes=3):
+        """Which points lie inside the mesh: a bool tensor [n], the majority over the first `votes` (odd, at most 5) of INSIDE_DIRECTIONS of
+        "the ray from the point crosses an odd number of triangles" -- one crossings_tensors(points=..., direction=...) call per direction.
+        Caveat: the count follows pt_trace's acceptance rule.  A ray through a shared edge counts both triangles, a ray through a vertex the
+        whole fan, a duplicated face counts twice (the Cornell OBJ has two duplicated quads, and the box is open anyway).  Such rays are why
+        there is a vote; and the answer means something for CLOSED meshes only."""
+        if votes not in (1, 3, 5):
+            raise ValueError("votes must be 1, 3 or 5")
+        odd = None
+        for d in INSIDE_DIRECTIONS[:votes]:
+            c = self.crossings_tensors(points=points, direction=d) & 1
+            odd = c if odd is None else odd + c
+        return odd * 2 > votes
+
+    def signed_distance_tensors(self, points, votes=3, max_dist=None):
+        """Signed distance to a closed mesh: one nearest_tensors call and one inside_tensors call -> (sdf, prim, u, v): sdf = sqrt(dist2) outside,
+        -sqrt(dist2) inside, NaN where no triangle lies within max_dist (prim = -1 there)."""
+        import torch
+        near = self.nearest_tensors(points, max_dist=max_dist)
+        inside = self.inside_tensors(points, votes=votes)
+        dist = torch.sqrt(near["dist2"])
+        sdf = torch.where(inside, -dist, dist)
+        sdf = torch.where(near["prim"] < 0, torch.full_like(sdf, float("nan")), sdf)
+        return sdf, near["prim"], near["u"], near["v"]
 
     def radiance_device(self, n, rays_ptr, radiance_ptr, seeds_ptr=None, moment2_ptr=None, spp=32, max_depth=8, tmin=0.001, tmax=10000.0, env=None,
                         frame=0, index_base=0, flags=0, extend=EXTEND_AUTO, chunk_rays=0):

@@ -782,6 +782,22 @@ pt_status pt_nearest_device(pt_scene *s, const pt_nearest_desc *d, uint64_t n, f
     return guarded(s->ctx, [&] { return ptn_nearest_device(s, d, n, device_ms); });
 }
 
+void pt_crossings_desc_default(pt_crossings_desc *d)
+{
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    d->tmax = INFINITY;
+    d->form = PT_CROSSINGS_AUTO;
+}
+
+pt_status pt_crossings_device(pt_scene *s, const pt_crossings_desc *d, uint64_t n, float *device_ms)
+{
+    if (!s) return PT_ERR_INVALID_ARG;
+    if (!d) return pt_bad(s->ctx, "null argument");
+    PT_HIP(s->ctx, hipSetDevice(s->ctx->device));
+    return guarded(s->ctx, [&] { return ptx_crossings_device(s, d, n, device_ms); });
+}
+
 pt_status pt_trace_workspace_bytes(const pt_ctx *ctx, uint64_t *bytes)
 {
     if (!ctx || !bytes) return PT_ERR_INVALID_ARG;

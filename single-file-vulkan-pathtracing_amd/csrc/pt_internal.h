@@ -493,6 +493,8 @@ pt_status ptt_trace_device(pt_scene *s, const pt_trace_desc *d, uint64_t n, floa
 void ptt_free(pt_ctx *ctx);
 // nearest.hip: pt_nearest_device (validates everything but the null scene / desc); no workspace of its own
 pt_status ptn_nearest_device(pt_scene *s, const pt_nearest_desc *d, uint64_t n, float *device_ms);
+// crossings.hip: pt_crossings_device (validates everything but the null scene / desc); no workspace of its own
+pt_status ptx_crossings_device(pt_scene *s, const pt_crossings_desc *d, uint64_t n, float *device_ms);
 // radiance_device.hip: pt_radiance_device (validates everything but the null scene / desc) and the context's workspace behind it
 pt_status ptr_radiance_device(pt_scene *s, const pt_radiance_desc *d, uint64_t n, float *device_ms);
 void ptr_free(pt_ctx *ctx);

@@ -9,6 +9,7 @@
 //   trace_device.hip    pt_trace_device: rays in device memory packed into the queues, the extend launch per chunk, hit records into the caller's arrays
 //   trace_fused.hip     ... its single-kernel form (PT_TRACE_FUSED): k_trace_fused, its plan and its launch
 //   nearest.hip         pt_nearest_device: k_nearest (closest point on the mesh for device points), its plan and its launch
+//   crossings.hip       pt_crossings_device: k_crossings (crossing counts and winding for device rays), its plan and its launch
 //   film_work.hip       the film's workspace: how many slots a render gets (RenderShape) and the buffers behind them
 //   render.hip          pt_render / _prepare / _adaptive / _guided / pt_trace: one CallPlan (pipeline resolved, kernels planned once) and one Job per call;
 //                       wavefront: batches, pipelines on streams, rounds, polls; fused: shape, launches; shared: redo, selection, radiance record, timed tail
